@@ -2,6 +2,8 @@
 """bench.py — 256x256 cDDPM slices/sec (1000-step) on N MI355X, one process per GPU.
 
     python bench.py --gpus 1 --steps 4 --warmup 1
+    python bench.py --gpus 1 --steps 4 --warmup 1 --full        # + every side measurement (see below)
+    python bench.py --gpus 1 --steps 4 --warmup 1 --dump-outputs DIR
     python bench.py --gpus 8 ...            # no WORLD_SIZE in the env: this process launches the 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -18,6 +20,11 @@ chain runs the same kernels on the same shapes, so  slices/s = B_total / (1000 *
 Slices are independent chains: ranks shard the slice batch, the only collectives are the one-off RCCL
 broadcast of the packed weights from rank 0 and the final gather of the samples ("scaling": "weak", batch 16
 per GPU); the reference analogue of the broadcast is Disc_diff/guided_diffusion/dist_util.py:54-83.
+
+A plain run sets up, warms up, times the K steps once and prints the result line.  `--full` adds what the headline figure
+does not need: 3 repeats of the K steps (median), the per-kernel hipEvent pass and roofline block, the other arithmetic modes,
+the DPM-Solver++ sampler line, BASELINE configs[2..4] under `workloads`, the CPU baseline and the comparison with the CPU oracle.
+`--dump-outputs DIR` writes the samples of the last timed step (what dsd_sample hands back) as DIR/sample.npy, float32.
 
 Rehearsal hooks (never set by the driver): DSD_BENCH_BACKEND=gloo runs the ranks over gloo,
 DSD_BENCH_SINGLE_DEVICE=1 puts every rank on device 0, DSD_BENCH_STUB=1 replaces the compute leg by a CPU stub so
@@ -73,7 +80,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--repeats", type=int, default=3, help="the K timed steps are run this many times; value = median repeat")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (modes, samplers, workloads, CPU baseline, "
+                                                        "per-kernel profile); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples of the last timed step as DIR/sample.npy (float32)")
+    ap.add_argument("--repeats", type=int, default=None, help="the K timed steps are run this many times; value = median repeat "
+                                                               "(default 1, 3 with --full)")
     ap.add_argument("--batch", type=int, default=16, help="slices per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "v2-1-cddpm-ds-disc.yaml"))
@@ -89,7 +101,10 @@ def parse_args(argv=None):
                                                          "kernel from the host (measured equal at batch 16, no gain at batch 1)")
     ap.add_argument("--winograd", action="store_true", help="bf16x6 only: the F(2,3)-along-W kernel for the large 3x3 layers "
                                                             "(include/dsdiff.h: dsd_set_winograd); otherwise a separate line in `modes`")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 # ======================================================================================== launcher (parent process)
@@ -517,6 +532,20 @@ class GpuLeg:
         return roofline, kern
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, x):
+    """The samples after the last timed step (all ranks' slices, in rank order) as float32 .npy: 256 KB per 256x256 slice;
+    past DUMP_MAX_BYTES only the first slices that fit are written (the same ones in every run)."""
+    import numpy as np
+    a = x.detach().float().cpu().numpy()
+    per_slice = max(1, a[0].nbytes) if len(a) else 1
+    a = a[:max(1, DUMP_MAX_BYTES // per_slice)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample.npy"), a)
+
+
 # ======================================================================================== one rank
 def run_rank(args):
     rank = int(os.environ.get("RANK", "0"))
@@ -553,8 +582,8 @@ def run_rank(args):
         vals = [float(v.item()) for v in allr]
         return max(vals), [round(v, 3) for v in vals]
 
-    main_res = leg.measure(args.precision, args.steps, args.warmup, 0 if args.no_profile else 2, barrier, reduce_max,
-                           repeats=args.repeats)
+    main_res = leg.measure(args.precision, args.steps, args.warmup, 2 if args.full and not args.no_profile else 0, barrier,
+                           reduce_max, repeats=args.repeats)
     # per-rank device footprint (slab + arena + weight pieces + scratch, dsd_device_bytes): no rank may hold a second copy
     dev_bytes = [main_res["info"].get("device_bytes", 0)]
     if world > 1:
@@ -578,11 +607,13 @@ def run_rank(args):
         gather_ms = (time.time() - tg) * 1e3
         if rank == 0 and stub:
             assert [float(p.flatten()[0]) for p in parts] == [float(r) for r in range(world)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg.x if world == 1 else torch.cat(parts))
     rccl_ranks = dist.get_world_size() if world > 1 else 1
 
     workloads = None
     modes, samplers, cpu, rel = {args.precision: {k: main_res[k] for k in ("ms_per_step", "value", "whole_step_tflops")}}, None, None, None
-    if not stub and world == 1:
+    if args.full and not stub and world == 1:
         from diffusion_models_dsdiff_amd import _lib
         from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion.script_util import create_gaussian_diffusion
         model, B, H, W = leg.model, args.batch, args.size, args.size

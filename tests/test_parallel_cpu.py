@@ -151,7 +151,7 @@ def test_bench_self_launch_eight_ranks_gloo():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DSD_BENCH_BACKEND="gloo", DSD_BENCH_STUB="1", OMP_NUM_THREADS="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,6 +162,27 @@ def test_bench_self_launch_eight_ranks_gloo():
     assert out["timing"]["repeats"] == 3 and len(out["timing"]["ms_per_step_repeats"]) == 3
     assert out["ms_per_step"] == sorted(out["timing"]["ms_per_step_repeats"])[1] and out["ms_per_step"] >= 16.0   # rank 7 sleeps 16 ms / step
     assert abs(out["value"] - 8 * 16 / (1000.0 * out["ms_per_step"] / 1e3)) < 1e-3 * out["value"]
+
+
+def test_bench_plain_run_times_once_and_dumps_outputs(tmp_path):
+    """A plain run times the K steps once (--full adds the repeats) and --dump-outputs writes what the timed steps computed:
+    the samples of every rank in rank order, float32 (stubbed compute leg, gloo)."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(DSD_BENCH_BACKEND="gloo", DSD_BENCH_STUB="1", OMP_NUM_THREADS="1")
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["timing"]["repeats"] == 1 and out["ms_per_step"] == out["timing"]["ms_per_step_repeats"][0]
+    assert len(out["modes"]) == 1 and out["samplers"] is None and out["workloads"] is None and out["kernels"] is None
+    a = np.load(out_dir / "sample.npy")
+    assert a.dtype == np.float32 and a.shape == (2 * 16, 1, 8, 8)
+    assert np.array_equal(a[:16], np.zeros_like(a[:16])) and np.array_equal(a[16:], np.ones_like(a[16:]))   # rank r's slices hold r
 
 
 def test_bench_rejects_gpus_world_mismatch():
