@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ..._lib import DSD_NCOEF, DsdDpmSchedule, check, dptr, lib, stream_ptr
-from ..._sched import find_unet
+from ..._sched import check_latent_io, find_unet, is_latent_denoiser
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
 
@@ -289,8 +289,16 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor) -> torch.T
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
     B, Cx, H, W = x.shape
-    assert Cx == 1, "the denoised image has one channel"
     unet, cc = find_unet(fn.model), fn.c_concat()
+    if unet is not None and cc is not None and is_latent_denoiser(unet):
+        # latent state [B,Cz,h,w] under the plain UNetModel: dsd_sample_dpm_latent
+        unet.sync_params()
+        cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
+        check_latent_io(unet, x, cond)
+        check(lib().dsd_sample_dpm_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
+                                          stream_ptr()))
+        return x
+    assert Cx == 1, "the denoised image has one channel"
     if unet is not None and cc is not None:
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()

@@ -39,18 +39,36 @@ class Schedule:
 
 
 def find_unet(model):
-    """Locate the native DSUnetModel behind the object the reference passes as ``model``
-    (DiffusionWrapper.diffusion_model, ddpm.py:1323; or the U-Net itself)."""
+    """Locate the native denoiser behind the object the reference passes as ``model``
+    (DiffusionWrapper.diffusion_model, ddpm.py:1323; or the network itself): the four-stream DSUnetModel, or the plain
+    UNetModel that denoises VAE latents (run by the latent loops, dsd_sample_latent / dsd_sample_dpm_latent)."""
     from .UNet_DS_Diff.model import DSUnetModel
-    if isinstance(model, DSUnetModel):
+    from .ldm.modules.diffusionmodules.openaimodel import UNetModel
+    kinds = (DSUnetModel, UNetModel)
+    if isinstance(model, kinds):
         return model
     inner = getattr(model, "diffusion_model", None)
-    if isinstance(inner, DSUnetModel):
+    if isinstance(inner, kinds):
         return inner
     inner = getattr(getattr(model, "model", None), "diffusion_model", None)
-    if isinstance(inner, DSUnetModel):
+    if isinstance(inner, kinds):
         return inner
     return None
+
+
+def is_latent_denoiser(unet) -> bool:
+    """True for the plain UNetModel (multi-channel latent state, DSD_BLOCK_UNET handle)."""
+    from .ldm.modules.diffusionmodules.openaimodel import UNetModel
+    return isinstance(unet, UNetModel)
+
+
+def check_latent_io(unet, x: torch.Tensor, cond: torch.Tensor) -> None:
+    """Shape checks of the latent loops that the C entry points cannot see (they take one H, W)."""
+    if unet.use_spatial_transformer:
+        raise ValueError("the latent loops take 'concat' conditioning only; this UNetModel has a spatial transformer")
+    if cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:]):
+        raise ValueError(f"conditioning {tuple(cond.shape)} does not match the latent state {tuple(x.shape)} "
+                         "(same batch and spatial size needed for the 'concat' conditioning)")
 
 
 def _seed_from_torch() -> int:
@@ -62,12 +80,27 @@ def _seed_from_torch() -> int:
 def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor,
                     step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                     first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
-    """x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations."""
+    """x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations.
+    With the plain UNetModel the state is a latent x_T [B,Cz,H,W] (dsd_sample_latent; step_noise [steps,B,Cz,H,W])."""
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     unet.sync_params()
     x = x_T.detach().float().contiguous().clone()
     cond = cond.detach().float().contiguous()
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, x, cond)
+        B, Cz, H, W = x.shape
+        if step_noise is not None:
+            step_noise = step_noise.detach().float().contiguous()
+            if tuple(step_noise.shape) != (sched.steps, B, Cz, H, W):
+                raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
+        if seed is None:
+            seed = _seed_from_torch()
+        check(lib().dsd_sample_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise),
+                                      C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+        return x
     B, Cx, H, W = x.shape
     assert Cx == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
     if step_noise is not None:

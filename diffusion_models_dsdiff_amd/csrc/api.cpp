@@ -224,7 +224,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -292,7 +292,7 @@ int dsd_graph_stats(dsd_handle* h, int* captures, int* launches) {
 
 int dsd_set_slice_ids(dsd_handle* h, const int64_t* ids_host, int n) {
     DSD_TRY
-    DSD_CHECK(h && !h->is_block && n >= 0 && (ids_host || n == 0), "bad argument");
+    DSD_CHECK(h && (!h->is_block || h->block_kind == DSD_BLOCK_UNET) && n >= 0 && (ids_host || n == 0), "bad argument");
     set_device(h->device);
     if (h->slice_ids) {
         DSD_HIP(hipDeviceSynchronize());
@@ -467,6 +467,68 @@ int dsd_op_sampler_update(const dsd_schedule* sc, int k, const float* model_out,
     DSD_CATCH
 }
 
+// ------------------------------------------------------------------------------------------- latent loops (UNET block)
+// The state x [B,Cz,h,w] is copied once into channels [0,Cz) of the denoiser's persistent NCHW input [B,Cz+Cc,h,w] and the
+// conditioning into channels [Cz,Cz+Cc) (DiffusionWrapper 'concat', ddpm.py:1331-1333); every update then reads and writes the
+// state in place there, so the next network evaluation reads x_{t-1} with no concatenation and no copy.  The final state is
+// copied back to x.  Returns the state's row stride: (Cz+Cc)*h*w elements.
+static int64_t latent_bind(dsd_handle* h, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W, int out_ch,
+                           hipStream_t s) {
+    DSD_CHECK(h && cond && x, "null argument");
+    DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
+    DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
+    const std::vector<int32_t>& a = h->iargs;
+    DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
+    DSD_CHECK(a[0] == Cz + Cc, "the UNetModel takes %d input channels but state + conditioning have %d + %d", a[0], Cz, Cc);
+    DSD_CHECK(a[2] == out_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], out_ch);
+    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
+    const int64_t hw = (int64_t)H * W, Cin = Cz + Cc;
+    net_plan(h, B, (int)Cin, H, W, 0, 0, 1, 0, 0, s);
+    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
+    ensure_buf(&h->mout, &h->mout_cap, (size_t)B * out_ch * hw * sizeof(float));
+    ensure_buf(&h->lat_in, &h->lat_in_cap, (size_t)B * Cin * hw * sizeof(float));
+    const size_t row = (size_t)Cin * hw * sizeof(float);
+    DSD_HIP(hipMemcpy2DAsync(h->lat_in, row, x, (size_t)Cz * hw * sizeof(float), (size_t)Cz * hw * sizeof(float), B,
+                             hipMemcpyDeviceToDevice, s));
+    if (Cc)
+        DSD_HIP(hipMemcpy2DAsync(h->lat_in + Cz * hw, row, cond, (size_t)Cc * hw * sizeof(float), (size_t)Cc * hw * sizeof(float), B,
+                                 hipMemcpyDeviceToDevice, s));
+    h->io = IO();
+    h->io.x_nchw = h->lat_in;
+    h->io.aux = h->tbuf;
+    h->io.out = h->mout;
+    return Cin * hw;
+}
+
+static void latent_unbind(dsd_handle* h, float* x, int Cz, int B, int64_t hw, int64_t x_bs, hipStream_t s) {
+    DSD_HIP(hipMemcpy2DAsync(x, (size_t)Cz * hw * sizeof(float), h->lat_in, (size_t)x_bs * sizeof(float),
+                             (size_t)Cz * hw * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+}
+
+int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, int Cz, const float* noise,
+                      uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    check_schedule(sc);
+    DSD_CHECK(!(sc->learned_range && Cz > 1),
+              "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, (sc->learned_range ? 2 : 1) * Cz, s);
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        fill_t(h->tbuf, B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        sampler_update(step_coef(sc, k), h->mout, h->lat_in, noise ? noise + (size_t)k * B * Cz * hw : nullptr, philox_seed,
+                       (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
 // ------------------------------------------------------------------------------------------- DPM-Solver(++)
 static void check_dpm_schedule(const dsd_dpm_schedule* sc) {
     DSD_CHECK(sc && sc->steps > 0 && sc->coef && sc->t_input && sc->order, "bad DPM schedule");
@@ -515,6 +577,31 @@ int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond,
         dpm_step(dpm_coef(sc, k), h->mout, out_ch, x, m_cur, m_prev, s_buf, sc->threshold_ratio, sc->threshold_max, B, (int)hw, s);
         std::swap(m_cur, m_prev);
     }
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond, int Cc, float* x, int Cz, int B, int H,
+                          int W, void* stream) {
+    DSD_TRY
+    check_dpm_schedule(sc);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)Cz * hw;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s);
+    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * n + B) * sizeof(float));
+    float* m_cur = h->dpm_m;
+    float* m_prev = h->dpm_m + (size_t)B * n;
+    float* s_buf = h->dpm_m + (size_t)2 * B * n;
+    for (int k = 0; k < sc->steps; ++k) {
+        fill_t(h->tbuf, B, sc->t_input[k], s);
+        net_run_cached(h, s);
+        // one sample = all Cz*h*w elements: the dynamic-thresholding quantile is per sample over C*h*w (sampler.py:379-388)
+        dpm_step(dpm_coef(sc, k), h->mout, 1, h->lat_in, m_cur, m_prev, s_buf, sc->threshold_ratio, sc->threshold_max, B, (int)n, s,
+                 x_bs);
+        std::swap(m_cur, m_prev);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
     net_check_overflow(h, s);
     DSD_CATCH
 }
@@ -925,6 +1012,14 @@ int dsd_op_gaussian_sample(const float* moments, const float* noise, uint64_t ph
     DSD_TRY
     DSD_CHECK(moments && z && B >= 0 && E >= 1 && H >= 1 && W >= 1, "bad argument");
     gaussian_sample(moments, noise, philox_seed, B, E, H * W, z, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_posterior_sample_scaled(const float* moments, const float* noise, uint64_t philox_seed, int B, int E, int H, int W,
+                                   float scale, float* z, void* stream) {
+    DSD_TRY
+    DSD_CHECK(moments && z && B >= 0 && E >= 1 && H >= 1 && W >= 1, "bad argument");
+    gaussian_sample(moments, noise, philox_seed, B, E, H * W, z, (hipStream_t)stream, scale);
     DSD_CATCH
 }
 

@@ -690,9 +690,15 @@ int conv2d_stats_chunks(const ConvArgs& a) {
     const int tm = cdiv(M, BM);
     const int pr = effective_precision(a, tm);
     if (pr == PREC_F32) return 0;
-    int nt = pick_nt(a.Cout, tm, pr, a.lanes), ks = 1, ad = 0;
+    const int nt0 = pick_nt(a.Cout, tm, pr, a.lanes);
+    int nt = nt0, ks = 1, ad = 0;
     conv2d_split_plan(a, nt, &nt, &ks, &ad);
     if (ks > 1 || (ad == 1 && nt >= 4)) return 0;   // (128-row kernels with >= 4 column tiles have no registers for it)
+    // Without split-K no scratch is planned, and conv2d() then launches the layer with allow_split = false, which keeps the
+    // default structure: statistics only when that launch tiles the rows the same way (the f = 8 VAE's 64x64 layers do not)
+    int nt_l = nt0, ks_l = 1, ad_l = 0;
+    conv2d_split_plan(a, nt0, &nt_l, &ks_l, &ad_l, false);
+    if (ad_l != ad || (ad_l == 1 && nt_l >= 4)) return 0;
     const int rows = ad == 2 ? 2 * BM : BM;
     const int ohw = OH * OW;
     return ohw % rows == 0 ? ohw / rows : 0;

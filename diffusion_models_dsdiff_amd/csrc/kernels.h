@@ -230,11 +230,13 @@ struct StepCoef {
     int mode, pred, learned_range, clip, nonzero;
     float eta;
 };
-// model_out: [B,Cm,HW] (Cm = 1, or 2 with learned_range); x in/out [B,1,HW]; noise [B,1,HW] or null (Philox)
-// slice_ids (optional, device [B]): global slice index of every batch row — the Philox counter of element p of row b is
-// slice_ids[b]*HW + p instead of b*HW + p, so a slice's noise does not depend on how the volume was sharded or batched
+// model_out: [B,Cm*Cz,HW] (Cm = 1, or 2 with learned_range and Cz = 1); x in/out [B,Cz,HW] with row stride x_bs (0 = Cz*HW);
+// noise [B,Cz,HW] or null (Philox)
+// slice_ids (optional, device [B]): global slice index of every batch row — the Philox counter of element r = c*HW + p of row b
+// is slice_ids[b]*Cz*HW + r instead of b*Cz*HW + r, so a slice's noise does not depend on how the volume was sharded or batched
 void sampler_update(const StepCoef& sc, const float* model_out, float* x, const float* noise, uint64_t seed,
-                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr, const int64_t* slice_ids = nullptr);
+                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr, const int64_t* slice_ids = nullptr,
+                    int Cz = 1, int64_t x_bs = 0);
 // DPM-Solver(++) multistep: coefficients of one network evaluation + update (host tables, include/dsdiff.h dsd_dpm_schedule)
 struct DpmCoef {
     float alpha, sigma;      // marginal alpha_t, sigma_t at the evaluation time
@@ -244,12 +246,13 @@ struct DpmCoef {
     int data_pred, thresh;
 };
 void dpm_step(const DpmCoef& c, const float* model_out, int Cm, float* x, float* m_cur, const float* m_prev, float* s_buf,
-              float ratio, float max_val, int B, int HW, hipStream_t s);
+              float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s);
 void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_t s);
 // DiagonalGaussianDistribution.sample (ldm/modules/distributions/distributions.py:24-37): moments [B,2E,HW] (NCHW) ->
-// z = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps, eps = noise[B,E,HW] or Philox normals (noise == nullptr)
-void gaussian_sample(const float* moments, const float* noise, uint64_t seed, int B, int E, int HW, float* z, hipStream_t s);
+// z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps), eps = noise[B,E,HW] or Philox normals (noise == nullptr)
+void gaussian_sample(const float* moments, const float* noise, uint64_t seed, int B, int E, int HW, float* z, hipStream_t s,
+                     float scale = 1.0f);
 void fill_t(float* t, int B, float v, hipStream_t s);
 
 }  // namespace dsd

@@ -595,6 +595,10 @@ void dsd::net_set_param(dsd_handle* h, const char* name, const float* src, const
     }
 }
 
+bool dsd::net_unet_has_spatial_transformer(const dsd_handle* h) {
+    return h->is_block && h->block_kind == DSD_BLOCK_UNET && st_opt_from_iargs(h->iargs).on != 0;
+}
+
 void dsd::net_drop_graph(dsd_handle* h) {
     if (h->gexec) {
         (void)hipDeviceSynchronize();
@@ -644,6 +648,7 @@ void dsd::net_free(dsd_handle* h) {
     if (h->mout) (void)hipFree(h->mout);
     if (h->zplane) (void)hipFree(h->zplane);
     if (h->dpm_m) (void)hipFree(h->dpm_m);
+    if (h->lat_in) (void)hipFree(h->lat_in);
     if (h->freqs) (void)hipFree(h->freqs);
     if (h->ovf) (void)hipFree(h->ovf);
     if (h->slice_ids) (void)hipFree(h->slice_ids);

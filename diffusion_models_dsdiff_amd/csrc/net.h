@@ -133,6 +133,7 @@ struct dsd_handle {
     float* mout = nullptr;     // [B,out_ch,H,W]
     float* zplane = nullptr;   // [H*W] zeros
     float* dpm_m = nullptr;    // dsd_sample_dpm: m_k, m_{k-1} [B,H*W] each + thresholds [B]
+    float* lat_in = nullptr;   // latent loops (UNET block): the denoiser's NCHW input [B,Cz+Cc,h,w]; channels [0,Cz) are the state
     float* freqs = nullptr;    // [model_channels/2] optional timestep-embedding frequency table (host-supplied)
     int64_t* slice_ids = nullptr;  // [n_slice_ids] global slice index of every batch row (Philox counter base), optional
     int n_slice_ids = 0;
@@ -176,7 +177,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0;
 
     float* P(const std::string& name) const;
     const dsd::Param& PP(const std::string& name) const;
@@ -196,6 +197,8 @@ void net_launch_ops(dsd_handle* h, hipStream_t s);
 // the same forward through the captured hipGraph when one is valid for the current plan and bindings (sampling loops)
 void net_run_cached(dsd_handle* h, hipStream_t s);
 void net_drop_graph(dsd_handle* h);
+// DSD_BLOCK_UNET handles: built with use_spatial_transformer (a SpatialTransformer on `context` in every attention slot)
+bool net_unet_has_spatial_transformer(const dsd_handle* h);
 // frees the weight pieces of the arithmetic family (bf16 / fp16) that `precision` does not use
 void net_drop_other_pieces(dsd_handle* h, int precision);
 size_t net_piece_bytes(const dsd_handle* h);

@@ -60,18 +60,23 @@ void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_
     check_launch("philox_normal");
 }
 
+// One sample is n = Cz*HW elements (r = c*HW + p inside it).  The state row b lives at x + b*x_bs: x_bs = n for a state of its
+// own, (Cz+Cc)*HW when the state is the first Cz channels of the denoiser's NCHW input (the latent loop writes x_{t-1} straight
+// into the buffer the network reads next).  model_out, noise and x0_out are contiguous [B,Cm*Cz,HW] / [B,Cz,HW].  The Philox
+// counter of (row b, channel c, pixel p) is (slice_ids ? slice_ids[b] : b)*n + r: distinct channels never share a normal.
 __global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const float* __restrict__ mo,
                                                              float* __restrict__ x, const float* __restrict__ noise,
-                                                             uint64_t seed, uint64_t step, int B, int HW,
+                                                             uint64_t seed, uint64_t step, int B, int64_t n, int64_t x_bs,
                                                              float* __restrict__ x0_out, const int64_t* __restrict__ slice_ids) {
-    const int64_t total = (int64_t)B * HW;
-    const int Cm = sc.learned_range ? 2 : 1;
+    const int64_t total = (int64_t)B * n;
+    const int Cm = sc.learned_range ? 2 : 1;   // learned range: Cz == 1 (checked by the callers)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / HW;
-        const int64_t p = i - b * HW;
-        const float out = mo[(b * Cm) * HW + p];
-        const float xt = x[i];
-        const float z = noise ? noise[i] : philox_normal_at(slice_ids ? slice_ids[b] * HW + p : i, seed, step);
+        const int64_t b = i / n;
+        const int64_t p = i - b * n;
+        const int64_t xi = b * x_bs + p;
+        const float out = mo[(b * Cm) * n + p];
+        const float xt = x[xi];
+        const float z = noise ? noise[i] : philox_normal_at(slice_ids ? slice_ids[b] * n + p : i, seed, step);
         const float* c = sc.c;
         float x0, res;
         if (sc.mode == DSD_MODE_B_DDIM) {
@@ -108,24 +113,26 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const 
                 const float mean = c[4] * x0 + c[5] * xt;
                 float logvar = c[6];
                 if (sc.learned_range) {  // gaussian_diffusion.py:287-293
-                    const float v = mo[(b * Cm + 1) * HW + p];
+                    const float v = mo[(b * Cm + 1) * n + p];
                     const float frac = (v + 1.f) / 2.f;
                     logvar = frac * c[7] + (1.f - frac) * c[6];
                 }
                 res = mean + nz * expf(0.5f * logvar) * z;
             }
         }
-        x[i] = res;
+        x[xi] = res;
         if (x0_out) x0_out[i] = x0;
     }
 }
 
 void sampler_update(const StepCoef& sc, const float* model_out, float* x, const float* noise, uint64_t seed,
-                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids) {
-    const int64_t total = (int64_t)B * HW;
+                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz, int64_t x_bs) {
+    const int64_t n = (int64_t)Cz * HW;
+    const int64_t total = (int64_t)B * n;
     if (!total) return;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(sampler_update_kernel, dim3(blocks), dim3(256), 0, s, sc, model_out, x, noise, seed, step, B, HW, x0_out, slice_ids);
+    hipLaunchKernelGGL(sampler_update_kernel, dim3(blocks), dim3(256), 0, s, sc, model_out, x, noise, seed, step, B, n,
+                       x_bs > 0 ? x_bs : n, x0_out, slice_ids);
     check_launch("sampler_update");
 }
 
@@ -138,14 +145,16 @@ void sampler_update(const StepCoef& sc, const float* model_out, float* x, const 
 //               'linear': sorted[floor(r)] lerp sorted[ceil(r)], r = q*(n-1) in fp32) by an exact 4-pass radix select
 //   dpm_update  m_k <- clamp(m_k,-s,s)/s ; x <- first-order (:509-553) or second-order multistep update (:760-816)
 // Every product/sum is a separately rounded fp32 op in the reference's order (file-wide contract(off)).
+// HW = elements per sample (Cz*h*w for a latent state); x row b at x + b*x_bs (x_bs = HW, or (Cz+Cc)*h*w inside the
+// denoiser's input buffer); m and the model output are contiguous.
 __global__ __launch_bounds__(256) void dpm_model_kernel(DpmCoef c, const float* __restrict__ mo, int Cm,
                                                         const float* __restrict__ x, float* __restrict__ m, int B,
-                                                        int HW) {
+                                                        int HW, int64_t x_bs) {
     const int64_t total = (int64_t)B * HW;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / HW;
         const float out = mo[(b * Cm) * HW + (i - b * HW)];   // a learned-sigma model: first channel only (gaussian_diffusion.py:484-485)
-        const float xt = x[i];
+        const float xt = x[b * x_bs + (i - b * HW)];
         float eps;
         if (c.pred == DSD_PRED_EPS)
             eps = out;
@@ -214,7 +223,7 @@ __global__ __launch_bounds__(1024) void dpm_quantile_kernel(const float* __restr
 
 __global__ __launch_bounds__(256) void dpm_update_kernel(DpmCoef c, float* __restrict__ m0, const float* __restrict__ m1,
                                                          const float* __restrict__ s_thr, float* __restrict__ x, int B,
-                                                         int HW) {
+                                                         int HW, int64_t x_bs) {
     const int64_t total = (int64_t)B * HW;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         float m = m0[i];
@@ -224,30 +233,32 @@ __global__ __launch_bounds__(256) void dpm_update_kernel(DpmCoef c, float* __res
             m0[i] = m;
         }
         if (!x) continue;                                     // thresholding only (dsd_op_dpm_threshold)
+        const int64_t xi = (i / HW) * x_bs + (i % HW);
         float res;
         if (c.order == 0) {
             res = m;                                          // denoise_to_zero_fn :503-507
         } else {
-            res = c.cx * x[i] - c.cm * m;
+            res = c.cx * x[xi] - c.cm * m;
             if (c.order == 2) res = res - c.cd * (c.ir0 * (m - m1[i]));
         }
-        x[i] = res;
+        x[xi] = res;
     }
 }
 
 void dpm_step(const DpmCoef& c, const float* model_out, int Cm, float* x, float* m_cur, const float* m_prev, float* s_buf,
-              float ratio, float max_val, int B, int HW, hipStream_t s) {
+              float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
     const int64_t total = (int64_t)B * HW;
     if (!total) return;
+    if (x_bs <= 0) x_bs = HW;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(dpm_model_kernel, dim3(blocks), dim3(256), 0, s, c, model_out, Cm, x, m_cur, B, HW);
+    hipLaunchKernelGGL(dpm_model_kernel, dim3(blocks), dim3(256), 0, s, c, model_out, Cm, x, m_cur, B, HW, x_bs);
     check_launch("dpm_model");
     const bool thr = c.thresh && c.data_pred;
     if (thr) {
         hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m_cur, HW, ratio, max_val, s_buf);
         check_launch("dpm_quantile");
     }
-    hipLaunchKernelGGL(dpm_update_kernel, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW);
+    hipLaunchKernelGGL(dpm_update_kernel, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW, x_bs);
     check_launch("dpm_update");
 }
 
@@ -259,13 +270,16 @@ void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float m
     DpmCoef c{};
     c.order = 0;
     hipLaunchKernelGGL(dpm_update_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)B * n + 255) / 256, 4096)), dim3(256), 0, s, c,
-                       y, (const float*)nullptr, s_buf, (float*)nullptr, B, n);
+                       y, (const float*)nullptr, s_buf, (float*)nullptr, B, n, (int64_t)n);
     check_launch("dpm_update");
     DSD_HIP(hipStreamSynchronize(s));
 }
 
+// scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed
+// (1.0 for the plain DiagonalGaussianDistribution.sample: x * 1.0f is exact).  With B = batch*K rows ordered (sample, key),
+// z [B*K,E,HW] IS the [batch,K*E,HW] 'concat' conditioning: key k of a sample lands in channels [k*E,(k+1)*E).
 __global__ void gaussian_sample_kernel(const float* __restrict__ mo, const float* __restrict__ noise, uint64_t seed, int B, int E,
-                                       int HW, float* __restrict__ z) {
+                                       int HW, float scale, float* __restrict__ z) {
     const int64_t total = (int64_t)B * E * HW;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / ((int64_t)E * HW);
@@ -275,14 +289,15 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mo, const float
         logvar = fminf(fmaxf(logvar, -30.f), 20.f);             // distributions.py:28
         const float std = expf(0.5f * logvar);
         const float eps = noise ? noise[i] : philox_normal_at(i, seed, 0);
-        z[i] = mean + std * eps;                                // :36
+        z[i] = scale * (mean + std * eps);                      // :36, then ddpm.py:667
     }
 }
-void gaussian_sample(const float* moments, const float* noise, uint64_t seed, int B, int E, int HW, float* z, hipStream_t s) {
+void gaussian_sample(const float* moments, const float* noise, uint64_t seed, int B, int E, int HW, float* z, hipStream_t s,
+                     float scale) {
     const int64_t total = (int64_t)B * E * HW;
     if (!total) return;
     hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, moments,
-                       noise, seed, B, E, HW, z);
+                       noise, seed, B, E, HW, scale, z);
     check_launch("gaussian_sample");
 }
 

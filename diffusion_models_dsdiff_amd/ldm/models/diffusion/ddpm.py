@@ -1,5 +1,6 @@
 """DiffusionWrapper + DDPM schedule — drop-in for the sampling-relevant part of ldm/models/diffusion/ddpm.py
-(register_schedule :138-178, predict_* :284-302, q_posterior :304-311, DiffusionWrapper :1319-1365)."""
+(register_schedule :138-178, predict_* :284-302, q_posterior :304-311, DiffusionWrapper :1319-1365) and the sampling surface
+of LatentDiffusion (:526-1115: first stage with scale_factor, 'concat' apply_model, DDPM sample on the device latent loop)."""
 from __future__ import annotations
 
 from fractions import Fraction
@@ -98,3 +99,244 @@ class DDPM(nn.Module):
     @property
     def device(self):
         return self.betas.device
+
+
+def _fp32(v) -> float:
+    """A Python float or a 0-d tensor as the fp32 value torch multiplies an fp32 tensor by."""
+    if torch.is_tensor(v):
+        return float(v.detach().float().cpu().reshape(()).item())
+    return float(np.float32(v))
+
+
+def latent_diffusion_param_table(unet_config, ddconfig, embed_dim, scale_by_std=False):
+    """(name, shape) of LatentDiffusion's parameters as the reference's state_dict spells them ("model.diffusion_model.*",
+    "first_stage_model.*", and the "scale_factor" buffer with scale_by_std), read from table-only library handles: no GPU
+    needed.  The same names a LatentDiffusion instance reports (and loads a reference checkpoint by)."""
+    import ctypes as C
+    from .... import _lib
+    from ...modules.diffusionmodules.model import _iargs as vae_iargs
+    from ...modules.diffusionmodules.openaimodel import unet_iargs
+    L = _lib.lib()
+    iu = unet_iargs(**dict(unet_config.get("params", unet_config)))
+    dd = dict(ddconfig)
+    dd["in_channels"] = dd["out_ch"] = 1                     # autoencoder.py:46-48
+    iv = vae_iargs(dd["ch"], dd["out_ch"], dd.get("ch_mult", (1, 2, 4, 8)), dd["num_res_blocks"], dd.get("attn_resolutions", []),
+                   dd["in_channels"], dd["resolution"], dd["z_channels"], dd.get("double_z", True), embed_dim, True)
+    out = []
+    for prefix, kind, ia in (("model.diffusion_model.", _lib.BLOCK_UNET, iu), ("first_stage_model.", _lib.BLOCK_VAE_ENCODER, iv),
+                             ("first_stage_model.", _lib.BLOCK_VAE_DECODER, iv)):
+        h = C.c_void_p()
+        _lib.check(L.dsd_block_create(kind, (C.c_int32 * len(ia))(*[int(v) for v in ia]), len(ia), -1, C.byref(h)))
+        name, shape, ndim = C.c_char_p(), (C.c_int64 * 4)(), C.c_int()
+        try:
+            for i in range(L.dsd_param_count(h)):
+                _lib.check(L.dsd_param_info(h, i, C.byref(name), shape, C.byref(ndim)))
+                out.append((prefix + name.value.decode(), tuple(shape[k] for k in range(ndim.value))))
+        finally:
+            L.dsd_destroy(h)
+    if scale_by_std:
+        out.append(("scale_factor", ()))
+    return out
+
+
+_WEIGHT_PREFIXES = ("model.diffusion_model.", "first_stage_model.")
+
+
+def select_checkpoint(sd, own_keys, ignore_keys=()):
+    """The part of a reference checkpoint LatentDiffusion loads: ``(keep, missing, unexpected)``.  Keys starting with one of
+    ``ignore_keys`` are dropped (ddpm.py:214-219); keys the model does not have (EMA copies, logvar, loss / discriminator
+    weights) are ``unexpected`` and ignored.  Every denoiser ("model.diffusion_model.*") and first-stage
+    ("first_stage_model.*") weight must be present: a checkpoint whose first stage is named otherwise (a diffusers-style
+    AutoencoderKL) would otherwise leave the network at its initial weights without a word, so that raises a KeyError."""
+    own = list(own_keys)
+    own_set = set(own)
+    sd = {k: v for k, v in sd.items() if not any(k.startswith(ik) for ik in ignore_keys)}
+    keep = {k: v for k, v in sd.items() if k in own_set}
+    unexpected = [k for k in sd if k not in own_set]
+    missing = [k for k in own if k not in keep]
+    lost = [k for k in missing if k.startswith(_WEIGHT_PREFIXES)]
+    if lost:
+        raise KeyError(f"checkpoint lacks {len(lost)} network weight(s) of LatentDiffusion, e.g. {lost[:4]}; "
+                       f"unexpected keys there: {unexpected[:4]}")
+    return keep, missing, unexpected
+
+
+class LatentDiffusion(DDPM):
+    """The sampling surface of ldm/models/diffusion/ddpm.py:526-1115 (LatentDiffusion) as trainers/trainer_latent_diffusion.py
+    uses it: a KL first stage (AutoencoderKL) around a native UNetModel with 'concat' conditioning.  ``sample`` (DDPM,
+    :1048-1115) and the DDIMSampler / DPMSolverSampler handed this object run in the library's device-resident latent loops
+    (dsd_sample_latent / dsd_sample_dpm_latent).  Training (losses, scale_by_std estimation, EMA, Lightning) is out of scope."""
+
+    def __init__(self, first_stage_config, cond_stage_config=None, num_timesteps_cond=None, cond_stage_key="image",
+                 cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None,
+                 scale_factor=1.0, scale_by_std=False, force_null_conditioning=False, *args, **kwargs):
+        self.force_null_conditioning = force_null_conditioning
+        self.num_timesteps_cond = 1 if num_timesteps_cond is None else num_timesteps_cond
+        self.scale_by_std = scale_by_std
+        assert self.num_timesteps_cond <= kwargs.get("timesteps", 1000)
+        if conditioning_key is None:                                     # :546-550
+            conditioning_key = "concat" if concat_mode else "crossattn"
+        if cond_stage_config == "__is_unconditional__" and not self.force_null_conditioning:
+            conditioning_key = None
+        if conditioning_key not in ("concat", None):
+            raise NotImplementedError(f"conditioning_key={conditioning_key!r}: the latent path runs 'concat' conditioning only")
+        ckpt_path = kwargs.pop("ckpt_path", None)
+        ignore_keys = kwargs.pop("ignore_keys", [])
+        kwargs.pop("reset_ema", None), kwargs.pop("reset_num_ema_updates", None)
+        self.image_size = kwargs.get("image_size", 256)
+        self.channels = kwargs.get("channels", 3)
+        self.first_stage_key = kwargs.get("first_stage_key", "image")
+        super().__init__(*args, conditioning_key=conditioning_key, **kwargs)
+        self.concat_mode = concat_mode
+        self.cond_stage_trainable = cond_stage_trainable
+        self.cond_stage_key = cond_stage_key
+        self.cond_stage_forward = cond_stage_forward
+        if not scale_by_std:
+            self.scale_factor = scale_factor
+        else:
+            self.register_buffer("scale_factor", torch.tensor(scale_factor))
+        self.instantiate_first_stage(first_stage_config)
+        self.clip_denoised = False                                       # :572
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys)
+
+    # ------------------------------------------------------------------ construction / checkpoints
+    def instantiate_first_stage(self, config):
+        """:620-625.  ``config``: {"target": ...AutoencoderKL, "params": {...}} (the yaml's first_stage_config) or a module."""
+        from ..autoencoder import AutoencoderKL
+        if isinstance(config, nn.Module):
+            model = config
+        else:
+            target = config.get("target", "ldm.models.autoencoder.AutoencoderKL")
+            if not target.endswith("AutoencoderKL"):
+                raise NotImplementedError(f"first stage {target!r}: the latent path runs the KL autoencoder (AutoencoderKL)")
+            model = AutoencoderKL(**dict(config.get("params", {})))
+        self.first_stage_model = model.eval()
+        for p in self.first_stage_model.parameters():
+            p.requires_grad = False
+
+    def init_from_ckpt(self, path, ignore_keys=list(), only_model=False):
+        """:210-250: loads by name and drops ``ignore_keys``; training-only entries (EMA, logvar, losses) are reported and
+        ignored.  A checkpoint that lacks any denoiser or first-stage weight raises (see select_checkpoint)."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if "state_dict" in sd:
+            sd = sd["state_dict"]
+        keep, missing, unexpected = select_checkpoint(sd, self.state_dict().keys(), ignore_keys)
+        self.load_state_dict(keep, strict=False)
+        print(f"Restored from {path} with {len(missing)} missing and {len(unexpected)} unexpected keys")
+        if missing:
+            print(f"Missing Keys: {missing}")
+        if unexpected:
+            print(f"Unexpected Keys: {unexpected}")
+        return missing, unexpected
+
+    def on_train_batch_start(self, *args, **kwargs):
+        if self.scale_by_std:
+            raise NotImplementedError("scale_by_std estimation (ddpm.py:599-608) is training; set scale_factor from the checkpoint")
+
+    # ------------------------------------------------------------------ first stage
+    @torch.no_grad()
+    def encode_first_stage(self, x):
+        """:841-843 -> DiagonalGaussianDistribution."""
+        return self.first_stage_model.encode(x)
+
+    @torch.no_grad()
+    def get_first_stage_encoding(self, encoder_posterior, noise=None, seed=None):
+        """:660-667: ``scale_factor * posterior.sample()``, one fused kernel.  ``noise`` / ``seed`` are extensions."""
+        from ...modules.distributions.distributions import DiagonalGaussianDistribution
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            return encoder_posterior.sample_scaled(_fp32(self.scale_factor), noise=noise, seed=seed)
+        if torch.is_tensor(encoder_posterior):
+            return self.scale_factor * encoder_posterior
+        raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+
+    def inverse_scale(self) -> float:
+        """``1. / self.scale_factor`` as decode_first_stage rounds it (:836): a Python float is inverted in float64 and the product
+        taken in fp32; a 0-d fp32 buffer is inverted in fp32."""
+        sf = self.scale_factor
+        if torch.is_tensor(sf):
+            return float((1. / sf.detach().float().cpu()).reshape(()).item())
+        return float(np.float32(1. / sf))
+
+    @torch.no_grad()
+    def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
+        """:827-838."""
+        if predict_cids:
+            raise NotImplementedError("codebook first stages are not on the latent path")
+        z = z.float() * self.inverse_scale()
+        return self.first_stage_model.decode(z)
+
+    @torch.no_grad()
+    def encode_conditions(self, images, noise=None, seed=None):
+        """The trainer's per-key condition encoding (trainers/trainer_latent_diffusion.py:177-189): K one-channel condition images
+        per sample -> ``{"c_concat": [z]}`` with z [B, K*embed_dim, h, w], key k in channels [k*E, (k+1)*E).  All B*K images go
+        through ONE encoder pass; the scaled posterior sample of row (b, k) lands in its slot directly.  ``images``: a list of K
+        [B,1,H,W] tensors or a [B,K,H,W] tensor; ``noise`` [B,K*E,h,w] (the reference's per-key draws, concatenated)."""
+        if isinstance(images, (list, tuple)):
+            images = torch.cat(list(images), 1)
+        B, K, H, W = images.shape
+        x = images.float().contiguous().reshape(B * K, 1, H, W)
+        post = self.encode_first_stage(x)
+        z = post.sample_scaled(_fp32(self.scale_factor), noise=noise, seed=seed)
+        return {"c_concat": [z.reshape(B, K * z.shape[1], z.shape[2], z.shape[3])]}
+
+    # ------------------------------------------------------------------ denoiser
+    def apply_model(self, x_noisy, t, cond, return_ids=False):
+        """:857-878, 'concat' conditioning."""
+        if not isinstance(cond, dict):
+            cond = {"c_concat": cond if isinstance(cond, list) else [cond]}
+        out = self.model(x_noisy, t, **cond)
+        return out[0] if isinstance(out, tuple) and not return_ids else out
+
+    def _schedule(self, timesteps=None):
+        """B_DDPM over t = timesteps-1 .. 0 (p_sample :961-993 via p_mean_variance :929-959, q_posterior :304-311)."""
+        from .... import _lib
+        from ...._sched import Schedule
+        if self.parameterization == "v":
+            raise NotImplementedError("LatentDiffusion.p_mean_variance supports eps / x0 only (ddpm.py:941-946); sample v-models "
+                                      "with DDIMSampler or DPMSolverSampler")
+        T = self.num_timesteps if timesteps is None else min(int(timesteps), self.num_timesteps)
+        idx = np.arange(T - 1, -1, -1)
+        g = lambda name: getattr(self, name).detach().cpu().numpy()[idx]
+        coef = np.zeros((T, _lib.DSD_NCOEF), dtype=np.float32)
+        coef[:, 0], coef[:, 1] = g("sqrt_alphas_cumprod"), g("sqrt_one_minus_alphas_cumprod")
+        coef[:, 2], coef[:, 3] = g("sqrt_recip_alphas_cumprod"), g("sqrt_recipm1_alphas_cumprod")
+        coef[:, 4], coef[:, 5] = g("posterior_mean_coef1"), g("posterior_mean_coef2")
+        coef[:, 6] = g("posterior_log_variance_clipped")
+        pred = {"eps": _lib.PRED_EPS, "x0": _lib.PRED_X0}[self.parameterization]
+        return Schedule(_lib.MODE_B_DDPM, pred, coef, idx.astype(np.float32), (idx != 0).astype(np.int32),
+                        clip_denoised=self.clip_denoised)
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None,
+                      step_noise=None, seed=None):
+        """:1048-1093 on the device.  ``step_noise`` ([steps,B,C,h,w]) / ``seed`` are extensions for reproducible runs."""
+        from ...._sched import find_unet, run_device_loop
+        if mask is not None or quantize_denoised or callback is not None or img_callback is not None:
+            raise NotImplementedError("mask / quantize / per-step callbacks are not on the device loop")
+        device = self.betas.device if self.betas.is_cuda else torch.device("cuda")
+        img = x_T if x_T is not None else torch.randn(shape, device=device)
+        if start_T is not None:
+            timesteps = min(timesteps or self.num_timesteps, start_T)
+        c = cond["c_concat"] if isinstance(cond, dict) else (cond if isinstance(cond, list) else [cond])
+        out = run_device_loop(find_unet(self.model), self._schedule(timesteps), img.to(device),
+                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed)
+        if return_intermediates:
+            return out, [img, out]
+        return out
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
+               quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
+        """:1095-1115."""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        if cond is not None:
+            if isinstance(cond, dict):
+                cond = {k: [x[:batch_size] for x in v] if isinstance(v, list) else v[:batch_size] for k, v in cond.items()}
+            else:
+                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
+                                  timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0,
+                                  step_noise=kwargs.get("step_noise"), seed=kwargs.get("seed"))

@@ -16,6 +16,23 @@ from ...._lib import check, dptr, lib, stream_ptr
 from ....blocks import _Block, ResBlock, AttentionBlock, Upsample, Downsample  # noqa: F401  (reference import paths)
 
 
+def unet_iargs(in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, channel_mult=(1, 2, 4, 8),
+               num_heads=-1, num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
+               use_new_attention_order=False, legacy=True, use_spatial_transformer=False, transformer_depth=1, context_dim=None,
+               use_linear_in_transformer=False, **ignored):
+    """The DSD_BLOCK_UNET handle arguments (include/dsdiff.h) for UNetModel's constructor keywords: the one place they are laid
+    out, for the module and for table-only handles."""
+    channel_mult = list(channel_mult)
+    nrb = len(channel_mult) * [num_res_blocks] if isinstance(num_res_blocks, int) else list(num_res_blocks)
+    ar = list(attention_resolutions)
+    if isinstance(context_dim, (list, tuple)):
+        context_dim = list(context_dim)[0]
+    st = [1, int(transformer_depth), int(context_dim), int(bool(use_linear_in_transformer))] if use_spatial_transformer else []
+    return [in_channels, model_channels, out_channels, num_heads, num_head_channels, num_heads_upsample, int(bool(use_scale_shift_norm)),
+            int(bool(resblock_updown)), int(bool(use_new_attention_order)), int(bool(legacy)), len(channel_mult)] + channel_mult + nrb + \
+        [len(ar)] + ar + st
+
+
 class UNetModel(_Block):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0,
                  channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False, use_fp16=False,
@@ -57,10 +74,10 @@ class UNetModel(_Block):
         self.dtype = torch.float32
         ar = self.attention_resolutions
         self.use_spatial_transformer, self.context_dim = bool(use_spatial_transformer), context_dim
-        st = [1, int(transformer_depth), int(context_dim), int(bool(use_linear_in_transformer))] if use_spatial_transformer else []
-        self._create(_lib.BLOCK_UNET, [in_channels, model_channels, out_channels, num_heads, num_head_channels, num_heads_upsample,
-                                       int(bool(use_scale_shift_norm)), int(bool(resblock_updown)), int(bool(use_new_attention_order)),
-                                       int(bool(legacy)), len(channel_mult)] + channel_mult + nrb + [len(ar)] + ar + st, device_index)
+        self._create(_lib.BLOCK_UNET, unet_iargs(in_channels, model_channels, out_channels, nrb, ar, channel_mult, num_heads,
+                                                 num_head_channels, num_heads_upsample, use_scale_shift_norm, resblock_updown,
+                                                 use_new_attention_order, legacy, use_spatial_transformer, transformer_depth,
+                                                 context_dim, use_linear_in_transformer), device_index)
         half = model_channels // 2
         freqs = torch.exp(-math.log(10000) * torch.arange(start=0, end=half, dtype=torch.float32) / half).contiguous()
         check(lib().dsd_set_timestep_freqs(self._h, C.c_void_p(freqs.data_ptr()), half))

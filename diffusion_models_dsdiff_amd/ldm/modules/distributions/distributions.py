@@ -44,6 +44,26 @@ class DiagonalGaussianDistribution(object):
         check(lib().dsd_op_gaussian_sample(dptr(p), dptr(noise), C.c_uint64(seed), B, E2 // 2, H, W, dptr(z), stream_ptr()))
         return z
 
+    @torch.no_grad()
+    def sample_scaled(self, scale, noise=None, seed=None):
+        """``scale * self.sample()`` in one kernel (dsd_op_posterior_sample_scaled): LatentDiffusion.get_first_stage_encoding
+        (ddpm.py:660-667), the sample formed first and then multiplied by the fp32 ``scale``."""
+        if self.deterministic:
+            return self.mean * float(scale)
+        p = self.parameters.float().contiguous()
+        if not p.is_cuda:
+            raise RuntimeError("DiagonalGaussianDistribution.sample runs on the MI355X only (no CPU fallback)")
+        B, E2, H, W = p.shape
+        z = torch.empty((B, E2 // 2, H, W), device=p.device, dtype=torch.float32)
+        if noise is not None:
+            noise = noise.to(p.device).float().contiguous()
+            assert noise.numel() == z.numel(), (tuple(noise.shape), tuple(z.shape))
+        if seed is None:
+            seed = _seed_from_torch()
+        check(lib().dsd_op_posterior_sample_scaled(dptr(p), dptr(noise), C.c_uint64(seed), B, E2 // 2, H, W, C.c_float(scale),
+                                                   dptr(z), stream_ptr()))
+        return z
+
     # The two closed forms the training loss uses (:39-58); plain torch on whatever device the moments live on.
     def kl(self, other=None):
         """KL(self || other) per sample, ``other`` = the standard normal when omitted."""

@@ -8,7 +8,8 @@ import importlib
 _PKG = __name__.split(".")[0]
 # reference dotted paths served natively
 _NATIVE_PREFIXES = ("UNet_DS_Diff.model", "ldm.util", "ldm.models.diffusion.ddpm", "ldm.models.diffusion.ddim",
-                    "Disc_diff.guided_diffusion", "trainers.trainer_ddpm")
+                    "Disc_diff.guided_diffusion", "trainers.trainer_ddpm", "ldm.modules.diffusionmodules.openaimodel",
+                    "ldm.models.autoencoder")
 
 
 def exists(x):

@@ -17,6 +17,12 @@
  *                                        Disc_diff/guided_diffusion/gaussian_diffusion.py:524-616,705-786
  *                                     DDPMModel.p_sample_loop        trainers/trainer_ddpm.py:447-482
  *                                     DDIMSampler.ddim_sampling      ldm/models/diffusion/ddim.py:128-261
+ *   dsd_sample_latent              <- DDIMSampler.ddim_sampling / LatentDiffusion.p_sample_loop on VAE latents
+ *                                        ldm/models/diffusion/ddim.py:128-261, ldm/models/diffusion/ddpm.py:1048-1115
+ *                                        (call sites trainers/trainer_latent_diffusion.py:492-544)
+ *   dsd_sample_dpm_latent          <- DPMSolverSampler.sample on VAE latents  ldm/models/diffusion/dpm_solver_new/sampler.py:35-103
+ *   dsd_op_posterior_sample_scaled <- LatentDiffusion.get_first_stage_encoding(encode_first_stage(x))
+ *                                        ldm/models/diffusion/ddpm.py:660-667 with distributions.py:24-37
  *   dsd_block_*                    <- ResBlock / AttentionBlock / Upsample / Downsample
  *                                        ldm/modules/diffusionmodules/openaimodel.py:93-164,167-284,426-473
  *                                     FeatureDisentangle             UNet_DS_Diff/model.py:152-168
@@ -230,6 +236,19 @@ int dsd_sample(dsd_handle* h, const dsd_schedule* sched, const float* cond, int 
 int dsd_op_sampler_update(const dsd_schedule* sched, int k, const float* model_out, float* x, const float* noise,
                           uint64_t philox_seed, int B, int H, int W, float* pred_xstart, void* stream);
 
+/* ---- latent sampling loops (DSD_BLOCK_UNET denoiser) -------------------------------------
+ * The loops of dsd_sample / dsd_sample_dpm on a multi-channel state: x [B,Cz,H,W] (VAE latents, in = x_T, out = sample, in
+ * place) denoised by a DSD_BLOCK_UNET handle (the plain UNetModel, no spatial transformer) with in_channels = Cz + Cc and
+ * out_channels = Cz (2 with a learned-range variance, which needs Cz = 1).  cond [B,Cc,H,W] is concatenated after the state
+ * (DiffusionWrapper 'concat', ldm/models/diffusion/ddpm.py:1331-1333): both are copied ONCE into the denoiser's persistent
+ * NCHW input, and every update writes x_{t-1} straight into its state channels.  Schedules, first_step / n_steps,
+ * dsd_set_slice_ids (Philox counter (seed, step, slice, channel, pixel)) and dsd_set_graph replay (one stream, no forks) work
+ * as for the four-stream model.  noise: NULL -> Philox, else [steps,B,Cz,H,W].
+ * Replaces DDIMSampler.sample / ddim_sampling (ldm/models/diffusion/ddim.py:57-261) and LatentDiffusion.p_sample_loop
+ * (ddpm.py:1048-1115) as trainers/trainer_latent_diffusion.py:492-544 calls them. */
+int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sched, const float* cond, int Cc, float* x, int Cz, const float* noise,
+                      uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
+
 /* ---- DPM-Solver(++) multistep sampler -----------------------------------------------------
  * Replaces DPM_Solver(...).sample(method="multistep", order<=2) of Disc_diff/guided_diffusion/sampler.py:1017-1222
  * (call site GaussianDiffusion.dpm_solver_sample_loop, gaussian_diffusion.py:467-522) and of its twin
@@ -258,6 +277,11 @@ typedef struct dsd_dpm_schedule {
  * contributes its first channel only (gaussian_diffusion.py:484-485). */
 int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int B, int H, int W,
                    void* stream);
+/* dsd_sample_dpm on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser (out_channels = Cz), set up as in
+ * dsd_sample_latent.  Dynamic thresholding takes the quantile per sample over all Cz*H*W elements (dynamic_thresholding_fn,
+ * ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:418).  Replaces DPMSolverSampler.sample (sampler.py:35-103). */
+int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int Cz, int B, int H,
+                          int W, void* stream);
 /* Iteration k's post-network part alone: model_out [B,Cm,H,W], x updated in place, m_cur [B,1,H,W] receives m_k,
  * m_prev = m_{k-1} (may be NULL when order[k] < 2). */
 int dsd_op_dpm_step(const dsd_dpm_schedule* sched, int k, const float* model_out, int Cm, float* x, float* m_cur,
@@ -396,6 +420,12 @@ int dsd_op_linear(const float* x, int N, int K, const float* w, const float* bia
  * -> z [B,E,H,W] = mean + exp(0.5*clamp(logvar,-30,20)) * eps; eps = noise [B,E,H,W] or on-device Philox normals. */
 int dsd_op_gaussian_sample(const float* moments, const float* noise_or_null, uint64_t philox_seed, int B, int E, int H, int W,
                            float* z, void* stream);
+/* scale * DiagonalGaussianDistribution(moments).sample(): LatentDiffusion.get_first_stage_encoding (ddpm.py:660-667), the sample
+ * formed first, then scaled.  moments [B,2E,H,W] -> z [B,E,H,W].  With the B rows ordered (sample, key) — K condition images
+ * per sample encoded in ONE pass of B = batch*K one-channel images (trainers/trainer_latent_diffusion.py:177-189) — z is the
+ * [batch,K*E,H,W] 'concat' conditioning, key k in channels [k*E,(k+1)*E). */
+int dsd_op_posterior_sample_scaled(const float* moments, const float* noise_or_null, uint64_t philox_seed, int B, int E, int H,
+                                   int W, float scale, float* z, void* stream);
 /* Philox4x32-10 + Box-Muller stream used by dsd_sample when noise == NULL: fills n normals. */
 int dsd_op_philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, void* stream);
 

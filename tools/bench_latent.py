@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""The latent trainer's inference (trainers/trainer_latent_diffusion.py:153-189,492-544) on one GPU with synthetic weights:
+batch 16 of 256^2 one-channel slices, the SD-v1 f = 8 first stage (32x32x4 latents), K condition keys encoded in one pass,
+50-step DDIM (eta 0) on a UNetModel with the unet_config of the reference's v2-1-cddpm-disc yaml (in_channels 4*(K+1)), decode.
+Three loops for the same steps, alternated in one process: the device loop (dsd_sample_latent) with graph replay off, with
+replay on, and the per-step Python loop (network call + dsd_op_sampler_update, the closure path).  hipEvents, median / min / max
+of --repeats runs.  Prints one JSON line.
+
+    python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--json out.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SD_VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=1, out_ch=1, ch=128, ch_mult=[1, 2, 4, 4], num_res_blocks=2,
+              attn_resolutions=[], dropout=0.0)
+UNET = dict(image_size=32, model_channels=96, out_channels=4, num_res_blocks=2, attention_resolutions=[32, 16, 8],
+            channel_mult=[1, 1, 2, 2, 3, 3], num_head_channels=48, use_new_attention_order=True, legacy=False)
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return out, a.elapsed_time(b)
+
+
+def stats(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def run_k(K, args):
+    from diffusion_models_dsdiff_amd import _lib
+    from diffusion_models_dsdiff_amd._sched import run_device_loop, sampler_update
+    from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
+    from oracle.synth import synth_params, randn
+    dd = dict(SD_VAE)
+    up = dict(UNET, in_channels=4 * (K + 1))
+    ld = LatentDiffusion(first_stage_config=AutoencoderKL(dd, None, 4), conditioning_key="concat", scale_factor=0.18215,
+                         timesteps=1000, parameterization="v",
+                         unet_config={"target": "ldm.modules.diffusionmodules.openaimodel.UNetModel", "params": up})
+    ld.load_state_dict(synth_params([(k, tuple(v.shape)) for k, v in ld.state_dict().items() if "." in k], 700 + K), strict=False)
+    ld = ld.cuda()
+    unet = ld.model.diffusion_model
+    B, h = args.batch, args.size // 8
+    cond = randn((B, K, args.size, args.size), 710).cuda()
+    xT = randn((B, 4, h, h), 711).cuda()
+    smp = DDIMSampler(ld)
+    smp.make_schedule(args.steps, ddim_eta=0.0, verbose=False)
+    sched = smp._schedule(False, True)
+    L = _lib.lib()
+
+    def device(graph):
+        _lib.check(L.dsd_set_graph(unet._h, int(graph)))
+        try:
+            return run_device_loop(unet, sched, xT, c, seed=1)
+        finally:
+            _lib.check(L.dsd_set_graph(unet._h, 0))
+
+    def host():
+        x = xT.clone()
+        cc = c.contiguous()
+        for k in range(sched.steps):
+            out = unet(torch.cat([x, cc], 1), torch.full((B,), float(sched.t_model[k]), device="cuda"))
+            sampler_update(sched, k, out, x, None, seed=1)
+        return x
+
+    c = ld.encode_conditions(cond, seed=3)["c_concat"][0]          # warm-up: plans, code objects
+    y = device(False)
+    device(True)
+    device(True)
+    host()
+    ld.decode_first_stage(y)
+    torch.cuda.synchronize()
+    t = {"encode_ms": [], "device_loop_ms": [], "device_loop_graph_ms": [], "python_loop_ms": [], "decode_ms": []}
+    outs = {}
+    for _ in range(args.repeats):
+        c, ms = timed(lambda: ld.encode_conditions(cond, seed=3)["c_concat"][0])
+        t["encode_ms"].append(ms)
+        outs["dev"], ms = timed(lambda: device(False))
+        t["device_loop_ms"].append(ms)
+        outs["graph"], ms = timed(lambda: device(True))
+        t["device_loop_graph_ms"].append(ms)
+        outs["host"], ms = timed(host)
+        t["python_loop_ms"].append(ms)
+        _, ms = timed(lambda: ld.decode_first_stage(outs["dev"]))
+        t["decode_ms"].append(ms)
+    res = {k: stats(v) for k, v in t.items()}
+    for k in ("device_loop", "device_loop_graph", "python_loop"):
+        res[k + "_ms_per_step"] = res[k + "_ms"]["median"] / sched.steps
+    e2e = res["encode_ms"]["median"] + res["device_loop_ms"]["median"] + res["decode_ms"]["median"]
+    res["end_to_end_ms"] = e2e
+    res["slices_per_s"] = B / (e2e / 1000.)
+    res["graph_bit_identical"] = bool(torch.equal(outs["dev"], outs["graph"]))
+    res["python_loop_bit_identical"] = bool(torch.equal(outs["dev"], outs["host"]))
+    res["unet_config"] = up
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--keys", default="1,3")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    from diffusion_models_dsdiff_amd import _lib
+    name, ncu, _ = _lib.require_gpu(0)
+    out = {"bench": "latent_inference", "gpu": name, "batch": args.batch, "size": args.size, "latent": [4, args.size // 8, args.size // 8],
+           "first_stage": dict(SD_VAE, embed_dim=4), "scale_factor": 0.18215, "sampler": f"DDIM eta 0, {args.steps} steps",
+           "repeats": args.repeats, "keys": {}}
+    for K in [int(v) for v in args.keys.split(",")]:
+        out["keys"][str(K)] = run_k(K, args)
+    line = json.dumps(out)
+    print(line)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
