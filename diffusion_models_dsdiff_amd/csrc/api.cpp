@@ -641,6 +641,23 @@ int dsd_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w_o
     DSD_CATCH
 }
 
+int dsd_subpixel_weights_host(const float* w_oihw, int Cout, int Cin, double* out) {
+    DSD_TRY
+    DSD_CHECK(w_oihw && out && Cout > 0 && Cin > 0, "bad argument");
+    for (int ph = 0; ph < 4; ++ph)
+        for (int co = 0; co < Cout; ++co)
+            for (int t = 0; t < 4; ++t)
+                for (int ci = 0; ci < Cin; ++ci) {
+                    double acc = 0.0;
+                    for (int kh = 0; kh < 3; ++kh)
+                        for (int kw = 0; kw < 3; ++kw)
+                            if (subpixel_tap(ph >> 1, kh) == (t >> 1) && subpixel_tap(ph & 1, kw) == (t & 1))
+                                acc += (double)w_oihw[(((size_t)co * Cin + ci) * 3 + kh) * 3 + kw];
+                    out[(((size_t)ph * Cout + co) * 4 + t) * Cin + ci] = acc;
+                }
+    DSD_CATCH
+}
+
 int dsd_set_conv_mfma16(int on) {
     const int prev = conv2d_get_mfma16();
     conv2d_set_mfma16(on);
@@ -816,6 +833,13 @@ int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float
                                            "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
         wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
         a.w_wino = wpk.p;
+    }
+    // an upsample layer the planner runs in the sub-pixel form: phase weights built for this call
+    const bool sub = conv2d_subpixel_ok(a);
+    Tmp wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0);
+    if (sub) {
+        subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
+        a.w_subpixel = wsub.p;
     }
     Tmp scratch(conv2d_scratch_bytes(a));
     a.scratch = scratch.as<float>();

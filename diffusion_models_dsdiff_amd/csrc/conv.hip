@@ -600,6 +600,10 @@ double conv2d_flops(const ConvArgs& a) {
     return 2.0 * a.N * OH * OW * (double)a.Cout * a.ks * a.ks * a.Cin;
 }
 
+// what the launched kernel multiplies: the sub-pixel form does 4 of the 9 taps per output pixel (conv2d_flops stays the
+// layer's algorithmic 3x3-over-the-upsampled-map count)
+double conv2d_exec_flops(const ConvArgs& a) { return a.w_subpixel ? conv2d_flops(a) * 4.0 / 9.0 : conv2d_flops(a); }
+
 // kernel variant: 0 = default (buffer-load kernel when eligible), 1 = force the flat-load kernel.
 // ConvArgs.variant >= 0 wins, else env DSD_CONV_VARIANT, else 0.
 static int conv_variant(const ConvArgs& a) {
@@ -648,6 +652,7 @@ static int effective_precision(const ConvArgs& a, int tiles_m) {
 }
 
 size_t conv2d_scratch_bytes(const ConvArgs& a) {
+    if (a.w_subpixel) return 0;
     if (a.precision == PREC_F32 || a.Cin % 32 != 0 || a.Cin % 4 != 0) return 0;
     if (conv2d_wino_eligible(a)) return 0;
     int OH, OW;
@@ -683,6 +688,7 @@ int conv2d_stats_chunks(const ConvArgs& a) {
         return ppb ? OH * OW / ppb : 0;
     }
     if (a.out_nchw) return 0;
+    if (a.w_subpixel) return conv2d_subpixel_shape_ok(a) ? 4 * a.H * a.W / (2 * BM) : 0;   // (phase, 256-pixel chunk)
     if (conv2d_wino_eligible(a)) return conv2d_wino_stats_chunks(a);
     int OH, OW;
     conv_out_hw(a, &OH, &OW);
@@ -705,6 +711,7 @@ int conv2d_stats_chunks(const ConvArgs& a) {
 }
 
 bool conv2d_fuses_gn(const ConvArgs& a) {
+    if (a.w_subpixel) return false;
     if (a.Cin % 4 != 0 || a.ks * a.ks * a.Cin < 32 || a.precision != PREC_BF16X6 || a.w_split == nullptr) return false;
     static const bool off = getenv("DSD_NO_GN_FUSE") != nullptr;   // A/B
     if (off || conv2d_wino_eligible(a)) return false;
@@ -735,6 +742,7 @@ const char* conv2d_variant(const ConvArgs& a) {
         if (a.Cout % 4 == 0 && a.Cout / 4 <= 256 && Ktot <= 9 && !a.out_nchw && (!a.emb || a.emb_stride % 4 == 0)) return "conv_direct_cols";
         return (a.Cout % 4 == 0 && (size_t)Ktot * a.Cout * 4 <= DIRECT_LDS_MAX) ? "conv_direct_lds" : "conv_scalar";
     }
+    if (a.w_subpixel) return "conv_bf16x6<5>/tr+subpixel";   // (conv2d_subpixel: one kernel, one tile width)
     int OH, OW;
     conv_out_hw(a, &OH, &OW);
     static const char* names[4][6] = {{"", "conv_mfma<1>", "conv_mfma<2>", "conv_mfma<3>", "conv_mfma<4>", "conv_mfma<5>"},
@@ -767,6 +775,10 @@ void conv2d(ConvArgs a, hipStream_t s) {
     DSD_CHECK(a.ks == 1 || a.ks == 3, "conv2d: kernel size %d unsupported", a.ks);
     DSD_CHECK(a.gn_scale == nullptr || conv2d_fuses_gn(a), "conv2d: GroupNorm coefficients given, but this problem does not run on the kernel that applies them");
     DSD_CHECK(a.stride == 1 || a.stride == 2, "conv2d: stride %d unsupported", a.stride);
+    if (a.w_subpixel) {   // the caller built the phase weights because conv2d_subpixel_ok() chose this form
+        if ((int64_t)a.N * a.H * a.W > 0 && a.Cout > 0) conv2d_subpixel(a, s);
+        return;
+    }
     ConvP p{};
     p.x = a.x; p.w = a.w; p.bias = a.bias; p.emb = a.emb; p.res = a.res; p.y = a.y;
     p.N = a.N; p.H = a.H; p.W = a.W; p.Cin = a.Cin; p.Cout = a.Cout; p.ks = a.ks; p.stride = a.stride;

@@ -95,6 +95,39 @@ void split_weights(const float* w, int64_t n, int np, void* planes, hipStream_t 
     check_launch("split_weights");
 }
 
+// Sub-pixel weights of conv3x3(nearest_x2(x)): w (fp32 packed OHWI [Cout][3][3][Cin]) -> planes[3][4 phases][Cout][2][2][Cin]
+// bf16.  Phase tap (a, b) of phase (py, px) is the fp64 sum of the original taps (kh, kw) with subpixel_tap(py, kh) == a and
+// subpixel_tap(px, kw) == b (1, 2 or 4 of them), written as three bf16 pieces with split_weights' semantics (the residual is
+// carried in fp64, so what is left is at most 2^-24 of the sum).
+__global__ void subpixel_weights_kernel(const float* __restrict__ w, int Cout, int Cin, unsigned short* __restrict__ planes) {
+    const int64_t n = (int64_t)16 * Cout * Cin;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int ci = (int)(e % Cin);
+        const int64_t r = e / Cin;
+        const int t = (int)(r & 3), co = (int)((r >> 2) % Cout), ph = (int)(r / (4 * (int64_t)Cout));
+        const int py = ph >> 1, px = ph & 1, ta = t >> 1, tb = t & 1;
+        double acc = 0.0;
+        for (int kh = 0; kh < 3; ++kh)
+            for (int kw = 0; kw < 3; ++kw)
+                if (subpixel_tap(py, kh) == ta && subpixel_tap(px, kw) == tb) acc += (double)w[((int64_t)co * 9 + kh * 3 + kw) * Cin + ci];
+        for (int q = 0; q < 3; ++q) {
+            const __bf16 b = (__bf16)(float)acc;
+            planes[(int64_t)q * n + e] = __builtin_bit_cast(unsigned short, b);
+            acc -= (double)(float)b;
+        }
+    }
+}
+
+size_t subpixel_weight_bytes(int Cout, int Cin) { return (size_t)16 * Cout * Cin * 2 * 3; }
+
+void subpixel_weights(const float* w_ohwi, int Cout, int Cin, void* planes, hipStream_t s) {
+    const int64_t n = (int64_t)16 * Cout * Cin;
+    if (!n) return;
+    hipLaunchKernelGGL(subpixel_weights_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, s, w_ohwi,
+                       Cout, Cin, (unsigned short*)planes);
+    check_launch("subpixel_weights");
+}
+
 bool conv2d_split_eligible(const ConvArgs& a) {
     if (a.Cin % SBK != 0 || a.w_split == nullptr) return false;
     const int64_t x_bs = a.x_bs >= 0 ? a.x_bs : (int64_t)a.H * a.W * a.Cin;
@@ -138,6 +171,51 @@ static bool conv_tr_ok(const SplitP& p) {
     return tr_enabled() && !p.stamps && tr_shape_ok(p.ks, p.stride, p.pad, p.OW, p.IWg, p.OH, p.IHg, p.ksplit, p.out_nchw, p.ohw, p.M, p.Cin);
 }
 // would conv2d_split(a, nt, ksplit, ad) run the tap-reuse instantiation?  (conv2d_variant: its launches are a kind of their own)
+// the planner's rule for the sub-pixel form (conv2d_subpixel_ok): the tap-reuse kernel on the low-resolution map
+bool conv2d_subpixel_shape_ok(const ConvArgs& a) {
+    if (!(tr_enabled() && !a.stamps && a.ks == 3 && a.stride == 1 && a.ups && a.pad_lo < 0 && a.pad_total < 0 && !a.out_nchw &&
+          a.gn_scale == nullptr && a.Cin % SBK == 0 && a.Cout % (5 * 32) == 0))
+        return false;
+    const int64_t x_bs = a.x_bs >= 0 ? a.x_bs : (int64_t)a.H * a.W * a.Cin;
+    const int64_t xb = ((int64_t)(a.N - 1) * x_bs + (int64_t)a.H * a.W * a.Cin) * 4;
+    return tr_shape_ok(3, 1, 1, a.W, a.W, a.H, a.H, 1, 0, a.H * a.W, (int64_t)a.N * a.H * a.W, a.Cin) && xb < 0xFFFFFF00ll &&
+           (int64_t)subpixel_weight_bytes(a.Cout, a.Cin) < 0xFFFFFF00ll;
+}
+bool conv2d_subpixel_ok(const ConvArgs& a) {
+    static const bool off = getenv("DSD_NO_SUBPIXEL") != nullptr;   // A/B: the folded gather for every upsample layer
+    return !off && a.precision == PREC_BF16X6 && a.variant < 0 && !mfma16_enabled() && a.w_wino == nullptr && conv2d_subpixel_shape_ok(a);
+}
+
+void conv2d_subpixel(const ConvArgs& a, hipStream_t s) {
+    DSD_CHECK(a.w_subpixel && conv2d_subpixel_shape_ok(a), "conv2d: sub-pixel weights given for a problem the sub-pixel kernel does not take");
+    SplitP p{};
+    p.x = a.x; p.w = a.w_subpixel; p.bias = a.bias; p.emb = a.emb; p.res = a.res; p.y = a.y;
+    p.N = a.N; p.H = a.H; p.W = a.W; p.Cin = a.Cin; p.Cout = 4 * a.Cout; p.sub_cout = a.Cout; p.ks = 2; p.stride = 1; p.pad = 1;
+    p.ups = 0; p.emb_stride = a.emb_stride; p.out_nchw = 0;
+    p.y_ld = a.y_ld > 0 ? a.y_ld : a.Cout;
+    p.x_bs = a.x_bs >= 0 ? a.x_bs : (int64_t)a.H * a.W * a.Cin;
+    p.IHg = p.OH = a.H;
+    p.IWg = p.OW = a.W;
+    p.ohw = a.H * a.W;
+    p.M = a.N * p.ohw;
+    p.Ktot = 4 * a.Cin;
+    p.cchunks = a.Cin / SBK;
+    p.tiles_m = p.M / (2 * SBM);
+    p.tiles_n = p.Cout / (5 * 32);
+    p.x_bytes = (unsigned)(((int64_t)(a.N - 1) * p.x_bs + (int64_t)a.H * a.W * a.Cin) * 4);
+    p.w_plane_bytes = (unsigned)((int64_t)p.Cout * p.Ktot * 2);
+    p.w_bytes = p.w_plane_bytes * 3u;
+    p.ksplit = 1;
+    if (a.stats) {
+        DSD_CHECK(a.stats_chunks == 4 * p.ohw / (2 * SBM), "conv2d: sub-pixel statistics come in %d chunks per sample, not %d",
+                  4 * p.ohw / (2 * SBM), a.stats_chunks);
+        p.stats = a.stats;
+        p.stats_chunks = a.stats_chunks;
+    }
+    hipLaunchKernelGGL((conv_split_subpixel_kernel<5>), dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(256), 0, s, p);
+    check_launch("conv_split_subpixel");
+}
+
 bool conv2d_split_tr(const ConvArgs& a, int nt, int ksplit, int ad) {
     if (!(tr_enabled() && !a.stamps && a.precision == PREC_BF16X6 && ad == 2 && tr_nt_ok(nt))) return false;
     int OH, OW;

@@ -44,6 +44,7 @@ struct SplitP {
     int diag;            // what-if bits of the diagnostic instantiation
     const float* gn_scale;   // GN instantiation: GroupNorm coefficients of the input, [N][Cin] each
     const float* gn_shift;
+    int sub_cout;   // sub-pixel instantiation: output channels; Cout is then 4 x sub_cout, the GEMM columns (phase, channel)
 };
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -249,6 +250,43 @@ __device__ __forceinline__ void stats_reduce(const SplitP& p, const double (&cs)
         double* o = p.stats + (((int64_t)nb * p.stats_chunks + chunk) * p.Cout + n) * 2;
         o[0] = s;
         o[1] = q;
+    }
+}
+
+// Sub-pixel epilogue: GEMM row m = low-resolution pixel (i, j) of sample nb, column tile = channels [c0, c0 + 32 NT) of phase
+// (py, px) -> output pixel (2i + py, 2j + px) of the 2H x 2W map.  Every tile is interior (whole image rows of one sample,
+// Cout a multiple of the tile width); bias, embedding and residual are added in the order of split_epilogue.
+template <int NT, bool STATS>
+__device__ __forceinline__ void subpixel_epilogue(const SplitP& p, const f32x16 (&acc)[NT], int m0, int c0, int wave, int lrow,
+                                                  int half, int py, int px, StatAcc<NT>& st, bool first_block) {
+    const int C = p.sub_cout;
+    const int lw = __builtin_ctz((unsigned)p.OW);   // (the tap-reuse widths are powers of two)
+    const int nb = m0 / p.ohw;
+    float bj[NT], ev[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        bj[j] = p.bias ? p.bias[c0 + j * 32 + lrow] : 0.f;
+        ev[j] = p.emb ? p.emb[(int64_t)nb * p.emb_stride + c0 + j * 32 + lrow] : 0.f;
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int rb = m0 - nb * p.ohw + wave * 32 + 8 * g + 4 * half;   // pixel inside the sample
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int r = rb + rr, i = r >> lw, jx = r & (p.OW - 1);
+            const int64_t o = (int64_t)nb * 4 * p.ohw + (int64_t)(2 * i + py) * (2 * p.OW) + 2 * jx + px;
+            if (STATS && g == 3 && rr == 3) st.rows += 16;
+            float* yp = p.y + o * p.y_ld + c0 + lrow;
+            const float* rp = p.res ? p.res + o * C + c0 + lrow : nullptr;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                float v = acc[j][4 * g + rr] + bj[j];
+                if (p.emb) v += ev[j];
+                if (p.res) v += rp[j * 32];
+                yp[j * 32] = v;
+                if (STATS) st.add(j, v, first_block && g == 0 && rr == 0);
+            }
+        }
     }
 }
 
@@ -507,8 +545,13 @@ static __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsig
 // operands, half the VALU work per tile; needs the weight stages in the unpadded swizzled layout to fit 158 KB): correct, but
 // 402.4 vs 396.7 ms per step same-box (+1.4 %: 12 instead of 8 fragment reads per tile and 64-bit LDS writes cost more than
 // the VALU saved); and pinning "one MFMA, five VALU" with sched_group_barrier in the units that activate a chunk: no change.
-template <int NT, int NP, bool F16, int RB, bool DMA = false, int DIAG = 0, bool TR = false, bool GN = false>
-__global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(SplitP p) {
+// SUB (with TR): conv3x3(nearest_x2(x)) as four 2x2 convolutions on the low-resolution map, one per output phase (py, px)
+// (conv2d_subpixel_ok, conv.hip).  The problem is the low-resolution one with ks = 2 and Cout = 4 x the output channels;
+// a column tile belongs to one phase, whose filter rows are input rows i + py - 1 + {0, 1} and whose taps are the one-pixel
+// shifts px - 1 + {0, 1}.  Two tiles per filter row instead of three: the next row is written to LDS during the first of
+// them (the second one fetches its pieces) and the row after it loaded during the second; the loop is unrolled by two.
+template <int NT, int NP, bool F16, int RB, bool DMA, int DIAG, bool TR, bool GN, bool SUB>
+__device__ __forceinline__ void conv_split_ad_body(SplitP p) {   // (by value: the kernels built before it keep their code)
     constexpr bool STAMP = DIAG > 0;
     constexpr int WI = DIAG > 0 ? DIAG - 1 : 0;
     // vector-memory loads issued one at a time, each right after the register it refills has been consumed, instead of in
@@ -572,6 +615,9 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
     const int tile_m = L / p.tiles_n;
     const int m0 = tile_m * (SBM * RB);
     const int n0 = tile_n * BROWS;
+    static_assert(!SUB || (TR && !GN), "the sub-pixel form is built on the tap-reuse staging path");
+    const int sph = SUB ? n0 / p.sub_cout : 0;   // (sub-pixel) phase of this column tile: py = sph >> 1, px = sph & 1
+    const int sp_y = sph >> 1, sp_x = sph & 1;
 
     // ---- A: this lane's RB output pixels (rows of the implicit GEMM) and its 8-float slot inside a 16-k step
     int a_h[RB], a_w[RB];
@@ -639,6 +685,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
         for (int r = 0; r < RB; ++r) {
             a_lm[r] = (wave * RB + r) * 32 + lrow;
             a_ow[r] = a_lm[r] % p.OW;
+            if (SUB) {   // the phase's column offset, folded into the tap shift of lds_piece
+                a_lm[r] += sp_x;
+                a_ow[r] += sp_x;
+            }
         }
         const int nb = m0 / p.ohw;
         const int oh0 = (m0 - nb * p.ohw) / p.OW;
@@ -648,11 +698,13 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
             const int px = q >> 3;
             const int lc = (q & 7) ^ ((px >> 1) & 7);
             const int sg = px / p.OW, col = px - sg * p.OW;
-            g_oh[i] = oh0 + sg - 1;
+            g_oh[i] = oh0 + sg - 1 + sp_y;   // (sub-pixel: filter row h2 is input row i + py - 1 + h2)
             g_off[i] = ((unsigned)nb * (unsigned)p.x_bs + (unsigned)(col >> p.ups) * (unsigned)p.Cin) * 4u + (unsigned)(lc * 16);
         }
     }
     u32x4 stg[8];           // (tap reuse) the next filter row on its way global -> LDS
+    // LDS stage of filter row (c2, h2): rows alternate between the two stages (two rows per chunk in the sub-pixel form)
+    auto stage_of = [](int c2, int h2) { return SUB ? (h2 & 1) : ((c2 + h2) & 1); };
     f32x4 gsc = {0.f, 0.f, 0.f, 0.f}, gsh = {0.f, 0.f, 0.f, 0.f};   // (GN) scale / shift of this thread's four channels of the chunk on its way
     const int g_lc = (tid & 7) ^ ((tid >> 4) & 7);                  // = the lc of every slot of this thread (i * 32 pixels: (px >> 1) & 7 does not depend on i)
     const int g_nb = TR ? m0 / p.ohw : 0;
@@ -684,7 +736,7 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
             }
             w = __builtin_bit_cast(u32x4, o);
         }
-        *reinterpret_cast<u32x4*>(Bs + A_OFF + ((c2 + h2) & 1) * A_STAGE + (i * 256 + tid) * 16) = w;
+        *reinterpret_cast<u32x4*>(Bs + A_OFF + stage_of(c2, h2) * A_STAGE + (i * 256 + tid) * 16) = w;
     };
     f32x4 ra[RB][4];   // [row block][k-step lo/hi 4 floats]
     u32x4 rb[NBL];
@@ -817,6 +869,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
         if (tid < 16) *reinterpret_cast<u32x4*>(Bs + A_OFF + (tid >> 3) * A_STAGE + 256 * 128 + (tid & 7) * 16) = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int i = 0; i < 8; ++i) store_row(i, 0, 0);
+        if (SUB) {   // filter row (0, 1): written to LDS during the first tile
+#pragma unroll
+            for (int i = 0; i < 8; ++i) load_row(i, 0, 1);
+        }
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < RB; ++r)
@@ -849,6 +905,7 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
     // One k-tile.  KWC: the tap column of the tile as a compile-time constant in the tap-reuse instantiation, whose loop is
     // unrolled by three so that "first / second tile of a filter row" costs no branch (a branch inside the MFMA stream lets the
     // compiler sink the split work of a whole tile into its last block: measured 5564 cycles per k-tile); -1 otherwise.
+    constexpr int KW_LAST = SUB ? 1 : 2, KH_LAST = SUB ? 1 : 2;   // (tap reuse) last tap of a filter row, last row of a chunk
     auto tile = [&](auto KWC, const int kt) __attribute__((always_inline)) {
         constexpr int kw_cur = TR ? decltype(KWC)::value : 0;
         const int so = (kt & 1) * STAGE;
@@ -871,10 +928,15 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
             }
             __builtin_amdgcn_sched_barrier(0);
             if (TR) {   // the NEXT filter row: loaded during the first tile of this one, written to LDS during the second
-                const bool wrap = kh_cur == 2;
+                const bool wrap = kh_cur == KH_LAST;
                 const int c2 = wrap ? cc_cur + 1 : cc_cur, h2 = wrap ? 0 : kh_cur + 1;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
+                    if (SUB) {   // (two tiles per filter row: see SUB above)
+                        if (s == 0 && i * NT / 8 == j && kw_cur == 0) store_row(i, c2, h2);
+                        if (s == 1 && i * NT / 8 == j && kw_cur == 1) load_row(i, cc_cur + 1, kh_cur);
+                        continue;
+                    }
                     if (s == 1 && i * NT / 8 == j && kw_cur == 0) {
                         if (i == 0) load_coef(c2);   // (stored rows of the previous filter row are all in LDS by now: second tile)
                         load_row(i, c2, h2);
@@ -901,8 +963,8 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
                 if (u >= 1 && u <= 8) split_piece(u - 1);
                 if (u <= 7) {
                     const int t = u, r = (t & 3) >> 1, i = (t < 4 ? 2 : 0) + (t & 1);
-                    const int kw_n = kw_cur == 2 ? 0 : kw_cur + 1;
-                    const int par_n = kw_cur == 2 ? (c2 + h2) & 1 : (cc_cur + kh_cur) & 1;
+                    const int kw_n = kw_cur == KW_LAST ? 0 : kw_cur + 1;
+                    const int par_n = kw_cur == KW_LAST ? stage_of(c2, h2) : stage_of(cc_cur, kh_cur);
                     a_nx[0] = lds_piece(r, i, par_n, kw_n);
                 }
                 // the 128-column tile has 8 units for the 8 pieces: the last one is split in the unit that fetched it
@@ -976,13 +1038,18 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
         for (int r = 0; r < RB; ++r)
 #pragma unroll
             for (int q = 0; q < NP; ++q) af[1][r][q] = afn1[r][q];
-        if (TR && kw_cur == 2) {   // last tap of a filter row -> the next filter row (scalar selects)
-            const bool wh = kh_cur == 2;
+        if (TR && kw_cur == KW_LAST) {   // last tap of a filter row -> the next filter row (scalar selects)
+            const bool wh = kh_cur == KH_LAST;
             kh_cur = wh ? 0 : kh_cur + 1;
             cc_cur += wh ? 1 : 0;
         }
     };
-    if (TR) {   // (K unsplit and 3 x 3: the tile count is a multiple of three and the first tile has kw = 0)
+    if (SUB) {   // (K unsplit and 2 x 2: the tile count is even and the first tile has kw = 0)
+        for (int kt = 0; kt < KT; kt += 2) {
+            tile(std::integral_constant<int, 0>{}, kt);
+            tile(std::integral_constant<int, 1>{}, kt + 1);
+        }
+    } else if (TR) {   // (K unsplit and 3 x 3: the tile count is a multiple of three and the first tile has kw = 0)
         for (int kt = 0; kt < KT; kt += 3) {
             tile(std::integral_constant<int, 0>{}, kt);
             tile(std::integral_constant<int, 1>{}, kt + 1);
@@ -992,6 +1059,27 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
         for (int kt = 0; kt < KT; ++kt) tile(std::integral_constant<int, -1>{}, kt);
     }
     stamp(2);
+    if (SUB) {   // statistics: chunk = phase x (ohw / tile rows) + the tile's chunk inside its phase (4x the plain chunk count)
+        const int c0 = n0 - sph * p.sub_cout;
+        StatAcc<NT> st;
+        st.clear();
+        if (p.stats) {
+#pragma unroll
+            for (int r = 0; r < RB; ++r) subpixel_epilogue<NT, true>(p, acc[r], m0, c0, wave * RB + r, lrow, half, sp_y, sp_x, st, r == 0);
+            double ds[NT], dq[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) ds[j] = dq[j] = 0.0;
+            st.flush(ds, dq);
+            SplitP q = p;
+            q.Cout = p.sub_cout;
+            q.stats = p.stats + (int64_t)sph * (p.ohw / (SBM * RB)) * p.sub_cout * 2;
+            stats_reduce<NT>(q, ds, dq, Bs, m0, c0, SBM * RB, tid, wave, lrow, half);
+        } else {
+#pragma unroll
+            for (int r = 0; r < RB; ++r) subpixel_epilogue<NT, false>(p, acc[r], m0, c0, wave * RB + r, lrow, half, sp_y, sp_x, st, r == 0);
+        }
+        return;
+    }
     if (p.ksplit > 1) {   // raw partial sums; bias / embedding / residual are added once, by the reduction
         SplitP q = p;
         q.y = p.partial + (int64_t)chunk * p.M * p.Cout;
@@ -1025,6 +1113,17 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(Spl
     for (int r = 0; r < RB; ++r) split_epilogue<NT>(p, acc[r], m0, n0, wave * RB + r, lrow, half, SBM * RB);
     if (STAMP) wait_all();
     stamp(3);
+}
+
+template <int NT, int NP, bool F16, int RB, bool DMA = false, int DIAG = 0, bool TR = false, bool GN = false>
+__global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void conv_split_ad_kernel(SplitP p) {
+    conv_split_ad_body<NT, NP, F16, RB, DMA, DIAG, TR, GN, false>(p);
+}
+
+// the sub-pixel form of a nearest-x2 upsample + 3x3 convolution (SUB above): bf16x6, tap reuse, 256-row tile
+template <int NT>
+__global__ __launch_bounds__(256, 1) void conv_split_subpixel_kernel(SplitP p) {
+    conv_split_ad_body<NT, 3, false, 2, false, 0, true, false, true>(p);
 }
 
 // the diagnostic instantiations (conv_split_diag.hip): launch the one p.diag names, fail on any other value

@@ -27,6 +27,9 @@ struct ConvArgs {
     int precision = 0;          // PREC_F32 | PREC_BF16X3 | PREC_BF16X6 (conv_split.hip)
     const void* w_split = nullptr;  // [3][Cout][ks*ks*Cin] bf16 pieces of w (needed for the split precisions)
     const void* w_wino = nullptr;   // transformed + split + packed weights of the F(2,3) kernel (conv_wino.hip), optional
+    // sub-pixel form of an upsample layer (conv2d_subpixel_ok): [3][4 phases][Cout][2][2][Cin] bf16 pieces of the phase weights
+    // (subpixel_weights); when present, conv2d() runs the layer as four 2x2 convolutions on the low-resolution map
+    const void* w_subpixel = nullptr;
     int* ovf = nullptr;             // device flag set by the f16x3 kernels when an operand exceeds the fp16 range
     float* scratch = nullptr;       // split-K partial sums (conv2d_scratch_bytes() bytes); without it small grids run unsplit
     size_t scratch_bytes = 0;
@@ -79,12 +82,22 @@ void conv2d(ConvArgs a, hipStream_t s);
 void split_weights(const float* w, int64_t n, int np, void* planes, hipStream_t s, bool f16 = false, int* ovf = nullptr);
 bool conv2d_split_eligible(const ConvArgs& a);
 bool conv2d_split_tr(const ConvArgs& a, int nt, int ksplit, int ad);   // the tap-reuse instantiation would take it
+// Sub-pixel upsample convolution (conv_split.hip): output pixel (2i + py, 2j + px) of conv3x3(nearest_x2(x)) reads input rows
+// i + py - 1 + {0, 1} and columns j + px - 1 + {0, 1}; original filter row (column) k of phase p lands on phase tap
+// subpixel_tap(p, k) (p = 0: k = 0 -> 0, k = 1, 2 -> 1;  p = 1: k = 0, 1 -> 0, k = 2 -> 1).  The zero padding maps exactly.
+__host__ __device__ inline int subpixel_tap(int p, int k) { return (p + k + 1) / 2 - p; }
+bool conv2d_subpixel_shape_ok(const ConvArgs& a);   // the sub-pixel kernel can take this problem
+bool conv2d_subpixel_ok(const ConvArgs& a);         // the planner runs it that way (bf16x6, no structure forced): build w_subpixel
+size_t subpixel_weight_bytes(int Cout, int Cin);
+void subpixel_weights(const float* w_ohwi, int Cout, int Cin, void* planes, hipStream_t s);
+void conv2d_subpixel(const ConvArgs& a, hipStream_t s);
 // process-wide switch of the tap-reuse kernel's MFMA shape (0: 32x32x16, 1: 16x16x32 — conv_tr16.hip); A/B runs in one process
 void conv2d_set_mfma16(int on);
 int conv2d_get_mfma16();
 bool conv2d_fuses_gn(const ConvArgs& a);   // conv2d(a) can apply GroupNorm + SiLU to its input itself (a.gn_scale / a.gn_shift)
 void conv2d_split(const ConvArgs& a, int nt, int ksplit, int structure, hipStream_t s);
-double conv2d_flops(const ConvArgs& a);
+double conv2d_flops(const ConvArgs& a);        // the layer's algorithmic count (3x3 over the upsampled map for an upsample layer)
+double conv2d_exec_flops(const ConvArgs& a);   // what the launched kernel multiplies (4/9 of that in the sub-pixel form)
 size_t conv2d_scratch_bytes(const ConvArgs& a);   // workspace conv2d() can use for these arguments (0 = none)
 // N-tile width (in 32-column units) and split-K factor the split-precision path runs this problem with; nt_default is the
 // width the generic cost model (conv.hip pick_nt) would take

@@ -582,7 +582,7 @@ void dsd::net_set_param(dsd_handle* h, const char* name, const float* src, const
         h->any_param_upload = true;
     }
     const std::string conv_name = p.name.size() > 7 ? p.name.substr(0, p.name.size() - 7) : p.name;   // "<conv>.weight" -> "<conv>"
-    for (const std::string& key : {conv_name, conv_name + "#f16", conv_name + "#wino", p.name + "#h16", p.name + "#b16"}) {
+    for (const std::string& key : {conv_name, conv_name + "#f16", conv_name + "#wino", conv_name + "#sub", p.name + "#h16", p.name + "#b16"}) {
         auto sp = h->wsplit.find(key);
         if (sp != h->wsplit.end()) {
             DSD_HIP(hipDeviceSynchronize());
@@ -843,7 +843,26 @@ struct Builder {
         const int y_ld = dst ? dst->c : 0;
         if (res) DSD_CHECK(res->n == x.n && res->h == OH && res->w == OW && res->c == cout, "conv %s: residual shape mismatch", name.c_str());
         const int prec = conv_prec();
-        if (prec != PREC_F32 && x.c % 32 == 0 && plane < 0) {   // split-bf16 arithmetic: pieces of the (packed) weight
+        a.precision = prec;
+        // nearest-x2 upsample + 3x3 in bf16x6: four 2x2 phase convolutions on the low-resolution map (conv2d_subpixel_ok),
+        // phase weights built once per layer; the layer's ordinary 3x3 pieces are then read by nothing and never made
+        const bool subpixel = prec != PREC_F32 && plane < 0 && !hd->use_winograd && conv2d_subpixel_ok(a);
+        a.precision = PREC_F32;
+        if (subpixel) {
+            const std::string skey = name + "#sub";
+            auto it = hd->wsplit.find(skey);
+            if (it == hd->wsplit.end()) {
+                void* planes = nullptr;
+                const size_t sb = subpixel_weight_bytes(cout, x.c);
+                DSD_HIP(hipMalloc(&planes, sb));
+                subpixel_weights(a.w, cout, x.c, planes, ps);   // (on the caller's stream, as split_weights below)
+                split_any = true;
+                it = hd->wsplit.emplace(skey, planes).first;
+                hd->wsplit_bytes[skey] = sb;
+            }
+            a.w_subpixel = it->second;
+            a.precision = prec;
+        } else if (prec != PREC_F32 && x.c % 32 == 0 && plane < 0) {   // split-bf16 arithmetic: pieces of the (packed) weight
             const bool f16 = prec == PREC_F16X3;
             const std::string key = f16 ? name + "#f16" : name;
             auto it = hd->wsplit.find(key);
@@ -938,7 +957,7 @@ struct Builder {
                 c.gn_shift = reinterpret_cast<const float*>(h->arena + gsh);
             }
             conv2d(c, s);
-        }, skb ? 2 : 1, conv2d_variant(a), conv2d_flops(a),
+        }, skb ? 2 : 1, conv2d_variant(a), conv2d_exec_flops(a),
            4.0 * ((double)x.n * x.h * x.w * x.c + (double)cout * x.c * ks * ks + (double)x.n * OH * OW * cout * (has_res ? 2 : 1)));
         if (skb) release_raw(skoff, skb);
         return y;

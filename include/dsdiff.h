@@ -378,6 +378,11 @@ int dsd_bench_mfma_peak(int variant, int workgroups_per_cu, float ms_target, int
  * v_mfma_f32_32x32x16_bf16.  Same results up to fp32 summation order.  Default: the environment variable
  * DSD_CONV_MFMA16 (0).  Returns the previous setting. */
 int dsd_set_conv_mfma16(int on);
+/* Phase weights of the sub-pixel form of conv3x3(nearest_x2(x)) (host-side, no GPU work): w_oihw [Cout][Cin][3][3] ->
+ * out [4 phases (py, px)][Cout][2][2][Cin], each phase tap the fp64 sum of the original taps it covers.  Output pixel
+ * (2i + py, 2j + px) is then sum over (a, b) of x[i + py - 1 + a][j + px - 1 + b] . out[py, px][:, a, b, :] (zero outside).
+ * The library's bf16x6 mode runs upsample layers this way where the tap-reuse kernel takes the low-resolution map. */
+int dsd_subpixel_weights_host(const float* w_oihw, int Cout, int Cin, double* out);
 int dsd_conv_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, int precision, int* structure, int* nt,
                   int* ksplit, uint64_t* scratch_bytes);
 /* GroupNorm(32, C, eps) [+ SiLU] on x[N,HW,C]. */
