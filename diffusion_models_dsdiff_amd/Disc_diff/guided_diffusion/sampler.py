@@ -6,8 +6,8 @@ The noise-schedule scalars are host-side fp32 torch expressions in the reference
 (network evaluation, data/noise prediction, dynamic thresholding, first/second-order multistep update) runs on the
 MI355X through ``dsd_sample_dpm`` (include/dsdiff.h).  Built: ``method='multistep'`` with ``order`` 1 or 2, both
 ``algorithm_type``s, both ``solver_type``s, all three ``skip_type``s, ``lower_order_final``, ``denoise_to_zero``,
-dynamic thresholding.  Singlestep / adaptive solvers, order 3, guidance and python correctors raise
-``NotImplementedError`` — there is no CPU fallback.
+dynamic thresholding, classifier-free guidance (``dsd_sample_dpm_guided``: both halves in one 2B-row network pass).  Singlestep /
+adaptive solvers, order 3, classifier guidance and python correctors raise ``NotImplementedError`` — there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ..._lib import DSD_NCOEF, DsdDpmSchedule, check, dptr, lib, stream_ptr
-from ..._sched import check_latent_io, find_unet, is_latent_denoiser
+from ..._sched import Guidance, cat_unconditional, check_latent_io, find_unet, is_latent_denoiser
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
 
@@ -96,9 +96,12 @@ class _ModelFn:
     """What ``model_wrapper`` returns: the network, its output type and its conditioning, kept apart so the solver can
     hand them to the device loop.  Calling it evaluates the noise prediction at continuous time (:247-279)."""
 
-    def __init__(self, model, noise_schedule, model_type, model_kwargs, condition):
+    def __init__(self, model, noise_schedule, model_type, model_kwargs, condition, unconditional_condition=None,
+                 guidance_scale=1.):
         self.model, self.noise_schedule, self.model_type = model, noise_schedule, model_type
         self.model_kwargs, self.condition = dict(model_kwargs or {}), condition
+        # classifier-free guidance (:324-332); None = off (guidance_scale 1.0 or no unconditional condition)
+        self.unconditional_condition, self.guidance_scale = unconditional_condition, float(guidance_scale)
 
     def input_time(self, t_continuous):
         """get_model_input_time :236-245."""
@@ -124,6 +127,8 @@ class _ModelFn:
         return src
 
     def __call__(self, x, t_continuous):
+        if self.unconditional_condition is not None:
+            raise NotImplementedError("a guided model function is evaluated inside the device loop (DPM_Solver.sample) only")
         ns = self.noise_schedule
         t = torch.as_tensor(t_continuous, dtype=torch.float32).reshape(-1).expand(x.shape[0])
         out = self.network(x, self.input_time(t).to(x.device))
@@ -143,12 +148,22 @@ class _ModelFn:
 def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, guidance_type="uncond", condition=None,
                   unconditional_condition=None, guidance_scale=1., classifier_fn=None, classifier_kwargs={}):
     """:151-302 / dpm_solver_pytorch.py:188-336.  ``model`` is the denoiser as the reference passes it (the native
-    DSUnetModel, a DiffusionWrapper around it, or any callable ``model(x, t_input, [cond], **model_kwargs)``)."""
+    DSUnetModel / UNetModel, a DiffusionWrapper around it, or any callable ``model(x, t_input, [cond], **model_kwargs)``).
+    ``guidance_type="classifier-free"`` with an ``unconditional_condition`` and ``guidance_scale != 1`` (:324-332) runs the
+    guided device loop; the unconditional condition comes in the form of ``condition``.  The reference takes tensors there (its
+    ``torch.cat([unconditional_condition, condition])`` raises on anything else); the dict (``c_concat`` lists) and list forms
+    are accepted as an extension."""
     assert model_type in ["noise", "x_start", "v", "score"]
     assert guidance_type in ["uncond", "classifier", "classifier-free"]
-    if guidance_type == "classifier" or (guidance_type == "classifier-free" and guidance_scale != 1.
-                                          and unconditional_condition is not None):
-        raise NotImplementedError("classifier / classifier-free guidance is not part of the conditional-DDPM path")
+    if guidance_type == "classifier":
+        raise NotImplementedError("classifier guidance (guidance_type='classifier': a classifier gradient per step) cannot run "
+                                  "inside the device loop; classifier-free guidance can")
+    if guidance_type == "classifier-free" and guidance_scale != 1. and unconditional_condition is not None:
+        if model_type == "score":
+            raise NotImplementedError("score-type networks are not part of the conditional-DDPM path")
+        if condition is None:
+            raise ValueError("classifier-free guidance needs the condition the unconditional one replaces")
+        return _ModelFn(model, noise_schedule, model_type, model_kwargs, condition, unconditional_condition, guidance_scale)
     return _ModelFn(model, noise_schedule, model_type, model_kwargs, condition if guidance_type != "uncond" else None)
 
 
@@ -284,17 +299,37 @@ class DPM_Solver:
 
 
 @torch.no_grad()
-def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor) -> torch.Tensor:
+def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: Optional[Guidance] = None) -> torch.Tensor:
+    """The multistep loop on the device.  ``guidance`` (default: what ``fn`` carries from model_wrapper): classifier-free
+    guidance, dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided; its unconditional conditioning must have the shape, dtype
+    and device of the concatenated condition."""
+    unet, cc = find_unet(fn.model), fn.c_concat()
+    if guidance is None and fn.unconditional_condition is not None:
+        u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device).detach().float()
+        guidance = Guidance(u, fn.guidance_scale, sched.steps)
+    guided = guidance is not None
+    if guided:
+        if cc is None:
+            raise ValueError("classifier-free guidance needs the 'concat' condition the unconditional one replaces")
+        guidance.check(torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), sched.steps)
+        if unet is None:
+            raise NotImplementedError("classifier-free guidance runs in the device loop only: it needs a native DSUnetModel / "
+                                      "UNetModel behind the model")
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
     B, Cx, H, W = x.shape
-    unet, cc = find_unet(fn.model), fn.c_concat()
+    if guided:
+        g = guidance.bind()
     if unet is not None and cc is not None and is_latent_denoiser(unet):
         # latent state [B,Cz,h,w] under the plain UNetModel: dsd_sample_dpm_latent
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
         check_latent_io(unet, x, cond)
+        if guided:
+            check(lib().dsd_sample_dpm_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cx,
+                                                     B, H, W, stream_ptr()))
+            return x
         check(lib().dsd_sample_dpm_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
                                           stream_ptr()))
         return x
@@ -303,6 +338,10 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor) -> torch.T
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
         assert cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
+        if guided:
+            check(lib().dsd_sample_dpm_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), B, H, W,
+                                              stream_ptr()))
+            return x
         check(lib().dsd_sample_dpm(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), B, H, W, stream_ptr()))
         return x
     # any other callable: python loop over the network, fused HIP post-network step per evaluation

@@ -29,6 +29,8 @@ EXPORTS = [
     "dsd_profile_enable", "dsd_profile_count", "dsd_profile_get", "dsd_profile_op_count", "dsd_profile_op_get", "dsd_profile_op_name", "dsd_forward", "dsd_sample", "dsd_op_sampler_update", "dsd_sample_dpm", "dsd_op_dpm_step", "dsd_op_dpm_threshold", "dsd_block_create", "dsd_block_forward", "dsd_bench_conv2d", "dsd_bench_conv2d_stamps", "dsd_bench_mfma_peak", "dsd_conv_plan", "dsd_subpixel_weights_host", "dsd_set_conv_mfma16", "dsd_op_conv2d", "dsd_op_conv2d_prec", "dsd_op_gn_silu_conv_out1",
     "dsd_op_gaussian_sample", "dsd_op_group_norm", "dsd_op_qkv_attention", "dsd_op_gemm_half", "dsd_bench_gemm_half", "dsd_bench_attention_half", "dsd_op_attention_half", "dsd_op_timestep_embedding", "dsd_op_linear", "dsd_op_philox_normal",
     "dsd_sample_latent", "dsd_sample_dpm_latent", "dsd_op_posterior_sample_scaled",
+    "dsd_sample_guided", "dsd_sample_latent_guided", "dsd_sample_dpm_guided", "dsd_sample_dpm_latent_guided",
+    "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
 ]
 
 
@@ -57,6 +59,10 @@ class DsdDpmSchedule(C.Structure):
         ("threshold_ratio", C.c_float), ("threshold_max", C.c_float), ("coef", C.POINTER(C.c_float)),
         ("t_input", C.POINTER(C.c_float)), ("order", C.POINTER(C.c_int32)),
     ]
+
+
+class DsdGuidance(C.Structure):
+    _fields_ = [("uncond", C.c_void_p), ("scale", C.POINTER(C.c_float)), ("n_scale", C.c_int32)]
 
 
 class DsdError(RuntimeError):
@@ -154,6 +160,16 @@ def lib() -> C.CDLL:
     L.dsd_sample_latent.argtypes = [vp, C.POINTER(DsdSchedule), f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
     L.dsd_sample_dpm_latent.argtypes = [vp, C.POINTER(DsdDpmSchedule), f32p, i32, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_posterior_sample_scaled.argtypes = [f32p, f32p, C.c_uint64, i32, i32, i32, i32, C.c_float, f32p, vp]
+    gp = C.POINTER(DsdGuidance)
+    L.dsd_sample_guided.argtypes = [vp, C.POINTER(DsdSchedule), gp, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_sample_latent_guided.argtypes = [vp, C.POINTER(DsdSchedule), gp, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32,
+                                           i32, i32, vp]
+    L.dsd_sample_dpm_guided.argtypes = [vp, C.POINTER(DsdDpmSchedule), gp, f32p, i32, f32p, i32, i32, i32, vp]
+    L.dsd_sample_dpm_latent_guided.argtypes = [vp, C.POINTER(DsdDpmSchedule), gp, f32p, i32, f32p, i32, i32, i32, i32, vp]
+    L.dsd_op_sampler_update_guided.argtypes = [C.POINTER(DsdSchedule), i32, f32p, f32p, C.c_float, f32p, i64, f32p, C.c_uint64,
+                                               i32, i32, i32, i32, f32p, vp]
+    L.dsd_op_dpm_step_guided.argtypes = [C.POINTER(DsdDpmSchedule), i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p,
+                                         i32, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -224,7 +224,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -473,7 +473,7 @@ int dsd_op_sampler_update(const dsd_schedule* sc, int k, const float* model_out,
 // state in place there, so the next network evaluation reads x_{t-1} with no concatenation and no copy.  The final state is
 // copied back to x.  Returns the state's row stride: (Cz+Cc)*h*w elements.
 static int64_t latent_bind(dsd_handle* h, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W, int out_ch,
-                           hipStream_t s) {
+                           hipStream_t s, const float* uncond = nullptr) {
     DSD_CHECK(h && cond && x, "null argument");
     DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
     DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
@@ -483,16 +483,21 @@ static int64_t latent_bind(dsd_handle* h, const float* cond, int Cc, const float
     DSD_CHECK(a[2] == out_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], out_ch);
     DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
     const int64_t hw = (int64_t)H * W, Cin = Cz + Cc;
-    net_plan(h, B, (int)Cin, H, W, 0, 0, 1, 0, 0, s);
-    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-    ensure_buf(&h->mout, &h->mout_cap, (size_t)B * out_ch * hw * sizeof(float));
-    ensure_buf(&h->lat_in, &h->lat_in_cap, (size_t)B * Cin * hw * sizeof(float));
+    // classifier-free guidance (uncond given): 2B rows, x_in = cat([x]*2), c_in = cat([uncond, cond]) (ddim.py:197-218)
+    const int rows = uncond ? 2 * B : B;
+    net_plan(h, rows, (int)Cin, H, W, 0, 0, 1, 0, 0, s);
+    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
+    ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
+    ensure_buf(&h->lat_in, &h->lat_in_cap, (size_t)rows * Cin * hw * sizeof(float));
     const size_t row = (size_t)Cin * hw * sizeof(float);
-    DSD_HIP(hipMemcpy2DAsync(h->lat_in, row, x, (size_t)Cz * hw * sizeof(float), (size_t)Cz * hw * sizeof(float), B,
-                             hipMemcpyDeviceToDevice, s));
-    if (Cc)
-        DSD_HIP(hipMemcpy2DAsync(h->lat_in + Cz * hw, row, cond, (size_t)Cc * hw * sizeof(float), (size_t)Cc * hw * sizeof(float), B,
+    for (int half = 0; half * B < rows; ++half) {
+        float* dst = h->lat_in + (size_t)half * B * Cin * hw;
+        DSD_HIP(hipMemcpy2DAsync(dst, row, x, (size_t)Cz * hw * sizeof(float), (size_t)Cz * hw * sizeof(float), B,
                                  hipMemcpyDeviceToDevice, s));
+        if (Cc)
+            DSD_HIP(hipMemcpy2DAsync(dst + Cz * hw, row, (uncond && half == 0) ? uncond : cond, (size_t)Cc * hw * sizeof(float),
+                                     (size_t)Cc * hw * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+    }
     h->io = IO();
     h->io.x_nchw = h->lat_in;
     h->io.aux = h->tbuf;
@@ -615,6 +620,188 @@ int dsd_op_dpm_step(const dsd_dpm_schedule* sc, int k, const float* model_out, i
     Tmp sb((size_t)B * sizeof(float));
     dpm_step(dpm_coef(sc, k), model_out, Cm, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio, sc->threshold_max, B, H * W,
              (hipStream_t)stream);
+    DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    DSD_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- classifier-free guidance
+// ddim.py:194-219 / dpm_solver_pytorch.py:324-332: both halves in ONE network pass over 2B rows (uncond half first), combined
+// by the guided update kernels (sampler.hip), which write x_{t-1} to both state rows.  Noise and slice ids stay per logical sample.
+static void check_guidance(const dsd_guidance* g, int steps) {
+    DSD_CHECK(g, "null guidance");
+    DSD_CHECK(g->uncond, "guidance needs the unconditional conditioning (uncond is null)");
+    DSD_CHECK(g->scale && g->n_scale == steps, "guidance carries %d scales but the schedule executes %d steps (one scale per step)",
+              g->scale ? g->n_scale : 0, steps);
+}
+
+static void check_guided_schedule(const dsd_schedule* sc) {
+    DSD_CHECK(sc, "bad schedule");
+    DSD_CHECK(!sc->learned_range, "classifier-free guidance does not take a learned-range variance (learned_range is set)");
+    DSD_CHECK(sc->mode == DSD_MODE_B_DDIM,
+              "classifier-free guidance exists only in the DDIM loop of the LDM family (DSD_MODE_B_DDIM); the reference has none in "
+              "mode %d", sc->mode);
+    check_schedule(sc);
+}
+
+// the four-stream model's 2B-row planes: state [2B,1,H,W] then conditions [2B,Cc,H,W] = cat([uncond, cond]); step-invariant
+// halves copied once per call
+static float* guided_bind(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int B, int H, int W,
+                          int out_ch, hipStream_t s) {
+    const int64_t hw = (int64_t)H * W;
+    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
+    net_plan(h, 2 * B, Cc + 1, H, W, Cc == 1, 0, 0, 0, Cc == 1 ? h->share_zero_streams : 0, s);
+    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)2 * B * sizeof(float));
+    ensure_buf(&h->mout, &h->mout_cap, (size_t)2 * B * out_ch * hw * sizeof(float));
+    ensure_buf(&h->cfg_io, &h->cfg_io_cap, (size_t)2 * B * (1 + Cc) * hw * sizeof(float));
+    float* xs = h->cfg_io;
+    float* cs = xs + (size_t)2 * B * hw;
+    const size_t xb = (size_t)B * hw * sizeof(float), cb = xb * Cc;
+    DSD_HIP(hipMemcpyAsync(xs, x, xb, hipMemcpyDeviceToDevice, s));
+    DSD_HIP(hipMemcpyAsync(xs + (size_t)B * hw, x, xb, hipMemcpyDeviceToDevice, s));
+    DSD_HIP(hipMemcpyAsync(cs, g->uncond, cb, hipMemcpyDeviceToDevice, s));
+    DSD_HIP(hipMemcpyAsync(cs + (size_t)B * Cc * hw, cond, cb, hipMemcpyDeviceToDevice, s));
+    bind_sampling_io(h, xs, cs, Cc, hw, s);
+    return xs;
+}
+
+int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    check_guided_schedule(sc);
+    check_guidance(g, sc->steps);
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    float* xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        fill_t(h->tbuf, 2 * B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * hw, g->scale[k], xs,
+                           noise ? noise + (size_t)k * B * hw : nullptr, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids);
+    }
+    DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                             void* stream) {
+    DSD_TRY
+    check_guided_schedule(sc);
+    check_guidance(g, sc->steps);
+    DSD_CHECK(Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g->uncond);
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        fill_t(h->tbuf, 2 * B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * Cz * hw, g->scale[k], h->lat_in,
+                           noise ? noise + (size_t)k * B * Cz * hw : nullptr, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids,
+                           Cz, x_bs);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_op_sampler_update_guided(const dsd_schedule* sc, int k, const float* out_uncond, const float* out_cond, float scale,
+                                 float* x, int64_t x_row_stride, const float* noise, uint64_t philox_seed, int B, int Cz, int H,
+                                 int W, float* pred_xstart, void* stream) {
+    DSD_TRY
+    check_guided_schedule(sc);
+    DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x, "bad argument");
+    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
+    DSD_CHECK(x_row_stride == 0 || x_row_stride >= (int64_t)Cz * H * W, "x_row_stride %lld is smaller than one sample (%lld)",
+              (long long)x_row_stride, (long long)Cz * H * W);
+    sampler_update_cfg(step_coef(sc, k), out_uncond, out_cond, scale, x, noise, philox_seed, (uint64_t)k, B, H * W,
+                       (hipStream_t)stream, pred_xstart, nullptr, Cz, x_row_stride);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                          int B, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    check_dpm_schedule(sc);
+    check_guidance(g, sc->steps);
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    const int out_ch = h->cfg.out_channels;
+    DSD_CHECK(out_ch == 1 || out_ch == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", out_ch);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    float* xs = guided_bind(h, g, cond, Cc, x, B, H, W, out_ch, s);
+    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * hw + B) * sizeof(float));
+    float* m_cur = h->dpm_m;
+    float* m_prev = h->dpm_m + (size_t)B * hw;
+    float* s_buf = h->dpm_m + (size_t)2 * B * hw;
+    for (int k = 0; k < sc->steps; ++k) {
+        fill_t(h->tbuf, 2 * B, sc->t_input[k], s);
+        net_run_cached(h, s);
+        dpm_step_cfg(dpm_coef(sc, k), h->mout, h->mout + (size_t)B * out_ch * hw, out_ch, g->scale[k], xs, m_cur, m_prev, s_buf,
+                     sc->threshold_ratio, sc->threshold_max, B, (int)hw, s);
+        std::swap(m_cur, m_prev);
+    }
+    DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
+                                 float* x, int Cz, int B, int H, int W, void* stream) {
+    DSD_TRY
+    check_dpm_schedule(sc);
+    check_guidance(g, sc->steps);
+    DSD_CHECK(Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)Cz * hw;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g->uncond);
+    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * n + B) * sizeof(float));
+    float* m_cur = h->dpm_m;
+    float* m_prev = h->dpm_m + (size_t)B * n;
+    float* s_buf = h->dpm_m + (size_t)2 * B * n;
+    for (int k = 0; k < sc->steps; ++k) {
+        fill_t(h->tbuf, 2 * B, sc->t_input[k], s);
+        net_run_cached(h, s);
+        dpm_step_cfg(dpm_coef(sc, k), h->mout, h->mout + (size_t)B * n, 1, g->scale[k], h->lat_in, m_cur, m_prev, s_buf,
+                     sc->threshold_ratio, sc->threshold_max, B, (int)n, s, x_bs);
+        std::swap(m_cur, m_prev);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sc, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
+                           float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
+                           void* stream) {
+    DSD_TRY
+    check_dpm_schedule(sc);
+    DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x && m_cur && (Cm == 1 || Cm == 2), "bad argument");
+    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
+    DSD_CHECK(Cm == 1 || Cz == 1, "a two-channel (learned-sigma) output needs one state channel; Cz = %d", Cz);
+    DSD_CHECK(sc->order[k] < 2 || m_prev, "a second-order update needs m_prev");
+    const int64_t n = (int64_t)Cz * H * W;
+    DSD_CHECK(x_row_stride == 0 || x_row_stride >= n, "x_row_stride %lld is smaller than one sample (%lld)", (long long)x_row_stride,
+              (long long)n);
+    Tmp sb((size_t)B * sizeof(float));
+    dpm_step_cfg(dpm_coef(sc, k), out_uncond, out_cond, Cm, scale, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio,
+                 sc->threshold_max, B, (int)n, (hipStream_t)stream, x_row_stride);
     DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
     DSD_CATCH
 }

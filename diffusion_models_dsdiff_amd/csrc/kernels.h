@@ -260,6 +260,16 @@ struct DpmCoef {
 };
 void dpm_step(const DpmCoef& c, const float* model_out, int Cm, float* x, float* m_cur, const float* m_prev, float* s_buf,
               float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
+// Classifier-free guidance: the network ran on 2B rows (uncond half first), out_u / out_c are the two [B,..] halves of its
+// output and x is the 2B-row state (logical sample b at rows b and B+b, row stride x_bs); both rows receive x_{t-1}.  noise,
+// x0_out, slice_ids, m_cur / m_prev and s_buf are per logical sample, as in the unguided launchers.
+// DDIM: out = out_u + scale*(out_c - out_u), then sampler_update's DSD_MODE_B_DDIM arithmetic
+void sampler_update_cfg(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
+                        uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr,
+                        const int64_t* slice_ids = nullptr, int Cz = 1, int64_t x_bs = 0);
+// DPM-Solver: noise = noise_u + scale*(noise_c - noise_u) on the two noise predictions, then dpm_step's arithmetic
+void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
+                  const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s);
 void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_t s);
 // DiagonalGaussianDistribution.sample (ldm/modules/distributions/distributions.py:24-37): moments [B,2E,HW] (NCHW) ->

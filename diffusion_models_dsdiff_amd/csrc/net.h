@@ -134,6 +134,7 @@ struct dsd_handle {
     float* zplane = nullptr;   // [H*W] zeros
     float* dpm_m = nullptr;    // dsd_sample_dpm: m_k, m_{k-1} [B,H*W] each + thresholds [B]
     float* lat_in = nullptr;   // latent loops (UNET block): the denoiser's NCHW input [B,Cz+Cc,h,w]; channels [0,Cz) are the state
+    float* cfg_io = nullptr;   // guided loops of the four-stream model: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
     float* freqs = nullptr;    // [model_channels/2] optional timestep-embedding frequency table (host-supplied)
     int64_t* slice_ids = nullptr;  // [n_slice_ids] global slice index of every batch row (Philox counter base), optional
     int n_slice_ids = 0;
@@ -177,7 +178,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0;
 
     float* P(const std::string& name) const;
     const dsd::Param& PP(const std::string& name) const;

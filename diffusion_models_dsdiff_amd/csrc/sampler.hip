@@ -60,6 +60,22 @@ void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_
     check_launch("philox_normal");
 }
 
+// p_sample_ddim after the network output is formed (ddim.py:222-260): returns x_{t-1}, x0 = the (clipped) pred_x0
+__device__ __forceinline__ float ddim_update(const StepCoef& sc, float out, float xt, float z, float& x0) {
+    const float* c = sc.c;
+    float e_t;
+    if (sc.pred == DSD_PRED_V) {
+        e_t = c[0] * out + c[1] * xt;   // predict_eps_from_z_and_v ddpm.py:298-302
+        x0 = c[0] * xt - c[1] * out;    // predict_start_from_z_and_v ddpm.py:290-296
+    } else {
+        e_t = out;
+        x0 = (xt - c[7] * e_t) / sqrtf(c[4]);
+    }
+    if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    const float dir = sqrtf(1.f - c[5] - c[6] * c[6]) * e_t;
+    return sqrtf(c[5]) * x0 + dir + c[6] * z;
+}
+
 // One sample is n = Cz*HW elements (r = c*HW + p inside it).  The state row b lives at x + b*x_bs: x_bs = n for a state of its
 // own, (Cz+Cc)*HW when the state is the first Cz channels of the denoiser's NCHW input (the latent loop writes x_{t-1} straight
 // into the buffer the network reads next).  model_out, noise and x0_out are contiguous [B,Cm*Cz,HW] / [B,Cz,HW].  The Philox
@@ -80,18 +96,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const 
         const float* c = sc.c;
         float x0, res;
         if (sc.mode == DSD_MODE_B_DDIM) {
-            // ddim.py:222-260
-            float e_t;
-            if (sc.pred == DSD_PRED_V) {
-                e_t = c[0] * out + c[1] * xt;   // predict_eps_from_z_and_v ddpm.py:298-302
-                x0 = c[0] * xt - c[1] * out;    // predict_start_from_z_and_v ddpm.py:290-296
-            } else {
-                e_t = out;
-                x0 = (xt - c[7] * e_t) / sqrtf(c[4]);
-            }
-            if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-            const float dir = sqrtf(1.f - c[5] - c[6] * c[6]) * e_t;
-            res = sqrtf(c[5]) * x0 + dir + c[6] * z;
+            res = ddim_update(sc, out, xt, z, x0);
         } else {
             if (sc.pred == DSD_PRED_V)
                 x0 = c[0] * xt - c[1] * out;
@@ -147,6 +152,20 @@ void sampler_update(const StepCoef& sc, const float* model_out, float* x, const 
 // Every product/sum is a separately rounded fp32 op in the reference's order (file-wide contract(off)).
 // HW = elements per sample (Cz*h*w for a latent state); x row b at x + b*x_bs (x_bs = HW, or (Cz+Cc)*h*w inside the
 // denoiser's input buffer); m and the model output are contiguous.
+// noise prediction from the network output (model_wrapper.noise_pred_fn :247-265)
+__device__ __forceinline__ float dpm_noise_pred(const DpmCoef& c, float out, float xt) {
+    if (c.pred == DSD_PRED_EPS) return out;
+    if (c.pred == DSD_PRED_X0) return (xt - c.alpha * out) / c.sigma;
+    return c.alpha * out + c.sigma * xt;
+}
+// first-order (:509-553) / second-order multistep (:760-816) update from m = m_k, m1 = m_{k-1}
+__device__ __forceinline__ float dpm_update_value(const DpmCoef& c, float m, float m1, float xt) {
+    if (c.order == 0) return m;                               // denoise_to_zero_fn :503-507
+    float res = c.cx * xt - c.cm * m;
+    if (c.order == 2) res = res - c.cd * (c.ir0 * (m - m1));
+    return res;
+}
+
 __global__ __launch_bounds__(256) void dpm_model_kernel(DpmCoef c, const float* __restrict__ mo, int Cm,
                                                         const float* __restrict__ x, float* __restrict__ m, int B,
                                                         int HW, int64_t x_bs) {
@@ -155,13 +174,7 @@ __global__ __launch_bounds__(256) void dpm_model_kernel(DpmCoef c, const float* 
         const int64_t b = i / HW;
         const float out = mo[(b * Cm) * HW + (i - b * HW)];   // a learned-sigma model: first channel only (gaussian_diffusion.py:484-485)
         const float xt = x[b * x_bs + (i - b * HW)];
-        float eps;
-        if (c.pred == DSD_PRED_EPS)
-            eps = out;
-        else if (c.pred == DSD_PRED_X0)
-            eps = (xt - c.alpha * out) / c.sigma;
-        else
-            eps = c.alpha * out + c.sigma * xt;
+        const float eps = dpm_noise_pred(c, out, xt);
         m[i] = c.data_pred ? (xt - c.sigma * eps) / c.alpha : eps;
     }
 }
@@ -234,14 +247,7 @@ __global__ __launch_bounds__(256) void dpm_update_kernel(DpmCoef c, float* __res
         }
         if (!x) continue;                                     // thresholding only (dsd_op_dpm_threshold)
         const int64_t xi = (i / HW) * x_bs + (i % HW);
-        float res;
-        if (c.order == 0) {
-            res = m;                                          // denoise_to_zero_fn :503-507
-        } else {
-            res = c.cx * x[xi] - c.cm * m;
-            if (c.order == 2) res = res - c.cd * (c.ir0 * (m - m1[i]));
-        }
-        x[xi] = res;
+        x[xi] = dpm_update_value(c, m, c.order == 2 ? m1[i] : 0.f, x[xi]);
     }
 }
 
@@ -273,6 +279,167 @@ void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float m
                        y, (const float*)nullptr, s_buf, (float*)nullptr, B, n, (int64_t)n);
     check_launch("dpm_update");
     DSD_HIP(hipStreamSynchronize(s));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Classifier-free guidance (ddim.py:194-219, dpm_solver_pytorch.py:324-332).  The network has been evaluated on 2B rows —
+// x_in = cat([x]*2), c_in = cat([uncond, cond]) — so its output arrives as two [B,..] halves and the state occupies 2B rows:
+// logical sample b at x + b*x_bs (uncond half) and at x + (B+b)*x_bs (cond half).  Both rows hold x_t on entry; the kernels
+// read the first and write x_{t-1} to both, so the next evaluation needs no copy.  Everything else — noise, Philox counters,
+// slice_ids, x0_out, m, the thresholding quantile — is indexed by the B logical samples.
+// V = 4: 16-byte accesses (n, x_bs multiples of 4 and 16-byte aligned pointers; the launchers check), V = 1 otherwise.
+template <int V> struct alignas(4 * V) Pack { float v[V]; };
+template <int V> __device__ __forceinline__ Pack<V> ld_pack(const float* p) { return *reinterpret_cast<const Pack<V>*>(p); }
+template <int V> __device__ __forceinline__ void st_pack(float* p, const Pack<V>& a) { *reinterpret_cast<Pack<V>*>(p) = a; }
+
+// normals i .. i+V-1 of the (seed, step) stream; i % V == 0.  V = 4 is one Philox block: the values philox_normal_at gives
+template <int V> __device__ __forceinline__ Pack<V> philox_normal_pack(int64_t i, uint64_t seed, uint64_t step) {
+    Pack<V> z;
+    if constexpr (V == 4) {
+        uint32_t r[4];
+        const uint64_t blk = (uint64_t)i >> 2;
+        philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
+                      (uint32_t)(seed >> 32), r);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;
+            const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
+            const float rad = sqrtf(-2.0f * logf(u1));
+            const float ang = 6.283185307179586f * u2;
+            z.v[2 * h] = rad * cosf(ang);
+            z.v[2 * h + 1] = rad * sinf(ang);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) z.v[j] = philox_normal_at(i + j, seed, step);
+    }
+    return z;
+}
+
+// DDIM: out = out_u + s * (out_c - out_u) on the raw network outputs (ddim.py:219), then the unguided arithmetic
+template <int V>
+__global__ __launch_bounds__(256) void sampler_update_cfg_kernel(StepCoef sc, const float* __restrict__ mo_u,
+                                                                 const float* __restrict__ mo_c, float gs, float* __restrict__ x,
+                                                                 const float* __restrict__ noise, uint64_t seed, uint64_t step,
+                                                                 int B, int64_t n, int64_t x_bs, float* __restrict__ x0_out,
+                                                                 const int64_t* __restrict__ slice_ids) {
+    const int64_t nv = n / V, total = (int64_t)B * nv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t li = b * n + p;                         // in the [B,n] tensors
+        const int64_t xi = b * x_bs + p;
+        const Pack<V> ou = ld_pack<V>(mo_u + li), oc = ld_pack<V>(mo_c + li), xt = ld_pack<V>(x + xi);
+        const Pack<V> z = noise ? ld_pack<V>(noise + li)
+                                : philox_normal_pack<V>(slice_ids ? slice_ids[b] * n + p : li, seed, step);
+        Pack<V> res, x0;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float out = ou.v[j] + gs * (oc.v[j] - ou.v[j]);
+            res.v[j] = ddim_update(sc, out, xt.v[j], z.v[j], x0.v[j]);
+        }
+        st_pack<V>(x + xi, res);
+        st_pack<V>(x + xi + (int64_t)B * x_bs, res);
+        if (x0_out) st_pack<V>(x0_out + li, x0);
+    }
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static int cfg_blocks(int64_t work) { return (int)std::min<int64_t>((work + 255) / 256, 2048); }
+
+void sampler_update_cfg(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
+                        uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz,
+                        int64_t x_bs) {
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    if (x_bs <= 0) x_bs = n;
+    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x) && aligned16(noise) &&
+                    aligned16(x0_out);
+    if (v4)
+        hipLaunchKernelGGL(sampler_update_cfg_kernel<4>, dim3(cfg_blocks(B * (n / 4))), dim3(256), 0, s, sc, out_u, out_c, scale, x,
+                           noise, seed, step, B, n, x_bs, x0_out, slice_ids);
+    else
+        hipLaunchKernelGGL(sampler_update_cfg_kernel<1>, dim3(cfg_blocks(B * n)), dim3(256), 0, s, sc, out_u, out_c, scale, x, noise,
+                           seed, step, B, n, x_bs, x0_out, slice_ids);
+    check_launch("sampler_update_cfg");
+}
+
+// DPM-Solver: each half becomes a noise prediction from its own output and the shared x_t, then
+// noise = noise_u + s * (noise_c - noise_u) (dpm_solver_pytorch.py:324-332); m as in dpm_model_kernel
+template <int V>
+__global__ __launch_bounds__(256) void dpm_model_cfg_kernel(DpmCoef c, const float* __restrict__ mo_u, const float* __restrict__ mo_c,
+                                                            int Cm, float gs, const float* __restrict__ x, float* __restrict__ m,
+                                                            int B, int HW, int64_t x_bs) {
+    const int64_t nv = HW / V, total = (int64_t)B * nv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t oi = (b * Cm) * HW + p;                 // a learned-sigma model: first channel only
+        const Pack<V> ou = ld_pack<V>(mo_u + oi), oc = ld_pack<V>(mo_c + oi), xt = ld_pack<V>(x + b * x_bs + p);
+        Pack<V> r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float eu = dpm_noise_pred(c, ou.v[j], xt.v[j]);
+            const float ec = dpm_noise_pred(c, oc.v[j], xt.v[j]);
+            const float eps = eu + gs * (ec - eu);
+            r.v[j] = c.data_pred ? (xt.v[j] - c.sigma * eps) / c.alpha : eps;
+        }
+        st_pack<V>(m + b * HW + p, r);
+    }
+}
+
+// dpm_update_kernel on the 2B-row state: thresholds m_k in place, writes x_{t-1} to both rows of every logical sample
+template <int V>
+__global__ __launch_bounds__(256) void dpm_update_cfg_kernel(DpmCoef c, float* __restrict__ m0, const float* __restrict__ m1,
+                                                             const float* __restrict__ s_thr, float* __restrict__ x, int B, int HW,
+                                                             int64_t x_bs) {
+    const int64_t nv = HW / V, total = (int64_t)B * nv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t li = b * HW + p, xi = b * x_bs + p;
+        Pack<V> m = ld_pack<V>(m0 + li);
+        if (s_thr) {
+            const float s = s_thr[b];
+#pragma unroll
+            for (int j = 0; j < V; ++j) m.v[j] = fminf(fmaxf(m.v[j], -s), s) / s;
+            st_pack<V>(m0 + li, m);
+        }
+        const Pack<V> xt = ld_pack<V>(x + xi);
+        Pack<V> mp = m;
+        if (c.order == 2) mp = ld_pack<V>(m1 + li);
+        Pack<V> res;
+#pragma unroll
+        for (int j = 0; j < V; ++j) res.v[j] = dpm_update_value(c, m.v[j], mp.v[j], xt.v[j]);
+        st_pack<V>(x + xi, res);
+        st_pack<V>(x + xi + (int64_t)B * x_bs, res);
+    }
+}
+
+void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
+                  const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
+    if (!B || !HW) return;
+    if (x_bs <= 0) x_bs = HW;
+    const bool v4 = HW % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x) && aligned16(m_cur) &&
+                    aligned16(m_prev);
+    const int blocks = cfg_blocks(v4 ? (int64_t)B * (HW / 4) : (int64_t)B * HW);
+    if (v4)
+        hipLaunchKernelGGL(dpm_model_cfg_kernel<4>, dim3(blocks), dim3(256), 0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
+    else
+        hipLaunchKernelGGL(dpm_model_cfg_kernel<1>, dim3(blocks), dim3(256), 0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
+    check_launch("dpm_model_cfg");
+    const bool thr = c.thresh && c.data_pred;
+    if (thr) {   // per logical sample: m_cur is [B,HW]
+        hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m_cur, HW, ratio, max_val, s_buf);
+        check_launch("dpm_quantile");
+    }
+    if (v4)
+        hipLaunchKernelGGL(dpm_update_cfg_kernel<4>, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW,
+                           x_bs);
+    else
+        hipLaunchKernelGGL(dpm_update_cfg_kernel<1>, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW,
+                           x_bs);
+    check_launch("dpm_update_cfg");
 }
 
 // scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed

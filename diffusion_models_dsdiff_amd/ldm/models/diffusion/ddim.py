@@ -1,12 +1,14 @@
 """DDIMSampler — drop-in for ldm/models/diffusion/ddim.py (make_schedule :25-55, sample :57-126,
-ddim_sampling :128-185, p_sample_ddim :187-261), executed by dsd_sample (mode B_DDIM)."""
+ddim_sampling :128-185, p_sample_ddim :187-261), executed by dsd_sample (mode B_DDIM); with
+``unconditional_guidance_scale`` / ``unconditional_conditioning`` / ``ucg_schedule`` by dsd_sample_guided."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from .... import _lib
-from ...._sched import Schedule, find_unet, run_device_loop
+from ...._sched import (Guidance, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active,
+                         run_device_loop)
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -84,20 +86,28 @@ class DDIMSampler(object):
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None,
                ucg_schedule=None, step_noise=None, seed=None, **kwargs):
-        """:57-126 -> (samples, intermediates).  Unsupported reference options raise instead of being ignored."""
+        """:57-126 -> (samples, intermediates).  Unsupported reference options raise instead of being ignored.
+        Classifier-free guidance (:194-219) runs in the device loop: ``unconditional_conditioning`` comes in the form of
+        ``conditioning`` (dict with c_concat lists, list, or tensor); ``ucg_schedule`` holds one scale per executed step."""
         if mask is not None or quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
-                or unconditional_guidance_scale != 1. or temperature != 1. or noise_dropout != 0. or ucg_schedule is not None:
-            raise NotImplementedError("inpainting mask / guidance / quantisation options are not on the medical hot path")
+                or temperature != 1. or noise_dropout != 0.:
+            raise NotImplementedError("inpainting mask / quantisation / score corrector / dynamic threshold / temperature / "
+                                      "noise dropout are not on the medical hot path")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose,
                            ddim_discretize=kwargs.get("ddim_discretize", "uniform"))
         C_, H, W = shape
         size = (batch_size, C_, H, W)
         use_orig = kwargs.get("ddim_use_original_steps", False)
+        sched = self._schedule(use_orig, clip_denoised)
         device = self.model.betas.device
+        guidance = None
+        if ucg_schedule is not None:
+            assert len(ucg_schedule) == sched.steps                                   # :166
+        if guidance_active(unconditional_guidance_scale, unconditional_conditioning, ucg_schedule):
+            u = cat_unconditional(conditioning, unconditional_conditioning, device)
+            guidance = Guidance(u, ucg_schedule if ucg_schedule is not None else unconditional_guidance_scale, sched.steps)
         img = x_T if x_T is not None else torch.randn(size, device=device)
-        c = conditioning["c_concat"] if isinstance(conditioning, dict) else (
-            conditioning if isinstance(conditioning, list) else [conditioning])
         unet = find_unet(self.model.model if hasattr(self.model, "model") else self.model)
-        out = run_device_loop(unet, self._schedule(use_orig, clip_denoised), img.to(device),
-                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed)
+        out = run_device_loop(unet, sched, img.to(device), cat_conditioning(conditioning, device), step_noise=step_noise,
+                              seed=seed, guidance=guidance)
         return out, {"x_inter": [img, out], "pred_x0": [img, out]}

@@ -340,3 +340,21 @@ class LatentDiffusion(DDPM):
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
                                   timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0,
                                   step_noise=kwargs.get("step_noise"), seed=kwargs.get("seed"))
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, sampler, ddim_steps, **kwargs):
+        """trainers/trainer_latent_diffusion.py:526-544: the sampler switch of the latent trainer (``dpm`` | ``ddim`` | DDPM
+        ancestral) -> (samples, intermediates).  ``unconditional_guidance_scale`` / ``unconditional_conditioning`` (and every
+        other keyword) go to the DDIM and DPM-Solver samplers as they do there; the ancestral loop has no guidance."""
+        from .ddim import DDIMSampler
+        from .dpm_solver_new.sampler import DPMSolverSampler
+        shape = (self.channels, self.image_size, self.image_size)
+        actual = tuple(cond["c_concat"][0].shape[2:])
+        if actual != shape[1:]:
+            shape = (self.channels, *actual)
+        if sampler == "dpm":
+            return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, **kwargs)
+        if sampler == "ddim":
+            return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, eta=kwargs.get("ddim_eta") or 0.,
+                                            **kwargs)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)

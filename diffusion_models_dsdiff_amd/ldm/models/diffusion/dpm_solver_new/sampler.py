@@ -33,16 +33,24 @@ class DPMSolverSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, **kwargs):
-        """:35-103 -> (samples, None)."""
-        if mask is not None or quantize_x0 or score_corrector is not None or \
-                (unconditional_guidance_scale != 1. and unconditional_conditioning is not None):
-            raise NotImplementedError("inpainting mask / guidance / quantisation options are not on the medical hot path")
+        """:35-103 -> (samples, None).  ``unconditional_guidance_scale`` / ``unconditional_conditioning`` run classifier-free
+        guidance in the device loop.  The reference supports the tensor form of the two conditionings there (its
+        ``torch.cat([unconditional_condition, condition])`` raises TypeError on a dict); the dict (``c_concat`` lists) and list
+        forms, in which the unconditional conditioning mirrors the conditioning, are accepted as an extension."""
+        if mask is not None or quantize_x0 or score_corrector is not None:
+            raise NotImplementedError("inpainting mask / quantisation / score corrector options are not on the medical hot path")
         C_, H, W = shape
         size = (batch_size, C_, H, W)
         device = self.model.betas.device
         img = torch.randn(size, device=device) if x_T is None else x_T
         ns = NoiseScheduleVP("discrete", betas=self.betas)
         if not isinstance(conditioning, dict):
+            if unconditional_conditioning is not None:        # the same wrapping keeps the two in one form
+                assert not isinstance(unconditional_conditioning, dict) and \
+                    isinstance(unconditional_conditioning, list) == isinstance(conditioning, list), \
+                    "unconditional_conditioning must come in the form of the conditioning"
+                unconditional_conditioning = dict(c_concat=unconditional_conditioning if isinstance(
+                    unconditional_conditioning, list) else [unconditional_conditioning])
             conditioning = dict(c_concat=conditioning if isinstance(conditioning, list) else [conditioning])
         model_fn = model_wrapper(_ApplyModel(self.model), ns, model_type=MODEL_TYPES[self.model.parameterization],
                                  guidance_type="classifier-free", condition=conditioning,

@@ -21,6 +21,12 @@
  *                                        ldm/models/diffusion/ddim.py:128-261, ldm/models/diffusion/ddpm.py:1048-1115
  *                                        (call sites trainers/trainer_latent_diffusion.py:492-544)
  *   dsd_sample_dpm_latent          <- DPMSolverSampler.sample on VAE latents  ldm/models/diffusion/dpm_solver_new/sampler.py:35-103
+ *   dsd_sample_guided / dsd_sample_latent_guided / dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided
+ *                                  <- the same samplers with unconditional_guidance_scale / unconditional_conditioning
+ *                                        ldm/models/diffusion/ddim.py:194-219 (p_sample_ddim, ucg_schedule :165-167)
+ *                                        ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:324-332
+ *                                        (model_wrapper guidance_type="classifier-free")
+ *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
  *   dsd_op_posterior_sample_scaled <- LatentDiffusion.get_first_stage_encoding(encode_first_stage(x))
  *                                        ldm/models/diffusion/ddpm.py:660-667 with distributions.py:24-37
  *   dsd_block_*                    <- ResBlock / AttentionBlock / Upsample / Downsample
@@ -286,6 +292,52 @@ int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sched, const fl
  * m_prev = m_{k-1} (may be NULL when order[k] < 2). */
 int dsd_op_dpm_step(const dsd_dpm_schedule* sched, int k, const float* model_out, int Cm, float* x, float* m_cur,
                     const float* m_prev, int B, int H, int W, void* stream);
+/* ---- classifier-free guidance -------------------------------------------------------------
+ * The reference's unconditional_guidance_scale / unconditional_conditioning (DDIMSampler.sample, DPMSolverSampler.sample,
+ * model_wrapper(guidance_type="classifier-free")).  Per step the denoiser is evaluated in ONE pass over 2B rows —
+ * x_in = cat([x]*2), c_in = cat([uncond, cond]) (ddim.py:197-218) — in library-owned buffers, and the two output halves are
+ * combined in front of the update, each sampler in its reference's order (fp32, nothing contracted):
+ *   DDIM        out   = out_u   + s*(out_c   - out_u)    on the raw network outputs (ddim.py:219), then the B_DDIM update
+ *   DPM-Solver  noise = noise_u + s*(noise_c - noise_u)  on the noise predictions each half forms from its own output and the
+ *               shared x_t (dpm_solver_pytorch.py:324-332), then data prediction / thresholding (quantile per logical sample) /
+ *               multistep update
+ * The update writes x_{t-1} to both state rows of a sample.  Noise (fed: [steps,B,..]; Philox) and dsd_set_slice_ids are keyed by
+ * the B logical samples, never by the 2B rows: a guided run with seed S draws the normals of the unguided run with seed S.
+ * dsd_set_share_zero_streams, the stream lanes and dsd_set_graph replay work as in the unguided loops.
+ * uncond: device, laid out like cond ([B,Cc,H,W]).  scale: host, one fp32 scale per executed step (a constant
+ * unconditional_guidance_scale is the array filled with it; ucg_schedule is the array itself, ddim.py:165-167); n_scale must
+ * equal the schedule's steps.  A step whose scale is 1.0 still runs the guided arithmetic.  The callers keep guidance OFF
+ * (uncond None or scale 1.0, ddim.py:194) on the unguided entry points. */
+typedef struct dsd_guidance {
+    const float* uncond;   /* device, [B,Cc,H,W] like cond */
+    const float* scale;    /* host, n_scale */
+    int32_t n_scale;
+} dsd_guidance;
+/* dsd_sample with guidance: DSD_MODE_B_DDIM only (the reference has no guidance in the family-A loops or the DDPM loop), no
+ * learned-range variance.  Other arguments as dsd_sample. */
+int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
+/* dsd_sample_latent with guidance (DSD_MODE_B_DDIM only): the denoiser's persistent NCHW input holds 2B rows. */
+int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                             void* stream);
+/* dsd_sample_dpm / dsd_sample_dpm_latent with guidance; scale[k] belongs to network evaluation k. */
+int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                          int B, int H, int W, void* stream);
+int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sched, const dsd_guidance* g, const float* cond, int Cc,
+                                 float* x, int Cz, int B, int H, int W, void* stream);
+/* One guided update alone (iteration k, DSD_MODE_B_DDIM).  out_uncond / out_cond: the two [B,Cz,H,W] halves of the network
+ * output.  x: the 2B-row state, logical sample b at x + b*x_row_stride and x + (B+b)*x_row_stride (x_row_stride = 0: Cz*H*W,
+ * i.e. a contiguous [2B,Cz,H,W]); the first B rows are read, all 2B receive x_{t-1}.  noise [B,Cz,H,W] or NULL (Philox),
+ * pred_xstart (optional) [B,Cz,H,W]. */
+int dsd_op_sampler_update_guided(const dsd_schedule* sched, int k, const float* out_uncond, const float* out_cond, float scale,
+                                 float* x, int64_t x_row_stride, const float* noise, uint64_t philox_seed, int B, int Cz, int H,
+                                 int W, float* pred_xstart, void* stream);
+/* Iteration k's post-network part of the guided DPM-Solver loop: out_uncond / out_cond [B,Cm*Cz,H,W] (Cm = 2 needs Cz = 1), x
+ * as in dsd_op_sampler_update_guided, m_cur / m_prev [B,Cz,H,W]; the thresholding quantile is per logical sample over Cz*H*W. */
+int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sched, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
+                           float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
+                           void* stream);
 /* Dynamic thresholding alone: y = clamp(x0,-s,s)/s with s_b = max(quantile_ratio(|x0_b|), max_val); x0,y [B,n], s [B]. */
 int dsd_op_dpm_threshold(const float* x0, int B, int n, float ratio, float max_val, float* y, float* s_out, void* stream);
 

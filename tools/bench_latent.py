@@ -5,8 +5,13 @@ batch 16 of 256^2 one-channel slices, the SD-v1 f = 8 first stage (32x32x4 laten
 Three loops for the same steps, alternated in one process: the device loop (dsd_sample_latent) with graph replay off, with
 replay on, and the per-step Python loop (network call + dsd_op_sampler_update, the closure path).  hipEvents, median / min / max
 of --repeats runs.  Prints one JSON line.
+With --guidance-scale S (S != 1) three more loops join the alternation: the guided device loop at the batch
+(dsd_sample_latent_guided: 2B network rows per step, u = zeros), the unguided loop at the batch, and the unguided loop at twice
+the batch — the same network work as the guided one, so guided(B) against unguided(2B) is what the combine and the doubled
+state cost.  Each of the three is preceded by one untimed step of its own, so that no timed run pays for the plan of another
+batch size.
 
-    python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--json out.json]
+    python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--json out.json]
 """
 import argparse
 import json
@@ -40,7 +45,7 @@ def stats(v):
 
 def run_k(K, args):
     from diffusion_models_dsdiff_amd import _lib
-    from diffusion_models_dsdiff_amd._sched import run_device_loop, sampler_update
+    from diffusion_models_dsdiff_amd._sched import Guidance, run_device_loop, sampler_update
     from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
@@ -76,7 +81,18 @@ def run_k(K, args):
             sampler_update(sched, k, out, x, None, seed=1)
         return x
 
+    def cfg_loop(kind, n_steps=0):
+        if kind == "guided":
+            return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps,
+                                   guidance=Guidance(torch.zeros_like(c), args.guidance_scale, sched.steps))
+        if kind == "unguided":
+            return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)
+        return run_device_loop(unet, sched, torch.cat([xT, xT]), torch.cat([c, c]), seed=1, n_steps=n_steps)   # "unguided_2x"
+
+    cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
     c = ld.encode_conditions(cond, seed=3)["c_concat"][0]          # warm-up: plans, code objects
+    for kind in cfg_kinds:
+        cfg_loop(kind)
     y = device(False)
     device(True)
     device(True)
@@ -84,6 +100,7 @@ def run_k(K, args):
     ld.decode_first_stage(y)
     torch.cuda.synchronize()
     t = {"encode_ms": [], "device_loop_ms": [], "device_loop_graph_ms": [], "python_loop_ms": [], "decode_ms": []}
+    t.update({kind + "_loop_ms": [] for kind in cfg_kinds})
     outs = {}
     for _ in range(args.repeats):
         c, ms = timed(lambda: ld.encode_conditions(cond, seed=3)["c_concat"][0])
@@ -96,9 +113,18 @@ def run_k(K, args):
         t["python_loop_ms"].append(ms)
         _, ms = timed(lambda: ld.decode_first_stage(outs["dev"]))
         t["decode_ms"].append(ms)
+        for kind in cfg_kinds:
+            cfg_loop(kind, n_steps=1)                              # untimed: settles the plan of this batch size
+            torch.cuda.synchronize()
+            _, ms = timed(lambda: cfg_loop(kind))
+            t[kind + "_loop_ms"].append(ms)
     res = {k: stats(v) for k, v in t.items()}
-    for k in ("device_loop", "device_loop_graph", "python_loop"):
+    for k in ("device_loop", "device_loop_graph", "python_loop") + tuple(kind + "_loop" for kind in cfg_kinds):
         res[k + "_ms_per_step"] = res[k + "_ms"]["median"] / sched.steps
+    if cfg_kinds:
+        res["guidance_scale"] = args.guidance_scale
+        res["guided_over_unguided_2x"] = res["guided_loop_ms"]["median"] / res["unguided_2x_loop_ms"]["median"]
+        res["guided_over_unguided"] = res["guided_loop_ms"]["median"] / res["unguided_loop_ms"]["median"]
     e2e = res["encode_ms"]["median"] + res["device_loop_ms"]["median"] + res["decode_ms"]["median"]
     res["end_to_end_ms"] = e2e
     res["slices_per_s"] = B / (e2e / 1000.)
@@ -115,6 +141,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--keys", default="1,3")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--guidance-scale", type=float, default=1.0,
+                    help="!= 1: also time the guided loop against the unguided loop at the batch and at twice the batch")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     from diffusion_models_dsdiff_amd import _lib
