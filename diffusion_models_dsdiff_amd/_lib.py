@@ -31,6 +31,8 @@ EXPORTS = [
     "dsd_sample_latent", "dsd_sample_dpm_latent", "dsd_op_posterior_sample_scaled",
     "dsd_sample_guided", "dsd_sample_latent_guided", "dsd_sample_dpm_guided", "dsd_sample_dpm_latent_guided",
     "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
+    "dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent",
+    "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
 ]
 
 
@@ -63,6 +65,14 @@ class DsdDpmSchedule(C.Structure):
 
 class DsdGuidance(C.Structure):
     _fields_ = [("uncond", C.c_void_p), ("scale", C.POINTER(C.c_float)), ("n_scale", C.c_int32)]
+
+
+class DsdInpaint(C.Structure):
+    _fields_ = [("x0", C.c_void_p), ("mask", C.c_void_p), ("mask_channels", C.c_int32), ("noise", C.c_void_p)]
+
+
+class DsdInvertSchedule(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("coef", C.POINTER(C.c_float)), ("t_model", C.POINTER(C.c_float))]
 
 
 class DsdError(RuntimeError):
@@ -170,6 +180,16 @@ def lib() -> C.CDLL:
                                                i32, i32, i32, i32, f32p, vp]
     L.dsd_op_dpm_step_guided.argtypes = [C.POINTER(DsdDpmSchedule), i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p,
                                          i32, i32, i32, i32, vp]
+    ip, vs = C.POINTER(DsdInpaint), C.POINTER(DsdInvertSchedule)
+    L.dsd_sample_masked.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_sample_latent_masked.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32,
+                                           i32, i32, i32, vp]
+    L.dsd_invert.argtypes = [vp, vs, gp, f32p, i32, f32p, i32, i32, i32, i32, i32, vp]
+    L.dsd_invert_latent.argtypes = [vp, vs, gp, f32p, i32, f32p, i32, i32, i32, i32, i32, i32, vp]
+    L.dsd_op_mask_blend.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, f32p, i64, i32, f32p, C.c_uint64, C.c_uint64, i32, i32,
+                                    i32, i32, vp]
+    L.dsd_op_q_sample.argtypes = [f32p, f32p, f32p, f32p, C.c_uint64, C.c_uint64, f32p, i64, i32, i32, i32, i32, vp]
+    L.dsd_op_ddim_invert_step.argtypes = [C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, i64, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -7,7 +7,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import DSD_NCOEF, DsdGuidance, DsdSchedule, check, dptr, lib, stream_ptr
+from ._lib import DSD_NCOEF, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
 
 
 class Schedule:
@@ -71,6 +71,42 @@ class Guidance:
         g.scale = self.scale.ctypes.data_as(C.POINTER(C.c_float))
         g.n_scale = int(self.scale.shape[0])
         return g
+
+
+class Inpaint:
+    """Masked sampling of a device loop (dsd_inpaint; ddim.py:160-163, ddpm.py:1085-1087): ``x0`` is the image the mask keeps,
+    laid out like the state; ``mask`` is [B,1,H,W] (broadcast over the channels, the form log_images builds) or [B,C,H,W], 1 where
+    x0 is kept and 0 where the loop samples; ``noise`` ([steps,B,C,H,W], optional) feeds q_sample's draws, else Philox."""
+
+    def __init__(self, x0: torch.Tensor, mask: torch.Tensor, noise: Optional[torch.Tensor] = None):
+        if mask is None:
+            raise ValueError("masked sampling needs a mask")
+        if x0 is None:
+            raise ValueError("a mask needs the image it keeps (x0)")
+        self.x0, self.mask, self.noise = x0, mask, noise
+
+    def check(self, x: torch.Tensor, steps: int) -> None:
+        """Against the state ``x`` [B,C,H,W] of a loop that executes ``steps`` iterations."""
+        B, Cz, H, W = x.shape
+        like = lambda t: torch.is_tensor(t) and t.dtype == x.dtype and t.device == x.device
+        desc = lambda t: f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', None)} {getattr(t, 'device', None)}"
+        if not like(self.x0) or tuple(self.x0.shape) != tuple(x.shape):
+            raise ValueError(f"x0 must have the shape, dtype and device of the state: {desc(self.x0)} against {desc(x)}")
+        if not like(self.mask) or self.mask.dim() != 4 or tuple(self.mask.shape) not in ((B, 1, H, W), (B, Cz, H, W)):
+            raise ValueError(f"the mask must be [B,1,H,W] or [B,C,H,W] with the dtype and device of the state: {desc(self.mask)} "
+                             f"against {desc(x)}")
+        if self.noise is not None and (not like(self.noise) or tuple(self.noise.shape) != (int(steps), B, Cz, H, W)):
+            raise ValueError(f"mask_noise must be [steps,B,C,H,W] = {(int(steps), B, Cz, H, W)} with the dtype and device of the "
+                             f"state: {desc(self.noise)}")
+
+    def bind(self) -> DsdInpaint:
+        """The C struct (the tensors it points to stay alive on self)."""
+        self._x0, self._mask = self.x0.detach().float().contiguous(), self.mask.detach().float().contiguous()
+        self._noise = self.noise.detach().float().contiguous() if self.noise is not None else None
+        p = DsdInpaint()
+        p.x0, p.mask, p.mask_channels = self._x0.data_ptr(), self._mask.data_ptr(), int(self._mask.shape[1])
+        p.noise = self._noise.data_ptr() if self._noise is not None else None
+        return p
 
 
 def guidance_active(scale, uncond, ucg_schedule=None) -> bool:
@@ -143,16 +179,25 @@ def _seed_from_torch() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
+def philox_seed(seed: Optional[int] = None) -> int:
+    """``seed`` itself, or one drawn from torch's generator when none is given."""
+    return int(seed) if seed is not None else _seed_from_torch()
+
+
 @torch.no_grad()
 def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor,
                     step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                    first_step: int = 0, n_steps: int = 0, guidance: Optional[Guidance] = None) -> torch.Tensor:
+                    first_step: int = 0, n_steps: int = 0, guidance: Optional[Guidance] = None,
+                    inpaint: Optional[Inpaint] = None) -> torch.Tensor:
     """x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations.
     With the plain UNetModel the state is a latent x_T [B,Cz,H,W] (dsd_sample_latent; step_noise [steps,B,Cz,H,W]).
     ``guidance``: classifier-free guidance (dsd_sample_guided / dsd_sample_latent_guided, mode B_DDIM); its unconditional
-    conditioning must have the shape, dtype and device of ``cond``."""
+    conditioning must have the shape, dtype and device of ``cond``.
+    ``inpaint``: masked sampling (dsd_sample_masked / dsd_sample_latent_masked, modes B_DDIM and B_DDPM), guided or not."""
     if guidance is not None:
         guidance.check(cond, sched.steps)
+    if inpaint is not None:
+        inpaint.check(x_T, sched.steps)
     if unet is None:
         raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
     if not x_T.is_cuda:
@@ -161,6 +206,7 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
     x = x_T.detach().float().contiguous().clone()
     cond = cond.detach().float().contiguous()
     g = guidance.bind() if guidance is not None else None
+    inp = inpaint.bind() if inpaint is not None else None
     if is_latent_denoiser(unet):
         check_latent_io(unet, x, cond)
         B, Cz, H, W = x.shape
@@ -170,6 +216,11 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
                 raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
         if seed is None:
             seed = _seed_from_torch()
+        if inp is not None:
+            check(lib().dsd_sample_latent_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp),
+                                                 dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise), C.c_uint64(seed), B, H,
+                                                 W, first_step, n_steps, stream_ptr()))
+            return x
         if g is not None:
             check(lib().dsd_sample_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cz,
                                                  dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
@@ -184,6 +235,11 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
         assert step_noise.shape == (sched.steps, B, 1, H, W), "step_noise must be [steps,B,1,H,W]"
     if seed is None:
         seed = _seed_from_torch()
+    if inp is not None:
+        check(lib().dsd_sample_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp), dptr(cond),
+                                      cond.shape[1], dptr(x), dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps,
+                                      stream_ptr()))
+        return x
     if g is not None:
         check(lib().dsd_sample_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), dptr(step_noise),
                                       C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
@@ -227,3 +283,98 @@ def sampler_update_guided(sched: Schedule, k: int, out_uncond: torch.Tensor, out
                                              x2.shape[1] * H * W, dptr(noise.float().contiguous()) if noise is not None else None,
                                              C.c_uint64(seed), B, Cz, H, W, dptr(x0), stream_ptr()))
     return x0
+
+
+def invert_coefficients(alphas_next: torch.Tensor, alphas: torch.Tensor) -> np.ndarray:
+    """[steps,2] fp32 (cx, ce) of DDIMSampler.encode's update (ddim.py:292-295), formed with the reference's own torch
+    expressions on 0-d tensors of the reference's dtypes and rounded to fp32 once — where a 0-d tensor meets the fp32 state.
+    ``alphas_next`` is fp32; ``alphas`` is float64 for the DDIM sub-schedule (torch.tensor of a numpy float64 array, :276), so
+    there the scalar arithmetic is float64; with use_original_steps both are fp32 buffers."""
+    n = int(alphas_next.shape[0])
+    coef = np.zeros((n, 2), dtype=np.float32)
+    for i in range(n):
+        cx = (alphas_next[i] / alphas[i]).sqrt()
+        ce = alphas_next[i].sqrt() * ((1 / alphas_next[i] - 1).sqrt() - (1 / alphas[i] - 1).sqrt())
+        coef[i, 0], coef[i, 1] = float(cx.to(torch.float32)), float(ce.to(torch.float32))
+    return coef
+
+
+@torch.no_grad()
+def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor, guidance: Optional[Guidance] = None,
+                    first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
+    """DDIM inversion on the device (dsd_invert / dsd_invert_latent): ``coef`` [steps,2] from invert_coefficients.  The model
+    time of iteration i is the loop index i itself — DDIMSampler.encode passes ``i``, not a timestep of the schedule
+    (ddim.py:282); a quirk of the reference, kept for parity."""
+    coef = np.ascontiguousarray(coef, dtype=np.float32)
+    steps = int(coef.shape[0])
+    assert coef.shape == (steps, 2)
+    if guidance is not None:
+        guidance.check(cond, steps)
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
+    if not x0.is_cuda:
+        raise RuntimeError("DDIM inversion runs on the MI355X only (no CPU fallback): x0 is on the CPU")
+    unet.sync_params()
+    x = x0.detach().float().contiguous().clone()
+    cond = cond.detach().float().contiguous()
+    t_model = np.arange(steps, dtype=np.float32)
+    sc = DsdInvertSchedule()
+    sc.steps = steps
+    sc.coef = coef.ctypes.data_as(C.POINTER(C.c_float))
+    sc.t_model = t_model.ctypes.data_as(C.POINTER(C.c_float))
+    g = guidance.bind() if guidance is not None else None
+    gp = C.byref(g) if g is not None else None
+    B, Cz, H, W = x.shape
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, x, cond)
+        check(lib().dsd_invert_latent(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), Cz, B, H, W, first_step,
+                                      n_steps, stream_ptr()))
+        return x
+    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
+    check(lib().dsd_invert(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), B, H, W, first_step, n_steps,
+                           stream_ptr()))
+    return x
+
+
+def _rows(x: torch.Tensor, state_channels: Optional[int]):
+    """(Cz, row stride) of a contiguous [rows,C,H,W] tensor whose first ``state_channels`` (default: all) channels are the state."""
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+    return int(state_channels or x.shape[1]), int(x.shape[1] * x.shape[2] * x.shape[3])
+
+
+@torch.no_grad()
+def mask_blend(a: float, s: float, x0: torch.Tensor, mask: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor],
+               seed: int = 0, step: int = 0, guided: bool = False, state_channels: Optional[int] = None) -> None:
+    """One blend (dsd_op_mask_blend), x updated in place: x = (a*x0 + s*z)*mask + (1 - mask)*x.  ``x`` is [B,Cz,H,W], or a
+    [B,Cz+Cc,H,W] denoiser input with ``state_channels`` = Cz; ``guided``: 2B rows, row b read, rows b and B+b written."""
+    B, Cz, H, W = x0.shape
+    cz, stride = _rows(x, state_channels)
+    assert cz == Cz and x.shape[0] == (2 * B if guided else B) and tuple(x.shape[2:]) == (H, W)
+    check(lib().dsd_op_mask_blend(float(a), float(s), dptr(x0.float().contiguous()), dptr(mask.float().contiguous()),
+                                  int(mask.shape[1]), dptr(x), stride, int(guided),
+                                  dptr(noise.float().contiguous()) if noise is not None else None, C.c_uint64(seed),
+                                  C.c_uint64(step), B, Cz, H, W, stream_ptr()))
+
+
+@torch.no_grad()
+def q_sample_rows(a: torch.Tensor, s: torch.Tensor, x0: torch.Tensor, noise: Optional[torch.Tensor], seed: int = 0,
+                  step: int = 0) -> torch.Tensor:
+    """a[b]*x0_b + s[b]*z_b (dsd_op_q_sample): a, s device fp32 [B] (coefficient tables gathered by t); z fed or Philox."""
+    B, Cz, H, W = x0.shape
+    out = torch.empty((B, Cz, H, W), device=x0.device, dtype=torch.float32)
+    check(lib().dsd_op_q_sample(dptr(a.float().contiguous()), dptr(s.float().contiguous()), dptr(x0.float().contiguous()),
+                                dptr(noise.float().contiguous()) if noise is not None else None, C.c_uint64(seed),
+                                C.c_uint64(step), dptr(out), 0, B, Cz, H, W, stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def ddim_invert_step(cx: float, ce: float, out_cond: torch.Tensor, x: torch.Tensor, out_uncond: Optional[torch.Tensor] = None,
+                     scale: float = 1.0, state_channels: Optional[int] = None) -> None:
+    """One inversion step (dsd_op_ddim_invert_step), x updated in place; with ``out_uncond`` the guided step on 2B rows."""
+    B, Cz, H, W = out_cond.shape
+    cz, stride = _rows(x, state_channels)
+    assert cz == Cz and x.shape[0] == (2 * B if out_uncond is not None else B) and tuple(x.shape[2:]) == (H, W)
+    check(lib().dsd_op_ddim_invert_step(float(cx), float(ce), dptr(out_uncond.float().contiguous()) if out_uncond is not None else None,
+                                        dptr(out_cond.float().contiguous()), float(scale), dptr(x), stride, B, Cz, H, W,
+                                        stream_ptr()))

@@ -806,6 +806,203 @@ int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sc, int k, const float* out_u
     DSD_CATCH
 }
 
+// ------------------------------------------------------------------------------------------- image-to-image
+// Masked sampling: ddim.py:160-163 blends in front of every network evaluation, ddpm.py:1085-1087 after every update.  Every
+// check runs before anything is bound or copied, so a rejected call leaves the state untouched.
+static void check_masked(const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, int Cz) {
+    check_schedule(sc);
+    DSD_CHECK(sc->mode == DSD_MODE_B_DDPM || sc->mode == DSD_MODE_B_DDIM,
+              "masked sampling exists only in the loops of the LDM family (DSD_MODE_B_DDPM / DSD_MODE_B_DDIM); the reference has no "
+              "mask in mode %d", sc->mode);
+    DSD_CHECK(!(g && sc->mode == DSD_MODE_B_DDPM), "the masked DDPM loop (DSD_MODE_B_DDPM) has no guidance in the reference");
+    if (g) {
+        check_guided_schedule(sc);
+        check_guidance(g, sc->steps);
+    }
+    DSD_CHECK(inp && inp->mask, "masked sampling needs a mask (mask is null)");
+    DSD_CHECK(inp->x0, "a mask needs the image it keeps (x0 is null)");
+    DSD_CHECK(inp->mask_channels == 1 || inp->mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken",
+              inp->mask_channels, Cz);
+}
+
+static void blend_step(const dsd_schedule* sc, int k, const dsd_inpaint* inp, float* x, int64_t x_bs, bool dup, uint64_t seed, int B,
+                       int Cz, int64_t hw, const int64_t* ids, hipStream_t s) {
+    const float* c = sc->coef + (size_t)k * DSD_NCOEF;
+    q_sample_blend(c[0], c[1], nullptr, nullptr, inp->x0, inp->mask, inp->mask_channels, x,
+                   inp->noise ? inp->noise + (size_t)k * B * Cz * hw : nullptr, seed, (uint64_t)k, B, Cz, (int)hw, s, x_bs, dup, ids);
+}
+
+int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
+                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                      void* stream) {
+    DSD_TRY
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    check_masked(sc, g, inp, 1);
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
+    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    float* xs = x;
+    if (g) {
+        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
+    } else {
+        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
+        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
+        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
+        bind_sampling_io(h, x, cond, Cc, hw, s);
+    }
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const bool ddim = sc->mode == DSD_MODE_B_DDIM;
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        if (ddim) blend_step(sc, k, inp, xs, hw, g != nullptr, philox_seed, B, 1, hw, ids, s);
+        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        const float* nz = noise ? noise + (size_t)k * B * hw : nullptr;
+        if (g)
+            sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * hw, g->scale[k], xs, nz, philox_seed, (uint64_t)k, B,
+                               (int)hw, s, nullptr, ids);
+        else
+            sampler_update(step_coef(sc, k), h->mout, xs, nz, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids);
+        if (!ddim) blend_step(sc, k, inp, xs, hw, false, philox_seed, B, 1, hw, ids, s);
+    }
+    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
+                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
+                             int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    check_masked(sc, g, inp, Cz);
+    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const bool ddim = sc->mode == DSD_MODE_B_DDIM;
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        if (ddim) blend_step(sc, k, inp, h->lat_in, x_bs, g != nullptr, philox_seed, B, Cz, hw, ids, s);
+        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        const float* nz = noise ? noise + (size_t)k * B * Cz * hw : nullptr;
+        if (g)
+            sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * Cz * hw, g->scale[k], h->lat_in, nz, philox_seed,
+                               (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
+        else
+            sampler_update(step_coef(sc, k), h->mout, h->lat_in, nz, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
+        if (!ddim) blend_step(sc, k, inp, h->lat_in, x_bs, false, philox_seed, B, Cz, hw, ids, s);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+// DDIM inversion (ddim.py:263-308): the sampling loops' bindings, the inversion step in place of the update
+static void check_invert(const dsd_invert_schedule* sc, const dsd_guidance* g) {
+    DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
+    if (g) check_guidance(g, sc->steps);
+}
+
+int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
+               int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    check_invert(sc, g);
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    float* xs = x;
+    if (g) {
+        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
+    } else {
+        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
+        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
+        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
+        bind_sampling_io(h, x, cond, Cc, hw, s);
+    }
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], g ? h->mout : nullptr, g ? h->mout + (size_t)B * hw : h->mout,
+                         g ? g->scale[k] : 1.f, xs, B, 1, (int)hw, s);
+    }
+    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_invert_latent(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                      int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    check_invert(sc, g);
+    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    set_device(h ? h->device : 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
+    const int k0 = first_step < 0 ? 0 : first_step;
+    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
+    for (int k = k0; k < k1; ++k) {
+        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
+        net_run_cached(h, s);
+        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], g ? h->mout : nullptr, g ? h->mout + (size_t)B * Cz * hw : h->mout,
+                         g ? g->scale[k] : 1.f, h->lat_in, B, Cz, (int)hw, s, x_bs);
+    }
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+static void check_op_state(int B, int Cz, int H, int W, int64_t x_row_stride) {
+    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
+    DSD_CHECK(x_row_stride == 0 || x_row_stride >= (int64_t)Cz * H * W, "x_row_stride %lld is smaller than one sample (%lld)",
+              (long long)x_row_stride, (long long)Cz * H * W);
+}
+
+int dsd_op_mask_blend(float a, float s, const float* x0, const float* mask, int mask_channels, float* x, int64_t x_row_stride,
+                      int guided, const float* noise, uint64_t philox_seed, uint64_t step, int B, int Cz, int H, int W,
+                      void* stream) {
+    DSD_TRY
+    DSD_CHECK(x0 && mask && x, "null argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    DSD_CHECK(mask_channels == 1 || mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken", mask_channels, Cz);
+    q_sample_blend(a, s, nullptr, nullptr, x0, mask, mask_channels, x, noise, philox_seed, step, B, Cz, H * W, (hipStream_t)stream,
+                   x_row_stride, guided != 0);
+    DSD_CATCH
+}
+
+int dsd_op_q_sample(const float* a, const float* s, const float* x0, const float* noise, uint64_t philox_seed, uint64_t step,
+                    float* out, int64_t out_row_stride, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(a && s && x0 && out, "null argument");
+    check_op_state(B, Cz, H, W, out_row_stride);
+    q_sample_blend(0.f, 0.f, a, s, x0, nullptr, 0, out, noise, philox_seed, step, B, Cz, H * W, (hipStream_t)stream, out_row_stride);
+    DSD_CATCH
+}
+
+int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const float* out_cond, float scale, float* x,
+                            int64_t x_row_stride, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(out_cond && x, "null argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    ddim_invert_step(cx, ce, out_uncond, out_cond, scale, x, B, Cz, H * W, (hipStream_t)stream, x_row_stride);
+    DSD_CATCH
+}
+
 int dsd_op_dpm_threshold(const float* x0, int B, int n, float ratio, float max_val, float* y, float* s_out, void* stream) {
     DSD_TRY
     DSD_CHECK(x0 && y && s_out && B >= 0 && n >= 1 && ratio >= 0.f && ratio <= 1.f, "bad argument");

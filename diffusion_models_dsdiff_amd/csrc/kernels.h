@@ -270,6 +270,16 @@ void sampler_update_cfg(const StepCoef& sc, const float* out_u, const float* out
 // DPM-Solver: noise = noise_u + scale*(noise_c - noise_u) on the two noise predictions, then dpm_step's arithmetic
 void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
                   const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
+// Image-to-image.  q_sample (+ mask blend): img_orig = a*x0 + s*z with a, s scalars or per row from the device arrays a_row /
+// s_row; mask != nullptr ([B,mask_ch,HW], mask_ch 1 or Cz): x = img_orig*mask + (1 - mask)*x, else x = img_orig.  x0 / noise are
+// [B,Cz,HW]; the state row b is x + b*x_bs (0 = Cz*HW); dup: also written to row B+b (guided 2B-row state).  noise == nullptr:
+// Philox stream (seed, step + 2^32), counter keyed by slice_ids like the update's.
+void q_sample_blend(float a, float s, const float* a_row, const float* s_row, const float* x0, const float* mask, int mask_ch,
+                    float* x, const float* noise, uint64_t seed, uint64_t step, int B, int Cz, int HW, hipStream_t st,
+                    int64_t x_bs = 0, bool dup = false, const int64_t* slice_ids = nullptr);
+// DDIM inversion step: x = cx*x + ce*e, e = out_c or (out_u != nullptr) out_u + scale*(out_c - out_u), then written to both rows
+void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c, float scale, float* x, int B, int Cz, int HW,
+                      hipStream_t st, int64_t x_bs = 0);
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s);
 void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_t s);
 // DiagonalGaussianDistribution.sample (ldm/modules/distributions/distributions.py:24-37): moments [B,2E,HW] (NCHW) ->

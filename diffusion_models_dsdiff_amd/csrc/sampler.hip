@@ -442,6 +442,111 @@ void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int 
     check_launch("dpm_update_cfg");
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Image-to-image: q_sample / mask blend (ddim.py:160-163, ddpm.py:356-359,1085-1087) and the DDIM inversion step (ddim.py:282-295).
+// Logical sample b: x0 and noise rows are contiguous [B,n] (n = Cz*HW), the state row sits at x + b*x_bs, and with `dup` (a guided
+// loop's 2B-row state) the result also goes to row B+b.
+//   img_orig = a*x0 + s*z                       a, s: the iteration's scalars, or per row from a_row / s_row (q_sample, t is [B])
+//   x        = img_orig*mask + (1 - mask)*x     mask [B,mc,HW], mc = 1 (broadcast over the channels) or Cz; mask == nullptr: x = img_orig
+// z is fed, or normal slice*n + p of the Philox stream (seed, step + 2^32): the update of iteration `step` draws from (seed, step),
+// so the two never share a counter block.  V = 4 needs n % 4 == 0 and, for a one-channel mask, HW % 4 == 0 (a pack stays inside
+// one channel); the launcher checks.
+static constexpr uint64_t kBlendStream = 1ull << 32;
+
+// Grid: x over the packs of one sample (capped, strided), y = the sample — the row's coefficients and its slice id are
+// block-uniform and no 64-bit division is left.  BLEND selects the mask blend (scalar a, s) or the plain q_sample (a_row, s_row):
+// one kernel with every argument live spilled scalar registers.
+template <int V, bool BLEND>
+__global__ __launch_bounds__(256) void q_sample_blend_kernel(float a, float s, const float* __restrict__ a_row,
+                                                             const float* __restrict__ s_row, const float* __restrict__ x0,
+                                                             const float* __restrict__ mask, int mc, float* __restrict__ x,
+                                                             const float* __restrict__ noise, uint64_t seed, uint64_t step, int B,
+                                                             int n, int hw, int64_t x_bs, int dup,
+                                                             const int64_t* __restrict__ slice_ids) {
+    const int b = blockIdx.y;
+    const float ca = BLEND ? a : a_row[b], cs = BLEND ? s : s_row[b];
+    const int64_t row = (int64_t)b * n;                                       // in the [B,n] tensors
+    const int64_t ctr = slice_ids ? slice_ids[b] * n : row;                   // Philox counter of the row's first element
+    float* xr = x + (int64_t)b * x_bs;
+    for (int p = (blockIdx.x * 256 + threadIdx.x) * V; p < n; p += gridDim.x * 256 * V) {
+        const Pack<V> xs = ld_pack<V>(x0 + row + p);
+        const Pack<V> z = noise ? ld_pack<V>(noise + row + p) : philox_normal_pack<V>(ctr + p, seed, step + kBlendStream);
+        Pack<V> res;
+#pragma unroll
+        for (int j = 0; j < V; ++j) res.v[j] = ca * xs.v[j] + cs * z.v[j];            // q_sample ddpm.py:358-359
+        if constexpr (BLEND) {
+            const Pack<V> m = ld_pack<V>(mask + (mc == 1 ? (int64_t)b * hw + p % hw : row + p));
+            const Pack<V> xt = ld_pack<V>(xr + p);
+#pragma unroll
+            for (int j = 0; j < V; ++j) res.v[j] = res.v[j] * m.v[j] + (1.f - m.v[j]) * xt.v[j];   // ddim.py:163
+        }
+        st_pack<V>(xr + p, res);
+        if (BLEND && dup) st_pack<V>(xr + p + (int64_t)B * x_bs, res);
+    }
+}
+
+void q_sample_blend(float a, float s, const float* a_row, const float* s_row, const float* x0, const float* mask, int mask_ch,
+                    float* x, const float* noise, uint64_t seed, uint64_t step, int B, int Cz, int HW, hipStream_t st, int64_t x_bs,
+                    bool dup, const int64_t* slice_ids) {
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    DSD_CHECK(n <= (int64_t)1 << 30, "q_sample / mask blend: one sample has %lld elements; up to 2^30 are taken", (long long)n);
+    if (x_bs <= 0) x_bs = n;
+    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && (!mask || mask_ch != 1 || HW % 4 == 0) && aligned16(x0) && aligned16(mask) &&
+                    aligned16(x) && aligned16(noise);
+    DSD_CHECK(B <= 65535, "q_sample / mask blend: %d samples; up to 65535 are taken", B);
+    const dim3 grid((unsigned)std::min<int64_t>((n / (v4 ? 4 : 1) + 255) / 256, 2048), (unsigned)B);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, s, a_row, s_row, x0, mask, mask_ch, x, noise, seed, step, B, (int)n, HW,
+                           x_bs, dup ? 1 : 0, slice_ids);
+    };
+    if (mask)
+        v4 ? launch(q_sample_blend_kernel<4, true>) : launch(q_sample_blend_kernel<1, true>);
+    else
+        v4 ? launch(q_sample_blend_kernel<4, false>) : launch(q_sample_blend_kernel<1, false>);
+    check_launch("q_sample_blend");
+}
+
+// DDIM inversion (ddim.py:292-295): x_next = cx*x + ce*e as xt_weighted + weighted_noise_pred, e the raw network output or,
+// guided (mo_u != nullptr), e_u + gs*(e_c - e_u) from the two output halves (:287-290); x_next goes to rows b and, guided, B+b.
+template <int V>
+__global__ __launch_bounds__(256) void ddim_invert_kernel(float cx, float ce, const float* __restrict__ mo_u,
+                                                          const float* __restrict__ mo_c, float gs, float* __restrict__ x, int B,
+                                                          int64_t n, int64_t x_bs) {
+    const int64_t nv = n / V, total = (int64_t)B * nv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t li = b * n + p, xi = b * x_bs + p;
+        Pack<V> e = ld_pack<V>(mo_c + li);
+        const Pack<V> xt = ld_pack<V>(x + xi);
+        if (mo_u) {
+            const Pack<V> eu = ld_pack<V>(mo_u + li);
+#pragma unroll
+            for (int j = 0; j < V; ++j) e.v[j] = eu.v[j] + gs * (e.v[j] - eu.v[j]);
+        }
+        Pack<V> res;
+#pragma unroll
+        for (int j = 0; j < V; ++j) res.v[j] = cx * xt.v[j] + ce * e.v[j];
+        st_pack<V>(x + xi, res);
+        if (mo_u) st_pack<V>(x + xi + (int64_t)B * x_bs, res);
+    }
+}
+
+void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c, float scale, float* x, int B, int Cz, int HW,
+                      hipStream_t st, int64_t x_bs) {
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    if (x_bs <= 0) x_bs = n;
+    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x);
+    if (v4)
+        hipLaunchKernelGGL(ddim_invert_kernel<4>, dim3(cfg_blocks(B * (n / 4))), dim3(256), 0, st, cx, ce, out_u, out_c, scale, x, B, n,
+                           x_bs);
+    else
+        hipLaunchKernelGGL(ddim_invert_kernel<1>, dim3(cfg_blocks(B * n)), dim3(256), 0, st, cx, ce, out_u, out_c, scale, x, B, n, x_bs);
+    check_launch("ddim_invert");
+}
+
 // scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed
 // (1.0 for the plain DiagonalGaussianDistribution.sample: x * 1.0f is exact).  With B = batch*K rows ordered (sample, key),
 // z [B*K,E,HW] IS the [batch,K*E,HW] 'concat' conditioning: key k of a sample lands in channels [k*E,(k+1)*E).

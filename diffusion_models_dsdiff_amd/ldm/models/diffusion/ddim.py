@@ -1,14 +1,21 @@
 """DDIMSampler — drop-in for ldm/models/diffusion/ddim.py (make_schedule :25-55, sample :57-126,
 ddim_sampling :128-185, p_sample_ddim :187-261), executed by dsd_sample (mode B_DDIM); with
-``unconditional_guidance_scale`` / ``unconditional_conditioning`` / ``ucg_schedule`` by dsd_sample_guided."""
+``unconditional_guidance_scale`` / ``unconditional_conditioning`` / ``ucg_schedule`` by dsd_sample_guided; with ``mask`` / ``x0``
+by dsd_sample_masked.  encode :263-308 runs dsd_invert, stochastic_encode :310-324 dsd_op_q_sample, decode :326-346 the tail of
+the sampling loop."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from .... import _lib
-from ...._sched import (Guidance, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active,
-                         run_device_loop)
+from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active,
+                         invert_coefficients, philox_seed, q_sample_rows, run_device_loop, run_invert_loop)
+
+
+class MaskWithoutX0(AssertionError, NotImplementedError):
+    """``mask`` without ``x0``: the reference asserts (ddim.py:161); this sampler used to answer every mask with
+    NotImplementedError.  Callers written against either keep working."""
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -85,14 +92,18 @@ class DDIMSampler(object):
                clip_denoised=True, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None,
-               ucg_schedule=None, step_noise=None, seed=None, **kwargs):
+               ucg_schedule=None, step_noise=None, seed=None, mask_noise=None, **kwargs):
         """:57-126 -> (samples, intermediates).  Unsupported reference options raise instead of being ignored.
         Classifier-free guidance (:194-219) runs in the device loop: ``unconditional_conditioning`` comes in the form of
-        ``conditioning`` (dict with c_concat lists, list, or tensor); ``ucg_schedule`` holds one scale per executed step."""
-        if mask is not None or quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
-                or temperature != 1. or noise_dropout != 0.:
-            raise NotImplementedError("inpainting mask / quantisation / score corrector / dynamic threshold / temperature / "
-                                      "noise dropout are not on the medical hot path")
+        ``conditioning`` (dict with c_concat lists, list, or tensor); ``ucg_schedule`` holds one scale per executed step.
+        ``mask`` / ``x0`` (:160-163) run in the device loop too, guided or not: in front of every network evaluation the state
+        becomes q_sample(x0, t)*mask + (1 - mask)*state.  ``mask_noise`` ([steps,B,C,H,W]) feeds q_sample's draws (an extension
+        like ``step_noise``); without it they are Philox normals of ``seed``."""
+        if quantize_x0 or score_corrector is not None or dynamic_threshold is not None or temperature != 1. or noise_dropout != 0.:
+            raise NotImplementedError("quantisation / score corrector / dynamic threshold / temperature / noise dropout are not "
+                                      "on the medical hot path")
+        if mask is not None and x0 is None:
+            raise MaskWithoutX0("a mask needs x0, the image it keeps (ddim.py:161)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose,
                            ddim_discretize=kwargs.get("ddim_discretize", "uniform"))
         C_, H, W = shape
@@ -107,7 +118,98 @@ class DDIMSampler(object):
             u = cat_unconditional(conditioning, unconditional_conditioning, device)
             guidance = Guidance(u, ucg_schedule if ucg_schedule is not None else unconditional_guidance_scale, sched.steps)
         img = x_T if x_T is not None else torch.randn(size, device=device)
-        unet = find_unet(self.model.model if hasattr(self.model, "model") else self.model)
-        out = run_device_loop(unet, sched, img.to(device), cat_conditioning(conditioning, device), step_noise=step_noise,
-                              seed=seed, guidance=guidance)
+        inpaint = None
+        if mask is not None:                                                          # x0 alone changes nothing (:160)
+            inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
+        out = run_device_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device), step_noise=step_noise,
+                              seed=seed, guidance=guidance, inpaint=inpaint)
         return out, {"x_inter": [img, out], "pred_x0": [img, out]}
+
+    def _unet(self):
+        return find_unet(self.model.model if hasattr(self.model, "model") else self.model)
+
+    def _guidance(self, cond, scale, uncond, steps, device):
+        if not guidance_active(scale, uncond):
+            return None
+        return Guidance(cat_unconditional(cond, uncond, device), scale, steps)
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None):
+        """:263-308, deterministic DDIM inversion on the device -> (x_next, out).  The reference hands the loop index i to the
+        network as its time (:282) and feeds the output to the update as a noise prediction whatever the parameterization; the
+        first is kept, a v-model raises.  Intermediates are read between first_step / n_steps segments of the loop."""
+        if callback is not None:
+            raise NotImplementedError("per-step callbacks are not on the device loop")
+        if self.model.parameterization == "v":
+            raise NotImplementedError("DDIMSampler.encode takes the network output as a noise prediction (ddim.py:284-295); for a "
+                                      "v-model the reference's inversion is not one, so it is not reproduced")
+        num_reference_steps = self.ddpm_num_timesteps if use_original_steps else self.ddim_timesteps.shape[0]
+        assert t_enc <= num_reference_steps                                           # :268
+        n = int(t_enc)
+        if use_original_steps:
+            buf = lambda name: getattr(self.model, name).detach().float().cpu()
+            alphas_next, alphas = buf("alphas_cumprod")[:n], buf("alphas_cumprod_prev")[:n]
+        else:
+            alphas_next = torch.from_numpy(np.asarray(self.ddim_alphas[:n], dtype=np.float32))
+            alphas = torch.tensor(np.asarray(self.ddim_alphas_prev[:n], dtype=np.float64))                  # :276
+        coef = invert_coefficients(alphas_next, alphas)
+        device = self.model.betas.device
+        if unconditional_guidance_scale != 1.:
+            assert unconditional_conditioning is not None                             # :286
+        cond = cat_conditioning(c, device)
+        guidance = self._guidance(c, unconditional_guidance_scale, unconditional_conditioning, n, device)
+        marks = []                                                                    # :296-302
+        for i in range(n):
+            if return_intermediates and (i % (n // return_intermediates) == 0 and i < n - 1 or i >= n - 2):
+                marks.append(i)
+        x_next, unet, done = x0.to(device), self._unet(), 0
+        intermediates = []
+        for i in marks + ([n - 1] if n and (not marks or marks[-1] != n - 1) else []):
+            x_next = run_invert_loop(unet, coef, x_next, cond, guidance, first_step=done, n_steps=i + 1 - done)
+            done = i + 1
+            if i in marks:
+                intermediates.append(x_next)
+        out = {"x_encoded": x_next, "intermediate_steps": marks}
+        if return_intermediates:
+            out.update({"intermediates": intermediates})
+        return x_next, out
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, seed=None):
+        """:310-324: sqrt(alphas)[t] * x0 + sqrt(1 - alphas)[t] * noise, ``t`` a [B] index tensor into the current schedule.
+        ``seed`` (extension): Philox normals when no ``noise`` is given."""
+        if use_original_steps:
+            sa = self.model.sqrt_alphas_cumprod.detach().float().cpu()
+            s1 = self.model.sqrt_one_minus_alphas_cumprod.detach().float().cpu()
+        else:
+            sa = torch.sqrt(torch.from_numpy(np.asarray(self.ddim_alphas, dtype=np.float32)))
+            s1 = torch.from_numpy(np.asarray(self.ddim_sqrt_one_minus_alphas, dtype=np.float32))
+        if not x0.is_cuda:
+            raise RuntimeError("stochastic_encode runs on the MI355X only (no CPU fallback): x0 is on the CPU")
+        idx = t.detach().long().cpu()
+        return q_sample_rows(sa[idx].to(x0.device), s1[idx].to(x0.device), x0, noise.to(x0.device) if noise is not None else None,
+                             seed=philox_seed(seed) if noise is None else 0)
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, callback=None, step_noise=None, seed=None):
+        """:326-346: the last ``t_start`` iterations of the current schedule (timesteps[:t_start], flipped), i.e. the sampling
+        loop from first_step = steps - t_start, with the eta of the last make_schedule and p_sample_ddim's default clipping.
+        ``step_noise`` ([t_start,B,C,H,W]) / ``seed`` are extensions."""
+        if callback is not None:
+            raise NotImplementedError("per-step callbacks are not on the device loop")
+        sched = self._schedule(use_original_steps, True)
+        t_start = min(int(t_start), sched.steps)
+        first = sched.steps - t_start
+        if t_start <= 0:
+            return x_latent
+        device = self.model.betas.device
+        guidance = self._guidance(cond, unconditional_guidance_scale, unconditional_conditioning, sched.steps, device)
+        if step_noise is not None:                                                    # rows of the executed iterations
+            full = torch.zeros((sched.steps,) + tuple(step_noise.shape[1:]), device=device, dtype=torch.float32)
+            full[first:] = step_noise.to(device)
+            step_noise = full
+        return run_device_loop(self._unet(), sched, x_latent.to(device), cat_conditioning(cond, device), step_noise=step_noise,
+                               seed=seed, first_step=first, guidance=guidance)
+

@@ -288,6 +288,19 @@ class LatentDiffusion(DDPM):
         out = self.model(x_noisy, t, **cond)
         return out[0] if isinstance(out, tuple) and not return_ids else out
 
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, seed=None):
+        """:356-359: sqrt_alphas_cumprod[t] * x_start + sqrt_one_minus_alphas_cumprod[t] * noise, ``t`` [B] (rows may differ),
+        one kernel.  ``seed`` (extension): Philox normals when no ``noise`` is given, else drawn from torch's generator."""
+        from ...._sched import philox_seed, q_sample_rows
+        if not x_start.is_cuda:
+            raise RuntimeError("q_sample runs on the MI355X only (no CPU fallback): x_start is on the CPU")
+        dev = x_start.device
+        idx = t.detach().long().to(dev)
+        a, s = self.sqrt_alphas_cumprod.detach().float().to(dev)[idx], self.sqrt_one_minus_alphas_cumprod.detach().float().to(dev)[idx]
+        return q_sample_rows(a, s, x_start, noise.to(dev) if noise is not None else None,
+                             seed=philox_seed(seed) if noise is None else 0)
+
     def _schedule(self, timesteps=None):
         """B_DDPM over t = timesteps-1 .. 0 (p_sample :961-993 via p_mean_variance :929-959, q_posterior :304-311)."""
         from .... import _lib
@@ -310,18 +323,26 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None,
-                      step_noise=None, seed=None):
-        """:1048-1093 on the device.  ``step_noise`` ([steps,B,C,h,w]) / ``seed`` are extensions for reproducible runs."""
-        from ...._sched import find_unet, run_device_loop
-        if mask is not None or quantize_denoised or callback is not None or img_callback is not None:
-            raise NotImplementedError("mask / quantize / per-step callbacks are not on the device loop")
+                      step_noise=None, seed=None, mask_noise=None):
+        """:1048-1093 on the device.  ``step_noise`` ([steps,B,C,h,w]) / ``seed`` are extensions for reproducible runs.
+        ``mask`` / ``x0`` (:1071-1073,1085-1087): after every update, the last included, the state becomes
+        q_sample(x0, t)*mask + (1 - mask)*state; ``mask_noise`` ([steps,B,C,h,w]) feeds q_sample's draws, else Philox of ``seed``."""
+        from ...._sched import Inpaint, find_unet, run_device_loop
+        if quantize_denoised or callback is not None or img_callback is not None:
+            raise NotImplementedError("quantize / per-step callbacks are not on the device loop")
+        if mask is not None:
+            assert x0 is not None                                            # :1072
+            assert x0.shape[2:3] == mask.shape[2:3]                          # :1073 spatial size has to match
         device = self.betas.device if self.betas.is_cuda else torch.device("cuda")
         img = x_T if x_T is not None else torch.randn(shape, device=device)
         if start_T is not None:
             timesteps = min(timesteps or self.num_timesteps, start_T)
         c = cond["c_concat"] if isinstance(cond, dict) else (cond if isinstance(cond, list) else [cond])
+        inpaint = None
+        if mask is not None:
+            inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
         out = run_device_loop(find_unet(self.model), self._schedule(timesteps), img.to(device),
-                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed)
+                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed, inpaint=inpaint)
         if return_intermediates:
             return out, [img, out]
         return out
@@ -339,7 +360,8 @@ class LatentDiffusion(DDPM):
                 cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
                                   timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0,
-                                  step_noise=kwargs.get("step_noise"), seed=kwargs.get("seed"))
+                                  step_noise=kwargs.get("step_noise"), seed=kwargs.get("seed"),
+                                  mask_noise=kwargs.get("mask_noise"))
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, sampler, ddim_steps, **kwargs):

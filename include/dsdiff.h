@@ -338,6 +338,56 @@ int dsd_op_sampler_update_guided(const dsd_schedule* sched, int k, const float* 
 int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sched, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
                            float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
                            void* stream);
+/* ---- image-to-image: masked sampling and DDIM inversion -----------------------------------
+ * Masked sampling (DDIMSampler.sample(mask=, x0=), ddim.py:160-163; LatentDiffusion.p_sample_loop(mask=, x0=), ddpm.py:1085-1087):
+ *   img_orig = sqrt_acp[t]*x0 + sqrt_1m_acp[t]*z        (q_sample, ddpm.py:356-359; coef[k][0], coef[k][1] of the iteration)
+ *   x        = img_orig*mask + (1 - mask)*x             (mask 1 keeps x0, 0 samples)
+ * DSD_MODE_B_DDIM blends BEFORE the network evaluation of every executed iteration (none after the last update);
+ * DSD_MODE_B_DDPM blends AFTER every update, the last included, so the kept region ends as q_sample(x0, 0).  The family-A
+ * loops have no mask in the reference and are rejected; so is a masked B_DDPM loop with guidance.
+ * z: noise[k] of the fed [steps,B,Cz,H,W], or Philox normals of the stream (philox_seed, k + 2^32) — the update of iteration k
+ * draws from (philox_seed, k) — keyed by logical sample and dsd_set_slice_ids like the update's noise.
+ * The blend runs outside the captured network (dsd_set_graph), next to the update; first_step / n_steps as in dsd_sample. */
+typedef struct dsd_inpaint {
+    const float* x0;        /* device, [B,Cz,H,W] like the state */
+    const float* mask;      /* device, [B,mask_channels,H,W] */
+    int32_t mask_channels;  /* 1 (broadcast over the state's channels) or Cz */
+    const float* noise;     /* device, [steps,B,Cz,H,W] blend noise, or NULL: Philox */
+} dsd_inpaint;
+/* dsd_sample / dsd_sample_guided (g != NULL) with a mask; dsd_sample_latent / dsd_sample_latent_guided with a mask. */
+int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
+                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                      void* stream);
+int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
+                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
+                             int W, int first_step, int n_steps, void* stream);
+/* DDIM inversion (DDIMSampler.encode, ddim.py:263-308).  Iteration i evaluates the network at model time t_model[i] — the
+ * reference passes the loop index i itself (:282), not a timestep of the schedule; the caller fills t_model accordingly — and
+ * applies x <- coef[2i]*x + coef[2i+1]*e  (xt_weighted + weighted_noise_pred, :292-295), e the network output or, with guidance,
+ * e_u + s*(e_c - e_u) (:287-290).  coef: host, produced with the reference's expressions and dtypes, rounded to fp32 once. */
+typedef struct dsd_invert_schedule {
+    int32_t steps;
+    const float* coef;      /* host, steps*2: cx, ce */
+    const float* t_model;   /* host, steps */
+} dsd_invert_schedule;
+/* x: [B,1,H,W] (four-stream model) / [B,Cz,H,W] (DSD_BLOCK_UNET) in = x0, out = the encoded state, in place.  g: NULL or the
+ * guidance (2B network rows per step, as in the guided sampling loops). */
+int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
+               int H, int W, int first_step, int n_steps, void* stream);
+int dsd_invert_latent(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                      int Cz, int B, int H, int W, int first_step, int n_steps, void* stream);
+/* The blend alone.  x: state rows at x + b*x_row_stride (0: Cz*H*W); guided != 0: the 2B-row state, row b is read, rows b and
+ * B+b are written.  noise [B,Cz,H,W] or NULL: Philox stream (philox_seed, step + 2^32). */
+int dsd_op_mask_blend(float a, float s, const float* x0, const float* mask, int mask_channels, float* x, int64_t x_row_stride,
+                      int guided, const float* noise, uint64_t philox_seed, uint64_t step, int B, int Cz, int H, int W,
+                      void* stream);
+/* q_sample with per-row coefficients (LatentDiffusion.q_sample, DDIMSampler.stochastic_encode): out_b = a[b]*x0_b + s[b]*z_b;
+ * a, s: device [B]; out rows at out + b*out_row_stride (0: contiguous). */
+int dsd_op_q_sample(const float* a, const float* s, const float* x0, const float* noise, uint64_t philox_seed, uint64_t step,
+                    float* out, int64_t out_row_stride, int B, int Cz, int H, int W, void* stream);
+/* One inversion step.  out_uncond == NULL: x (B rows) <- cx*x + ce*out_cond; else the guided step on the 2B-row state. */
+int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const float* out_cond, float scale, float* x,
+                            int64_t x_row_stride, int B, int Cz, int H, int W, void* stream);
 /* Dynamic thresholding alone: y = clamp(x0,-s,s)/s with s_b = max(quantile_ratio(|x0_b|), max_val); x0,y [B,n], s [B]. */
 int dsd_op_dpm_threshold(const float* x0, int B, int n, float ratio, float max_val, float* y, float* s_out, void* stream);
 

@@ -1,0 +1,324 @@
+"""CPU side of image-to-image sampling (tests/golden/img2img.npz, tests/golden/gen_img2img.py): the reference's masked DDIM runs,
+DDIMSampler.encode / decode / stochastic_encode reproduced by the oracle networks plus the blend (ddim.py:160-163) and the
+inversion step (:282-295) restated here in torch with the reference's dtypes — which pins the fixture to the reference and the
+orders the device kernels follow — then the host-side coefficient packing and the argument checks that raise before any GPU call."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import samplers as OS, schedules as S, unet as O
+from util import golden, fixture_params, rel_l2, randn, cond_image
+
+STEPS = 20
+TOL = 1e-5        # the bar of test_latent_ldm_cpu.py / test_cfg_cpu.py for their chains
+
+
+# ---------------------------------------------------------------------------------------- restated loops (shared with the GPU tests)
+def center_mask(shape):
+    """[B,1,h,w], the centre half zero: the form LatentDiffusion.log_images builds (ddpm.py:1250-1254)."""
+    b, _, h, w = shape
+    m = torch.ones(b, 1, h, w)
+    m[:, :, h // 4:h - h // 4, w // 4:w - w // 4] = 0.
+    return m
+
+
+def q_sample(od, x0, t, z):
+    """ddpm.py:356-359."""
+    T, e = od.tab, od._ext
+    return e(T["sqrt_alphas_cumprod"], t, x0.shape) * x0 + e(T["sqrt_one_minus_alphas_cumprod"], t, x0.shape) * z
+
+
+def blend(od, x0, mask, t, z, img):
+    """ddim.py:162-163 / ddpm.py:1086-1087."""
+    img_orig = q_sample(od, x0, t, z)
+    return img_orig * mask + (1. - mask) * img
+
+
+def guided(net, c, u, scale):
+    """ddim.py:194-219 (sampling) and :283-290 (inversion): one 2B pass, out_u + s*(out_c - out_u) on the raw outputs."""
+    def f(x, t):
+        if scale == 1.:
+            return net(torch.cat([x, c], 1), t)
+        ou, oc = net(torch.cat([torch.cat([x] * 2), torch.cat([u, c])], 1), torch.cat([t] * 2)).chunk(2)
+        return ou + scale * (oc - ou)
+    return f
+
+
+def ddim_tables(od, eta):
+    ts = S.make_ddim_timesteps("uniform", STEPS, od.num_timesteps)
+    sig, a, a_prev = S.make_ddim_sampling_parameters(od.tab["alphas_cumprod"].numpy(), ts, eta)
+    return ts, sig, a, a_prev, np.sqrt(1. - a)
+
+
+def ddim_chain(od, f, img, z, eta, n_last=None, pre=None, clip=True):
+    """ddim_sampling :156-177 + p_sample_ddim :221-260 over the last ``n_last`` indices (decode :330-346; None: all), with
+    ``pre(k, t, img)`` in front of every network evaluation (the mask blend)."""
+    ts, sig, a, a_prev, s1m = ddim_tables(od, eta)
+    ts = ts[:n_last] if n_last is not None else ts
+    b, total = img.shape[0], ts.shape[0]
+    full = lambda v: torch.full((b, 1, 1, 1), float(v))
+    for k, step in enumerate(np.flip(ts)):
+        index = total - k - 1
+        t = torch.full((b,), int(step), dtype=torch.long)
+        if pre is not None:
+            img = pre(k, t, img)
+        out = f(img, t)
+        x0, e_t = od.x0_eps(img, t, out)
+        if od.parameterization != "v":
+            x0 = (img - full(s1m[index]) * e_t) / full(a[index]).sqrt()
+        if clip:
+            x0 = x0.clamp(-1., 1.)
+        dir_xt = (1. - full(a_prev[index]) - full(sig[index]) ** 2).sqrt() * e_t
+        img = full(a_prev[index]).sqrt() * x0 + dir_xt + full(sig[index]) * z[k]
+    return img
+
+
+def invert_chain(od, f, x0, n, keep=()):
+    """DDIMSampler.encode :275-295 with its dtypes: alphas_next fp32, alphas = torch.tensor(numpy float64); model time = i."""
+    _, _, a, a_prev, _ = ddim_tables(od, 0.)
+    alphas_next, alphas = torch.from_numpy(np.ascontiguousarray(a[:n])), torch.tensor(a_prev[:n])
+    assert alphas_next.dtype == torch.float32 and alphas.dtype == torch.float64
+    x_next, inter = x0, []
+    for i in range(n):
+        t = torch.full((x0.shape[0],), i, dtype=torch.long)
+        noise_pred = f(x_next, t)
+        xt_weighted = (alphas_next[i] / alphas[i]).sqrt() * x_next
+        weighted_noise_pred = alphas_next[i].sqrt() * ((1 / alphas_next[i] - 1).sqrt() - (1 / alphas[i] - 1).sqrt()) * noise_pred
+        x_next = xt_weighted + weighted_noise_pred
+        assert x_next.dtype == torch.float32
+        if i in keep:
+            inter.append(x_next)
+    return x_next, inter
+
+
+def ddpm_masked_chain(od, f, img, z, zb, x0, mask, timesteps, clip=False):
+    """LatentDiffusion.p_sample_loop :1075-1092 with p_sample :961-993 (eps / x0 models, p_mean_variance :929-959): the blend
+    AFTER every update, the last included.  f(img, t) is the network on the 'concat' input."""
+    T, e = od.tab, od._ext
+    b = img.shape[0]
+    for k, i in enumerate(reversed(range(timesteps))):
+        t = torch.full((b,), i, dtype=torch.long)
+        xr, _ = od.x0_eps(img, t, f(img, t))
+        if clip:
+            xr = xr.clamp(-1., 1.)
+        mean = e(T["posterior_mean_coef1"], t, img.shape) * xr + e(T["posterior_mean_coef2"], t, img.shape) * img
+        nz = (1 - (t == 0).float()).reshape(b, 1, 1, 1)
+        img = mean + nz * (0.5 * e(T["posterior_log_variance_clipped"], t, img.shape)).exp() * z[k]
+        img = blend(od, x0, mask, t, zb[k], img)
+    return img
+
+
+def latent_env():
+    g, gl = golden("img2img"), golden("latent_ldm")
+    up = json.loads(str(g["lat_unet_cfg"]))
+    assert up == json.loads(str(gl["unet_cfg"]))
+    ucfg, usd = O.UNetConfig.from_params(up), fixture_params(gl, "unet")
+    net = lambda xx, tt: O.plain_unet_forward(ucfg, usd, xx, tt)
+    c = randn((2, 8, 8, 8), int(g["lat_c_seed"]))
+    return g, net, c, torch.zeros_like(c), randn((2, 4, 8, 8), int(g["lat_xT_seed"]))
+
+
+def pixel_env():
+    g, gm = golden("img2img"), golden("model")
+    cfg, sd = O.UNetConfig.from_params(json.loads(str(gm["tiny_cfg"]))), fixture_params(gm, "tiny")
+    net = lambda xx, tt: O.unet_forward(cfg, sd, xx, tt)[0]
+    c = cond_image((2, 1, 32, 32), int(g["pix_cond_seed"]))
+    return g, net, c, torch.zeros_like(c), randn((2, 1, 32, 32), int(g["pix_xT_seed"]))
+
+
+MASKED = (("mask_eta0", 0., "step_eta0", "blend_eta0", 1.), ("mask_eta1", 1., "step_eta1", "blend_eta1", 1.),
+          ("mask_cfg", 0., "step_eta0", "blend_cfg", 3.))
+
+
+# ---------------------------------------------------------------------------------------- fixture chains
+@pytest.mark.parametrize("space", ["lat", "pix"])
+def test_oracle_reproduces_masked_ddim(space):
+    g, net, c, u, xT = latent_env() if space == "lat" else pixel_env()
+    od = OS.DiffusionB(timesteps=1000, parameterization="v")
+    x0, mask = randn(tuple(xT.shape), int(g["x0_seed"])), center_mask(xT.shape)
+    for key, eta, ss, bs, scale in MASKED:
+        z = randn((STEPS,) + tuple(xT.shape), int(g[ss + "_seed"]))
+        zb = randn((STEPS,) + tuple(xT.shape), int(g[bs + "_seed"]))
+        assert scale == 1. or scale == float(g["scale"])
+        f = guided(net, c, u, scale)
+        y = ddim_chain(od, f, xT.clone(), z, eta, pre=lambda k, t, img: blend(od, x0, mask, t, zb[k], img))
+        assert rel_l2(y, g[f"{space}_{key}_y"]) < TOL, (space, key)
+        assert rel_l2(ddim_chain(od, f, xT.clone(), z, eta), g[f"{space}_{key}_nomask_y"]) < TOL, (space, key)
+        # a loop that ignores the mask cannot pass the chain bar
+        assert rel_l2(g[f"{space}_{key}_y"], g[f"{space}_{key}_nomask_y"]) > 1e-2
+
+
+@pytest.mark.parametrize("space", ["lat", "pix"])
+def test_oracle_reproduces_encode_decode_stochastic_encode(space):
+    g, net, c, u, xT = latent_env() if space == "lat" else pixel_env()
+    od = OS.DiffusionB(timesteps=1000, parameterization="eps")
+    x0 = randn(tuple(xT.shape), int(g["x0_seed"]))
+    n12, scale = int(g["t_enc"]), float(g["scale"])
+    for key, n, sc in (("enc20", STEPS, 1.), ("enc12", n12, 1.), ("enc20_cfg", STEPS, scale), ("enc12_cfg", n12, scale)):
+        keep = tuple(int(v) for v in g[f"{space}_enc12_inter_steps"]) if key == "enc12" else ()
+        y, inter = invert_chain(od, guided(net, c, u, sc), x0, n, keep)
+        assert rel_l2(y, g[f"{space}_{key}_y"]) < TOL, (space, key)
+        if keep:
+            assert keep == (0, 4, 8, 10, 11)                                  # :296-302 with return_intermediates = 3
+            assert rel_l2(torch.stack(inter), g[f"{space}_enc12_inter"]) < TOL
+    assert rel_l2(g[f"{space}_enc12_cfg_y"], g[f"{space}_enc12_y"]) > 1e-2    # the guided fixture is guided
+    z = torch.zeros((n12,) + tuple(xT.shape))                                 # eta 0: sigma_t = 0
+    y = ddim_chain(od, guided(net, c, u, 1.), torch.from_numpy(g[f"{space}_enc12_y"]), z, 0., n_last=n12)
+    assert rel_l2(y, g[f"{space}_dec12_y"]) < TOL
+    # stochastic_encode :318-324: sqrt(ddim_alphas)[t] in fp32, rows at different indices
+    _, _, a, _, s1m = ddim_tables(od, 0.)
+    t = torch.as_tensor(g["senc_t"]).long()
+    assert t.tolist() == [3, 17]
+    sa = torch.sqrt(torch.from_numpy(np.ascontiguousarray(a)))
+    y = od._ext(sa, t, x0.shape) * x0 + od._ext(torch.from_numpy(s1m), t, x0.shape) * randn(tuple(x0.shape), int(g["senc_seed"]))
+    assert rel_l2(y, g[f"{space}_senc_y"]) < 1e-7
+
+
+# ---------------------------------------------------------------------------------------- host-side coefficient packing
+def _ddpm(par="eps"):
+    from diffusion_models_dsdiff_amd.trainers.trainer_ddpm import DDPMModel
+    return DDPMModel(timesteps=1000, parameterization=par)
+
+
+def test_invert_coefficients_follow_the_reference_dtypes():
+    from diffusion_models_dsdiff_amd._sched import invert_coefficients
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    sm = DDIMSampler(_ddpm())
+    sm.make_schedule(STEPS, verbose=False)
+    assert np.asarray(sm.ddim_alphas).dtype == np.float32 and np.asarray(sm.ddim_alphas_prev).dtype == np.float64
+    an32, a64 = np.asarray(sm.ddim_alphas), np.asarray(sm.ddim_alphas_prev)
+    coef = invert_coefficients(torch.from_numpy(an32.copy()), torch.tensor(a64))
+    assert coef.shape == (STEPS, 2) and coef.dtype == np.float32
+    # the DDIM sub-schedule: alphas is float64, so the scalar arithmetic is float64 and is rounded to fp32 once (ddim.py:276,292-294)
+    an = an32.astype(np.float64)
+    sq32 = lambda v: np.sqrt(v.astype(np.float32)).astype(np.float64)        # the factors formed from the fp32 tensor alone
+    cx = np.sqrt(an / a64)
+    ce = sq32(an32) * (sq32(np.float32(1) / an32 - np.float32(1)) - np.sqrt(1 / a64 - 1))
+    assert np.array_equal(coef[:, 0], cx.astype(np.float32)) and np.array_equal(coef[:, 1], ce.astype(np.float32))
+    # all-fp32 arithmetic (use_original_steps: both are fp32 buffers) is another table
+    c32 = invert_coefficients(torch.from_numpy(an32.copy()), torch.from_numpy(a64.astype(np.float32)))
+    assert rel_l2(c32, coef) < 1e-6 and not np.array_equal(c32, coef)
+    assert np.all(coef[:, 0] < 1.) and np.all(coef[:, 1] > 0.)              # inversion: the state shrinks, noise is added
+
+
+def test_masked_schedules_carry_the_q_sample_coefficients():
+    """Pins a precondition of the blend, not new code: the B-mode schedule already carried sqrt_alphas_cumprod[t] and
+    sqrt_one_minus_alphas_cumprod[t] in coef[0..1], and the blend kernel reads its a and s from there."""
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    m = _ddpm("v")
+    sm = DDIMSampler(m)
+    sm.make_schedule(STEPS, ddim_eta=1.0, verbose=False)
+    sched = sm._schedule(False, True)
+    t = np.flip(sm.ddim_timesteps)
+    assert np.array_equal(sched.coef[:, 0], m.sqrt_alphas_cumprod.numpy()[t])
+    assert np.array_equal(sched.coef[:, 1], m.sqrt_one_minus_alphas_cumprod.numpy()[t])
+    assert np.array_equal(sched.t_model, t.astype(np.float32))
+
+
+def test_structs_and_header_agree():
+    from diffusion_models_dsdiff_amd import _lib
+    assert C.sizeof(_lib.DsdInpaint) == 32 and _lib.DsdInpaint.mask.offset == 8 and _lib.DsdInpaint.mask_channels.offset == 16
+    assert _lib.DsdInpaint.noise.offset == 24
+    assert C.sizeof(_lib.DsdInvertSchedule) == 24 and _lib.DsdInvertSchedule.coef.offset == 8
+    assert C.sizeof(_lib.DsdSchedule) == 48 and C.sizeof(_lib.DsdGuidance) == 24            # the existing layouts stay
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dsdiff.h")).read()
+    for sym in ("dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent", "dsd_op_mask_blend",
+                "dsd_op_q_sample", "dsd_op_ddim_invert_step"):
+        assert sym in _lib.EXPORTS and re.search(r"\bint %s\(" % sym, hdr), sym
+
+
+# ---------------------------------------------------------------------------------------- argument forms (no GPU call)
+def test_inpaint_checks():
+    from diffusion_models_dsdiff_amd._sched import Inpaint, run_device_loop
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    sm = DDIMSampler(_ddpm("v"))
+    sm.make_schedule(4, verbose=False)
+    sched = sm._schedule(False, True)
+    x, c = torch.zeros(2, 4, 8, 8), torch.zeros(2, 3, 8, 8)
+    m1, m4 = torch.ones(2, 1, 8, 8), torch.ones(2, 4, 8, 8)
+    for ok in (Inpaint(x, m1), Inpaint(x, m4), Inpaint(x, m1, torch.zeros(4, 2, 4, 8, 8))):
+        ok.check(x, 4)
+        with pytest.raises(RuntimeError, match="no native denoiser"):         # well-formed: reaches the loop
+            run_device_loop(None, sched, x, c, inpaint=ok)
+    with pytest.raises(ValueError, match="needs a mask"):
+        Inpaint(x, None)
+    with pytest.raises(ValueError, match="x0"):
+        Inpaint(None, m1)
+    for bad in (Inpaint(x[:, :2], m1), Inpaint(x[:1], m1), Inpaint(x.double(), m1), Inpaint(x.numpy(), m1)):
+        with pytest.raises(ValueError, match="x0 must have the shape, dtype and device"):
+            run_device_loop(None, sched, x, c, inpaint=bad)
+    for bad in (Inpaint(x, torch.ones(2, 2, 8, 8)), Inpaint(x, torch.ones(2, 1, 8, 4)), Inpaint(x, torch.ones(2, 8, 8)),
+                Inpaint(x, m1.double()), Inpaint(x, torch.ones(1, 1, 8, 8))):
+        with pytest.raises(ValueError, match=r"mask must be \[B,1,H,W\] or \[B,C,H,W\]"):
+            run_device_loop(None, sched, x, c, inpaint=bad)
+    for bad in (torch.zeros(3, 2, 4, 8, 8), torch.zeros(4, 2, 1, 8, 8), torch.zeros(4, 2, 4, 8, 8).double()):
+        with pytest.raises(ValueError, match="mask_noise"):
+            run_device_loop(None, sched, x, c, inpaint=Inpaint(x, m1, bad))
+
+
+def test_ddim_sampler_image_to_image_argument_forms():
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    sm = DDIMSampler(_ddpm("v"))
+    c, x = torch.zeros(2, 1, 8, 8), torch.zeros(2, 1, 8, 8)
+    run = lambda **kw: sm.sample(4, 2, (1, 8, 8), c, verbose=False, x_T=x, **kw)
+    with pytest.raises(AssertionError):                                       # ddim.py:161
+        run(mask=torch.ones(2, 1, 8, 8))
+    with pytest.raises(RuntimeError, match="no native denoiser"):             # x0 alone is ignored, as there
+        run(x0=x)
+    with pytest.raises(RuntimeError, match="no native denoiser"):
+        run(mask=torch.ones(2, 1, 8, 8), x0=x, mask_noise=torch.zeros(4, 2, 1, 8, 8))
+    with pytest.raises(ValueError, match="mask must be"):
+        run(mask=torch.ones(2, 1, 4, 4), x0=x)
+    with pytest.raises(ValueError, match="mask_noise"):
+        run(mask=torch.ones(2, 1, 8, 8), x0=x, mask_noise=torch.zeros(3, 2, 1, 8, 8))
+    for bad in (dict(quantize_x0=True), dict(score_corrector=object()), dict(dynamic_threshold=0.9), dict(temperature=0.5),
+                dict(noise_dropout=0.1)):
+        with pytest.raises(NotImplementedError):                              # the other options stay rejected
+            run(mask=torch.ones(2, 1, 8, 8), x0=x, **bad)
+    # encode / decode / stochastic_encode
+    sm.make_schedule(4, verbose=False)
+    with pytest.raises(NotImplementedError, match="noise prediction"):
+        sm.encode(x, c, 4)                                                    # a v-model
+    se = DDIMSampler(_ddpm("eps"))
+    se.make_schedule(4, verbose=False)
+    with pytest.raises(AssertionError):
+        se.encode(x, c, 5)                                                    # :268
+    with pytest.raises(AssertionError):
+        se.encode(x, c, 4, unconditional_guidance_scale=3.)                   # :286
+    with pytest.raises(NotImplementedError, match="callback"):
+        se.encode(x, c, 4, callback=lambda i: None)
+    with pytest.raises(NotImplementedError, match="callback"):
+        se.decode(x, c, 4, callback=lambda i: None)
+    for call in (lambda: se.encode(x, c, 4), lambda: se.encode(x, c, 4, unconditional_guidance_scale=3., unconditional_conditioning=c),
+                 lambda: se.decode(x, c, 3)):
+        with pytest.raises(RuntimeError, match="no native denoiser"):
+            call()
+    with pytest.raises(ValueError, match="shape, dtype and device"):
+        se.encode(x, c, 4, unconditional_guidance_scale=3., unconditional_conditioning=c[:, :, :4])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        se.stochastic_encode(x, torch.tensor([0, 3]))
+    xe, out = se.encode(x, c, 0)                                              # nothing to run: no network needed
+    assert torch.equal(xe, x) and out["intermediate_steps"] == [] and "intermediates" not in out
+    assert torch.equal(se.decode(x, c, 0), x)
+
+
+def test_latent_diffusion_and_dpm_solver_argument_forms():
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.dpm_solver_new.sampler import DPMSolverSampler
+    c, x = torch.zeros(2, 1, 8, 8), torch.zeros(2, 1, 8, 8)
+    with pytest.raises(NotImplementedError, match="mask"):                    # the reference ignores it there; this package raises
+        DPMSolverSampler(_ddpm("v")).sample(4, 2, (1, 8, 8), c, x_T=x, mask=torch.ones(2, 1, 8, 8), x0=x)
+    assert callable(LatentDiffusion.q_sample)
+    loop = LatentDiffusion.p_sample_loop
+    stub = type("Stub", (), {"betas": torch.zeros(1), "num_timesteps": 4})()
+    with pytest.raises(AssertionError):                                       # ddpm.py:1072
+        loop(stub, c, (2, 1, 8, 8), x_T=x, mask=torch.ones(2, 1, 8, 8))
+    with pytest.raises(AssertionError):                                       # :1073
+        loop(stub, c, (2, 1, 8, 8), x_T=x, mask=torch.ones(2, 1, 4, 8), x0=x)
+    with pytest.raises(NotImplementedError, match="callback"):
+        loop(stub, c, (2, 1, 8, 8), x_T=x, mask=torch.ones(2, 1, 8, 8), x0=x, callback=lambda i: None)

@@ -1,0 +1,518 @@
+"""Image-to-image sampling on the device (GPU): the q_sample / mask-blend and DDIM-inversion kernels against the same fp32
+expressions in torch, every chain of tests/golden/img2img.npz (the reference's own DDIMSampler, tests/golden/gen_img2img.py)
+through the public methods, the masked DDPM loop against its restatement (test_img2img_cpu.py), device loop against a host loop,
+graph replay, first_step splits, noise keyed by logical sample, and the rejections."""
+import ctypes as C
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import samplers as OS, unet as O
+from util import golden, fixture_params, rel_l2, randn, cond_image
+from test_img2img_cpu import MASKED, center_mask, ddpm_masked_chain
+
+pytestmark = pytest.mark.gpu
+
+STEPS = 20
+TOL = 1e-4          # the project's chain bar (test_cfg_gpu.py, test_latent_ldm_gpu.py)
+TOL_OP = 1e-6       # same arithmetic, other tiling
+SHAPES = [(8, 8), (6, 10), (5, 7), (24, 40)]    # 5x7: odd sample size (scalar accesses); 24x40 with Cz = 4: more than one block
+BLEND_STREAM = 1 << 32
+
+
+def _lib():
+    from diffusion_models_dsdiff_amd import _lib as L
+    return L
+
+
+def _philox(n, seed, step):
+    L = _lib()
+    z = torch.empty(n, device="cuda")
+    L.check(L.lib().dsd_op_philox_normal(L.dptr(z), n, C.c_uint64(seed), C.c_uint64(step), L.stream_ptr()))
+    return z
+
+
+# ---------------------------------------------------------------------------------------- models
+@pytest.fixture(scope="module")
+def pix():
+    """The `tiny` DSUnetModel of model.npz behind a DiffusionWrapper inside a DDPMModel; cond / x_T of loops.npz, u = zeros."""
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import DiffusionWrapper
+    from diffusion_models_dsdiff_amd.trainers.trainer_ddpm import DDPMModel
+    _lib().require_gpu(0)
+    g, gm = golden("img2img"), golden("model")
+    wrap = DiffusionWrapper({"target": "UNet_DS_Diff.model.DSUnetModel", "params": json.loads(str(gm["tiny_cfg"]))}, "concat")
+    wrap.diffusion_model.load_state_dict(fixture_params(gm, "tiny"), strict=True)
+    m = DDPMModel(timesteps=1000, parameterization="v").cuda()
+    m.model = wrap
+    shape = (2, 1, 32, 32)
+    c = cond_image(shape, int(g["pix_cond_seed"])).cuda()
+    return dict(g=g, m=m, wrap=wrap, unet=wrap.diffusion_model, c=c, u=torch.zeros_like(c),
+                xT=randn(shape, int(g["pix_xT_seed"])).cuda(), x0=randn(shape, int(g["x0_seed"])).cuda(),
+                mask=center_mask(shape).cuda(), key="pix")
+
+
+@pytest.fixture(scope="module")
+def lat():
+    """The latent UNetModel of latent_ldm.npz inside a LatentDiffusion (first stage built, never run); c = randn, u = zeros."""
+    from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
+    _lib().require_gpu(0)
+    g, gl = golden("img2img"), golden("latent_ldm")
+    dd = json.loads(str(gl["vae_cfg"]))
+    embed = dd.pop("embed_dim")
+    up = json.loads(str(g["lat_unet_cfg"]))
+    ld = LatentDiffusion(first_stage_config=AutoencoderKL(dd, None, embed), conditioning_key="concat", scale_factor=0.18215,
+                         timesteps=1000, parameterization="v", image_size=8, channels=4,
+                         unet_config={"target": "ldm.modules.diffusionmodules.openaimodel.UNetModel", "params": up})
+    ld.model.diffusion_model.load_state_dict(fixture_params(gl, "unet"), strict=True)
+    ld = ld.cuda()
+    shape = (2, 4, 8, 8)
+    c = randn((2, 8, 8, 8), int(g["lat_c_seed"])).cuda()
+    return dict(g=g, m=ld, wrap=ld.model, unet=ld.model.diffusion_model, c=c, u=torch.zeros_like(c),
+                xT=randn(shape, int(g["lat_xT_seed"])).cuda(), x0=randn(shape, int(g["x0_seed"])).cuda(),
+                mask=center_mask(shape).cuda(), key="lat")
+
+
+@pytest.fixture(params=["pix", "lat"])
+def env(request):
+    return request.getfixturevalue(request.param)
+
+
+class _as:
+    """The model's parameterization for the duration of a block (the fixtures' models are v-models; encode takes eps)."""
+
+    def __init__(self, e, par):
+        self.m, self.par = e["m"], par
+
+    def __enter__(self):
+        self.keep, self.m.parameterization = self.m.parameterization, self.par
+
+    def __exit__(self, *a):
+        self.m.parameterization = self.keep
+
+
+def _sampler(m, eta=0.0):
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    s = DDIMSampler(m)
+    s.make_schedule(STEPS, ddim_eta=eta, verbose=False)
+    return s
+
+
+def _ddim_sched(m, eta=0.0, clip=True):
+    return _sampler(m, eta)._schedule(False, clip)
+
+
+def _ddpm_sched(lat, steps):
+    """B_DDPM rows of t = steps-1 .. 0 for an eps-model; the tables depend on the betas alone, so both denoisers take it."""
+    with _as(lat, "eps"):
+        return lat["m"]._schedule(steps)
+
+
+def _slice_ids(unet, ids):
+    L = _lib()
+    arr = (C.c_int64 * max(1, len(ids)))(*ids)
+    L.check(L.lib().dsd_set_slice_ids(unet._h, arr, len(ids)))
+
+
+def _net(e, x, t, cond):
+    out = e["wrap"](x, t, c_concat=[cond])
+    return (out[0] if isinstance(out, tuple) else out).float().contiguous()
+
+
+def _noise(e, seed, steps=STEPS):
+    return randn((steps,) + tuple(e["xT"].shape), int(seed)).cuda()
+
+
+# ---------------------------------------------------------------------------------------- ops
+@pytest.mark.parametrize("Cz", [1, 4])
+@pytest.mark.parametrize("hw", SHAPES)
+def test_mask_blend_op_matches_torch(Cz, hw):
+    from diffusion_models_dsdiff_amd._sched import mask_blend
+    _lib().require_gpu(0)
+    B, (H, W) = 3, hw
+    gen = torch.Generator().manual_seed(300 * Cz + H)
+    r = lambda *s: torch.randn(*s, generator=gen)
+    a, s = torch.tensor(0.83, dtype=torch.float32), torch.tensor(0.5577, dtype=torch.float32)
+    x0, x, z, cc = r(B, Cz, H, W), r(B, Cz, H, W) * 1.5, r(B, Cz, H, W), r(2 * B, 3, H, W)
+    io = a * x0 + s * z                                                       # q_sample ddpm.py:358-359
+    for mc in sorted({1, Cz}):
+        for binary in (True, False):
+            m = torch.rand(B, mc, H, W, generator=gen)
+            m = (m > 0.5).float() if binary else m
+            want = io * m + (1. - m) * x                                      # ddim.py:163
+            tag = f"mask channels {mc} binary {binary}"
+            own = x.clone().cuda()
+            mask_blend(a, s, x0.cuda(), m.cuda(), own, z.cuda())
+            assert rel_l2(own, want) < TOL_OP, tag
+            if binary:                                                        # kept: q_sample to the bit; sampled: untouched
+                mb = m.expand(B, Cz, H, W).bool()
+                assert torch.equal(own.cpu()[mb], io[mb]) and torch.equal(own.cpu()[~mb], x[~mb]), tag
+            # the state inside the denoiser's input [B,Cz+Cc,H,W]: row stride != Cz*H*W, the other channels untouched
+            xin = torch.cat([x, cc[:B]], 1).cuda().contiguous()
+            mask_blend(a, s, x0.cuda(), m.cuda(), xin, z.cuda(), state_channels=Cz)
+            assert torch.equal(xin[:, :Cz], own) and torch.equal(xin[:, Cz:].cpu(), cc[:B]), tag
+            # guided: row b read, rows b and B+b written
+            x2 = torch.cat([torch.cat([x, r(B, Cz, H, W)]), cc], 1).cuda().contiguous()
+            mask_blend(a, s, x0.cuda(), m.cuda(), x2, z.cuda(), guided=True, state_channels=Cz)
+            assert torch.equal(x2[:B, :Cz], own) and torch.equal(x2[B:, :Cz], own) and torch.equal(x2[:, Cz:].cpu(), cc), tag
+            # Philox: the normals of (seed, step + 2^32) indexed by logical sample, whichever access width the kernel takes
+            zp = _philox(B * Cz * H * W, 4321, 7 + BLEND_STREAM).reshape(B, Cz, H, W)
+            xa, xb = x.clone().cuda(), x.clone().cuda()
+            mask_blend(a, s, x0.cuda(), m.cuda(), xa, None, seed=4321, step=7)
+            mask_blend(a, s, x0.cuda(), m.cuda(), xb, zp)
+            assert torch.equal(xa, xb) and not torch.equal(zp, _philox(B * Cz * H * W, 4321, 7).reshape(B, Cz, H, W)), tag
+
+
+@pytest.mark.parametrize("Cz", [1, 4])
+@pytest.mark.parametrize("hw", SHAPES)
+def test_q_sample_op_matches_torch(Cz, hw):
+    from diffusion_models_dsdiff_amd._sched import q_sample_rows
+    L = _lib()
+    L.require_gpu(0)
+    B, (H, W) = 3, hw
+    gen = torch.Generator().manual_seed(400 * Cz + H)
+    x0, z = torch.randn(B, Cz, H, W, generator=gen), torch.randn(B, Cz, H, W, generator=gen)
+    a, s = torch.tensor([0.99, 0.6, 0.1]), torch.tensor([0.1411, 0.8, 0.995])     # rows at different t
+    want = a.reshape(B, 1, 1, 1) * x0 + s.reshape(B, 1, 1, 1) * z
+    got = q_sample_rows(a.cuda(), s.cuda(), x0.cuda(), z.cuda())
+    assert rel_l2(got, want) < TOL_OP
+    zp = _philox(B * Cz * H * W, 99, 3 + BLEND_STREAM).reshape(B, Cz, H, W)
+    assert torch.equal(q_sample_rows(a.cuda(), s.cuda(), x0.cuda(), None, seed=99, step=3),
+                       q_sample_rows(a.cuda(), s.cuda(), x0.cuda(), zp))
+    # strided rows: the result as the first Cz channels of a [B,Cz+2,H,W] buffer, the rest untouched
+    buf = torch.full((B, Cz + 2, H, W), 7., device="cuda")
+    ad, sd, xd, zd = a.cuda(), s.cuda(), x0.cuda(), z.cuda()
+    L.check(L.lib().dsd_op_q_sample(L.dptr(ad), L.dptr(sd), L.dptr(xd), L.dptr(zd), C.c_uint64(0), C.c_uint64(0), L.dptr(buf),
+                                    (Cz + 2) * H * W, B, Cz, H, W, L.stream_ptr()))
+    assert torch.equal(buf[:, :Cz], got) and bool((buf[:, Cz:] == 7.).all())
+
+
+@pytest.mark.parametrize("Cz", [1, 4])
+@pytest.mark.parametrize("hw", SHAPES)
+def test_ddim_invert_step_op_matches_torch(Cz, hw):
+    from diffusion_models_dsdiff_amd._sched import ddim_invert_step
+    _lib().require_gpu(0)
+    B, (H, W), scale = 3, hw, 3.0
+    gen = torch.Generator().manual_seed(500 * Cz + H)
+    r = lambda *s: torch.randn(*s, generator=gen)
+    cx, ce = torch.tensor(0.9871, dtype=torch.float32), torch.tensor(0.0713, dtype=torch.float32)
+    ou, oc, x, cc = r(B, Cz, H, W), r(B, Cz, H, W), r(B, Cz, H, W) * 1.5, r(2 * B, 3, H, W)
+    want = cx * x + ce * oc                                                   # ddim.py:292-295
+    want_g = cx * x + ce * (ou + scale * (oc - ou))                           # :287-290
+    own = x.clone().cuda()
+    ddim_invert_step(cx, ce, oc.cuda(), own)
+    assert rel_l2(own, want) < TOL_OP
+    xin = torch.cat([x, cc[:B]], 1).cuda().contiguous()
+    ddim_invert_step(cx, ce, oc.cuda(), xin, state_channels=Cz)
+    assert torch.equal(xin[:, :Cz], own) and torch.equal(xin[:, Cz:].cpu(), cc[:B])
+    x2 = torch.cat([x, r(B, Cz, H, W)]).cuda()
+    ddim_invert_step(cx, ce, oc.cuda(), x2, out_uncond=ou.cuda(), scale=scale)
+    assert rel_l2(x2[:B], want_g) < TOL_OP and torch.equal(x2[:B], x2[B:])
+    x2in = torch.cat([torch.cat([x, x]), cc], 1).cuda().contiguous()
+    ddim_invert_step(cx, ce, oc.cuda(), x2in, out_uncond=ou.cuda(), scale=scale, state_channels=Cz)
+    assert torch.equal(x2in[:B, :Cz], x2[:B]) and torch.equal(x2in[B:, :Cz], x2[:B]) and torch.equal(x2in[:, Cz:].cpu(), cc)
+
+
+# ---------------------------------------------------------------------------------------- fixture chains, public methods
+@pytest.mark.parametrize("case", MASKED, ids=[c[0] for c in MASKED])
+def test_ddim_sampler_masked_vs_reference(env, case):
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    e, g = env, env["g"]
+    key, eta, ss, bs, scale = case
+    kw = dict(eta=eta, verbose=False, x_T=e["xT"], step_noise=_noise(e, g[ss + "_seed"]), unconditional_guidance_scale=scale,
+              unconditional_conditioning=dict(c_concat=[e["u"]]))
+    shape = tuple(e["xT"].shape[1:])
+    y, _ = DDIMSampler(e["m"]).sample(STEPS, 2, shape, dict(c_concat=[e["c"]]), mask=e["mask"], x0=e["x0"],
+                                      mask_noise=_noise(e, g[bs + "_seed"]), **kw)
+    ref, plain = g[f"{e['key']}_{key}_y"], g[f"{e['key']}_{key}_nomask_y"]
+    print(f"{e['key']}_{key}: rel-L2 to the reference {rel_l2(y, ref):.3e}, to its unmasked run {rel_l2(y, plain):.3e}")
+    assert tuple(y.shape) == ref.shape and rel_l2(y, ref) < TOL
+    assert rel_l2(y, plain) > 1e-2                                            # the mask is live
+    # x0 without a mask changes nothing (ddim.py:160): the unmasked loop
+    y0, _ = DDIMSampler(e["m"]).sample(STEPS, 2, shape, dict(c_concat=[e["c"]]), x0=e["x0"], **kw)
+    assert rel_l2(y0, plain) < TOL
+
+
+def test_encode_decode_stochastic_encode_vs_reference(env):
+    e, g = env, env["g"]
+    sp, n12, scale = e["key"], int(g["t_enc"]), float(g["scale"])
+    with _as(e, "eps"):
+        sm = _sampler(e["m"])
+        for key, n, sc in (("enc20", STEPS, 1.), ("enc12", n12, 1.), ("enc20_cfg", STEPS, scale), ("enc12_cfg", n12, scale)):
+            y, out = sm.encode(e["x0"], e["c"], n, unconditional_guidance_scale=sc, unconditional_conditioning=e["u"],
+                               return_intermediates=3 if key == "enc12" else None)
+            print(f"{sp}_{key}: rel-L2 to the reference {rel_l2(y, g[f'{sp}_{key}_y']):.3e}")
+            assert rel_l2(y, g[f"{sp}_{key}_y"]) < TOL and torch.equal(out["x_encoded"], y), key
+            if key == "enc12":
+                assert out["intermediate_steps"] == g[f"{sp}_enc12_inter_steps"].tolist()
+                assert rel_l2(torch.stack(out["intermediates"]), g[f"{sp}_enc12_inter"]) < TOL
+                assert torch.equal(out["intermediates"][-1], y)
+                enc12 = y
+            else:
+                assert out["intermediate_steps"] == [] and "intermediates" not in out
+        # the dict form of the conditioning, as sample takes it
+        y2, _ = sm.encode(e["x0"], dict(c_concat=[e["c"]]), n12, unconditional_guidance_scale=scale,
+                          unconditional_conditioning=dict(c_concat=[e["u"]]))
+        assert torch.equal(y2, y)
+        dec = sm.decode(torch.from_numpy(g[f"{sp}_enc12_y"]).cuda(), e["c"], n12)
+        assert rel_l2(dec, g[f"{sp}_dec12_y"]) < TOL
+        # measured, not asserted: the round trip's size is discretisation error (12 of 20 steps, model time = loop index)
+        print(f"{sp}: decode(encode(x0)) over {n12} steps, rel-L2 to x0 {rel_l2(sm.decode(enc12, e['c'], n12), e['x0']):.3e} "
+              f"(the reference's own chain: {rel_l2(g[f'{sp}_dec12_y'], e['x0']):.3e})")
+        t = torch.as_tensor(g["senc_t"]).cuda()
+        z = randn(tuple(e["x0"].shape), int(g["senc_seed"])).cuda()
+        assert rel_l2(sm.stochastic_encode(e["x0"], t, noise=z), g[f"{sp}_senc_y"]) < TOL_OP
+        a, b = sm.stochastic_encode(e["x0"], t, seed=5), sm.stochastic_encode(e["x0"], t, seed=5)
+        assert torch.equal(a, b) and not torch.equal(a, sm.stochastic_encode(e["x0"], t, seed=6))
+
+
+def test_decode_is_the_tail_of_the_sampling_loop(env):
+    """decode(x, c, t_start) runs iterations steps - t_start .. steps - 1 with the eta of the last make_schedule; guided too."""
+    from diffusion_models_dsdiff_amd._sched import Guidance, run_device_loop
+    e = env
+    sm = _sampler(e["m"], eta=1.0)
+    z = _noise(e, 31)
+    want = run_device_loop(e["unet"], sm._schedule(False, True), e["xT"], e["c"], step_noise=z, first_step=STEPS - 7,
+                           guidance=Guidance(e["u"], 3.0, STEPS))
+    got = sm.decode(e["xT"], e["c"], 7, unconditional_guidance_scale=3.0, unconditional_conditioning=e["u"], step_noise=z[STEPS - 7:])
+    assert torch.equal(got, want)
+    a = sm.decode(e["xT"], e["c"], 7, seed=3)
+    assert torch.equal(a, sm.decode(e["xT"], e["c"], 7, seed=3)) and not torch.equal(a, sm.decode(e["xT"], e["c"], 7, seed=4))
+
+
+def test_latent_diffusion_q_sample_masked_ddpm_and_sample_log(lat):
+    """LatentDiffusion.q_sample against ddpm.py:356-359; the masked ancestral loop (:1075-1092) against its restatement with the
+    oracle network (parity unpinned: the reference's ddpm.py does not import without Lightning); sample_log forwards mask / x0."""
+    e, g = lat, lat["g"]
+    ld, T = e["m"], 10
+    t = torch.tensor([999, 3], device="cuda")
+    z = randn((2, 4, 8, 8), 41).cuda()
+    want = (ld.sqrt_alphas_cumprod[t].reshape(2, 1, 1, 1) * e["x0"] + ld.sqrt_one_minus_alphas_cumprod[t].reshape(2, 1, 1, 1) * z)
+    assert rel_l2(ld.q_sample(e["x0"], t, noise=z), want) < TOL_OP
+    assert torch.equal(ld.q_sample(e["x0"], t, seed=8), ld.q_sample(e["x0"], t, seed=8))
+    cond = dict(c_concat=[e["c"]])
+    zs, zb = _noise(e, 42, T), _noise(e, 43, T)
+    gl = golden("latent_ldm")
+    ucfg, usd = O.UNetConfig.from_params(json.loads(str(g["lat_unet_cfg"]))), fixture_params(gl, "unet")
+    cc = e["c"].cpu()
+    ref = ddpm_masked_chain(OS.DiffusionB(timesteps=1000, parameterization="eps"),
+                            lambda img, tt: O.plain_unet_forward(ucfg, usd, torch.cat([img, cc], 1), tt), e["xT"].cpu(), zs.cpu(),
+                            zb.cpu(), e["x0"].cpu(), e["mask"].cpu(), T)
+    with _as(e, "eps"):
+        y = ld.p_sample_loop(cond, (2, 4, 8, 8), x_T=e["xT"], timesteps=T, mask=e["mask"], x0=e["x0"], step_noise=zs, mask_noise=zb)
+        plain = ld.p_sample_loop(cond, (2, 4, 8, 8), x_T=e["xT"], timesteps=T, step_noise=zs)
+        y2, inter = ld.sample_log(cond, 2, "ddpm", STEPS, x_T=e["xT"], timesteps=T, mask=e["mask"], x0=e["x0"], step_noise=zs,
+                                  mask_noise=zb)
+    print(f"masked DDPM loop against the restatement {rel_l2(y, ref):.3e}, against the unmasked loop {rel_l2(y, plain):.3e}")
+    assert rel_l2(y, ref) < TOL and rel_l2(y, plain) > 1e-2 and torch.equal(y, y2)
+    # the blend follows the last update: the kept region ends as q_sample(x0, 0)
+    keep = e["mask"].expand(2, 4, 8, 8).bool()
+    end = ld.sqrt_alphas_cumprod[0] * e["x0"] + ld.sqrt_one_minus_alphas_cumprod[0] * zb[-1]
+    assert torch.equal(y[keep], end[keep])
+    key = "lat_mask_eta1"
+    y, _ = ld.sample_log(cond, 2, "ddim", STEPS, ddim_eta=1.0, x_T=e["xT"], step_noise=_noise(e, g["step_eta1_seed"]),
+                         mask=e["mask"], x0=e["x0"], mask_noise=_noise(e, g["blend_eta1_seed"]))
+    assert rel_l2(y, g[key + "_y"]) < TOL
+
+
+def test_pixel_masked_ddpm_loop_matches_the_restatement(pix, lat):
+    """dsd_sample_masked in mode B_DDPM (the four-stream model; blend after every update) against the torch chain of
+    test_img2img_cpu.py with the oracle network: independent of the project's own ops."""
+    from diffusion_models_dsdiff_amd._sched import Inpaint, run_device_loop
+    e, T = pix, 8
+    gm = golden("model")
+    cfg, sd = O.UNetConfig.from_params(json.loads(str(gm["tiny_cfg"]))), fixture_params(gm, "tiny")
+    zs, zb, cc = _noise(e, 52, T), _noise(e, 53, T), e["c"].cpu()
+    ref = ddpm_masked_chain(OS.DiffusionB(timesteps=1000, parameterization="eps"),
+                            lambda img, tt: O.unet_forward(cfg, sd, torch.cat([img, cc], 1), tt)[0], e["xT"].cpu(), zs.cpu(),
+                            zb.cpu(), e["x0"].cpu(), e["mask"].cpu(), T)
+    sched = _ddpm_sched(lat, T)
+    y = run_device_loop(e["unet"], sched, e["xT"], e["c"], step_noise=zs, inpaint=Inpaint(e["x0"], e["mask"], zb))
+    plain = run_device_loop(e["unet"], sched, e["xT"], e["c"], step_noise=zs)
+    print(f"pixel masked DDPM loop against the restatement {rel_l2(y, ref):.3e}, against the unmasked loop {rel_l2(y, plain):.3e}")
+    assert rel_l2(y, ref) < TOL and rel_l2(y, plain) > 1e-2
+
+
+# ---------------------------------------------------------------------------------------- loop-level checks
+@pytest.mark.parametrize("mode", ["ddim_guided", "ddim", "ddpm"])
+def test_device_loop_matches_host_loop_graph_replay_and_split(env, lat, mode):
+    """dsd_sample_masked / dsd_sample_latent_masked against the loop written here — forward through the module, the update op,
+    the blend op in the loop's own order — with the same fed noise; hipGraph replay and a first_step split bit-identical."""
+    from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, run_device_loop, sampler_update, sampler_update_guided,
+                                                    mask_blend)
+    L = _lib()
+    e, B = env, 2
+    unet, c, u, xT = e["unet"], e["c"], e["u"], e["xT"]
+    guided, ddpm = mode == "ddim_guided", mode == "ddpm"
+    steps = 8 if ddpm else STEPS
+    sched = _ddpm_sched(lat, steps) if ddpm else _ddim_sched(e["m"], eta=1.0)
+    scales = np.linspace(1.5, 3.5, steps).astype(np.float32)
+    z, zb = _noise(e, 811, steps), _noise(e, 812, steps)
+    kw = lambda: dict(step_noise=z, guidance=Guidance(u, scales, steps) if guided else None, inpaint=Inpaint(e["x0"], e["mask"], zb))
+    dev = run_device_loop(unet, sched, xT, c, **kw())
+    x = (torch.cat([xT, xT]) if guided else xT.clone()).contiguous()
+    cin = torch.cat([u, c]) if guided else c
+    for k in range(steps):
+        blend = lambda: mask_blend(sched.coef[k, 0], sched.coef[k, 1], e["x0"], e["mask"], x, zb[k], guided=guided)
+        if not ddpm:
+            blend()                                                           # ddim.py:160-163: in front of the network
+        out = _net(e, x, torch.full((x.shape[0],), float(sched.t_model[k]), device="cuda"), cin)
+        if guided:
+            sampler_update_guided(sched, k, out[:B], out[B:], float(scales[k]), x, z[k])
+        else:
+            sampler_update(sched, k, out, x, z[k])
+        if ddpm:
+            blend()                                                           # ddpm.py:1085-1087: after the update
+    print(f"{e['key']} {mode}: device loop against the host loop {rel_l2(dev, x[:B]):.3e}")
+    assert rel_l2(dev, x[:B]) < TOL_OP
+    caps, launches = C.c_int(), C.c_int()
+    L.check(L.lib().dsd_graph_stats(unet._h, C.byref(caps), C.byref(launches)))
+    before = launches.value
+    L.check(L.lib().dsd_set_graph(unet._h, 1))
+    try:
+        rep = run_device_loop(unet, sched, xT, c, **kw())
+        rep2 = run_device_loop(unet, sched, xT, c, **kw())
+        L.check(L.lib().dsd_graph_stats(unet._h, C.byref(caps), C.byref(launches)))
+    finally:
+        L.check(L.lib().dsd_set_graph(unet._h, 0))
+    assert launches.value > before and torch.equal(rep, dev) and torch.equal(rep2, dev)
+    half = run_device_loop(unet, sched, xT, c, n_steps=steps // 2, **kw())
+    assert torch.equal(run_device_loop(unet, sched, half, c, first_step=steps // 2, **kw()), dev)
+
+
+def test_invert_loop_matches_host_loop_graph_replay_and_split(env):
+    from diffusion_models_dsdiff_amd._sched import Guidance, ddim_invert_step, invert_coefficients, run_invert_loop
+    L = _lib()
+    e, B, n = env, 2, 10
+    unet, c, u = e["unet"], e["c"], e["u"]
+    sm = _sampler(e["m"])
+    coef = invert_coefficients(torch.from_numpy(np.asarray(sm.ddim_alphas[:n], dtype=np.float32)),
+                               torch.tensor(np.asarray(sm.ddim_alphas_prev[:n])))
+    for guided in (False, True):
+        guid = lambda: Guidance(u, 3.0, n) if guided else None
+        dev = run_invert_loop(unet, coef, e["x0"], c, guid())
+        x = (torch.cat([e["x0"], e["x0"]]) if guided else e["x0"].clone()).contiguous()
+        for i in range(n):
+            out = _net(e, x, torch.full((x.shape[0],), float(i), device="cuda"), torch.cat([u, c]) if guided else c)   # model time = i
+            if guided:
+                ddim_invert_step(coef[i, 0], coef[i, 1], out[B:], x, out_uncond=out[:B], scale=3.0)
+            else:
+                ddim_invert_step(coef[i, 0], coef[i, 1], out, x)
+        print(f"{e['key']} guided={guided}: inversion loop against the host loop {rel_l2(dev, x[:B]):.3e}")
+        assert rel_l2(dev, x[:B]) < TOL_OP
+        L.check(L.lib().dsd_set_graph(unet._h, 1))
+        try:
+            rep = run_invert_loop(unet, coef, e["x0"], c, guid())
+        finally:
+            L.check(L.lib().dsd_set_graph(unet._h, 0))
+        half = run_invert_loop(unet, coef, e["x0"], c, guid(), n_steps=4)
+        assert torch.equal(rep, dev) and torch.equal(run_invert_loop(unet, coef, half, c, guid(), first_step=4), dev)
+
+
+def test_masked_guided_with_uncond_equal_cond_and_the_all_zero_mask(env):
+    """u == c at scale 3.0 must give the masked unguided run with the same seed (the blend noise is keyed by logical sample, not
+    by the 2B rows; bar: the project's batch-independence bar); an all-zero mask keeps nothing, so the masked loop is the unmasked
+    one bit for bit."""
+    from diffusion_models_dsdiff_amd._sched import Guidance, Inpaint, run_device_loop
+    e = env
+    sched = _ddim_sched(e["m"], eta=1.0)
+    inp = lambda: Inpaint(e["x0"], e["mask"])
+    run = lambda **kw: run_device_loop(e["unet"], sched, e["xT"], e["c"], **kw)
+    try:
+        _slice_ids(e["unet"], [11, 5])
+        plain = run(seed=9876, inpaint=inp())
+        guided = run(seed=9876, inpaint=inp(), guidance=Guidance(e["c"].clone(), 3.0, STEPS))
+        other = run(seed=9877, inpaint=inp())
+    finally:
+        _slice_ids(e["unet"], [])
+    print(f"{e['key']}: masked, u == c against the unguided run {rel_l2(guided, plain):.3e}")
+    assert rel_l2(guided, plain) < 1e-5 and rel_l2(other, plain) > 1e-2
+    zero = torch.zeros_like(e["mask"])
+    assert torch.equal(run(seed=5, inpaint=Inpaint(e["x0"], zero)), run(seed=5))
+    assert torch.equal(run(seed=5, inpaint=Inpaint(e["x0"], zero), guidance=Guidance(e["u"], 3.0, STEPS)),
+                       run(seed=5, guidance=Guidance(e["u"], 3.0, STEPS)))
+
+
+def test_slice_ids_key_the_blend_noise(env):
+    """With dsd_set_slice_ids the Philox blend noise of a slice does not depend on how slices are grouped into batches: eta 0 (no
+    update noise), a mask that keeps everything — the result is q_sample(x0, t_last) of the blend's own draws."""
+    from diffusion_models_dsdiff_amd._sched import Inpaint, run_device_loop
+    e = env
+    sched = _ddim_sched(e["m"], eta=0.0)
+    ones = torch.ones_like(e["mask"])
+
+    def run(rows, ids, n_steps=1):
+        _slice_ids(e["unet"], ids)
+        try:
+            return run_device_loop(e["unet"], sched, e["xT"][rows], e["c"][rows], seed=77, n_steps=n_steps,
+                                   inpaint=Inpaint(e["x0"][rows], ones[rows]))
+        finally:
+            _slice_ids(e["unet"], [])
+    both = run(slice(0, 2), [11, 5])
+    assert rel_l2(run(slice(0, 1), [11]), both[:1]) < 1e-5 and rel_l2(run(slice(1, 2), [5]), both[1:]) < 1e-5
+    assert rel_l2(run(slice(1, 2), [6]), both[1:]) > 1e-2                     # another slice, other normals
+    assert rel_l2(run(slice(1, 2), []), both[1:]) > 1e-2                      # without ids: keyed by the batch position
+
+
+# ---------------------------------------------------------------------------------------- rejections
+def test_masked_and_inversion_loops_reject_with_a_reason(env, lat):
+    from diffusion_models_dsdiff_amd._sched import Guidance, Inpaint, Schedule, run_device_loop
+    L = _lib()
+    e = env
+    unet, c, u, xT = e["unet"], e["c"], e["u"], e["xT"]
+    sched = _ddim_sched(e["m"])
+    inp = lambda: Inpaint(e["x0"], e["mask"])
+    for mode in (L.MODE_A_DDPM, L.MODE_A_DDIM):                               # no mask in the family-A loops
+        bad = Schedule(mode, L.PRED_EPS, sched.coef, sched.t_model, sched.nonzero)
+        with pytest.raises(L.DsdError, match="LDM family"):
+            run_device_loop(unet, bad, xT, c, inpaint=inp())
+    with pytest.raises(L.DsdError, match="DSD_MODE_B_DDPM.*no guidance"):     # the masked DDPM loop has no guidance
+        run_device_loop(unet, _ddpm_sched(lat, STEPS), xT, c, inpaint=inp(), guidance=Guidance(u, 3.0, STEPS))
+    with pytest.raises(ValueError, match="mask must be"):
+        run_device_loop(unet, sched, xT, c, inpaint=Inpaint(e["x0"], e["mask"][:, :, :4].contiguous()))
+    with pytest.raises(ValueError, match="x0 must have"):
+        run_device_loop(unet, sched, xT, c, inpaint=Inpaint(e["x0"].cpu(), e["mask"]))
+    # the C entry points themselves
+    x = xT.clone()
+    Cz, H, W = x.shape[1:]
+    scales = np.full(STEPS, 3.0, np.float32)
+    guid = L.DsdGuidance(u.data_ptr(), scales.ctypes.data_as(C.POINTER(C.c_float)), STEPS)
+
+    def call(p, g=None, sc=sched):
+        gp = C.byref(g) if g is not None else None
+        if e["key"] == "lat":
+            return L.lib().dsd_sample_latent_masked(unet._h, C.byref(sc.c), gp, C.byref(p), L.dptr(c), c.shape[1], L.dptr(x), Cz,
+                                                    None, C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
+        return L.lib().dsd_sample_masked(unet._h, C.byref(sc.c), gp, C.byref(p), L.dptr(c), c.shape[1], L.dptr(x), None,
+                                         C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
+    err = lambda: L.lib().dsd_last_error().decode()
+    x0p, mp = e["x0"].data_ptr(), e["mask"].data_ptr()
+    assert call(L.DsdInpaint(None, mp, 1, None)) != 0 and "x0 is null" in err()
+    assert call(L.DsdInpaint(x0p, None, 1, None)) != 0 and "mask is null" in err()
+    for ch in (0, 2, Cz + 1):
+        assert call(L.DsdInpaint(x0p, mp, ch, None)) != 0 and f"the mask has {ch} channels" in err()
+    assert call(L.DsdInpaint(x0p, mp, 1, None), L.DsdGuidance(None, guid.scale, STEPS)) != 0 and "uncond is null" in err()
+    assert call(L.DsdInpaint(x0p, mp, 1, None), L.DsdGuidance(u.data_ptr(), guid.scale, STEPS - 1)) != 0 and "scales" in err()
+    try:
+        _slice_ids(unet, [0, 1, 2, 3])
+        assert call(L.DsdInpaint(x0p, mp, 1, None), guid) != 0 and "4 ids but the batch has 2" in err()
+        assert call(L.DsdInpaint(x0p, mp, 1, None)) != 0 and "4 ids but the batch has 2" in err()
+    finally:
+        _slice_ids(unet, [])
+    # inversion: a bad schedule, a wrong scale count
+    coef, tm = np.zeros((4, 2), np.float32), np.arange(4, dtype=np.float32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def inv(sc, g=None):
+        gp = C.byref(g) if g is not None else None
+        if e["key"] == "lat":
+            return L.lib().dsd_invert_latent(unet._h, C.byref(sc), gp, L.dptr(c), c.shape[1], L.dptr(x), Cz, 2, H, W, 0, 0,
+                                             L.stream_ptr())
+        return L.lib().dsd_invert(unet._h, C.byref(sc), gp, L.dptr(c), c.shape[1], L.dptr(x), 2, H, W, 0, 0, L.stream_ptr())
+    assert inv(L.DsdInvertSchedule(0, fp(coef), fp(tm))) != 0 and "bad inversion schedule" in err()
+    assert inv(L.DsdInvertSchedule(4, None, fp(tm))) != 0 and "bad inversion schedule" in err()
+    assert inv(L.DsdInvertSchedule(4, fp(coef), fp(tm)), guid) != 0 and "scales" in err()
+    torch.cuda.synchronize()
+    assert torch.equal(x, xT)                                                 # nothing ran

@@ -10,8 +10,16 @@ With --guidance-scale S (S != 1) three more loops join the alternation: the guid
 the batch — the same network work as the guided one, so guided(B) against unguided(2B) is what the combine and the doubled
 state cost.  Each of the three is preceded by one untimed step of its own, so that no timed run pays for the plan of another
 batch size.
+With --mask the masked device loop (dsd_sample_latent_masked: centre half of the latent sampled, Philox blend noise) is timed
+against the unmasked loop, and with --encode the DDIM inversion loop (dsd_invert_latent, all steps) against plain sampling — the
+same network work per step, so each ratio is what the blend kernel / the inversion step costs.  Same alternation and untimed
+first step as the guided loops.
+With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
+run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this
+build's plain loop (the median of its device, unmasked and sample loops, which are the same call) to their mean.
 
-    python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--json out.json]
+    python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--mask] [--encode]
+                                 [--baseline other.json ...] [--json out.json]
 """
 import argparse
 import json
@@ -45,7 +53,8 @@ def stats(v):
 
 def run_k(K, args):
     from diffusion_models_dsdiff_amd import _lib
-    from diffusion_models_dsdiff_amd._sched import Guidance, run_device_loop, sampler_update
+    from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, invert_coefficients, run_device_loop, run_invert_loop,
+                                                    sampler_update)
     from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
@@ -89,10 +98,25 @@ def run_k(K, args):
             return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)
         return run_device_loop(unet, sched, torch.cat([xT, xT]), torch.cat([c, c]), seed=1, n_steps=n_steps)   # "unguided_2x"
 
+    x0 = randn((B, 4, h, h), 712).cuda()
+    mask = torch.ones(B, 1, h, h, device="cuda")
+    mask[:, :, h // 4:h - h // 4, h // 4:h - h // 4] = 0.
+    inv_coef = invert_coefficients(torch.from_numpy(smp.ddim_alphas.astype("float32")), torch.tensor(smp.ddim_alphas_prev))
+
+    def i2i_loop(kind, n_steps=0):
+        if kind == "masked":
+            return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps, inpaint=Inpaint(x0, mask))
+        if kind == "invert":
+            return run_invert_loop(unet, inv_coef, x0, c, n_steps=n_steps)
+        return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)       # "unmasked" / "sample": the plain loop
+
+    i2i_kinds = (("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ())
     cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
     c = ld.encode_conditions(cond, seed=3)["c_concat"][0]          # warm-up: plans, code objects
     for kind in cfg_kinds:
         cfg_loop(kind)
+    for kind in i2i_kinds:
+        i2i_loop(kind)
     y = device(False)
     device(True)
     device(True)
@@ -100,7 +124,7 @@ def run_k(K, args):
     ld.decode_first_stage(y)
     torch.cuda.synchronize()
     t = {"encode_ms": [], "device_loop_ms": [], "device_loop_graph_ms": [], "python_loop_ms": [], "decode_ms": []}
-    t.update({kind + "_loop_ms": [] for kind in cfg_kinds})
+    t.update({kind + "_loop_ms": [] for kind in cfg_kinds + i2i_kinds})
     outs = {}
     for _ in range(args.repeats):
         c, ms = timed(lambda: ld.encode_conditions(cond, seed=3)["c_concat"][0])
@@ -118,13 +142,22 @@ def run_k(K, args):
             torch.cuda.synchronize()
             _, ms = timed(lambda: cfg_loop(kind))
             t[kind + "_loop_ms"].append(ms)
+        for kind in i2i_kinds:
+            i2i_loop(kind, n_steps=1)                              # untimed, as above
+            torch.cuda.synchronize()
+            _, ms = timed(lambda: i2i_loop(kind))
+            t[kind + "_loop_ms"].append(ms)
     res = {k: stats(v) for k, v in t.items()}
-    for k in ("device_loop", "device_loop_graph", "python_loop") + tuple(kind + "_loop" for kind in cfg_kinds):
+    for k in ("device_loop", "device_loop_graph", "python_loop") + tuple(kind + "_loop" for kind in cfg_kinds + i2i_kinds):
         res[k + "_ms_per_step"] = res[k + "_ms"]["median"] / sched.steps
     if cfg_kinds:
         res["guidance_scale"] = args.guidance_scale
         res["guided_over_unguided_2x"] = res["guided_loop_ms"]["median"] / res["unguided_2x_loop_ms"]["median"]
         res["guided_over_unguided"] = res["guided_loop_ms"]["median"] / res["unguided_loop_ms"]["median"]
+    if args.mask:
+        res["masked_over_unmasked"] = res["masked_loop_ms"]["median"] / res["unmasked_loop_ms"]["median"]
+    if args.encode:
+        res["invert_over_sample"] = res["invert_loop_ms"]["median"] / res["sample_loop_ms"]["median"]
     e2e = res["encode_ms"]["median"] + res["device_loop_ms"]["median"] + res["decode_ms"]["median"]
     res["end_to_end_ms"] = e2e
     res["slices_per_s"] = B / (e2e / 1000.)
@@ -143,6 +176,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--guidance-scale", type=float, default=1.0,
                     help="!= 1: also time the guided loop against the unguided loop at the batch and at twice the batch")
+    ap.add_argument("--mask", action="store_true", help="also time the masked loop against the unmasked loop")
+    ap.add_argument("--encode", action="store_true", help="also time the DDIM inversion loop against plain sampling")
+    ap.add_argument("--baseline", action="append", default=[],
+                    help="bench line of another build on the same machine (repeatable): record its plain loop beside this one's")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     from diffusion_models_dsdiff_amd import _lib
@@ -152,6 +189,19 @@ def main():
            "repeats": args.repeats, "keys": {}}
     for K in [int(v) for v in args.keys.split(",")]:
         out["keys"][str(K)] = run_k(K, args)
+    if args.baseline:
+        base = []
+        for path in args.baseline:
+            with open(path) as f:
+                base.append(json.loads(f.readline()))
+        for K, res in out["keys"].items():
+            theirs = [b["keys"][K]["device_loop_ms"]["median"] for b in base if K in b["keys"]]
+            if not theirs:
+                continue
+            plain = [res[k]["median"] for k in ("device_loop_ms", "unmasked_loop_ms", "sample_loop_ms") if k in res]
+            res["baseline_device_loop_ms"] = theirs
+            res["plain_loop_ms"] = statistics.median(plain)
+            res["plain_over_baseline"] = res["plain_loop_ms"] / statistics.mean(theirs)
     line = json.dumps(out)
     print(line)
     if args.json:
