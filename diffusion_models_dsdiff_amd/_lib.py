@@ -15,7 +15,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 DSD_MAX_LEVELS = 8
 DSD_NCOEF = 8
-MODE_A_DDPM, MODE_A_DDIM, MODE_B_DDPM, MODE_B_DDIM = 0, 1, 2, 3
+MODE_A_DDPM, MODE_A_DDIM, MODE_B_DDPM, MODE_B_DDIM, MODE_B_PLMS = 0, 1, 2, 3, 4
+PLMS_PREDICT, PLMS_CORRECT, PLMS_AB2, PLMS_AB3, PLMS_AB4 = 0, 1, 2, 3, 4
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 5}
 (BLOCK_RES, BLOCK_ATTN, BLOCK_UPSAMPLE, BLOCK_DOWNSAMPLE, BLOCK_DISENTANGLE, BLOCK_SE, BLOCK_CROSSATTN,
@@ -33,6 +34,7 @@ EXPORTS = [
     "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
     "dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent",
     "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
+    "dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step",
 ]
 
 
@@ -190,6 +192,11 @@ def lib() -> C.CDLL:
                                     i32, i32, vp]
     L.dsd_op_q_sample.argtypes = [f32p, f32p, f32p, f32p, C.c_uint64, C.c_uint64, f32p, i64, i32, i32, i32, i32, vp]
     L.dsd_op_ddim_invert_step.argtypes = [C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, i64, i32, i32, i32, i32, vp]
+    L.dsd_sample_plms.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, C.c_float, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_sample_plms_latent.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, C.c_float, f32p, i32, f32p, i32, C.c_uint64, i32, i32, i32,
+                                         i32, i32, vp]
+    L.dsd_op_plms_step.argtypes = [i32, C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, f32p, i64,
+                                   C.c_float, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -250,6 +250,62 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
 
 
 @torch.no_grad()
+def run_plms_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor, threshold: Optional[float] = None,
+                  guidance: Optional[Guidance] = None, inpaint: Optional[Inpaint] = None, seed: Optional[int] = None,
+                  first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
+    """The PLMS device loop (dsd_sample_plms / dsd_sample_plms_latent) on a DSD_MODE_B_PLMS schedule: x_T [B,1,H,W] with the
+    four-stream model, [B,Cz,H,W] with the plain UNetModel.  ``threshold``: dynamic_threshold of norm_thresholding (None / <= 0:
+    off).  The history of noise predictions stays on the denoiser's handle: ``first_step`` = k > 0 continues the run whose
+    iterations 0 .. k-1 ran last on it (x_T = the state they returned) and fails otherwise.  ``seed`` keys the blend noise of
+    ``inpaint`` when it carries none; PLMS itself draws no noise."""
+    if guidance is not None:
+        guidance.check(cond, sched.steps)
+    if inpaint is not None:
+        inpaint.check(x_T, sched.steps)
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
+    if not x_T.is_cuda:
+        raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
+    unet.sync_params()
+    x = x_T.detach().float().contiguous().clone()
+    cond = cond.detach().float().contiguous()
+    g = guidance.bind() if guidance is not None else None
+    inp = inpaint.bind() if inpaint is not None else None
+    gp, ip = C.byref(g) if g is not None else None, C.byref(inp) if inp is not None else None
+    thr = C.c_float(float(threshold) if threshold is not None else 0.0)
+    seed = C.c_uint64(philox_seed(seed) if inp is not None and inp.noise is None else 0)
+    B, Cz, H, W = x.shape
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, x, cond)
+        check(lib().dsd_sample_plms_latent(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed, B, H,
+                                           W, first_step, n_steps, stream_ptr()))
+        return x
+    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
+    check(lib().dsd_sample_plms(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), seed, B, H, W,
+                                first_step, n_steps, stream_ptr()))
+    return x
+
+
+@torch.no_grad()
+def plms_step(order: int, a_t: float, a_prev: float, sqrt_1m_at: float, out_cond: torch.Tensor, h_new: torch.Tensor,
+              x: torch.Tensor, o1: Optional[torch.Tensor] = None, o2: Optional[torch.Tensor] = None,
+              x_saved: Optional[torch.Tensor] = None, out_uncond: Optional[torch.Tensor] = None, scale: float = 1.0,
+              threshold: Optional[float] = None, state_channels: Optional[int] = None) -> None:
+    """One PLMS update (dsd_op_plms_step; _lib.PLMS_PREDICT / PLMS_CORRECT / PLMS_AB2..4), x and the history updated in place.
+    ``h_new`` / ``o1`` / ``o2`` / ``x_saved`` are contiguous [B,Cz,H,W] planes; ``x`` is [B,Cz,H,W] (2B rows with ``out_uncond``),
+    or a [rows,Cz+Cc,H,W] denoiser input with ``state_channels`` = Cz."""
+    B, Cz, H, W = out_cond.shape
+    cz, stride = _rows(x, state_channels)
+    assert cz == Cz and x.shape[0] == (2 * B if out_uncond is not None else B) and tuple(x.shape[2:]) == (H, W)
+    for t in (h_new, o1, o2, x_saved):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, Cz, H, W))
+    check(lib().dsd_op_plms_step(int(order), float(a_t), float(a_prev), float(sqrt_1m_at),
+                                 dptr(out_uncond.float().contiguous()) if out_uncond is not None else None,
+                                 dptr(out_cond.float().contiguous()), float(scale), dptr(h_new), dptr(o1), dptr(o2), dptr(x_saved),
+                                 dptr(x), stride, float(threshold) if threshold is not None else 0.0, B, Cz, H, W, stream_ptr()))
+
+
+@torch.no_grad()
 def sampler_update(sched: Schedule, k: int, model_out: torch.Tensor, x: torch.Tensor,
                    noise: Optional[torch.Tensor], seed: int = 0, want_x0: bool = False):
     """One fused update (dsd_op_sampler_update); x is updated in place."""

@@ -224,7 +224,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -398,8 +398,15 @@ static StepCoef step_coef(const dsd_schedule* sc, int k) {
     return c;
 }
 
+static void reject_plms(const dsd_schedule* sc) {
+    DSD_CHECK(!sc || sc->mode != DSD_MODE_B_PLMS,
+              "DSD_MODE_B_PLMS carries a history of noise predictions across iterations: it runs in dsd_sample_plms / "
+              "dsd_sample_plms_latent only");
+}
+
 static void check_schedule(const dsd_schedule* sc) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
+    reject_plms(sc);
     DSD_CHECK(sc->mode >= DSD_MODE_A_DDPM && sc->mode <= DSD_MODE_B_DDIM, "unknown sampler mode %d", sc->mode);
     DSD_CHECK(sc->pred >= DSD_PRED_EPS && sc->pred <= DSD_PRED_V, "unknown prediction type %d", sc->pred);
     DSD_CHECK(!(sc->learned_range && sc->mode >= DSD_MODE_B_DDPM), "learned-range variance exists only in the guided-diffusion family");
@@ -636,6 +643,7 @@ static void check_guidance(const dsd_guidance* g, int steps) {
 
 static void check_guided_schedule(const dsd_schedule* sc) {
     DSD_CHECK(sc, "bad schedule");
+    reject_plms(sc);
     DSD_CHECK(!sc->learned_range, "classifier-free guidance does not take a learned-range variance (learned_range is set)");
     DSD_CHECK(sc->mode == DSD_MODE_B_DDIM,
               "classifier-free guidance exists only in the DDIM loop of the LDM family (DSD_MODE_B_DDIM); the reference has none in "
@@ -903,6 +911,159 @@ int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_gu
     }
     latent_unbind(h, x, Cz, B, hw, x_bs, s);
     net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+static void check_op_state(int B, int Cz, int H, int W, int64_t x_row_stride);
+
+// ------------------------------------------------------------------------------------------- PLMS
+// plms.py:119-245 on the bindings of the masked DDIM loops: the blend in front of the (first) network evaluation of an iteration,
+// the network through the cached graph, the PLMS kernels next to it.  Every check runs before anything is bound or copied.
+static void check_plms(const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, int Cz) {
+    DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
+    DSD_CHECK(sc->mode == DSD_MODE_B_PLMS, "the PLMS loops take a DSD_MODE_B_PLMS schedule; mode %d belongs to dsd_sample and its kin",
+              sc->mode);
+    DSD_CHECK(!sc->learned_range, "PLMS does not take a learned-range variance (learned_range is set)");
+    DSD_CHECK(sc->pred == DSD_PRED_EPS,
+              "PLMS feeds the network output to its update as a noise prediction (plms.py:227-243); prediction type %d is not one",
+              sc->pred);
+    for (int k = 0; k < sc->steps; ++k)
+        DSD_CHECK(sc->coef[(size_t)k * DSD_NCOEF + 6] == 0.f, "PLMS takes eta = 0 only: sigma of iteration %d is %g, not 0", k,
+                  (double)sc->coef[(size_t)k * DSD_NCOEF + 6]);
+    if (g) check_guidance(g, sc->steps);
+    if (inp) {
+        DSD_CHECK(inp->mask, "masked sampling needs a mask (mask is null)");
+        DSD_CHECK(inp->x0, "a mask needs the image it keeps (x0 is null)");
+        DSD_CHECK(inp->mask_channels == 1 || inp->mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken",
+                  inp->mask_channels, Cz);
+    }
+}
+
+// The iterations [k0, k1) of the range first_step / n_steps select, after the history has been found resident (first_step > 0) or
+// started (first_step = 0).  Nothing is allocated once the planes have their size.
+static void plms_range(dsd_handle* h, const dsd_schedule* sc, int B, int64_t n, int first_step, int n_steps, int* k0, int* k1) {
+    *k0 = first_step < 0 ? 0 : first_step;
+    *k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, *k0 + n_steps);
+    if (*k0 > 0 && *k0 < *k1)
+        DSD_CHECK(h->plms_next == *k0 && h->plms_B == B && h->plms_n == n && h->plms_steps == sc->steps,
+                  "PLMS history for iteration %d is not resident on this handle (it holds %s iteration %d of %d, %d samples of %lld "
+                  "elements): run the iterations before it first, with the same batch and schedule",
+                  *k0, h->plms_next < 0 ? "nothing;" : "the history for", h->plms_next, h->plms_steps, h->plms_B,
+                  (long long)h->plms_n);
+    const size_t planes = ((size_t)3 * B * n * sizeof(float) + 15) / 16 * 16;
+    ensure_buf(&h->plms_hist, &h->plms_hist_cap, planes + plms_norm_doubles(B, n) * sizeof(double));
+}
+
+static void plms_loop(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float thr, float* xs,
+                      int64_t x_bs, uint64_t seed, int B, int Cz, int64_t hw, int k0, int k1, hipStream_t s) {
+    const int64_t n = (int64_t)Cz * hw, plane = (int64_t)B * n;
+    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    const int rows = g ? 2 * B : B;
+    PlmsStep a;
+    a.thr = thr > 0.f ? thr : 0.f;
+    a.out_u = g ? h->mout : nullptr;
+    a.out_c = g ? h->mout + plane : h->mout;
+    a.x = xs;
+    a.x_bs = x_bs;
+    a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->plms_hist) + ((size_t)3 * plane * sizeof(float) + 15) / 16 * 16);
+    float* hist[3] = {h->plms_hist, h->plms_hist + plane, h->plms_hist + 2 * plane};
+    for (int k = k0; k < k1; ++k) {
+        h->plms_next = -1;                                                    // until this iteration's e_t is in its plane
+        if (inp) blend_step(sc, k, inp, xs, x_bs, g != nullptr, seed, B, Cz, hw, ids, s);
+        fill_t(h->tbuf, rows, sc->t_model[k], s);
+        net_run_cached(h, s);
+        const float* c = sc->coef + (size_t)k * DSD_NCOEF;
+        a.a_t = c[4]; a.a_prev = c[5]; a.sigma = c[6]; a.s1m = c[7];
+        a.scale = g ? g->scale[k] : 1.f;
+        if (k == 0) {                                                         // plms.py:228-232: Euler, second evaluation at t_next
+            a.order = DSD_PLMS_PREDICT;
+            a.h_new = hist[0]; a.x_saved = hist[1]; a.o1 = a.o2 = nullptr;
+            plms_step(a, B, Cz, (int)hw, s);
+            fill_t(h->tbuf, rows, sc->t_model[std::min(1, sc->steps - 1)], s);
+            net_run_cached(h, s);
+            a.order = DSD_PLMS_CORRECT;
+            plms_step(a, B, Cz, (int)hw, s);
+        } else {                                                              // newest prediction in plane (k-1) % 3; plane k % 3 retires
+            a.order = std::min(k, 3) + 1;
+            a.h_new = hist[k % 3]; a.o1 = hist[(k + 2) % 3]; a.o2 = hist[(k + 1) % 3]; a.x_saved = nullptr;
+            plms_step(a, B, Cz, (int)hw, s);
+        }
+        h->plms_next = k + 1;
+        h->plms_B = B; h->plms_n = n; h->plms_steps = sc->steps;
+    }
+}
+
+int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float dynamic_threshold,
+                    const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                    void* stream) {
+    DSD_TRY
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    check_plms(sc, g, inp, 1);
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
+    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    int k0, k1;
+    plms_range(h, sc, B, hw, first_step, n_steps, &k0, &k1);
+    float* xs = x;
+    if (g) {
+        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
+    } else {
+        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
+        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
+        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
+        bind_sampling_io(h, x, cond, Cc, hw, s);
+    }
+    plms_loop(h, sc, g, inp, dynamic_threshold, xs, hw, philox_seed, B, 1, hw, k0, k1, s);
+    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
+                           float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B, int H,
+                           int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    check_plms(sc, g, inp, Cz);
+    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    DSD_CHECK(h && h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
+    DSD_CHECK(Cz >= 1 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d B %d H %d W %d", Cz, B, H, W);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W;
+    int k0, k1;
+    plms_range(h, sc, B, (int64_t)Cz * hw, first_step, n_steps, &k0, &k1);
+    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
+    plms_loop(h, sc, g, inp, dynamic_threshold, h->lat_in, x_bs, philox_seed, B, Cz, hw, k0, k1, s);
+    latent_unbind(h, x, Cz, B, hw, x_bs, s);
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_op_plms_step(int order, float a_t, float a_prev, float sqrt_1m_at, const float* out_uncond, const float* out_cond, float scale,
+                     float* h_new, const float* o1, const float* o2, float* x_saved, float* x, int64_t x_row_stride,
+                     float dynamic_threshold, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(order >= DSD_PLMS_PREDICT && order <= DSD_PLMS_AB4, "unknown PLMS order %d", order);
+    DSD_CHECK(out_cond && h_new && x, "null argument");
+    DSD_CHECK(order > DSD_PLMS_CORRECT || x_saved, "the first PLMS step needs x_saved (null)");
+    DSD_CHECK(order < DSD_PLMS_AB2 || o1, "PLMS order %d needs o1 (null)", order);
+    DSD_CHECK(order < DSD_PLMS_AB3 || o2, "PLMS order %d needs o2 (null)", order);
+    check_op_state(B, Cz, H, W, x_row_stride);
+    PlmsStep a;
+    a.a_t = a_t; a.a_prev = a_prev; a.sigma = 0.f; a.s1m = sqrt_1m_at;
+    a.order = order;
+    a.thr = dynamic_threshold > 0.f ? dynamic_threshold : 0.f;
+    a.scale = scale;
+    a.out_u = out_uncond; a.out_c = out_cond;
+    a.h_new = h_new; a.o1 = o1; a.o2 = o2; a.x_saved = x_saved;
+    a.x = x; a.x_bs = x_row_stride;
+    Tmp part(a.thr > 0.f ? plms_norm_doubles(B, (int64_t)Cz * H * W) * sizeof(double) : 0);
+    a.part = part.as<double>();
+    plms_step(a, B, Cz, H * W, (hipStream_t)stream);
     DSD_CATCH
 }
 

@@ -280,6 +280,29 @@ void q_sample_blend(float a, float s, const float* a_row, const float* s_row, co
 // DDIM inversion step: x = cx*x + ce*e, e = out_c or (out_u != nullptr) out_u + scale*(out_c - out_u), then written to both rows
 void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c, float scale, float* x, int B, int Cz, int HW,
                       hipStream_t st, int64_t x_bs = 0);
+// PLMS (sampler.hip): one update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:206-243) on B logical samples of
+// n = Cz*HW elements.  order (DSD_PLMS_*): 0 predict / 1 correct = the two halves of the first step around its second network
+// evaluation, 2..4 = Adams-Bashforth on 1..3 earlier noise predictions.  out_u == nullptr: e_t = out_c, else e_t = out_u +
+// scale*(out_c - out_u) and x_{t-1} goes to rows b and B+b.  h_new: the history plane that receives e_t (order 0, 2, 3, 4; for
+// order 4 it holds the oldest prediction, which the same thread reads first) and from which order 1 reads it back; o1 / o2: the
+// newest and second-newest earlier predictions; x_saved [B,n]: written with x_t by order 0, read by order 1.  thr > 0:
+// pred_x0 *= thr / max(rms(pred_x0), thr) per sample; `part` then needs plms_norm_doubles(B, n) doubles of scratch.
+struct PlmsStep {
+    float a_t = 0.f, a_prev = 0.f, sigma = 0.f, s1m = 0.f;
+    int order = 0;
+    float thr = 0.f, scale = 1.f;
+    const float* out_u = nullptr;
+    const float* out_c = nullptr;
+    float* h_new = nullptr;
+    const float* o1 = nullptr;
+    const float* o2 = nullptr;
+    float* x_saved = nullptr;
+    float* x = nullptr;
+    int64_t x_bs = 0;
+    double* part = nullptr;
+};
+size_t plms_norm_doubles(int B, int64_t n);
+void plms_step(const PlmsStep& a, int B, int Cz, int HW, hipStream_t s);
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s);
 void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_t s);
 // DiagonalGaussianDistribution.sample (ldm/modules/distributions/distributions.py:24-37): moments [B,2E,HW] (NCHW) ->

@@ -650,6 +650,7 @@ void dsd::net_free(dsd_handle* h) {
     if (h->dpm_m) (void)hipFree(h->dpm_m);
     if (h->lat_in) (void)hipFree(h->lat_in);
     if (h->cfg_io) (void)hipFree(h->cfg_io);
+    if (h->plms_hist) (void)hipFree(h->plms_hist);
     if (h->freqs) (void)hipFree(h->freqs);
     if (h->ovf) (void)hipFree(h->ovf);
     if (h->slice_ids) (void)hipFree(h->slice_ids);

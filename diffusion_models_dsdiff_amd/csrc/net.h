@@ -135,6 +135,13 @@ struct dsd_handle {
     float* dpm_m = nullptr;    // dsd_sample_dpm: m_k, m_{k-1} [B,H*W] each + thresholds [B]
     float* lat_in = nullptr;   // latent loops (UNET block): the denoiser's NCHW input [B,Cz+Cc,h,w]; channels [0,Cz) are the state
     float* cfg_io = nullptr;   // guided loops of the four-stream model: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
+    // PLMS loops: three history planes [B,Cz,h,w] (a ring: iteration k >= 1 reads its newest prediction from plane (k-1) % 3 and
+    // retires plane k % 3) followed by the threshold's per-block partial sums.  The history outlives a call, so a later call
+    // with first_step > 0 continues it: plms_next is the iteration it is valid for (-1: none), for plms_B samples of plms_n
+    // elements under a schedule of plms_steps iterations.
+    float* plms_hist = nullptr;
+    int plms_next = -1, plms_B = 0, plms_steps = 0;
+    int64_t plms_n = 0;
     float* freqs = nullptr;    // [model_channels/2] optional timestep-embedding frequency table (host-supplied)
     int64_t* slice_ids = nullptr;  // [n_slice_ids] global slice index of every batch row (Philox counter base), optional
     int n_slice_ids = 0;
@@ -178,7 +185,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0;
 
     float* P(const std::string& name) const;
     const dsd::Param& PP(const std::string& name) const;

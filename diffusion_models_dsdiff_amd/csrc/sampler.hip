@@ -3,7 +3,8 @@
 // Mode A  = guided-diffusion: p_mean_variance / p_sample / ddim_sample
 //           (Disc_diff/guided_diffusion/gaussian_diffusion.py:244-350, 422-465, 618-665)
 // Mode B  = LDM: DDPMModel.p_sample / p_mean_variance (trainers/trainer_ddpm.py:461-482, with
-//           ldm/models/diffusion/ddpm.py:284-311) and DDIMSampler.p_sample_ddim (ldm/models/diffusion/ddim.py:187-261).
+//           ldm/models/diffusion/ddpm.py:284-311) and DDIMSampler.p_sample_ddim (ldm/models/diffusion/ddim.py:187-261);
+//           PLMSSampler.p_sample_plms with norm thresholding (ldm/models/diffusion/plms.py:178-245), further down.
 // The arithmetic is written in the reference's fp32 operation order; coefficient tables come from the host
 // (float64 there, rounded to fp32 once, like _extract_into_tensor(...).float() / the registered fp32 buffers).
 #include "kernels.h"
@@ -545,6 +546,133 @@ void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c
     else
         hipLaunchKernelGGL(ddim_invert_kernel<1>, dim3(cfg_blocks(B * n)), dim3(256), 0, st, cx, ce, out_u, out_c, scale, x, B, n, x_bs);
     check_launch("ddim_invert");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// PLMS (ldm/models/diffusion/plms.py:206-243; PlmsStep in kernels.h).  Grid as the blend's: x over the packs of one sample, y =
+// the sample, so the threshold's scale is block-uniform.  The history planes, x_saved and the two output halves are contiguous
+// [B,n]; the state row b sits at x + b*x_bs and, guided, the result also goes to row B+b.
+// plms_form: e_t, e' and the pred_x0 before thresholding of one pack — the one place both kernels take them from, so the norm
+// kernel sums exactly the values the update kernel scales.  The combinations are the reference's expressions, left to right,
+// every product and sum rounded on its own (file-wide contract(off)), the divisors literals with an IEEE division.
+template <int V>
+__device__ __forceinline__ void plms_form(const PlmsStep& a, int b, int p, int n, Pack<V>& et, Pack<V>& ep, Pack<V>& xt,
+                                          Pack<V>& x0) {
+    const int64_t li = (int64_t)b * n + p;
+    Pack<V> e = ld_pack<V>(a.out_c + li);
+    if (a.out_u) {                                                            // plms.py:189-193
+        const Pack<V> eu = ld_pack<V>(a.out_u + li);
+#pragma unroll
+        for (int j = 0; j < V; ++j) e.v[j] = eu.v[j] + a.scale * (e.v[j] - eu.v[j]);
+    }
+    if (a.order == DSD_PLMS_CORRECT) {                                        // :231-232, e = e_t_next
+        et = ld_pack<V>(a.h_new + li);
+        xt = ld_pack<V>(a.x_saved + li);
+#pragma unroll
+        for (int j = 0; j < V; ++j) ep.v[j] = (et.v[j] + e.v[j]) / 2.f;
+    } else {
+        et = e;
+        xt = ld_pack<V>(a.x + (int64_t)b * a.x_bs + p);
+        if (a.order == DSD_PLMS_PREDICT) {                                    // :230
+            ep = e;
+        } else if (a.order == DSD_PLMS_AB2) {                                 // :235
+            const Pack<V> o1 = ld_pack<V>(a.o1 + li);
+#pragma unroll
+            for (int j = 0; j < V; ++j) ep.v[j] = (3.f * et.v[j] - o1.v[j]) / 2.f;
+        } else if (a.order == DSD_PLMS_AB3) {                                 // :238
+            const Pack<V> o1 = ld_pack<V>(a.o1 + li), o2 = ld_pack<V>(a.o2 + li);
+#pragma unroll
+            for (int j = 0; j < V; ++j) ep.v[j] = (23.f * et.v[j] - 16.f * o1.v[j] + 5.f * o2.v[j]) / 12.f;
+        } else {                                                              // :241, o3 in the plane this step retires
+            const Pack<V> o1 = ld_pack<V>(a.o1 + li), o2 = ld_pack<V>(a.o2 + li), o3 = ld_pack<V>(a.h_new + li);
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                ep.v[j] = (55.f * et.v[j] - 59.f * o1.v[j] + 37.f * o2.v[j] - 9.f * o3.v[j]) / 24.f;
+        }
+    }
+    const float sa = sqrtf(a.a_t);
+#pragma unroll
+    for (int j = 0; j < V; ++j) x0.v[j] = (xt.v[j] - a.s1m * ep.v[j]) / sa;    // :214
+}
+
+// Per-sample sum of pred_x0^2 for norm_thresholding (sampling_util.py:14-16), read-only, launched in front of the update.
+// Deterministic: every thread sums its strided packs in fp64, the block folds its 256 sums in a fixed tree, and block j of
+// sample b writes part[b*gridDim.x + j]; the update kernel adds the partials in index order.  No atomics.
+static constexpr int kPlmsNormBlocks = 32;
+template <int V>
+__global__ __launch_bounds__(256) void plms_x0_norm_kernel(PlmsStep a, int n) {
+    __shared__ double red[256];
+    const int b = blockIdx.y;
+    double acc = 0.0;
+    for (int p = (blockIdx.x * 256 + threadIdx.x) * V; p < n; p += gridDim.x * 256 * V) {
+        Pack<V> et, ep, xt, x0;
+        plms_form<V>(a, b, p, n, et, ep, xt, x0);
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc += (double)x0.v[j] * (double)x0.v[j];
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.part[(int64_t)b * gridDim.x + blockIdx.x] = red[0];
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void plms_update_kernel(PlmsStep a, int B, int n, int nblk) {
+    const int b = blockIdx.y;
+    float thr_scale = 1.f;
+    if (a.thr > 0.f) {                                                        // value / max(sqrt(mean(x0^2)), value)
+        double sum = 0.0;
+        for (int j = 0; j < nblk; ++j) sum += a.part[(int64_t)b * nblk + j];
+        thr_scale = a.thr / fmaxf(sqrtf((float)(sum / (double)n)), a.thr);
+    }
+    const float sp = sqrtf(a.a_prev), sd = sqrtf(1.f - a.a_prev - a.sigma * a.sigma);   // :220,224; sigma = 0: no noise term
+    float* xr = a.x + (int64_t)b * a.x_bs;
+    for (int p = (blockIdx.x * 256 + threadIdx.x) * V; p < n; p += gridDim.x * 256 * V) {
+        const int64_t li = (int64_t)b * n + p;
+        Pack<V> et, ep, xt, x0, res;
+        plms_form<V>(a, b, p, n, et, ep, xt, x0);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (a.thr > 0.f) x0.v[j] = x0.v[j] * thr_scale;
+            res.v[j] = sp * x0.v[j] + sd * ep.v[j];
+        }
+        if (a.order != DSD_PLMS_CORRECT) st_pack<V>(a.h_new + li, et);        // the history takes the raw (guided) e_t (:165-166)
+        if (a.order == DSD_PLMS_PREDICT) st_pack<V>(a.x_saved + li, xt);
+        st_pack<V>(xr + p, res);
+        if (a.out_u) st_pack<V>(xr + p + (int64_t)B * a.x_bs, res);
+    }
+}
+
+size_t plms_norm_doubles(int B, int64_t) { return (size_t)B * kPlmsNormBlocks; }
+
+void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
+    PlmsStep a = step;
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    DSD_CHECK(n <= (int64_t)1 << 30, "PLMS update: one sample has %lld elements; up to 2^30 are taken", (long long)n);
+    DSD_CHECK(B <= 65535, "PLMS update: %d samples; up to 65535 are taken", B);
+    if (a.x_bs <= 0) a.x_bs = n;
+    const bool v4 = n % 4 == 0 && a.x_bs % 4 == 0 && aligned16(a.out_u) && aligned16(a.out_c) && aligned16(a.h_new) &&
+                    aligned16(a.o1) && aligned16(a.o2) && aligned16(a.x_saved) && aligned16(a.x);
+    const int64_t blocks = (n / (v4 ? 4 : 1) + 255) / 256;
+    const int nblk = (int)std::min<int64_t>(blocks, kPlmsNormBlocks);
+    if (a.thr > 0.f) {
+        DSD_CHECK(a.part, "PLMS update: the threshold needs its scratch");
+        if (v4)
+            hipLaunchKernelGGL(plms_x0_norm_kernel<4>, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
+        else
+            hipLaunchKernelGGL(plms_x0_norm_kernel<1>, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
+        check_launch("plms_x0_norm");
+    }
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, 2048), (unsigned)B);
+    if (v4)
+        hipLaunchKernelGGL(plms_update_kernel<4>, grid, dim3(256), 0, s, a, B, (int)n, nblk);
+    else
+        hipLaunchKernelGGL(plms_update_kernel<1>, grid, dim3(256), 0, s, a, B, (int)n, nblk);
+    check_launch("plms_update");
 }
 
 // scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed

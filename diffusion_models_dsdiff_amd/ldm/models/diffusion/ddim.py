@@ -41,6 +41,33 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     return sigmas, a_t, a_prev
 
 
+def pack_schedule(sampler, mode: int, use_original_steps: bool, clip_denoised: bool) -> Schedule:
+    """The coefficient rows of a sampler that has run make_schedule (DDIMSampler, PLMSSampler: the two share the tables,
+    ddim.py:25-55 / plms.py:26-57), row k = the k-th executed iteration, for the device loop of ``mode``."""
+    m = sampler.model
+    buf = lambda name: getattr(m, name).detach().float().cpu().numpy()
+    if use_original_steps:
+        ts = np.arange(sampler.ddpm_num_timesteps)
+        alphas, alphas_prev = buf("alphas_cumprod"), buf("alphas_cumprod_prev")
+        s1m, sig = buf("sqrt_one_minus_alphas_cumprod"), sampler.ddim_sigmas_for_original_num_steps
+    else:
+        ts = sampler.ddim_timesteps
+        alphas, alphas_prev = sampler.ddim_alphas, sampler.ddim_alphas_prev
+        s1m, sig = sampler.ddim_sqrt_one_minus_alphas, sampler.ddim_sigmas
+    n = len(ts)
+    order = np.arange(n - 1, -1, -1)              # index = total_steps - i - 1  (:163)
+    steps = np.asarray(ts)[order]                 # np.flip(timesteps)
+    coef = np.zeros((n, _lib.DSD_NCOEF), dtype=np.float32)
+    coef[:, 0] = buf("sqrt_alphas_cumprod")[steps]               # predict_*_from_z_and_v gather by t
+    coef[:, 1] = buf("sqrt_one_minus_alphas_cumprod")[steps]
+    coef[:, 4] = np.asarray(alphas)[order].astype(np.float32)    # torch.full(..., alphas[index]) -> fp32
+    coef[:, 5] = np.asarray(alphas_prev)[order].astype(np.float32)
+    coef[:, 6] = np.asarray(sig)[order].astype(np.float32)
+    coef[:, 7] = np.asarray(s1m)[order].astype(np.float32)
+    pred = {"eps": _lib.PRED_EPS, "v": _lib.PRED_V}[m.parameterization]
+    return Schedule(mode, pred, coef, steps.astype(np.float32), np.ones(n, dtype=np.int32), clip_denoised=clip_denoised)
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", device=torch.device("cuda"), **kwargs):
         self.model = model
@@ -63,29 +90,7 @@ class DDIMSampler(object):
             (1 - acp_prev) / (1 - acp_t) * (1 - acp_t / acp_prev))).numpy()
 
     def _schedule(self, use_original_steps: bool, clip_denoised: bool) -> Schedule:
-        m = self.model
-        buf = lambda name: getattr(m, name).detach().float().cpu().numpy()
-        if use_original_steps:
-            ts = np.arange(self.ddpm_num_timesteps)
-            alphas, alphas_prev = buf("alphas_cumprod"), buf("alphas_cumprod_prev")
-            s1m, sig = buf("sqrt_one_minus_alphas_cumprod"), self.ddim_sigmas_for_original_num_steps
-        else:
-            ts = self.ddim_timesteps
-            alphas, alphas_prev = self.ddim_alphas, self.ddim_alphas_prev
-            s1m, sig = self.ddim_sqrt_one_minus_alphas, self.ddim_sigmas
-        n = len(ts)
-        order = np.arange(n - 1, -1, -1)              # index = total_steps - i - 1  (:163)
-        steps = np.asarray(ts)[order]                 # np.flip(timesteps)
-        coef = np.zeros((n, _lib.DSD_NCOEF), dtype=np.float32)
-        coef[:, 0] = buf("sqrt_alphas_cumprod")[steps]               # predict_*_from_z_and_v gather by t
-        coef[:, 1] = buf("sqrt_one_minus_alphas_cumprod")[steps]
-        coef[:, 4] = np.asarray(alphas)[order].astype(np.float32)    # torch.full(..., alphas[index]) -> fp32
-        coef[:, 5] = np.asarray(alphas_prev)[order].astype(np.float32)
-        coef[:, 6] = np.asarray(sig)[order].astype(np.float32)
-        coef[:, 7] = np.asarray(s1m)[order].astype(np.float32)
-        pred = {"eps": _lib.PRED_EPS, "v": _lib.PRED_V}[m.parameterization]
-        return Schedule(_lib.MODE_B_DDIM, pred, coef, steps.astype(np.float32), np.ones(n, dtype=np.int32),
-                        clip_denoised=clip_denoised)
+        return pack_schedule(self, _lib.MODE_B_DDIM, use_original_steps, clip_denoised)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,

@@ -26,6 +26,9 @@
  *                                        ldm/models/diffusion/ddim.py:194-219 (p_sample_ddim, ucg_schedule :165-167)
  *                                        ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:324-332
  *                                        (model_wrapper guidance_type="classifier-free")
+ *   dsd_sample_plms / dsd_sample_plms_latent / dsd_op_plms_step
+ *                                  <- PLMSSampler.sample / p_sample_plms  ldm/models/diffusion/plms.py:59-245
+ *                                        with sampling_util.norm_thresholding (dynamic_threshold)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
  *   dsd_op_posterior_sample_scaled <- LatentDiffusion.get_first_stage_encoding(encode_first_stage(x))
  *                                        ldm/models/diffusion/ddpm.py:660-667 with distributions.py:24-37
@@ -205,7 +208,9 @@ int dsd_graph_stats(dsd_handle* h, int* captures, int* launches);
  * With it the on-device Philox noise of a slice is keyed by (seed, step, slice index, pixel) instead of its position in
  * the batch, so a volume gives the same samples however its slices are sharded over GPUs or grouped into batches. */
 int dsd_set_slice_ids(dsd_handle* h, const int64_t* ids_host, int n);
-enum { DSD_MODE_A_DDPM = 0, DSD_MODE_A_DDIM = 1, DSD_MODE_B_DDPM = 2, DSD_MODE_B_DDIM = 3 };
+enum { DSD_MODE_A_DDPM = 0, DSD_MODE_A_DDIM = 1, DSD_MODE_B_DDPM = 2, DSD_MODE_B_DDIM = 3,
+       /* PLMSSampler: dsd_sample_plms / dsd_sample_plms_latent only; every other entry point rejects it */
+       DSD_MODE_B_PLMS = 4 };
 enum { DSD_PRED_EPS = 0, DSD_PRED_X0 = 1, DSD_PRED_V = 2 };
 #define DSD_NCOEF 8
 /* Host-side schedule for `steps` loop iterations, iteration k = 0 is the FIRST executed (largest t).
@@ -216,6 +221,8 @@ enum { DSD_PRED_EPS = 0, DSD_PRED_X0 = 1, DSD_PRED_V = 2 };
  *        A_DDIM re-uses 0-3 and:  4 alpha_bar  5 alpha_bar_prev
  *   B_DDPM (ldm):          0 sqrt_acp 1 sqrt_1m_acp 2 sqrt_recip_acp 3 sqrt_recipm1_acp 4 coef1 5 coef2 6 post_log_var
  *   B_DDIM (ldm):          0 sqrt_acp 1 sqrt_1m_acp 4 a_t 5 a_prev 6 sigma_t 7 sqrt_1m_at
+ *   B_PLMS (ldm):          the slots of B_DDIM; sigma_t must be 0 (PLMS takes eta = 0 only).  The second network evaluation of
+ *                          iteration 0 runs at t_model[min(1, steps - 1)] (plms.py:150)
  * t_model[k]: the timestep value handed to the network at iteration k (timestep_map[t], optionally
  * rescaled, respace.py:123-128); nonzero[k]: 0 only where the reference masks the noise (t == 0). */
 typedef struct dsd_schedule {
@@ -388,6 +395,44 @@ int dsd_op_q_sample(const float* a, const float* s, const float* x0, const float
 /* One inversion step.  out_uncond == NULL: x (B rows) <- cx*x + ce*out_cond; else the guided step on the 2B-row state. */
 int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const float* out_cond, float scale, float* x,
                             int64_t x_row_stride, int B, int Cz, int H, int W, void* stream);
+/* ---- PLMS sampler with norm thresholding ---------------------------------------------------
+ * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
+ * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
+ * dsd_sample_guided) and combines the noise prediction e_t with the up to three earlier ones (plms.py:228-241, fp32, left to
+ * right, true division):
+ *   k = 0   x' = upd(e_t); e_next = network(x', t_model[min(1, steps-1)]); e' = (e_t + e_next) / 2     (two evaluations)
+ *   k = 1   e' = (3 e_t - o1) / 2          k = 2   e' = (23 e_t - 16 o1 + 5 o2) / 12
+ *   k >= 3  e' = (55 e_t - 59 o1 + 37 o2 - 9 o3) / 24
+ *   upd(e): pred_x0 = (x - sqrt_1m_at*e) / sqrt(a_t);  dynamic_threshold v > 0: pred_x0 *= v / max(rms(pred_x0), v), the rms over
+ *           the Cz*H*W elements of each logical sample (sampling_util.norm_thresholding);  x <- sqrt(a_prev)*pred_x0 +
+ *           sqrt(1 - a_prev)*e.  No update noise: sigma is 0, so temperature and noise_dropout act on a zero tensor.
+ * The history receives the raw (guided) e_t.  It lives in the handle: first_step = 0 starts it, first_step = k > 0 continues
+ * the history the previous call on this handle left for iteration k (same B, state shape and schedule length), and fails
+ * otherwise; split runs are bit-identical to the whole run.  The threshold's per-sample sum is formed from fixed per-block
+ * partial sums in fp64, combined in a fixed order: two runs are bit-identical.
+ * g: NULL or the guidance; inp: NULL or the mask, blended in front of the (first) network evaluation of every iteration as in
+ * the masked DDIM loop, with inp->noise / Philox stream (philox_seed, k + 2^32).  dynamic_threshold <= 0: off.
+ * Rejected: any other mode, sigma != 0, learned_range, a prediction type other than DSD_PRED_EPS (the reference feeds the
+ * network output to the update as a noise prediction whatever the parameterization). */
+int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
+                    float dynamic_threshold, const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W,
+                    int first_step, int n_steps, void* stream);
+/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser, set up as in dsd_sample_latent. */
+int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
+                           float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B,
+                           int H, int W, int first_step, int n_steps, void* stream);
+/* One PLMS update (with its norm pass) on caller buffers.  order: DSD_PLMS_PREDICT / DSD_PLMS_CORRECT are the two halves of
+ * iteration 0 around its second network evaluation, DSD_PLMS_AB2..AB4 the multistep updates on 1..3 earlier predictions.
+ * out_uncond == NULL: e = out_cond [B,Cz,H,W], x has B rows; else the guided combination and x is the 2B-row state (row b
+ * read, rows b and B+b written), rows at x + b*x_row_stride (0: Cz*H*W).  History planes are [B,Cz,H,W]:
+ *   PREDICT  h_new <- e_t, x_saved <- x, x <- upd(e_t)
+ *   CORRECT  e_t = h_new, e_next = the network output, x <- upd((e_t + e_next)/2) applied to x_saved; h_new stays e_t
+ *   AB2..4   h_new <- e_t (AB4: h_new holds o3, read first), o1 / o2 the newest / second-newest earlier predictions (read only)
+ * a_t, a_prev, sqrt_1m_at: coefficient slots 4, 5, 7 of the iteration. */
+enum { DSD_PLMS_PREDICT = 0, DSD_PLMS_CORRECT = 1, DSD_PLMS_AB2 = 2, DSD_PLMS_AB3 = 3, DSD_PLMS_AB4 = 4 };
+int dsd_op_plms_step(int order, float a_t, float a_prev, float sqrt_1m_at, const float* out_uncond, const float* out_cond,
+                     float scale, float* h_new, const float* o1, const float* o2, float* x_saved, float* x,
+                     int64_t x_row_stride, float dynamic_threshold, int B, int Cz, int H, int W, void* stream);
 /* Dynamic thresholding alone: y = clamp(x0,-s,s)/s with s_b = max(quantile_ratio(|x0_b|), max_val); x0,y [B,n], s [B]. */
 int dsd_op_dpm_threshold(const float* x0, int B, int n, float ratio, float max_val, float* y, float* s_out, void* stream);
 

@@ -1,0 +1,229 @@
+"""CPU side of the PLMS sampler (tests/golden/plms.npz, tests/golden/gen_plms.py): the reference's PLMSSampler runs reproduced by
+the oracle networks plus the chain of plms.py:147-245 restated here in torch with the reference's expressions and dtypes — which
+pins the fixture to the reference and the order the device kernels follow — then the schedule packing, the argument checks that
+raise before any GPU call, and the ctypes mirror of the header."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import samplers as OS, schedules as S, unet as O
+from util import golden, fixture_params, rel_l2, randn, cond_image
+from test_img2img_cpu import blend, center_mask, guided
+
+TOL = 1e-5        # the bar of test_cfg_cpu.py / test_img2img_cpu.py for their chains
+
+
+# ---------------------------------------------------------------------------------------- restated chain (shared with the GPU tests)
+def norm_thresholding(x0, value):
+    """sampling_util.py:14-16."""
+    s = x0.pow(2).flatten(1).mean(1).sqrt().clamp(min=value).reshape(-1, *((1,) * (x0.ndim - 1)))
+    return x0 * (value / s)
+
+
+def plms_update(x, e, a_t, a_prev, s1m, thr=None, sigma=0.):
+    """get_x_prev_and_pred_x0, plms.py:206-225, at eta 0: the noise term is sigma_t * randn * temperature = a zero tensor."""
+    b = x.shape[0]
+    full = lambda v: torch.full((b, 1, 1, 1), float(v))
+    pred_x0 = (x - full(s1m) * e) / full(a_t).sqrt()
+    if thr is not None:
+        pred_x0 = norm_thresholding(pred_x0, thr)
+    dir_xt = (1. - full(a_prev) - full(sigma) ** 2).sqrt() * e
+    return full(a_prev).sqrt() * pred_x0 + dir_xt
+
+
+def plms_combine(e_t, old, e_next=None):
+    """plms.py:228-241: e_t_prime from e_t and the history ``old`` (oldest first); the empty history takes ``e_next``."""
+    if len(old) == 0:
+        return (e_t + e_next) / 2
+    if len(old) == 1:
+        return (3 * e_t - old[-1]) / 2
+    if len(old) == 2:
+        return (23 * e_t - 16 * old[-1] + 5 * old[-2]) / 12
+    return (55 * e_t - 59 * old[-1] + 37 * old[-2] - 9 * old[-3]) / 24
+
+
+def plms_tables(od, steps):
+    ts = S.make_ddim_timesteps("uniform", steps, od.num_timesteps)
+    sig, a, a_prev = S.make_ddim_sampling_parameters(od.tab["alphas_cumprod"].numpy(), ts, 0.)
+    return ts, sig, a, a_prev, np.sqrt(1. - a)
+
+
+def plms_chain(od, f, img, steps, pre=None, thr=None, count=None):
+    """plms_sampling :147-176 + p_sample_plms :227-245; f(img, t) is the (guided) network on the state, ``pre(i, t, img)`` the
+    mask blend in front of an iteration's first evaluation; ``count`` (a list) receives one entry per network evaluation."""
+    ts, sig, a, a_prev, s1m = plms_tables(od, steps)
+    time_range, total, b = np.flip(ts), ts.shape[0], img.shape[0]
+    old = []
+
+    def net(x, t):
+        if count is not None:
+            count.append(int(t[0]))
+        return f(x, t)
+    for i, step in enumerate(time_range):
+        index = total - i - 1
+        t = torch.full((b,), int(step), dtype=torch.long)
+        t_next = torch.full((b,), int(time_range[min(i + 1, total - 1)]), dtype=torch.long)
+        if pre is not None:
+            img = pre(i, t, img)
+        upd = lambda e: plms_update(img, e, a[index], a_prev[index], s1m[index], thr, sig[index])
+        e_t = net(img, t)
+        e_next = net(upd(e_t), t_next) if not old else None
+        img = upd(plms_combine(e_t, old, e_next))
+        old.append(e_t)
+        if len(old) >= 4:
+            old.pop(0)
+    return img
+
+
+def latent_env():
+    g, gl = golden("plms"), golden("latent_ldm")
+    up = json.loads(str(g["lat_unet_cfg"]))
+    assert up == json.loads(str(gl["unet_cfg"]))
+    ucfg, usd = O.UNetConfig.from_params(up), fixture_params(gl, "unet")
+    net = lambda xx, tt: O.plain_unet_forward(ucfg, usd, xx, tt)
+    c = randn((2, 8, 8, 8), int(g["lat_c_seed"]))
+    return g, net, c, torch.zeros_like(c), randn((2, 4, 8, 8), int(g["lat_xT_seed"]))
+
+
+def pixel_env():
+    g, gm = golden("plms"), golden("model")
+    cfg, sd = O.UNetConfig.from_params(json.loads(str(gm["tiny_cfg"]))), fixture_params(gm, "tiny")
+    net = lambda xx, tt: O.unet_forward(cfg, sd, xx, tt)[0]
+    c = cond_image((2, 1, 32, 32), int(g["pix_cond_seed"]))
+    return g, net, c, torch.zeros_like(c), randn((2, 1, 32, 32), int(g["pix_xT_seed"]))
+
+
+def cases(g, space):
+    """name -> (steps, scale, blend-seed name or None, thresholded, twin) of the fixture."""
+    return {k: tuple(v) for k, v in json.loads(str(g[space + "_cases"])).items()}
+
+
+# ---------------------------------------------------------------------------------------- fixture chains
+@pytest.mark.parametrize("space", ["lat", "pix"])
+def test_restated_chain_reproduces_the_reference(space):
+    g, net, c, u, xT = latent_env() if space == "lat" else pixel_env()
+    od = OS.DiffusionB(timesteps=1000, parameterization="eps")
+    x0, mask, v = randn(tuple(xT.shape), int(g["x0_seed"])), center_mask(xT.shape), float(g[space + "_thr"])
+    table = cases(g, space)
+    if space == "lat":
+        assert {"plms20", "plms_s1", "plms_s2", "plms_s4", "plms_s5", "plms_cfg", "plms_mask", "plms_mask_cfg", "plms_thr",
+                "plms_mask_cfg_thr"} <= set(table)
+    else:
+        assert {"plms20", "plms_cfg", "plms_mask", "plms_thr"} <= set(table)
+    for name, (steps, scale, bs, thresholded, twin) in table.items():
+        assert scale == 1. or scale == float(g["scale"])
+        pre = None
+        if bs:
+            zb = randn((steps,) + tuple(xT.shape), int(g[bs + "_seed"]))
+            pre = lambda i, t, img: blend(od, x0, mask, t, zb[i], img)
+        count = []
+        y = plms_chain(od, guided(net, c, u, scale), xT.clone(), steps, pre=pre, thr=v if thresholded else None, count=count)
+        assert len(count) == steps + 1                                        # the first step evaluates twice
+        assert rel_l2(y, g[f"{space}_{name}_y"]) < TOL, (space, name, rel_l2(y, g[f"{space}_{name}_y"]))
+        if twin:                                                              # a loop that ignores the mask / threshold cannot pass
+            assert rel_l2(g[f"{space}_{name}_y"], g[f"{space}_{twin}_y"]) > 1e-2, (space, name)
+    count = []
+    plms_chain(od, guided(net, c, u, 1.), xT.clone(), 1, count=count)
+    assert count[0] == count[1]                                               # S = 1: the second evaluation at the same t
+
+
+# ---------------------------------------------------------------------------------------- host-side packing, argument forms
+def _ddpm(par="eps"):
+    from diffusion_models_dsdiff_amd.trainers.trainer_ddpm import DDPMModel
+    return DDPMModel(timesteps=1000, parameterization=par)
+
+
+def test_schedule_packing_matches_the_reference_tables():
+    from diffusion_models_dsdiff_amd import _lib
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.plms import PLMSSampler
+    g, m = golden("plms"), _ddpm()
+    sm = PLMSSampler(m)
+    sm.make_schedule(20, verbose=False)
+    for name in ("ddim_timesteps", "ddim_alphas", "ddim_alphas_prev", "ddim_sqrt_one_minus_alphas", "ddim_sigmas"):
+        assert np.array_equal(np.asarray(getattr(sm, name), dtype=np.float64), g[name].astype(np.float64)), name
+    sched = sm._schedule()
+    assert sched.c.mode == _lib.MODE_B_PLMS == 4 and sched.c.pred == _lib.PRED_EPS and sched.steps == 20
+    assert not sched.c.learned_range and not sched.c.clip_denoised
+    flip = lambda name: np.flip(g[name]).astype(np.float32)
+    assert np.array_equal(sched.coef[:, 4], flip("ddim_alphas")) and np.array_equal(sched.coef[:, 5], flip("ddim_alphas_prev"))
+    assert np.array_equal(sched.coef[:, 7], flip("ddim_sqrt_one_minus_alphas"))
+    assert np.all(sched.coef[:, 6] == 0.)                                     # eta 0: no noise term
+    t = np.flip(g["ddim_timesteps"])
+    assert np.array_equal(sched.t_model, t.astype(np.float32))
+    assert np.array_equal(sched.coef[:, 0], m.sqrt_alphas_cumprod.numpy()[t])             # the blend's q_sample pair
+    assert np.array_equal(sched.coef[:, 1], m.sqrt_one_minus_alphas_cumprod.numpy()[t])
+    # t_next of iteration k is t_model[min(k + 1, steps - 1)]: the last row is its own successor, and a one-step run's only one
+    one = PLMSSampler(m)
+    one.make_schedule(1, verbose=False)
+    assert one._schedule().t_model.tolist() == [1.0]
+    # the packing is DDIMSampler's own, with the mode changed
+    dd = DDIMSampler(m)
+    dd.make_schedule(20, verbose=False)
+    ds = dd._schedule(False, False)
+    assert ds.c.mode == _lib.MODE_B_DDIM and np.array_equal(ds.coef, sched.coef) and np.array_equal(ds.t_model, sched.t_model)
+
+
+def test_argument_errors_raise_before_any_gpu_call():
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import MaskWithoutX0
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.plms import PLMSSampler
+    sm = PLMSSampler(_ddpm("eps"))
+    c, x = torch.zeros(2, 1, 8, 8), torch.zeros(2, 1, 8, 8)
+    run = lambda S=4, s=sm, **kw: s.sample(S, 2, (1, 8, 8), c, verbose=False, x_T=x, **kw)
+    with pytest.raises(ValueError, match="ddim_eta must be 0 for PLMS"):
+        run(eta=0.5)
+    with pytest.raises(ValueError, match="ddim_eta must be 0 for PLMS"):
+        sm.make_schedule(4, ddim_eta=1.0, verbose=False)
+    with pytest.raises(IndexError):                                           # timesteps 1, 334, 667, 1000: past the table
+        run(S=3)
+    with pytest.raises(NotImplementedError, match="noise prediction"):
+        run(s=PLMSSampler(_ddpm("v")))
+    for bad in (dict(quantize_x0=True), dict(score_corrector=object()), dict(callback=lambda i: None),
+                dict(img_callback=lambda p, i: None)):
+        with pytest.raises(NotImplementedError):
+            run(**bad)
+    with pytest.raises(MaskWithoutX0):
+        run(mask=torch.ones(2, 1, 8, 8))
+    with pytest.raises(AssertionError):                                       # the reference asserts (plms.py:153)
+        run(mask=torch.ones(2, 1, 8, 8))
+    with pytest.raises(ValueError, match="mask must be"):
+        run(mask=torch.ones(2, 1, 4, 4), x0=x)
+    with pytest.raises(ValueError, match="mask_noise"):
+        run(mask=torch.ones(2, 1, 8, 8), x0=x, mask_noise=torch.zeros(3, 2, 1, 8, 8))
+    with pytest.raises(ValueError, match="shape, dtype and device"):
+        run(unconditional_guidance_scale=3., unconditional_conditioning=c[:, :, :4])
+    # well-formed calls reach the loop: temperature / noise_dropout act on a zero tensor, so they are accepted
+    for ok in (dict(), dict(temperature=0.5, noise_dropout=0.1), dict(dynamic_threshold=2.0), dict(x0=x),
+               dict(mask=torch.ones(2, 1, 8, 8), x0=x, mask_noise=torch.zeros(4, 2, 1, 8, 8)),
+               dict(unconditional_guidance_scale=3., unconditional_conditioning=c)):
+        with pytest.raises(RuntimeError, match="no native denoiser"):
+            run(**ok)
+
+
+def test_structs_enums_and_header_agree():
+    from diffusion_models_dsdiff_amd import _lib
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dsdiff.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"DSD_MODE_B_DDIM = 3,\s*DSD_MODE_B_PLMS = 4\b", code) and _lib.MODE_B_PLMS == 4
+    m = re.search(r"enum \{ DSD_PLMS_PREDICT = 0, DSD_PLMS_CORRECT = 1, DSD_PLMS_AB2 = 2, DSD_PLMS_AB3 = 3, DSD_PLMS_AB4 = 4 \}", code)
+    assert m and (_lib.PLMS_PREDICT, _lib.PLMS_CORRECT, _lib.PLMS_AB2, _lib.PLMS_AB3, _lib.PLMS_AB4) == (0, 1, 2, 3, 4)
+    assert C.sizeof(_lib.DsdSchedule) == 48 and C.sizeof(_lib.DsdGuidance) == 24 and C.sizeof(_lib.DsdInpaint) == 32   # unchanged
+    L = _lib.lib()
+    ctype = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float}
+    for sym in ("dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step"):
+        assert sym in _lib.EXPORTS
+        decl = re.search(r"\bint %s\((.*?)\);" % sym, code, flags=re.S)
+        assert decl, sym
+        params = [p.strip() for p in decl.group(1).split(",")]
+        argtypes = getattr(L, sym).argtypes
+        assert len(argtypes) == len(params), (sym, len(argtypes), len(params))
+        for p, a in zip(params, argtypes):                                    # scalars by type; every pointer is pointer-sized
+            if "*" in p:
+                assert C.sizeof(a) == C.sizeof(C.c_void_p), (sym, p)
+            else:
+                assert a is ctype[p.split()[0]], (sym, p, a)

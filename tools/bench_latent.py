@@ -14,12 +14,16 @@ With --mask the masked device loop (dsd_sample_latent_masked: centre half of the
 against the unmasked loop, and with --encode the DDIM inversion loop (dsd_invert_latent, all steps) against plain sampling — the
 same network work per step, so each ratio is what the blend kernel / the inversion step costs.  Same alternation and untimed
 first step as the guided loops.
+With --plms the PLMS device loop (dsd_sample_plms_latent: one network evaluation per step plus one more at the first step, so
+steps + 1 in all) is timed against the DDIM loop of the same steps: plms_over_ddim is expected near (steps + 1) / steps and is
+measured here, not assumed.  The network of this bench is a v-model, which PLMS does not take; the PLMS schedule is packed as for
+a noise-predicting one — the same kernels and the same work.
 With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
 run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this
 build's plain loop (the median of its device, unmasked and sample loops, which are the same call) to their mean.
 
     python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--mask] [--encode]
-                                 [--baseline other.json ...] [--json out.json]
+                                 [--plms] [--baseline other.json ...] [--json out.json]
 """
 import argparse
 import json
@@ -54,10 +58,11 @@ def stats(v):
 def run_k(K, args):
     from diffusion_models_dsdiff_amd import _lib
     from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, invert_coefficients, run_device_loop, run_invert_loop,
-                                                    sampler_update)
+                                                    run_plms_loop, sampler_update)
     from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.plms import PLMSSampler
     from oracle.synth import synth_params, randn
     dd = dict(SD_VAE)
     up = dict(UNET, in_channels=4 * (K + 1))
@@ -73,6 +78,9 @@ def run_k(K, args):
     smp = DDIMSampler(ld)
     smp.make_schedule(args.steps, ddim_eta=0.0, verbose=False)
     sched = smp._schedule(False, True)
+    pl = PLMSSampler(ld)
+    pl.make_schedule(args.steps, verbose=False)
+    plms_sched = pl._schedule().with_pred(_lib.PRED_EPS)
     L = _lib.lib()
 
     def device(graph):
@@ -108,9 +116,12 @@ def run_k(K, args):
             return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps, inpaint=Inpaint(x0, mask))
         if kind == "invert":
             return run_invert_loop(unet, inv_coef, x0, c, n_steps=n_steps)
-        return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)       # "unmasked" / "sample": the plain loop
+        if kind == "plms":
+            return run_plms_loop(unet, plms_sched, xT, c, n_steps=n_steps)
+        return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)       # "unmasked" / "sample" / "ddim": the plain loop
 
-    i2i_kinds = (("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ())
+    i2i_kinds = ((("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ()) +
+                 (("plms", "ddim") if args.plms else ()))
     cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
     c = ld.encode_conditions(cond, seed=3)["c_concat"][0]          # warm-up: plans, code objects
     for kind in cfg_kinds:
@@ -158,6 +169,9 @@ def run_k(K, args):
         res["masked_over_unmasked"] = res["masked_loop_ms"]["median"] / res["unmasked_loop_ms"]["median"]
     if args.encode:
         res["invert_over_sample"] = res["invert_loop_ms"]["median"] / res["sample_loop_ms"]["median"]
+    if args.plms:
+        res["plms_over_ddim"] = res["plms_loop_ms"]["median"] / res["ddim_loop_ms"]["median"]
+        res["plms_network_evaluations"] = sched.steps + 1
     e2e = res["encode_ms"]["median"] + res["device_loop_ms"]["median"] + res["decode_ms"]["median"]
     res["end_to_end_ms"] = e2e
     res["slices_per_s"] = B / (e2e / 1000.)
@@ -178,6 +192,7 @@ def main():
                     help="!= 1: also time the guided loop against the unguided loop at the batch and at twice the batch")
     ap.add_argument("--mask", action="store_true", help="also time the masked loop against the unmasked loop")
     ap.add_argument("--encode", action="store_true", help="also time the DDIM inversion loop against plain sampling")
+    ap.add_argument("--plms", action="store_true", help="also time the PLMS loop against the DDIM loop of the same steps")
     ap.add_argument("--baseline", action="append", default=[],
                     help="bench line of another build on the same machine (repeatable): record its plain loop beside this one's")
     ap.add_argument("--json", default=None)
@@ -198,7 +213,7 @@ def main():
             theirs = [b["keys"][K]["device_loop_ms"]["median"] for b in base if K in b["keys"]]
             if not theirs:
                 continue
-            plain = [res[k]["median"] for k in ("device_loop_ms", "unmasked_loop_ms", "sample_loop_ms") if k in res]
+            plain = [res[k]["median"] for k in ("device_loop_ms", "unmasked_loop_ms", "sample_loop_ms", "ddim_loop_ms") if k in res]
             res["baseline_device_loop_ms"] = theirs
             res["plain_loop_ms"] = statistics.median(plain)
             res["plain_over_baseline"] = res["plain_loop_ms"] / statistics.mean(theirs)
