@@ -184,6 +184,26 @@ def philox_seed(seed: Optional[int] = None) -> int:
     return int(seed) if seed is not None else _seed_from_torch()
 
 
+def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidance: Optional[Guidance],
+                 inpaint: Optional[Inpaint], cpu_message: str):
+    """The prologue every device loop shares: the guidance / inpaint checks, the denoiser and device tests, parameters synced,
+    the state cloned.  Returns (x, cond, bound guidance or None, bound inpaint or None)."""
+    if guidance is not None:
+        guidance.check(cond, steps)
+    if inpaint is not None:
+        inpaint.check(x_T, steps)
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
+    if not x_T.is_cuda:
+        raise RuntimeError(cpu_message)
+    unet.sync_params()
+    x = x_T.detach().float().contiguous().clone()
+    cond = cond.detach().float().contiguous()
+    g = guidance.bind() if guidance is not None else None
+    inp = inpaint.bind() if inpaint is not None else None
+    return x, cond, g, inp
+
+
 @torch.no_grad()
 def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor,
                     step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
@@ -194,19 +214,8 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
     ``guidance``: classifier-free guidance (dsd_sample_guided / dsd_sample_latent_guided, mode B_DDIM); its unconditional
     conditioning must have the shape, dtype and device of ``cond``.
     ``inpaint``: masked sampling (dsd_sample_masked / dsd_sample_latent_masked, modes B_DDIM and B_DDPM), guided or not."""
-    if guidance is not None:
-        guidance.check(cond, sched.steps)
-    if inpaint is not None:
-        inpaint.check(x_T, sched.steps)
-    if unet is None:
-        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
-    if not x_T.is_cuda:
-        raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
-    unet.sync_params()
-    x = x_T.detach().float().contiguous().clone()
-    cond = cond.detach().float().contiguous()
-    g = guidance.bind() if guidance is not None else None
-    inp = inpaint.bind() if inpaint is not None else None
+    x, cond, g, inp = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
+                                   "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     if is_latent_denoiser(unet):
         check_latent_io(unet, x, cond)
         B, Cz, H, W = x.shape
@@ -258,19 +267,8 @@ def run_plms_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor, 
     off).  The history of noise predictions stays on the denoiser's handle: ``first_step`` = k > 0 continues the run whose
     iterations 0 .. k-1 ran last on it (x_T = the state they returned) and fails otherwise.  ``seed`` keys the blend noise of
     ``inpaint`` when it carries none; PLMS itself draws no noise."""
-    if guidance is not None:
-        guidance.check(cond, sched.steps)
-    if inpaint is not None:
-        inpaint.check(x_T, sched.steps)
-    if unet is None:
-        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
-    if not x_T.is_cuda:
-        raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
-    unet.sync_params()
-    x = x_T.detach().float().contiguous().clone()
-    cond = cond.detach().float().contiguous()
-    g = guidance.bind() if guidance is not None else None
-    inp = inpaint.bind() if inpaint is not None else None
+    x, cond, g, inp = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
+                                   "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     gp, ip = C.byref(g) if g is not None else None, C.byref(inp) if inp is not None else None
     thr = C.c_float(float(threshold) if threshold is not None else 0.0)
     seed = C.c_uint64(philox_seed(seed) if inp is not None and inp.noise is None else 0)
@@ -364,21 +362,13 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     coef = np.ascontiguousarray(coef, dtype=np.float32)
     steps = int(coef.shape[0])
     assert coef.shape == (steps, 2)
-    if guidance is not None:
-        guidance.check(cond, steps)
-    if unet is None:
-        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
-    if not x0.is_cuda:
-        raise RuntimeError("DDIM inversion runs on the MI355X only (no CPU fallback): x0 is on the CPU")
-    unet.sync_params()
-    x = x0.detach().float().contiguous().clone()
-    cond = cond.detach().float().contiguous()
+    x, cond, g, _ = _loop_inputs(unet, x0, cond, steps, guidance, None,
+                                 "DDIM inversion runs on the MI355X only (no CPU fallback): x0 is on the CPU")
     t_model = np.arange(steps, dtype=np.float32)
     sc = DsdInvertSchedule()
     sc.steps = steps
     sc.coef = coef.ctypes.data_as(C.POINTER(C.c_float))
     sc.t_model = t_model.ctypes.data_as(C.POINTER(C.c_float))
-    g = guidance.bind() if guidance is not None else None
     gp = C.byref(g) if g is not None else None
     B, Cz, H, W = x.shape
     if is_latent_denoiser(unet):

@@ -389,32 +389,92 @@ int dsd_block_forward(dsd_handle* h, const float* x, int B, int C, int H, int W,
     DSD_CATCH
 }
 
-static StepCoef step_coef(const dsd_schedule* sc, int k) {
-    StepCoef c{};
-    for (int j = 0; j < DSD_NCOEF; ++j) c.c[j] = sc->coef[(size_t)k * DSD_NCOEF + j];
-    c.mode = sc->mode; c.pred = sc->pred; c.learned_range = sc->learned_range; c.clip = sc->clip_denoised;
-    c.nonzero = sc->nonzero ? sc->nonzero[k] : 1;
-    c.eta = sc->eta;
-    return c;
+}  // extern "C"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------- device sampling loops
+// Every loop is: the checks of the call (all of them before any device work, so a rejected call leaves the state untouched), a
+// LoopBinding (where the state lives), a step_range, run_loop with the sampler's step body, finish.
+struct LoopBinding {
+    float* xs = nullptr;            // the state the loop works on: row b at xs + b*x_bs, rows [0,B) (+ [B,2B) when guided)
+    int64_t x_bs = 0;
+    int B = 0, rows = 0, Cz = 1;    // rows = B, or 2B under classifier-free guidance (uncond half first)
+    int64_t hw = 0;
+    const float* out_u = nullptr;   // the halves of mout: uncond rows (null when unguided), cond rows
+    const float* out_c = nullptr;
+    const int64_t* ids = nullptr;   // slice ids keying the Philox noise, or null
+    float* x = nullptr;             // the caller's state: receives rows [0,B) in finish unless the loop ran on it (xs == x)
+    bool latent = false;            // xs is lat_in (strided rows) rather than x / cfg_io
+    int64_t n() const { return Cz * hw; }
+};
+
+struct Range { int k0, k1; };
+Range step_range(int first_step, int n_steps, int steps) {
+    const int k0 = first_step < 0 ? 0 : first_step;
+    return {k0, n_steps <= 0 ? steps : std::min(steps, k0 + n_steps)};
 }
 
-static void reject_plms(const dsd_schedule* sc) {
-    DSD_CHECK(!sc || sc->mode != DSD_MODE_B_PLMS,
-              "DSD_MODE_B_PLMS carries a history of noise predictions across iterations: it runs in dsd_sample_plms / "
-              "dsd_sample_plms_latent only");
+void check_slice_ids(const dsd_handle* h, int B) {
+    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
 }
 
-static void check_schedule(const dsd_schedule* sc) {
-    DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
-    reject_plms(sc);
-    DSD_CHECK(sc->mode >= DSD_MODE_A_DDPM && sc->mode <= DSD_MODE_B_DDIM, "unknown sampler mode %d", sc->mode);
-    DSD_CHECK(sc->pred >= DSD_PRED_EPS && sc->pred <= DSD_PRED_V, "unknown prediction type %d", sc->pred);
-    DSD_CHECK(!(sc->learned_range && sc->mode >= DSD_MODE_B_DDPM), "learned-range variance exists only in the guided-diffusion family");
+// the four-stream denoiser (DSUnetModel): a one-channel state beside 1 or 3 condition planes
+void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x, int B, int H, int W) {
+    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
+    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
+    check_slice_ids(h, B);
 }
 
-// DiffusionWrapper 'concat' (ddpm.py:1331-1333) without materialising the cat: streams read planes in place
-static void bind_sampling_io(dsd_handle* h, float* x, const float* cond, int Cc, int64_t hw, hipStream_t s) {
-    h->io.plane[0] = x;
+// the plain UNetModel (DSD_BLOCK_UNET) on a Cz-channel latent state with a 'concat' conditioning of Cc channels
+void check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W,
+                  int out_ch) {
+    DSD_CHECK(h && cond && x, "null argument");
+    DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
+    DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
+    const std::vector<int32_t>& a = h->iargs;
+    DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
+    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    DSD_CHECK(a[0] == Cz + Cc, "the UNetModel takes %d input channels but state + conditioning have %d + %d", a[0], Cz, Cc);
+    DSD_CHECK(a[2] == out_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], out_ch);
+    check_slice_ids(h, B);
+}
+
+LoopBinding make_binding(dsd_handle* h, const dsd_guidance* g, float* xs, int64_t x_bs, float* x, int Cz, int B, int64_t hw,
+                         int out_ch) {
+    LoopBinding b;
+    b.xs = xs; b.x_bs = x_bs; b.x = x;
+    b.B = B; b.rows = g ? 2 * B : B; b.Cz = Cz; b.hw = hw;
+    b.out_u = g ? h->mout : nullptr;
+    b.out_c = g ? h->mout + (size_t)B * out_ch * hw : h->mout;
+    b.ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
+    return b;
+}
+
+// The four-stream model reads planes in place (DiffusionWrapper 'concat', ddpm.py:1331-1333, without materialising the cat):
+// unguided the caller's x and cond; guided (ddim.py:197-218) the 2B-row planes of cfg_io — state [2B,1,H,W] then conditions
+// [2B,Cc,H,W] = cat([uncond, cond]) — whose step-invariant halves are copied once per call.
+LoopBinding bind_four_stream(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int B, int H, int W,
+                             int out_ch, hipStream_t s) {
+    const int64_t hw = (int64_t)H * W;
+    const int rows = g ? 2 * B : B;
+    net_plan(h, rows, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && (g || B > 1)) ? h->share_zero_streams : 0, s);
+    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
+    ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
+    float* xs = x;
+    if (g) {
+        ensure_buf(&h->cfg_io, &h->cfg_io_cap, (size_t)2 * B * (1 + Cc) * hw * sizeof(float));
+        xs = h->cfg_io;
+        float* cs = xs + (size_t)2 * B * hw;
+        const size_t xb = (size_t)B * hw * sizeof(float), cb = xb * Cc;
+        DSD_HIP(hipMemcpyAsync(xs, x, xb, hipMemcpyDeviceToDevice, s));
+        DSD_HIP(hipMemcpyAsync(xs + (size_t)B * hw, x, xb, hipMemcpyDeviceToDevice, s));
+        DSD_HIP(hipMemcpyAsync(cs, g->uncond, cb, hipMemcpyDeviceToDevice, s));
+        DSD_HIP(hipMemcpyAsync(cs + (size_t)B * Cc * hw, cond, cb, hipMemcpyDeviceToDevice, s));
+        cond = cs;
+    }
+    h->io.plane[0] = xs;
     h->io.plane_bs[0] = hw;
     h->io.plane[1] = cond;
     h->io.plane_bs[1] = (int64_t)Cc * hw;
@@ -432,66 +492,16 @@ static void bind_sampling_io(dsd_handle* h, float* x, const float* cond, int Cc,
     h->io.t_is_float = 1;
     h->io.out = h->mout;
     h->io.feats = nullptr;
+    return make_binding(h, g, xs, hw, x, 1, B, hw, out_ch);
 }
 
-int dsd_sample(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, const float* noise,
-               uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_schedule(sc);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    const int out_ch = h->cfg.out_channels;
-    DSD_CHECK(out_ch == (sc->learned_range ? 2 : 1), "model has %d output channels but the schedule expects %d", out_ch,
-              sc->learned_range ? 2 : 1);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
-    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-    ensure_buf(&h->mout, &h->mout_cap, (size_t)B * out_ch * hw * sizeof(float));
-    bind_sampling_io(h, x, cond, Cc, hw, s);
-    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        const StepCoef c = step_coef(sc, k);
-        sampler_update(c, h->mout, x, noise ? noise + (size_t)k * B * hw : nullptr, philox_seed, (uint64_t)k, B, (int)hw, s,
-                       nullptr, ids);
-    }
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-int dsd_op_sampler_update(const dsd_schedule* sc, int k, const float* model_out, float* x, const float* noise,
-                          uint64_t philox_seed, int B, int H, int W, float* pred_xstart, void* stream) {
-    DSD_TRY
-    check_schedule(sc);
-    DSD_CHECK(k >= 0 && k < sc->steps && model_out && x, "bad argument");
-    sampler_update(step_coef(sc, k), model_out, x, noise, philox_seed, (uint64_t)k, B, H * W, (hipStream_t)stream, pred_xstart);
-    DSD_CATCH
-}
-
-// ------------------------------------------------------------------------------------------- latent loops (UNET block)
-// The state x [B,Cz,h,w] is copied once into channels [0,Cz) of the denoiser's persistent NCHW input [B,Cz+Cc,h,w] and the
-// conditioning into channels [Cz,Cz+Cc) (DiffusionWrapper 'concat', ddpm.py:1331-1333); every update then reads and writes the
-// state in place there, so the next network evaluation reads x_{t-1} with no concatenation and no copy.  The final state is
-// copied back to x.  Returns the state's row stride: (Cz+Cc)*h*w elements.
-static int64_t latent_bind(dsd_handle* h, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W, int out_ch,
-                           hipStream_t s, const float* uncond = nullptr) {
-    DSD_CHECK(h && cond && x, "null argument");
-    DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
-    DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
-    const std::vector<int32_t>& a = h->iargs;
-    DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
-    DSD_CHECK(a[0] == Cz + Cc, "the UNetModel takes %d input channels but state + conditioning have %d + %d", a[0], Cz, Cc);
-    DSD_CHECK(a[2] == out_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], out_ch);
-    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
+// The state x [B,Cz,h,w] is copied once into channels [0,Cz) of the UNetModel's persistent NCHW input lat_in [rows,Cz+Cc,h,w]
+// and the conditioning into channels [Cz,Cz+Cc) (guided: x_in = cat([x]*2), c_in = cat([uncond, cond])); every update then reads
+// and writes the state in place there, so the next network evaluation reads x_{t-1} with no concatenation and no copy.
+LoopBinding bind_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B, int H, int W,
+                        int out_ch, hipStream_t s) {
     const int64_t hw = (int64_t)H * W, Cin = Cz + Cc;
-    // classifier-free guidance (uncond given): 2B rows, x_in = cat([x]*2), c_in = cat([uncond, cond]) (ddim.py:197-218)
-    const int rows = uncond ? 2 * B : B;
+    const int rows = g ? 2 * B : B;
     net_plan(h, rows, (int)Cin, H, W, 0, 0, 1, 0, 0, s);
     ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
     ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
@@ -502,42 +512,218 @@ static int64_t latent_bind(dsd_handle* h, const float* cond, int Cc, const float
         DSD_HIP(hipMemcpy2DAsync(dst, row, x, (size_t)Cz * hw * sizeof(float), (size_t)Cz * hw * sizeof(float), B,
                                  hipMemcpyDeviceToDevice, s));
         if (Cc)
-            DSD_HIP(hipMemcpy2DAsync(dst + Cz * hw, row, (uncond && half == 0) ? uncond : cond, (size_t)Cc * hw * sizeof(float),
+            DSD_HIP(hipMemcpy2DAsync(dst + Cz * hw, row, (g && half == 0) ? g->uncond : cond, (size_t)Cc * hw * sizeof(float),
                                      (size_t)Cc * hw * sizeof(float), B, hipMemcpyDeviceToDevice, s));
     }
     h->io = IO();
     h->io.x_nchw = h->lat_in;
     h->io.aux = h->tbuf;
     h->io.out = h->mout;
-    return Cin * hw;
+    LoopBinding b = make_binding(h, g, h->lat_in, Cin * hw, x, Cz, B, hw, out_ch);
+    b.latent = true;
+    return b;
 }
 
-static void latent_unbind(dsd_handle* h, float* x, int Cz, int B, int64_t hw, int64_t x_bs, hipStream_t s) {
-    DSD_HIP(hipMemcpy2DAsync(x, (size_t)Cz * hw * sizeof(float), h->lat_in, (size_t)x_bs * sizeof(float),
-                             (size_t)Cz * hw * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+// `latent` selects the denoiser: the plain UNetModel on a Cz-channel state, or the four-stream model (Cz = 1)
+void check_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B,
+                    int H, int W, int out_ch) {
+    if (latent) check_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch);
+    else check_four_stream(h, cond, Cc, x, B, H, W);
+}
+
+LoopBinding bind_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B,
+                          int H, int W, int out_ch, hipStream_t s) {
+    return latent ? bind_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s) : bind_four_stream(h, g, cond, Cc, x, B, H, W, out_ch, s);
+}
+
+// iterations [r.k0, r.k1): pre(k) in front of the network evaluation at time t[k] (through the cached graph), step(k) after it
+template <class Pre, class Step>
+void run_loop(dsd_handle* h, const LoopBinding& b, const float* t, Range r, hipStream_t s, Pre&& pre, Step&& step) {
+    for (int k = r.k0; k < r.k1; ++k) {
+        pre(k);
+        fill_t(h->tbuf, b.rows, t[k], s);
+        net_run_cached(h, s);
+        step(k);
+    }
+}
+
+void finish(dsd_handle* h, const LoopBinding& b, hipStream_t s) {
+    const size_t sample = (size_t)b.n() * sizeof(float);
+    if (b.latent)
+        DSD_HIP(hipMemcpy2DAsync(b.x, sample, b.xs, (size_t)b.x_bs * sizeof(float), sample, b.B, hipMemcpyDeviceToDevice, s));
+    else if (b.xs != b.x)
+        DSD_HIP(hipMemcpyAsync(b.x, b.xs, b.B * sample, hipMemcpyDeviceToDevice, s));
+    net_check_overflow(h, s);
+}
+
+StepCoef step_coef(const dsd_schedule* sc, int k) {
+    StepCoef c{};
+    for (int j = 0; j < DSD_NCOEF; ++j) c.c[j] = sc->coef[(size_t)k * DSD_NCOEF + j];
+    c.mode = sc->mode; c.pred = sc->pred; c.learned_range = sc->learned_range; c.clip = sc->clip_denoised;
+    c.nonzero = sc->nonzero ? sc->nonzero[k] : 1;
+    c.eta = sc->eta;
+    return c;
+}
+
+void check_schedule(const dsd_schedule* sc) {
+    DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
+    DSD_CHECK(sc->mode != DSD_MODE_B_PLMS,
+              "DSD_MODE_B_PLMS carries a history of noise predictions across iterations: it runs in dsd_sample_plms / "
+              "dsd_sample_plms_latent only");
+    DSD_CHECK(sc->mode >= DSD_MODE_A_DDPM && sc->mode <= DSD_MODE_B_DDIM, "unknown sampler mode %d", sc->mode);
+    DSD_CHECK(sc->pred >= DSD_PRED_EPS && sc->pred <= DSD_PRED_V, "unknown prediction type %d", sc->pred);
+    DSD_CHECK(!(sc->learned_range && sc->mode >= DSD_MODE_B_DDPM), "learned-range variance exists only in the guided-diffusion family");
+}
+
+// Classifier-free guidance (ddim.py:194-219 / dpm_solver_pytorch.py:324-332): both halves in ONE network pass over 2B rows (uncond
+// half first), combined by the update kernels (sampler.hip), which write x_{t-1} to both state rows.  Noise and slice ids stay per
+// logical sample.
+void check_guidance(const dsd_guidance* g, int steps) {
+    DSD_CHECK(g->uncond, "guidance needs the unconditional conditioning (uncond is null)");
+    DSD_CHECK(g->scale && g->n_scale == steps, "guidance carries %d scales but the schedule executes %d steps (one scale per step)",
+              g->scale ? g->n_scale : 0, steps);
+}
+
+void check_guided_schedule(const dsd_schedule* sc) {   // after check_schedule
+    DSD_CHECK(!sc->learned_range, "classifier-free guidance does not take a learned-range variance (learned_range is set)");
+    DSD_CHECK(sc->mode == DSD_MODE_B_DDIM,
+              "classifier-free guidance exists only in the DDIM loop of the LDM family (DSD_MODE_B_DDIM); the reference has none in "
+              "mode %d", sc->mode);
+}
+
+void check_mask(const dsd_inpaint* inp, int Cz) {
+    DSD_CHECK(inp && inp->mask, "masked sampling needs a mask (mask is null)");
+    DSD_CHECK(inp->x0, "a mask needs the image it keeps (x0 is null)");
+    DSD_CHECK(inp->mask_channels == 1 || inp->mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken",
+              inp->mask_channels, Cz);
+}
+
+void blend_step(const dsd_schedule* sc, int k, const dsd_inpaint* inp, const LoopBinding& b, uint64_t seed, hipStream_t s) {
+    const float* c = sc->coef + (size_t)k * DSD_NCOEF;
+    q_sample_blend(c[0], c[1], nullptr, nullptr, inp->x0, inp->mask, inp->mask_channels, b.xs,
+                   inp->noise ? inp->noise + (size_t)k * b.B * b.n() : nullptr, seed, (uint64_t)k, b.B, b.Cz, (int)b.hw, s, b.x_bs,
+                   b.out_u != nullptr, b.ids);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------- DDPM / DDIM
+// dsd_sample and its kin: the fused update after every evaluation; guided (g) in DSD_MODE_B_DDIM; masked (inp): ddim.py:160-163
+// blends in front of every network evaluation, ddpm.py:1085-1087 after every update (the masked entry points check inp itself).
+static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
+                   int Cc, float* x, int Cz, const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
+                   void* stream) {
+    check_schedule(sc);
+    if (inp) {
+        DSD_CHECK(sc->mode == DSD_MODE_B_DDPM || sc->mode == DSD_MODE_B_DDIM,
+                  "masked sampling exists only in the loops of the LDM family (DSD_MODE_B_DDPM / DSD_MODE_B_DDIM); the reference has no "
+                  "mask in mode %d", sc->mode);
+        DSD_CHECK(!(g && sc->mode == DSD_MODE_B_DDPM), "the masked DDPM loop (DSD_MODE_B_DDPM) has no guidance in the reference");
+    }
+    if (g) {
+        check_guided_schedule(sc);
+        check_guidance(g, sc->steps);
+    }
+    DSD_CHECK(!(sc->learned_range && Cz > 1),
+              "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
+    const int out_ch = (sc->learned_range ? 2 : 1) * Cz;
+    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch);
+    DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d", h->cfg.out_channels,
+              out_ch);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
+    const bool blend_first = inp && sc->mode == DSD_MODE_B_DDIM, blend_last = inp && !blend_first;
+    run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s,
+             [&](int k) {
+                 if (blend_first) blend_step(sc, k, inp, b, seed, s);
+             },
+             [&](int k) {
+                 sampler_update(step_coef(sc, k), b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs,
+                                noise ? noise + (size_t)k * B * b.n() : nullptr, seed, (uint64_t)k, B, (int)b.hw, s, nullptr, b.ids, Cz,
+                                b.x_bs);
+                 if (blend_last) blend_step(sc, k, inp, b, seed, s);
+             });
+    finish(h, b, s);
+}
+
+int dsd_sample(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, const float* noise,
+               uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    sample(false, h, sc, nullptr, nullptr, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
 }
 
 int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, int Cz, const float* noise,
                       uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
+    sample(true, h, sc, nullptr, nullptr, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    DSD_CHECK(g, "null guidance");
+    sample(false, h, sc, g, nullptr, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                             void* stream) {
+    DSD_TRY
+    DSD_CHECK(g, "null guidance");
+    sample(true, h, sc, g, nullptr, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
+                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                      void* stream) {
+    DSD_TRY
+    check_mask(inp, 1);
+    sample(false, h, sc, g, inp, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
+                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
+                             int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    check_mask(inp, Cz);
+    sample(true, h, sc, g, inp, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_op_sampler_update(const dsd_schedule* sc, int k, const float* model_out, float* x, const float* noise,
+                          uint64_t philox_seed, int B, int H, int W, float* pred_xstart, void* stream) {
+    DSD_TRY
     check_schedule(sc);
-    DSD_CHECK(!(sc->learned_range && Cz > 1),
-              "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, (sc->learned_range ? 2 : 1) * Cz, s);
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        sampler_update(step_coef(sc, k), h->mout, h->lat_in, noise ? noise + (size_t)k * B * Cz * hw : nullptr, philox_seed,
-                       (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
+    DSD_CHECK(k >= 0 && k < sc->steps && model_out && x, "bad argument");
+    sampler_update(step_coef(sc, k), nullptr, model_out, 1.f, x, noise, philox_seed, (uint64_t)k, B, H * W, (hipStream_t)stream,
+                   pred_xstart);
+    DSD_CATCH
+}
+
+static void check_op_state(int B, int Cz, int H, int W, int64_t x_row_stride) {
+    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
+    DSD_CHECK(x_row_stride == 0 || x_row_stride >= (int64_t)Cz * H * W, "x_row_stride %lld is smaller than one sample (%lld)",
+              (long long)x_row_stride, (long long)Cz * H * W);
+}
+
+int dsd_op_sampler_update_guided(const dsd_schedule* sc, int k, const float* out_uncond, const float* out_cond, float scale,
+                                 float* x, int64_t x_row_stride, const float* noise, uint64_t philox_seed, int B, int Cz, int H,
+                                 int W, float* pred_xstart, void* stream) {
+    DSD_TRY
+    check_schedule(sc);
+    check_guided_schedule(sc);
+    DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x, "bad argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    sampler_update(step_coef(sc, k), out_uncond, out_cond, scale, x, noise, philox_seed, (uint64_t)k, B, H * W, (hipStream_t)stream,
+                   pred_xstart, nullptr, Cz, x_row_stride);
     DSD_CATCH
 }
 
@@ -564,57 +750,56 @@ static DpmCoef dpm_coef(const dsd_dpm_schedule* sc, int k) {
     return d;
 }
 
+// One sample = all Cz*h*w elements: the dynamic-thresholding quantile is per sample over C*h*w (sampler.py:379-388).  The
+// four-stream model may carry a learned sigma in a second output channel, which the solver ignores.
+static void sample_dpm(bool latent, dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
+                       float* x, int Cz, int B, int H, int W, void* stream) {
+    check_dpm_schedule(sc);
+    if (g) check_guidance(g, sc->steps);
+    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int Cm = latent ? 1 : h->cfg.out_channels;
+    DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
+    const size_t plane = (size_t)B * b.n();
+    ensure_buf(&h->dpm_m, &h->dpm_m_cap, (2 * plane + B) * sizeof(float));
+    float *m_cur = h->dpm_m, *m_prev = h->dpm_m + plane, *s_buf = h->dpm_m + 2 * plane;
+    run_loop(h, b, sc->t_input, Range{0, sc->steps}, s, [](int) {}, [&](int k) {
+        dpm_step(dpm_coef(sc, k), b.out_u, b.out_c, Cm, g ? g->scale[k] : 1.f, b.xs, m_cur, m_prev, s_buf, sc->threshold_ratio,
+                 sc->threshold_max, B, (int)b.n(), s, b.x_bs);
+        std::swap(m_cur, m_prev);
+    });
+    finish(h, b, s);
+}
+
 int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond, int Cc, float* x, int B, int H, int W,
                    void* stream) {
     DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_dpm_schedule(sc);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    const int out_ch = h->cfg.out_channels;
-    DSD_CHECK(out_ch == 1 || out_ch == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", out_ch);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
-    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-    ensure_buf(&h->mout, &h->mout_cap, (size_t)B * out_ch * hw * sizeof(float));
-    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * hw + B) * sizeof(float));
-    bind_sampling_io(h, x, cond, Cc, hw, s);
-    float* m_cur = h->dpm_m;
-    float* m_prev = h->dpm_m + (size_t)B * hw;
-    float* s_buf = h->dpm_m + (size_t)2 * B * hw;
-    for (int k = 0; k < sc->steps; ++k) {
-        fill_t(h->tbuf, B, sc->t_input[k], s);
-        net_run_cached(h, s);
-        dpm_step(dpm_coef(sc, k), h->mout, out_ch, x, m_cur, m_prev, s_buf, sc->threshold_ratio, sc->threshold_max, B, (int)hw, s);
-        std::swap(m_cur, m_prev);
-    }
-    net_check_overflow(h, s);
+    sample_dpm(false, h, sc, nullptr, cond, Cc, x, 1, B, H, W, stream);
     DSD_CATCH
 }
 
 int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond, int Cc, float* x, int Cz, int B, int H,
                           int W, void* stream) {
     DSD_TRY
-    check_dpm_schedule(sc);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W, n = (int64_t)Cz * hw;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s);
-    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * n + B) * sizeof(float));
-    float* m_cur = h->dpm_m;
-    float* m_prev = h->dpm_m + (size_t)B * n;
-    float* s_buf = h->dpm_m + (size_t)2 * B * n;
-    for (int k = 0; k < sc->steps; ++k) {
-        fill_t(h->tbuf, B, sc->t_input[k], s);
-        net_run_cached(h, s);
-        // one sample = all Cz*h*w elements: the dynamic-thresholding quantile is per sample over C*h*w (sampler.py:379-388)
-        dpm_step(dpm_coef(sc, k), h->mout, 1, h->lat_in, m_cur, m_prev, s_buf, sc->threshold_ratio, sc->threshold_max, B, (int)n, s,
-                 x_bs);
-        std::swap(m_cur, m_prev);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
+    sample_dpm(true, h, sc, nullptr, cond, Cc, x, Cz, B, H, W, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                          int B, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(g, "null guidance");
+    sample_dpm(false, h, sc, g, cond, Cc, x, 1, B, H, W, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
+                                 float* x, int Cz, int B, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(g, "null guidance");
+    sample_dpm(true, h, sc, g, cond, Cc, x, Cz, B, H, W, stream);
     DSD_CATCH
 }
 
@@ -625,173 +810,9 @@ int dsd_op_dpm_step(const dsd_dpm_schedule* sc, int k, const float* model_out, i
     DSD_CHECK(k >= 0 && k < sc->steps && model_out && x && m_cur && (Cm == 1 || Cm == 2), "bad argument");
     DSD_CHECK(sc->order[k] < 2 || m_prev, "a second-order update needs m_prev");
     Tmp sb((size_t)B * sizeof(float));
-    dpm_step(dpm_coef(sc, k), model_out, Cm, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio, sc->threshold_max, B, H * W,
-             (hipStream_t)stream);
+    dpm_step(dpm_coef(sc, k), nullptr, model_out, Cm, 1.f, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio, sc->threshold_max, B,
+             H * W, (hipStream_t)stream);
     DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
-    DSD_CATCH
-}
-
-// ------------------------------------------------------------------------------------------- classifier-free guidance
-// ddim.py:194-219 / dpm_solver_pytorch.py:324-332: both halves in ONE network pass over 2B rows (uncond half first), combined
-// by the guided update kernels (sampler.hip), which write x_{t-1} to both state rows.  Noise and slice ids stay per logical sample.
-static void check_guidance(const dsd_guidance* g, int steps) {
-    DSD_CHECK(g, "null guidance");
-    DSD_CHECK(g->uncond, "guidance needs the unconditional conditioning (uncond is null)");
-    DSD_CHECK(g->scale && g->n_scale == steps, "guidance carries %d scales but the schedule executes %d steps (one scale per step)",
-              g->scale ? g->n_scale : 0, steps);
-}
-
-static void check_guided_schedule(const dsd_schedule* sc) {
-    DSD_CHECK(sc, "bad schedule");
-    reject_plms(sc);
-    DSD_CHECK(!sc->learned_range, "classifier-free guidance does not take a learned-range variance (learned_range is set)");
-    DSD_CHECK(sc->mode == DSD_MODE_B_DDIM,
-              "classifier-free guidance exists only in the DDIM loop of the LDM family (DSD_MODE_B_DDIM); the reference has none in "
-              "mode %d", sc->mode);
-    check_schedule(sc);
-}
-
-// the four-stream model's 2B-row planes: state [2B,1,H,W] then conditions [2B,Cc,H,W] = cat([uncond, cond]); step-invariant
-// halves copied once per call
-static float* guided_bind(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int B, int H, int W,
-                          int out_ch, hipStream_t s) {
-    const int64_t hw = (int64_t)H * W;
-    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
-    net_plan(h, 2 * B, Cc + 1, H, W, Cc == 1, 0, 0, 0, Cc == 1 ? h->share_zero_streams : 0, s);
-    ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)2 * B * sizeof(float));
-    ensure_buf(&h->mout, &h->mout_cap, (size_t)2 * B * out_ch * hw * sizeof(float));
-    ensure_buf(&h->cfg_io, &h->cfg_io_cap, (size_t)2 * B * (1 + Cc) * hw * sizeof(float));
-    float* xs = h->cfg_io;
-    float* cs = xs + (size_t)2 * B * hw;
-    const size_t xb = (size_t)B * hw * sizeof(float), cb = xb * Cc;
-    DSD_HIP(hipMemcpyAsync(xs, x, xb, hipMemcpyDeviceToDevice, s));
-    DSD_HIP(hipMemcpyAsync(xs + (size_t)B * hw, x, xb, hipMemcpyDeviceToDevice, s));
-    DSD_HIP(hipMemcpyAsync(cs, g->uncond, cb, hipMemcpyDeviceToDevice, s));
-    DSD_HIP(hipMemcpyAsync(cs + (size_t)B * Cc * hw, cond, cb, hipMemcpyDeviceToDevice, s));
-    bind_sampling_io(h, xs, cs, Cc, hw, s);
-    return xs;
-}
-
-int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_guided_schedule(sc);
-    check_guidance(g, sc->steps);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
-    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    float* xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, 2 * B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * hw, g->scale[k], xs,
-                           noise ? noise + (size_t)k * B * hw : nullptr, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids);
-    }
-    DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                             void* stream) {
-    DSD_TRY
-    check_guided_schedule(sc);
-    check_guidance(g, sc->steps);
-    DSD_CHECK(Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g->uncond);
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, 2 * B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * Cz * hw, g->scale[k], h->lat_in,
-                           noise ? noise + (size_t)k * B * Cz * hw : nullptr, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids,
-                           Cz, x_bs);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-int dsd_op_sampler_update_guided(const dsd_schedule* sc, int k, const float* out_uncond, const float* out_cond, float scale,
-                                 float* x, int64_t x_row_stride, const float* noise, uint64_t philox_seed, int B, int Cz, int H,
-                                 int W, float* pred_xstart, void* stream) {
-    DSD_TRY
-    check_guided_schedule(sc);
-    DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x, "bad argument");
-    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
-    DSD_CHECK(x_row_stride == 0 || x_row_stride >= (int64_t)Cz * H * W, "x_row_stride %lld is smaller than one sample (%lld)",
-              (long long)x_row_stride, (long long)Cz * H * W);
-    sampler_update_cfg(step_coef(sc, k), out_uncond, out_cond, scale, x, noise, philox_seed, (uint64_t)k, B, H * W,
-                       (hipStream_t)stream, pred_xstart, nullptr, Cz, x_row_stride);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                          int B, int H, int W, void* stream) {
-    DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_dpm_schedule(sc);
-    check_guidance(g, sc->steps);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
-    const int out_ch = h->cfg.out_channels;
-    DSD_CHECK(out_ch == 1 || out_ch == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", out_ch);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    float* xs = guided_bind(h, g, cond, Cc, x, B, H, W, out_ch, s);
-    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * hw + B) * sizeof(float));
-    float* m_cur = h->dpm_m;
-    float* m_prev = h->dpm_m + (size_t)B * hw;
-    float* s_buf = h->dpm_m + (size_t)2 * B * hw;
-    for (int k = 0; k < sc->steps; ++k) {
-        fill_t(h->tbuf, 2 * B, sc->t_input[k], s);
-        net_run_cached(h, s);
-        dpm_step_cfg(dpm_coef(sc, k), h->mout, h->mout + (size_t)B * out_ch * hw, out_ch, g->scale[k], xs, m_cur, m_prev, s_buf,
-                     sc->threshold_ratio, sc->threshold_max, B, (int)hw, s);
-        std::swap(m_cur, m_prev);
-    }
-    DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
-                                 float* x, int Cz, int B, int H, int W, void* stream) {
-    DSD_TRY
-    check_dpm_schedule(sc);
-    check_guidance(g, sc->steps);
-    DSD_CHECK(Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W, n = (int64_t)Cz * hw;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g->uncond);
-    ensure_buf(&h->dpm_m, &h->dpm_m_cap, ((size_t)2 * B * n + B) * sizeof(float));
-    float* m_cur = h->dpm_m;
-    float* m_prev = h->dpm_m + (size_t)B * n;
-    float* s_buf = h->dpm_m + (size_t)2 * B * n;
-    for (int k = 0; k < sc->steps; ++k) {
-        fill_t(h->tbuf, 2 * B, sc->t_input[k], s);
-        net_run_cached(h, s);
-        dpm_step_cfg(dpm_coef(sc, k), h->mout, h->mout + (size_t)B * n, 1, g->scale[k], h->lat_in, m_cur, m_prev, s_buf,
-                     sc->threshold_ratio, sc->threshold_max, B, (int)n, s, x_bs);
-        std::swap(m_cur, m_prev);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
     DSD_CATCH
 }
 
@@ -801,125 +822,20 @@ int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sc, int k, const float* out_u
     DSD_TRY
     check_dpm_schedule(sc);
     DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x && m_cur && (Cm == 1 || Cm == 2), "bad argument");
-    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
+    check_op_state(B, Cz, H, W, x_row_stride);
     DSD_CHECK(Cm == 1 || Cz == 1, "a two-channel (learned-sigma) output needs one state channel; Cz = %d", Cz);
     DSD_CHECK(sc->order[k] < 2 || m_prev, "a second-order update needs m_prev");
-    const int64_t n = (int64_t)Cz * H * W;
-    DSD_CHECK(x_row_stride == 0 || x_row_stride >= n, "x_row_stride %lld is smaller than one sample (%lld)", (long long)x_row_stride,
-              (long long)n);
     Tmp sb((size_t)B * sizeof(float));
-    dpm_step_cfg(dpm_coef(sc, k), out_uncond, out_cond, Cm, scale, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio,
-                 sc->threshold_max, B, (int)n, (hipStream_t)stream, x_row_stride);
+    dpm_step(dpm_coef(sc, k), out_uncond, out_cond, Cm, scale, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio,
+             sc->threshold_max, B, Cz * H * W, (hipStream_t)stream, x_row_stride);
     DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
     DSD_CATCH
 }
 
-// ------------------------------------------------------------------------------------------- image-to-image
-// Masked sampling: ddim.py:160-163 blends in front of every network evaluation, ddpm.py:1085-1087 after every update.  Every
-// check runs before anything is bound or copied, so a rejected call leaves the state untouched.
-static void check_masked(const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, int Cz) {
-    check_schedule(sc);
-    DSD_CHECK(sc->mode == DSD_MODE_B_DDPM || sc->mode == DSD_MODE_B_DDIM,
-              "masked sampling exists only in the loops of the LDM family (DSD_MODE_B_DDPM / DSD_MODE_B_DDIM); the reference has no "
-              "mask in mode %d", sc->mode);
-    DSD_CHECK(!(g && sc->mode == DSD_MODE_B_DDPM), "the masked DDPM loop (DSD_MODE_B_DDPM) has no guidance in the reference");
-    if (g) {
-        check_guided_schedule(sc);
-        check_guidance(g, sc->steps);
-    }
-    DSD_CHECK(inp && inp->mask, "masked sampling needs a mask (mask is null)");
-    DSD_CHECK(inp->x0, "a mask needs the image it keeps (x0 is null)");
-    DSD_CHECK(inp->mask_channels == 1 || inp->mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken",
-              inp->mask_channels, Cz);
-}
-
-static void blend_step(const dsd_schedule* sc, int k, const dsd_inpaint* inp, float* x, int64_t x_bs, bool dup, uint64_t seed, int B,
-                       int Cz, int64_t hw, const int64_t* ids, hipStream_t s) {
-    const float* c = sc->coef + (size_t)k * DSD_NCOEF;
-    q_sample_blend(c[0], c[1], nullptr, nullptr, inp->x0, inp->mask, inp->mask_channels, x,
-                   inp->noise ? inp->noise + (size_t)k * B * Cz * hw : nullptr, seed, (uint64_t)k, B, Cz, (int)hw, s, x_bs, dup, ids);
-}
-
-int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
-                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                      void* stream) {
-    DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_masked(sc, g, inp, 1);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
-    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
-    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    float* xs = x;
-    if (g) {
-        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
-    } else {
-        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
-        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
-        bind_sampling_io(h, x, cond, Cc, hw, s);
-    }
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const bool ddim = sc->mode == DSD_MODE_B_DDIM;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        if (ddim) blend_step(sc, k, inp, xs, hw, g != nullptr, philox_seed, B, 1, hw, ids, s);
-        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        const float* nz = noise ? noise + (size_t)k * B * hw : nullptr;
-        if (g)
-            sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * hw, g->scale[k], xs, nz, philox_seed, (uint64_t)k, B,
-                               (int)hw, s, nullptr, ids);
-        else
-            sampler_update(step_coef(sc, k), h->mout, xs, nz, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids);
-        if (!ddim) blend_step(sc, k, inp, xs, hw, false, philox_seed, B, 1, hw, ids, s);
-    }
-    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
-                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
-                             int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    check_masked(sc, g, inp, Cz);
-    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const bool ddim = sc->mode == DSD_MODE_B_DDIM;
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        if (ddim) blend_step(sc, k, inp, h->lat_in, x_bs, g != nullptr, philox_seed, B, Cz, hw, ids, s);
-        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        const float* nz = noise ? noise + (size_t)k * B * Cz * hw : nullptr;
-        if (g)
-            sampler_update_cfg(step_coef(sc, k), h->mout, h->mout + (size_t)B * Cz * hw, g->scale[k], h->lat_in, nz, philox_seed,
-                               (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
-        else
-            sampler_update(step_coef(sc, k), h->mout, h->lat_in, nz, philox_seed, (uint64_t)k, B, (int)hw, s, nullptr, ids, Cz, x_bs);
-        if (!ddim) blend_step(sc, k, inp, h->lat_in, x_bs, false, philox_seed, B, Cz, hw, ids, s);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
-    DSD_CATCH
-}
-
-static void check_op_state(int B, int Cz, int H, int W, int64_t x_row_stride);
-
 // ------------------------------------------------------------------------------------------- PLMS
-// plms.py:119-245 on the bindings of the masked DDIM loops: the blend in front of the (first) network evaluation of an iteration,
-// the network through the cached graph, the PLMS kernels next to it.  Every check runs before anything is bound or copied.
-static void check_plms(const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, int Cz) {
+// plms.py:119-245: the blend in front of the (first) network evaluation of an iteration, the PLMS kernels after it.  The history
+// of noise predictions stays on the handle: iterations from first_step > 0 need it resident, first_step = 0 starts it.
+static void check_plms_schedule(const dsd_schedule* sc) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
     DSD_CHECK(sc->mode == DSD_MODE_B_PLMS, "the PLMS loops take a DSD_MODE_B_PLMS schedule; mode %d belongs to dsd_sample and its kin",
               sc->mode);
@@ -930,96 +846,70 @@ static void check_plms(const dsd_schedule* sc, const dsd_guidance* g, const dsd_
     for (int k = 0; k < sc->steps; ++k)
         DSD_CHECK(sc->coef[(size_t)k * DSD_NCOEF + 6] == 0.f, "PLMS takes eta = 0 only: sigma of iteration %d is %g, not 0", k,
                   (double)sc->coef[(size_t)k * DSD_NCOEF + 6]);
-    if (g) check_guidance(g, sc->steps);
-    if (inp) {
-        DSD_CHECK(inp->mask, "masked sampling needs a mask (mask is null)");
-        DSD_CHECK(inp->x0, "a mask needs the image it keeps (x0 is null)");
-        DSD_CHECK(inp->mask_channels == 1 || inp->mask_channels == Cz, "the mask has %d channels; 1 or the state's %d are taken",
-                  inp->mask_channels, Cz);
-    }
 }
 
-// The iterations [k0, k1) of the range first_step / n_steps select, after the history has been found resident (first_step > 0) or
-// started (first_step = 0).  Nothing is allocated once the planes have their size.
-static void plms_range(dsd_handle* h, const dsd_schedule* sc, int B, int64_t n, int first_step, int n_steps, int* k0, int* k1) {
-    *k0 = first_step < 0 ? 0 : first_step;
-    *k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, *k0 + n_steps);
-    if (*k0 > 0 && *k0 < *k1)
-        DSD_CHECK(h->plms_next == *k0 && h->plms_B == B && h->plms_n == n && h->plms_steps == sc->steps,
+static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float thr,
+                        const float* cond, int Cc, float* x, int Cz, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
+                        void* stream) {
+    check_plms_schedule(sc);
+    if (g) check_guidance(g, sc->steps);
+    if (inp) check_mask(inp, Cz);
+    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
+    const int64_t n = (int64_t)Cz * H * W, plane = (int64_t)B * n;
+    const Range r = step_range(first_step, n_steps, sc->steps);
+    if (r.k0 > 0 && r.k0 < r.k1)
+        DSD_CHECK(h->plms_next == r.k0 && h->plms_B == B && h->plms_n == n && h->plms_steps == sc->steps,
                   "PLMS history for iteration %d is not resident on this handle (it holds %s iteration %d of %d, %d samples of %lld "
                   "elements): run the iterations before it first, with the same batch and schedule",
-                  *k0, h->plms_next < 0 ? "nothing;" : "the history for", h->plms_next, h->plms_steps, h->plms_B,
+                  r.k0, h->plms_next < 0 ? "nothing;" : "the history for", h->plms_next, h->plms_steps, h->plms_B,
                   (long long)h->plms_n);
-    const size_t planes = ((size_t)3 * B * n * sizeof(float) + 15) / 16 * 16;
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t planes = ((size_t)3 * plane * sizeof(float) + 15) / 16 * 16;   // nothing is allocated once the planes have their size
     ensure_buf(&h->plms_hist, &h->plms_hist_cap, planes + plms_norm_doubles(B, n) * sizeof(double));
-}
-
-static void plms_loop(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float thr, float* xs,
-                      int64_t x_bs, uint64_t seed, int B, int Cz, int64_t hw, int k0, int k1, hipStream_t s) {
-    const int64_t n = (int64_t)Cz * hw, plane = (int64_t)B * n;
-    const int64_t* ids = h->n_slice_ids == B ? h->slice_ids : nullptr;
-    const int rows = g ? 2 * B : B;
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz, s);
     PlmsStep a;
     a.thr = thr > 0.f ? thr : 0.f;
-    a.out_u = g ? h->mout : nullptr;
-    a.out_c = g ? h->mout + plane : h->mout;
-    a.x = xs;
-    a.x_bs = x_bs;
-    a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->plms_hist) + ((size_t)3 * plane * sizeof(float) + 15) / 16 * 16);
+    a.out_u = b.out_u;
+    a.out_c = b.out_c;
+    a.x = b.xs;
+    a.x_bs = b.x_bs;
+    a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->plms_hist) + planes);
     float* hist[3] = {h->plms_hist, h->plms_hist + plane, h->plms_hist + 2 * plane};
-    for (int k = k0; k < k1; ++k) {
-        h->plms_next = -1;                                                    // until this iteration's e_t is in its plane
-        if (inp) blend_step(sc, k, inp, xs, x_bs, g != nullptr, seed, B, Cz, hw, ids, s);
-        fill_t(h->tbuf, rows, sc->t_model[k], s);
-        net_run_cached(h, s);
-        const float* c = sc->coef + (size_t)k * DSD_NCOEF;
-        a.a_t = c[4]; a.a_prev = c[5]; a.sigma = c[6]; a.s1m = c[7];
-        a.scale = g ? g->scale[k] : 1.f;
-        if (k == 0) {                                                         // plms.py:228-232: Euler, second evaluation at t_next
-            a.order = DSD_PLMS_PREDICT;
-            a.h_new = hist[0]; a.x_saved = hist[1]; a.o1 = a.o2 = nullptr;
-            plms_step(a, B, Cz, (int)hw, s);
-            fill_t(h->tbuf, rows, sc->t_model[std::min(1, sc->steps - 1)], s);
-            net_run_cached(h, s);
-            a.order = DSD_PLMS_CORRECT;
-            plms_step(a, B, Cz, (int)hw, s);
-        } else {                                                              // newest prediction in plane (k-1) % 3; plane k % 3 retires
-            a.order = std::min(k, 3) + 1;
-            a.h_new = hist[k % 3]; a.o1 = hist[(k + 2) % 3]; a.o2 = hist[(k + 1) % 3]; a.x_saved = nullptr;
-            plms_step(a, B, Cz, (int)hw, s);
-        }
-        h->plms_next = k + 1;
-        h->plms_B = B; h->plms_n = n; h->plms_steps = sc->steps;
-    }
+    run_loop(h, b, sc->t_model, r, s,
+             [&](int k) {
+                 h->plms_next = -1;                                           // until this iteration's e_t is in its plane
+                 if (inp) blend_step(sc, k, inp, b, seed, s);
+             },
+             [&](int k) {
+                 const float* c = sc->coef + (size_t)k * DSD_NCOEF;
+                 a.a_t = c[4]; a.a_prev = c[5]; a.sigma = c[6]; a.s1m = c[7];
+                 a.scale = g ? g->scale[k] : 1.f;
+                 if (k == 0) {                                                // plms.py:228-232: Euler, second evaluation at t_next
+                     a.order = DSD_PLMS_PREDICT;
+                     a.h_new = hist[0]; a.x_saved = hist[1]; a.o1 = a.o2 = nullptr;
+                     plms_step(a, B, Cz, (int)b.hw, s);
+                     fill_t(h->tbuf, b.rows, sc->t_model[std::min(1, sc->steps - 1)], s);
+                     net_run_cached(h, s);
+                     a.order = DSD_PLMS_CORRECT;
+                     plms_step(a, B, Cz, (int)b.hw, s);
+                 } else {                                                     // newest prediction in plane (k-1) % 3; plane k % 3 retires
+                     a.order = std::min(k, 3) + 1;
+                     a.h_new = hist[k % 3]; a.o1 = hist[(k + 2) % 3]; a.o2 = hist[(k + 1) % 3]; a.x_saved = nullptr;
+                     plms_step(a, B, Cz, (int)b.hw, s);
+                 }
+                 h->plms_next = k + 1;
+                 h->plms_B = B; h->plms_n = n; h->plms_steps = sc->steps;
+             });
+    finish(h, b, s);
 }
 
 int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float dynamic_threshold,
                     const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
                     void* stream) {
     DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_plms(sc, g, inp, 1);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
-    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
-    DSD_CHECK(h->n_slice_ids == 0 || h->n_slice_ids == B, "dsd_set_slice_ids gave %d ids but the batch has %d slices", h->n_slice_ids, B);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    int k0, k1;
-    plms_range(h, sc, B, hw, first_step, n_steps, &k0, &k1);
-    float* xs = x;
-    if (g) {
-        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
-    } else {
-        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
-        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
-        bind_sampling_io(h, x, cond, Cc, hw, s);
-    }
-    plms_loop(h, sc, g, inp, dynamic_threshold, xs, hw, philox_seed, B, 1, hw, k0, k1, s);
-    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    net_check_overflow(h, s);
+    sample_plms(false, h, sc, g, inp, dynamic_threshold, cond, Cc, x, 1, philox_seed, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
@@ -1027,19 +917,7 @@ int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sc, const dsd_guid
                            float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B, int H,
                            int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
-    check_plms(sc, g, inp, Cz);
-    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
-    DSD_CHECK(h && h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
-    DSD_CHECK(Cz >= 1 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d B %d H %d W %d", Cz, B, H, W);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    int k0, k1;
-    plms_range(h, sc, B, (int64_t)Cz * hw, first_step, n_steps, &k0, &k1);
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
-    plms_loop(h, sc, g, inp, dynamic_threshold, h->lat_in, x_bs, philox_seed, B, Cz, hw, k0, k1, s);
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
+    sample_plms(true, h, sc, g, inp, dynamic_threshold, cond, Cc, x, Cz, philox_seed, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
@@ -1067,71 +945,35 @@ int dsd_op_plms_step(int order, float a_t, float a_prev, float sqrt_1m_at, const
     DSD_CATCH
 }
 
-// DDIM inversion (ddim.py:263-308): the sampling loops' bindings, the inversion step in place of the update
-static void check_invert(const dsd_invert_schedule* sc, const dsd_guidance* g) {
+// ------------------------------------------------------------------------------------------- DDIM inversion
+// ddim.py:263-308: the sampling loops' bindings, the inversion step in place of the update
+static void invert(bool latent, dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                   int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
     if (g) check_guidance(g, sc->steps);
+    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz, s);
+    run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s, [](int) {}, [&](int k) {
+        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs, B, Cz, (int)b.hw, s, b.x_bs);
+    });
+    finish(h, b, s);
 }
 
 int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
                int H, int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
-    check_invert(sc, g);
-    DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
-    DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
-    DSD_CHECK(h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    float* xs = x;
-    if (g) {
-        xs = guided_bind(h, g, cond, Cc, x, B, H, W, 1, s);
-    } else {
-        net_plan(h, B, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && B > 1) ? h->share_zero_streams : 0, s);
-        ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)B * sizeof(float));
-        ensure_buf(&h->mout, &h->mout_cap, (size_t)B * hw * sizeof(float));
-        bind_sampling_io(h, x, cond, Cc, hw, s);
-    }
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], g ? h->mout : nullptr, g ? h->mout + (size_t)B * hw : h->mout,
-                         g ? g->scale[k] : 1.f, xs, B, 1, (int)hw, s);
-    }
-    if (g) DSD_HIP(hipMemcpyAsync(x, xs, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    net_check_overflow(h, s);
+    invert(false, h, sc, g, cond, Cc, x, 1, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
 int dsd_invert_latent(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
                       int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
-    check_invert(sc, g);
-    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
-    set_device(h ? h->device : 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t hw = (int64_t)H * W;
-    const int64_t x_bs = latent_bind(h, cond, Cc, x, Cz, B, H, W, Cz, s, g ? g->uncond : nullptr);
-    const int k0 = first_step < 0 ? 0 : first_step;
-    const int k1 = n_steps <= 0 ? sc->steps : std::min(sc->steps, k0 + n_steps);
-    for (int k = k0; k < k1; ++k) {
-        fill_t(h->tbuf, g ? 2 * B : B, sc->t_model[k], s);
-        net_run_cached(h, s);
-        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], g ? h->mout : nullptr, g ? h->mout + (size_t)B * Cz * hw : h->mout,
-                         g ? g->scale[k] : 1.f, h->lat_in, B, Cz, (int)hw, s, x_bs);
-    }
-    latent_unbind(h, x, Cz, B, hw, x_bs, s);
-    net_check_overflow(h, s);
+    invert(true, h, sc, g, cond, Cc, x, Cz, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
-}
-
-static void check_op_state(int B, int Cz, int H, int W, int64_t x_row_stride) {
-    DSD_CHECK(B >= 1 && Cz >= 1 && H >= 1 && W >= 1, "bad shape: B %d Cz %d H %d W %d", B, Cz, H, W);
-    DSD_CHECK(x_row_stride == 0 || x_row_stride >= (int64_t)Cz * H * W, "x_row_stride %lld is smaller than one sample (%lld)",
-              (long long)x_row_stride, (long long)Cz * H * W);
 }
 
 int dsd_op_mask_blend(float a, float s, const float* x0, const float* mask, int mask_channels, float* x, int64_t x_row_stride,

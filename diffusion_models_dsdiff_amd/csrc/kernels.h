@@ -243,13 +243,17 @@ struct StepCoef {
     int mode, pred, learned_range, clip, nonzero;
     float eta;
 };
-// model_out: [B,Cm*Cz,HW] (Cm = 1, or 2 with learned_range and Cz = 1); x in/out [B,Cz,HW] with row stride x_bs (0 = Cz*HW);
-// noise [B,Cz,HW] or null (Philox)
+// out_c: the model output [B,Cm*Cz,HW] (Cm = 1, or 2 with learned_range and Cz = 1); x in/out [B,Cz,HW] with row stride x_bs
+// (0 = Cz*HW); noise [B,Cz,HW] or null (Philox)
 // slice_ids (optional, device [B]): global slice index of every batch row — the Philox counter of element r = c*HW + p of row b
 // is slice_ids[b]*Cz*HW + r instead of b*Cz*HW + r, so a slice's noise does not depend on how the volume was sharded or batched
-void sampler_update(const StepCoef& sc, const float* model_out, float* x, const float* noise, uint64_t seed,
-                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr, const int64_t* slice_ids = nullptr,
-                    int Cz = 1, int64_t x_bs = 0);
+// Classifier-free guidance (out_u != nullptr, DSD_MODE_B_DDIM): the network ran on 2B rows (uncond half first), out_u / out_c are
+// the two [B,..] halves of its output and x is the 2B-row state (logical sample b at rows b and B+b, row stride x_bs); the
+// update runs on out = out_u + scale*(out_c - out_u) and both rows receive x_{t-1}.  noise, x0_out and slice_ids stay per
+// logical sample.
+void sampler_update(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
+                    uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr,
+                    const int64_t* slice_ids = nullptr, int Cz = 1, int64_t x_bs = 0);
 // DPM-Solver(++) multistep: coefficients of one network evaluation + update (host tables, include/dsdiff.h dsd_dpm_schedule)
 struct DpmCoef {
     float alpha, sigma;      // marginal alpha_t, sigma_t at the evaluation time
@@ -258,18 +262,10 @@ struct DpmCoef {
     int pred;                // DSD_PRED_* of the network
     int data_pred, thresh;
 };
-void dpm_step(const DpmCoef& c, const float* model_out, int Cm, float* x, float* m_cur, const float* m_prev, float* s_buf,
-              float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
-// Classifier-free guidance: the network ran on 2B rows (uncond half first), out_u / out_c are the two [B,..] halves of its
-// output and x is the 2B-row state (logical sample b at rows b and B+b, row stride x_bs); both rows receive x_{t-1}.  noise,
-// x0_out, slice_ids, m_cur / m_prev and s_buf are per logical sample, as in the unguided launchers.
-// DDIM: out = out_u + scale*(out_c - out_u), then sampler_update's DSD_MODE_B_DDIM arithmetic
-void sampler_update_cfg(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
-                        uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr,
-                        const int64_t* slice_ids = nullptr, int Cz = 1, int64_t x_bs = 0);
-// DPM-Solver: noise = noise_u + scale*(noise_c - noise_u) on the two noise predictions, then dpm_step's arithmetic
-void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
-                  const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
+// out_u != nullptr: guided as in sampler_update, noise = noise_u + scale*(noise_c - noise_u) on the two noise predictions;
+// m_cur / m_prev and s_buf are per logical sample
+void dpm_step(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
+              const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
 // Image-to-image.  q_sample (+ mask blend): img_orig = a*x0 + s*z with a, s scalars or per row from the device arrays a_row /
 // s_row; mask != nullptr ([B,mask_ch,HW], mask_ch 1 or Cz): x = img_orig*mask + (1 - mask)*x, else x = img_orig.  x0 / noise are
 // [B,Cz,HW]; the state row b is x + b*x_bs (0 = Cz*HW); dup: also written to row B+b (guided 2B-row state).  noise == nullptr:

@@ -128,13 +128,13 @@ struct dsd_handle {
     size_t arena_cap = 0;
     dsd::Plan plan;
     dsd::IO io;
-    // sampling scratch
-    float* tbuf = nullptr;     // [B] timesteps (fp32)
-    float* mout = nullptr;     // [B,out_ch,H,W]
+    // sampling scratch, sized by the loop's binding (api.cpp LoopBinding: rows = B, or 2B under classifier-free guidance)
+    float* tbuf = nullptr;     // [rows] timesteps (fp32)
+    float* mout = nullptr;     // [rows,out_ch,H,W]: the binding's out_u (rows [0,B), guided only) and out_c halves
     float* zplane = nullptr;   // [H*W] zeros
-    float* dpm_m = nullptr;    // dsd_sample_dpm: m_k, m_{k-1} [B,H*W] each + thresholds [B]
-    float* lat_in = nullptr;   // latent loops (UNET block): the denoiser's NCHW input [B,Cz+Cc,h,w]; channels [0,Cz) are the state
-    float* cfg_io = nullptr;   // guided loops of the four-stream model: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
+    float* dpm_m = nullptr;    // DPM-Solver step body: m_k, m_{k-1} [B,Cz*H*W] each + thresholds [B]
+    float* lat_in = nullptr;   // latent binding (UNET block): the denoiser's NCHW input [rows,Cz+Cc,h,w]; channels [0,Cz) are the state
+    float* cfg_io = nullptr;   // guided four-stream binding: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
     // PLMS loops: three history planes [B,Cz,h,w] (a ring: iteration k >= 1 reads its newest prediction from plane (k-1) % 3 and
     // retires plane k % 3) followed by the threshold's per-block partial sums.  The history outlives a call, so a later call
     // with first_step > 0 continues it: plms_next is the iteration it is valid for (-1: none), for plms_B samples of plms_n

@@ -61,6 +61,47 @@ void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_
     check_launch("philox_normal");
 }
 
+// V = 4: 16-byte accesses (n, x_bs multiples of 4 and 16-byte aligned pointers; the launchers check), V = 1 otherwise.
+template <int V> struct alignas(4 * V) Pack { float v[V]; };
+template <int V> __device__ __forceinline__ Pack<V> ld_pack(const float* p) { return *reinterpret_cast<const Pack<V>*>(p); }
+template <int V> __device__ __forceinline__ void st_pack(float* p, const Pack<V>& a) { *reinterpret_cast<Pack<V>*>(p) = a; }
+
+// normals i .. i+V-1 of the (seed, step) stream; i % V == 0.  V = 4 is one Philox block: the values philox_normal_at gives
+template <int V> __device__ __forceinline__ Pack<V> philox_normal_pack(int64_t i, uint64_t seed, uint64_t step) {
+    Pack<V> z;
+    if constexpr (V == 4) {
+        uint32_t r[4];
+        const uint64_t blk = (uint64_t)i >> 2;
+        philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
+                      (uint32_t)(seed >> 32), r);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;
+            const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
+            const float rad = sqrtf(-2.0f * logf(u1));
+            const float ang = 6.283185307179586f * u2;
+            z.v[2 * h] = rad * cosf(ang);
+            z.v[2 * h + 1] = rad * sinf(ang);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) z.v[j] = philox_normal_at(i + j, seed, step);
+    }
+    return z;
+}
+
+// The launchers' side of V: 16-byte accesses when one sample (n elements) and the state's row stride are multiples of four
+// floats and every pointer the kernel takes packs from is 16-byte aligned (a null one counts as aligned).
+template <class... P> static bool can_vec4(int64_t n, int64_t x_bs, const P*... ptrs) {
+    return n % 4 == 0 && x_bs % 4 == 0 && (... && (((uintptr_t)ptrs & 15u) == 0));
+}
+// launch(std::integral_constant<int, V>) with V = 4 or 1
+template <class F> static void launch_vec(bool v4, F&& launch) {
+    if (v4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 1>{});
+}
+static int ew_blocks(int64_t work) { return (int)std::min<int64_t>((work + 255) / 256, 2048); }
+
 // p_sample_ddim after the network output is formed (ddim.py:222-260): returns x_{t-1}, x0 = the (clipped) pred_x0
 __device__ __forceinline__ float ddim_update(const StepCoef& sc, float out, float xt, float z, float& x0) {
     const float* c = sc.c;
@@ -77,68 +118,91 @@ __device__ __forceinline__ float ddim_update(const StepCoef& sc, float out, floa
     return sqrtf(c[5]) * x0 + dir + c[6] * z;
 }
 
-// One sample is n = Cz*HW elements (r = c*HW + p inside it).  The state row b lives at x + b*x_bs: x_bs = n for a state of its
-// own, (Cz+Cc)*HW when the state is the first Cz channels of the denoiser's NCHW input (the latent loop writes x_{t-1} straight
-// into the buffer the network reads next).  model_out, noise and x0_out are contiguous [B,Cm*Cz,HW] / [B,Cz,HW].  The Philox
-// counter of (row b, channel c, pixel p) is (slice_ids ? slice_ids[b] : b)*n + r: distinct channels never share a normal.
-__global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const float* __restrict__ mo,
-                                                             float* __restrict__ x, const float* __restrict__ noise,
-                                                             uint64_t seed, uint64_t step, int B, int64_t n, int64_t x_bs,
-                                                             float* __restrict__ x0_out, const int64_t* __restrict__ slice_ids) {
-    const int64_t total = (int64_t)B * n;
-    const int Cm = sc.learned_range ? 2 : 1;   // learned range: Cz == 1 (checked by the callers)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / n;
-        const int64_t p = i - b * n;
-        const int64_t xi = b * x_bs + p;
-        const float out = mo[(b * Cm) * n + p];
-        const float xt = x[xi];
-        const float z = noise ? noise[i] : philox_normal_at(slice_ids ? slice_ids[b] * n + p : i, seed, step);
-        const float* c = sc.c;
-        float x0, res;
-        if (sc.mode == DSD_MODE_B_DDIM) {
-            res = ddim_update(sc, out, xt, z, x0);
-        } else {
-            if (sc.pred == DSD_PRED_V)
-                x0 = c[0] * xt - c[1] * out;
-            else if (sc.pred == DSD_PRED_EPS)
-                x0 = c[2] * xt - c[3] * out;
-            else
-                x0 = out;
-            if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-            const float nz = sc.nonzero ? 1.f : 0.f;
-            if (sc.mode == DSD_MODE_A_DDIM) {
-                // gaussian_diffusion.py:646-664
-                const float eps = (c[2] * xt - x0) / c[3];
-                const float ab = c[4], abp = c[5];
-                const float sigma = sc.eta * sqrtf((1.f - abp) / (1.f - ab)) * sqrtf(1.f - ab / abp);
-                const float mean_pred = x0 * sqrtf(abp) + sqrtf(1.f - abp - sigma * sigma) * eps;
-                res = mean_pred + nz * sigma * z;
-            } else {
-                // DDPM: q_posterior mean + exp(0.5 logvar) z   (gaussian_diffusion.py:220-223,464; trainer_ddpm.py:467)
-                const float mean = c[4] * x0 + c[5] * xt;
-                float logvar = c[6];
-                if (sc.learned_range) {  // gaussian_diffusion.py:287-293
-                    const float v = mo[(b * Cm + 1) * n + p];
-                    const float frac = (v + 1.f) / 2.f;
-                    logvar = frac * c[7] + (1.f - frac) * c[6];
-                }
-                res = mean + nz * expf(0.5f * logvar) * z;
-            }
-        }
-        x[xi] = res;
-        if (x0_out) x0_out[i] = x0;
+// x_{t-1} of one element in any of the four modes; var = the learned-range variance channel (read only with learned_range)
+__device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float out, float xt, float z, float var, float& x0) {
+    if (sc.mode == DSD_MODE_B_DDIM) return ddim_update(sc, out, xt, z, x0);
+    const float* c = sc.c;
+    if (sc.pred == DSD_PRED_V)
+        x0 = c[0] * xt - c[1] * out;
+    else if (sc.pred == DSD_PRED_EPS)
+        x0 = c[2] * xt - c[3] * out;
+    else
+        x0 = out;
+    if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    const float nz = sc.nonzero ? 1.f : 0.f;
+    if (sc.mode == DSD_MODE_A_DDIM) {
+        // gaussian_diffusion.py:646-664
+        const float eps = (c[2] * xt - x0) / c[3];
+        const float ab = c[4], abp = c[5];
+        const float sigma = sc.eta * sqrtf((1.f - abp) / (1.f - ab)) * sqrtf(1.f - ab / abp);
+        const float mean_pred = x0 * sqrtf(abp) + sqrtf(1.f - abp - sigma * sigma) * eps;
+        return mean_pred + nz * sigma * z;
     }
+    // DDPM: q_posterior mean + exp(0.5 logvar) z   (gaussian_diffusion.py:220-223,464; trainer_ddpm.py:467)
+    const float mean = c[4] * x0 + c[5] * xt;
+    float logvar = c[6];
+    if (sc.learned_range) {  // gaussian_diffusion.py:287-293
+        const float frac = (var + 1.f) / 2.f;
+        logvar = frac * c[7] + (1.f - frac) * c[6];
+    }
+    return mean + nz * expf(0.5f * logvar) * z;
 }
 
-void sampler_update(const StepCoef& sc, const float* model_out, float* x, const float* noise, uint64_t seed,
-                    uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz, int64_t x_bs) {
+// One sample is n = Cz*HW elements (r = c*HW + p inside it).  The state row b lives at x + b*x_bs: x_bs = n for a state of its
+// own, (Cz+Cc)*HW when the state is the first Cz channels of the denoiser's NCHW input (the latent loop writes x_{t-1} straight
+// into the buffer the network reads next).  The model output, noise and x0_out are contiguous [B,Cm*Cz,HW] / [B,Cz,HW].  The
+// Philox counter of (row b, channel c, pixel p) is (slice_ids ? slice_ids[b] : b)*n + r: distinct channels never share a normal.
+// Classifier-free guidance (mo_u != nullptr; ddim.py:194-219): the network ran on 2B rows — x_in = cat([x]*2), c_in =
+// cat([uncond, cond]) — so its output arrives as the halves mo_u / mo_c and the state occupies 2B rows, logical sample b at rows
+// b and B+b.  Both hold x_t on entry; the kernel forms out = out_u + gs*(out_c - out_u) on the raw outputs (ddim.py:219), reads
+// row b and writes x_{t-1} to both, so the next evaluation needs no copy.  Everything else — noise, Philox counters, slice_ids,
+// x0_out — is indexed by the B logical samples.
+template <int V>
+__global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const float* __restrict__ mo_u,
+                                                             const float* __restrict__ mo_c, float gs, float* __restrict__ x,
+                                                             const float* __restrict__ noise, uint64_t seed, uint64_t step,
+                                                             int B, int64_t n, int64_t x_bs, float* __restrict__ x0_out,
+                                                             const int64_t* __restrict__ slice_ids) {
+    const int64_t nv = n / V;
+    // One pack per thread and no grid-stride loop: out of a loop the compiler hoists the constants of the inlined logf / sinf /
+    // cosf into scalar registers, more than there are once all four modes and both output halves are live (it spilled them).
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * nv) return;
+    const int Cm = sc.learned_range ? 2 : 1;                     // learned range: Cz == 1 (checked by the callers)
+    const int64_t b = i / nv;
+    const int64_t p = (i - b * nv) * V;
+    const int64_t li = b * n + p;                                // in the [B,n] tensors
+    const int64_t oi = (b * Cm) * n + p;                         // in the model output
+    const int64_t xi = b * x_bs + p;
+    Pack<V> out = ld_pack<V>(mo_c + oi);
+    if (mo_u) {
+        const Pack<V> ou = ld_pack<V>(mo_u + oi);
+#pragma unroll
+        for (int j = 0; j < V; ++j) out.v[j] = ou.v[j] + gs * (out.v[j] - ou.v[j]);
+    }
+    const Pack<V> xt = ld_pack<V>(x + xi);
+    const Pack<V> z = noise ? ld_pack<V>(noise + li) : philox_normal_pack<V>(slice_ids ? slice_ids[b] * n + p : li, seed, step);
+    Pack<V> var = {};
+    if (sc.learned_range && (sc.mode == DSD_MODE_A_DDPM || sc.mode == DSD_MODE_B_DDPM)) var = ld_pack<V>(mo_c + oi + n);
+    Pack<V> res, x0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) res.v[j] = sampler_update_value(sc, out.v[j], xt.v[j], z.v[j], var.v[j], x0.v[j]);
+    st_pack<V>(x + xi, res);
+    if (mo_u) st_pack<V>(x + xi + (int64_t)B * x_bs, res);
+    if (x0_out) st_pack<V>(x0_out + li, x0);
+}
+
+void sampler_update(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
+                    uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz,
+                    int64_t x_bs) {
     const int64_t n = (int64_t)Cz * HW;
-    const int64_t total = (int64_t)B * n;
-    if (!total) return;
-    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(sampler_update_kernel, dim3(blocks), dim3(256), 0, s, sc, model_out, x, noise, seed, step, B, n,
-                       x_bs > 0 ? x_bs : n, x0_out, slice_ids);
+    if (!B || !n) return;
+    if (x_bs <= 0) x_bs = n;
+    const bool v4 = can_vec4(n, x_bs, out_u, out_c, x, noise, x0_out);
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(sampler_update_kernel<decltype(V)::value>, dim3((unsigned)((B * (n / decltype(V)::value) + 255) / 256)),
+                           dim3(256), 0, s, sc, out_u, out_c, scale, x, noise, seed, step, B, n, x_bs, x0_out, slice_ids);
+    });
     check_launch("sampler_update");
 }
 
@@ -152,7 +216,8 @@ void sampler_update(const StepCoef& sc, const float* model_out, float* x, const 
 //   dpm_update  m_k <- clamp(m_k,-s,s)/s ; x <- first-order (:509-553) or second-order multistep update (:760-816)
 // Every product/sum is a separately rounded fp32 op in the reference's order (file-wide contract(off)).
 // HW = elements per sample (Cz*h*w for a latent state); x row b at x + b*x_bs (x_bs = HW, or (Cz+Cc)*h*w inside the
-// denoiser's input buffer); m and the model output are contiguous.
+// denoiser's input buffer); m and the model output are contiguous.  Guided (mo_u != nullptr): the 2B-row state and the two
+// output halves of sampler_update_kernel; m and the thresholding quantile stay per logical sample.
 // noise prediction from the network output (model_wrapper.noise_pred_fn :247-265)
 __device__ __forceinline__ float dpm_noise_pred(const DpmCoef& c, float out, float xt) {
     if (c.pred == DSD_PRED_EPS) return out;
@@ -167,16 +232,31 @@ __device__ __forceinline__ float dpm_update_value(const DpmCoef& c, float m, flo
     return res;
 }
 
-__global__ __launch_bounds__(256) void dpm_model_kernel(DpmCoef c, const float* __restrict__ mo, int Cm,
-                                                        const float* __restrict__ x, float* __restrict__ m, int B,
-                                                        int HW, int64_t x_bs) {
-    const int64_t total = (int64_t)B * HW;
+// guided: each half becomes a noise prediction from its own output and the shared x_t, then
+// noise = noise_u + gs * (noise_c - noise_u) (dpm_solver_pytorch.py:324-332)
+template <int V>
+__global__ __launch_bounds__(256) void dpm_model_kernel(DpmCoef c, const float* __restrict__ mo_u, const float* __restrict__ mo_c,
+                                                        int Cm, float gs, const float* __restrict__ x, float* __restrict__ m,
+                                                        int B, int HW, int64_t x_bs) {
+    const int64_t nv = HW / V, total = (int64_t)B * nv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / HW;
-        const float out = mo[(b * Cm) * HW + (i - b * HW)];   // a learned-sigma model: first channel only (gaussian_diffusion.py:484-485)
-        const float xt = x[b * x_bs + (i - b * HW)];
-        const float eps = dpm_noise_pred(c, out, xt);
-        m[i] = c.data_pred ? (xt - c.sigma * eps) / c.alpha : eps;
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t oi = (b * Cm) * HW + p;                 // a learned-sigma model: first channel only (gaussian_diffusion.py:484-485)
+        const Pack<V> oc = ld_pack<V>(mo_c + oi), xt = ld_pack<V>(x + b * x_bs + p);
+        Pack<V> ou = oc;
+        if (mo_u) ou = ld_pack<V>(mo_u + oi);
+        Pack<V> r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float eps = dpm_noise_pred(c, oc.v[j], xt.v[j]);
+            if (mo_u) {
+                const float eu = dpm_noise_pred(c, ou.v[j], xt.v[j]);
+                eps = eu + gs * (eps - eu);
+            }
+            r.v[j] = c.data_pred ? (xt.v[j] - c.sigma * eps) / c.alpha : eps;
+        }
+        st_pack<V>(m + b * HW + p, r);
     }
 }
 
@@ -235,165 +315,11 @@ __global__ __launch_bounds__(1024) void dpm_quantile_kernel(const float* __restr
     }
 }
 
+// thresholds m_k in place, then writes x_{t-1} to row b and, with dup (the guided 2B-row state), to row B+b
+template <int V>
 __global__ __launch_bounds__(256) void dpm_update_kernel(DpmCoef c, float* __restrict__ m0, const float* __restrict__ m1,
-                                                         const float* __restrict__ s_thr, float* __restrict__ x, int B,
-                                                         int HW, int64_t x_bs) {
-    const int64_t total = (int64_t)B * HW;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        float m = m0[i];
-        if (s_thr) {
-            const float s = s_thr[i / HW];
-            m = fminf(fmaxf(m, -s), s) / s;
-            m0[i] = m;
-        }
-        if (!x) continue;                                     // thresholding only (dsd_op_dpm_threshold)
-        const int64_t xi = (i / HW) * x_bs + (i % HW);
-        x[xi] = dpm_update_value(c, m, c.order == 2 ? m1[i] : 0.f, x[xi]);
-    }
-}
-
-void dpm_step(const DpmCoef& c, const float* model_out, int Cm, float* x, float* m_cur, const float* m_prev, float* s_buf,
-              float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
-    const int64_t total = (int64_t)B * HW;
-    if (!total) return;
-    if (x_bs <= 0) x_bs = HW;
-    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(dpm_model_kernel, dim3(blocks), dim3(256), 0, s, c, model_out, Cm, x, m_cur, B, HW, x_bs);
-    check_launch("dpm_model");
-    const bool thr = c.thresh && c.data_pred;
-    if (thr) {
-        hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m_cur, HW, ratio, max_val, s_buf);
-        check_launch("dpm_quantile");
-    }
-    hipLaunchKernelGGL(dpm_update_kernel, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW, x_bs);
-    check_launch("dpm_update");
-}
-
-void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s) {
-    if (!B || !n) return;
-    DSD_HIP(hipMemcpyAsync(y, x0, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, y, n, ratio, max_val, s_buf);
-    check_launch("dpm_quantile");
-    DpmCoef c{};
-    c.order = 0;
-    hipLaunchKernelGGL(dpm_update_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)B * n + 255) / 256, 4096)), dim3(256), 0, s, c,
-                       y, (const float*)nullptr, s_buf, (float*)nullptr, B, n, (int64_t)n);
-    check_launch("dpm_update");
-    DSD_HIP(hipStreamSynchronize(s));
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Classifier-free guidance (ddim.py:194-219, dpm_solver_pytorch.py:324-332).  The network has been evaluated on 2B rows —
-// x_in = cat([x]*2), c_in = cat([uncond, cond]) — so its output arrives as two [B,..] halves and the state occupies 2B rows:
-// logical sample b at x + b*x_bs (uncond half) and at x + (B+b)*x_bs (cond half).  Both rows hold x_t on entry; the kernels
-// read the first and write x_{t-1} to both, so the next evaluation needs no copy.  Everything else — noise, Philox counters,
-// slice_ids, x0_out, m, the thresholding quantile — is indexed by the B logical samples.
-// V = 4: 16-byte accesses (n, x_bs multiples of 4 and 16-byte aligned pointers; the launchers check), V = 1 otherwise.
-template <int V> struct alignas(4 * V) Pack { float v[V]; };
-template <int V> __device__ __forceinline__ Pack<V> ld_pack(const float* p) { return *reinterpret_cast<const Pack<V>*>(p); }
-template <int V> __device__ __forceinline__ void st_pack(float* p, const Pack<V>& a) { *reinterpret_cast<Pack<V>*>(p) = a; }
-
-// normals i .. i+V-1 of the (seed, step) stream; i % V == 0.  V = 4 is one Philox block: the values philox_normal_at gives
-template <int V> __device__ __forceinline__ Pack<V> philox_normal_pack(int64_t i, uint64_t seed, uint64_t step) {
-    Pack<V> z;
-    if constexpr (V == 4) {
-        uint32_t r[4];
-        const uint64_t blk = (uint64_t)i >> 2;
-        philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;
-            const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
-            const float rad = sqrtf(-2.0f * logf(u1));
-            const float ang = 6.283185307179586f * u2;
-            z.v[2 * h] = rad * cosf(ang);
-            z.v[2 * h + 1] = rad * sinf(ang);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j) z.v[j] = philox_normal_at(i + j, seed, step);
-    }
-    return z;
-}
-
-// DDIM: out = out_u + s * (out_c - out_u) on the raw network outputs (ddim.py:219), then the unguided arithmetic
-template <int V>
-__global__ __launch_bounds__(256) void sampler_update_cfg_kernel(StepCoef sc, const float* __restrict__ mo_u,
-                                                                 const float* __restrict__ mo_c, float gs, float* __restrict__ x,
-                                                                 const float* __restrict__ noise, uint64_t seed, uint64_t step,
-                                                                 int B, int64_t n, int64_t x_bs, float* __restrict__ x0_out,
-                                                                 const int64_t* __restrict__ slice_ids) {
-    const int64_t nv = n / V, total = (int64_t)B * nv;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / nv;
-        const int64_t p = (i - b * nv) * V;
-        const int64_t li = b * n + p;                         // in the [B,n] tensors
-        const int64_t xi = b * x_bs + p;
-        const Pack<V> ou = ld_pack<V>(mo_u + li), oc = ld_pack<V>(mo_c + li), xt = ld_pack<V>(x + xi);
-        const Pack<V> z = noise ? ld_pack<V>(noise + li)
-                                : philox_normal_pack<V>(slice_ids ? slice_ids[b] * n + p : li, seed, step);
-        Pack<V> res, x0;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float out = ou.v[j] + gs * (oc.v[j] - ou.v[j]);
-            res.v[j] = ddim_update(sc, out, xt.v[j], z.v[j], x0.v[j]);
-        }
-        st_pack<V>(x + xi, res);
-        st_pack<V>(x + xi + (int64_t)B * x_bs, res);
-        if (x0_out) st_pack<V>(x0_out + li, x0);
-    }
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static int cfg_blocks(int64_t work) { return (int)std::min<int64_t>((work + 255) / 256, 2048); }
-
-void sampler_update_cfg(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
-                        uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz,
-                        int64_t x_bs) {
-    const int64_t n = (int64_t)Cz * HW;
-    if (!B || !n) return;
-    if (x_bs <= 0) x_bs = n;
-    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x) && aligned16(noise) &&
-                    aligned16(x0_out);
-    if (v4)
-        hipLaunchKernelGGL(sampler_update_cfg_kernel<4>, dim3(cfg_blocks(B * (n / 4))), dim3(256), 0, s, sc, out_u, out_c, scale, x,
-                           noise, seed, step, B, n, x_bs, x0_out, slice_ids);
-    else
-        hipLaunchKernelGGL(sampler_update_cfg_kernel<1>, dim3(cfg_blocks(B * n)), dim3(256), 0, s, sc, out_u, out_c, scale, x, noise,
-                           seed, step, B, n, x_bs, x0_out, slice_ids);
-    check_launch("sampler_update_cfg");
-}
-
-// DPM-Solver: each half becomes a noise prediction from its own output and the shared x_t, then
-// noise = noise_u + s * (noise_c - noise_u) (dpm_solver_pytorch.py:324-332); m as in dpm_model_kernel
-template <int V>
-__global__ __launch_bounds__(256) void dpm_model_cfg_kernel(DpmCoef c, const float* __restrict__ mo_u, const float* __restrict__ mo_c,
-                                                            int Cm, float gs, const float* __restrict__ x, float* __restrict__ m,
-                                                            int B, int HW, int64_t x_bs) {
-    const int64_t nv = HW / V, total = (int64_t)B * nv;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / nv;
-        const int64_t p = (i - b * nv) * V;
-        const int64_t oi = (b * Cm) * HW + p;                 // a learned-sigma model: first channel only
-        const Pack<V> ou = ld_pack<V>(mo_u + oi), oc = ld_pack<V>(mo_c + oi), xt = ld_pack<V>(x + b * x_bs + p);
-        Pack<V> r;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float eu = dpm_noise_pred(c, ou.v[j], xt.v[j]);
-            const float ec = dpm_noise_pred(c, oc.v[j], xt.v[j]);
-            const float eps = eu + gs * (ec - eu);
-            r.v[j] = c.data_pred ? (xt.v[j] - c.sigma * eps) / c.alpha : eps;
-        }
-        st_pack<V>(m + b * HW + p, r);
-    }
-}
-
-// dpm_update_kernel on the 2B-row state: thresholds m_k in place, writes x_{t-1} to both rows of every logical sample
-template <int V>
-__global__ __launch_bounds__(256) void dpm_update_cfg_kernel(DpmCoef c, float* __restrict__ m0, const float* __restrict__ m1,
-                                                             const float* __restrict__ s_thr, float* __restrict__ x, int B, int HW,
-                                                             int64_t x_bs) {
+                                                         const float* __restrict__ s_thr, float* __restrict__ x, int B, int HW,
+                                                         int64_t x_bs, int dup) {
     const int64_t nv = HW / V, total = (int64_t)B * nv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / nv;
@@ -406,6 +332,7 @@ __global__ __launch_bounds__(256) void dpm_update_cfg_kernel(DpmCoef c, float* _
             for (int j = 0; j < V; ++j) m.v[j] = fminf(fmaxf(m.v[j], -s), s) / s;
             st_pack<V>(m0 + li, m);
         }
+        if (!x) continue;                                     // thresholding only (dsd_op_dpm_threshold)
         const Pack<V> xt = ld_pack<V>(x + xi);
         Pack<V> mp = m;
         if (c.order == 2) mp = ld_pack<V>(m1 + li);
@@ -413,34 +340,46 @@ __global__ __launch_bounds__(256) void dpm_update_cfg_kernel(DpmCoef c, float* _
 #pragma unroll
         for (int j = 0; j < V; ++j) res.v[j] = dpm_update_value(c, m.v[j], mp.v[j], xt.v[j]);
         st_pack<V>(x + xi, res);
-        st_pack<V>(x + xi + (int64_t)B * x_bs, res);
+        if (dup) st_pack<V>(x + xi + (int64_t)B * x_bs, res);
     }
 }
 
-void dpm_step_cfg(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
-                  const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
+static void dpm_update(bool v4, const DpmCoef& c, float* m0, const float* m1, const float* s_thr, float* x, int B, int HW,
+                       int64_t x_bs, bool dup, hipStream_t s) {
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(dpm_update_kernel<decltype(V)::value>, dim3(ew_blocks((int64_t)B * (HW / decltype(V)::value))), dim3(256),
+                           0, s, c, m0, m1, s_thr, x, B, HW, x_bs, dup ? 1 : 0);
+    });
+    check_launch("dpm_update");
+}
+
+void dpm_step(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
+              const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
     if (!B || !HW) return;
     if (x_bs <= 0) x_bs = HW;
-    const bool v4 = HW % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x) && aligned16(m_cur) &&
-                    aligned16(m_prev);
-    const int blocks = cfg_blocks(v4 ? (int64_t)B * (HW / 4) : (int64_t)B * HW);
-    if (v4)
-        hipLaunchKernelGGL(dpm_model_cfg_kernel<4>, dim3(blocks), dim3(256), 0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
-    else
-        hipLaunchKernelGGL(dpm_model_cfg_kernel<1>, dim3(blocks), dim3(256), 0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
-    check_launch("dpm_model_cfg");
+    const bool v4 = can_vec4(HW, x_bs, out_u, out_c, x, m_cur, m_prev);
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(dpm_model_kernel<decltype(V)::value>, dim3(ew_blocks((int64_t)B * (HW / decltype(V)::value))), dim3(256),
+                           0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
+    });
+    check_launch("dpm_model");
     const bool thr = c.thresh && c.data_pred;
     if (thr) {   // per logical sample: m_cur is [B,HW]
         hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m_cur, HW, ratio, max_val, s_buf);
         check_launch("dpm_quantile");
     }
-    if (v4)
-        hipLaunchKernelGGL(dpm_update_cfg_kernel<4>, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW,
-                           x_bs);
-    else
-        hipLaunchKernelGGL(dpm_update_cfg_kernel<1>, dim3(blocks), dim3(256), 0, s, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW,
-                           x_bs);
-    check_launch("dpm_update_cfg");
+    dpm_update(v4, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW, x_bs, out_u != nullptr, s);
+}
+
+void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s) {
+    if (!B || !n) return;
+    DSD_HIP(hipMemcpyAsync(y, x0, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, y, n, ratio, max_val, s_buf);
+    check_launch("dpm_quantile");
+    DpmCoef c{};
+    c.order = 0;
+    dpm_update(can_vec4(n, n, y), c, y, nullptr, s_buf, nullptr, B, n, n, false, s);
+    DSD_HIP(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -493,18 +432,14 @@ void q_sample_blend(float a, float s, const float* a_row, const float* s_row, co
     if (!B || !n) return;
     DSD_CHECK(n <= (int64_t)1 << 30, "q_sample / mask blend: one sample has %lld elements; up to 2^30 are taken", (long long)n);
     if (x_bs <= 0) x_bs = n;
-    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && (!mask || mask_ch != 1 || HW % 4 == 0) && aligned16(x0) && aligned16(mask) &&
-                    aligned16(x) && aligned16(noise);
+    const bool v4 = can_vec4(n, x_bs, x0, mask, x, noise) && (!mask || mask_ch != 1 || HW % 4 == 0);
     DSD_CHECK(B <= 65535, "q_sample / mask blend: %d samples; up to 65535 are taken", B);
     const dim3 grid((unsigned)std::min<int64_t>((n / (v4 ? 4 : 1) + 255) / 256, 2048), (unsigned)B);
-    auto launch = [&](auto kern) {
+    launch_vec(v4, [&](auto V) {
+        auto kern = mask ? q_sample_blend_kernel<decltype(V)::value, true> : q_sample_blend_kernel<decltype(V)::value, false>;
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, s, a_row, s_row, x0, mask, mask_ch, x, noise, seed, step, B, (int)n, HW,
                            x_bs, dup ? 1 : 0, slice_ids);
-    };
-    if (mask)
-        v4 ? launch(q_sample_blend_kernel<4, true>) : launch(q_sample_blend_kernel<1, true>);
-    else
-        v4 ? launch(q_sample_blend_kernel<4, false>) : launch(q_sample_blend_kernel<1, false>);
+    });
     check_launch("q_sample_blend");
 }
 
@@ -539,12 +474,10 @@ void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c
     const int64_t n = (int64_t)Cz * HW;
     if (!B || !n) return;
     if (x_bs <= 0) x_bs = n;
-    const bool v4 = n % 4 == 0 && x_bs % 4 == 0 && aligned16(out_u) && aligned16(out_c) && aligned16(x);
-    if (v4)
-        hipLaunchKernelGGL(ddim_invert_kernel<4>, dim3(cfg_blocks(B * (n / 4))), dim3(256), 0, st, cx, ce, out_u, out_c, scale, x, B, n,
-                           x_bs);
-    else
-        hipLaunchKernelGGL(ddim_invert_kernel<1>, dim3(cfg_blocks(B * n)), dim3(256), 0, st, cx, ce, out_u, out_c, scale, x, B, n, x_bs);
+    launch_vec(can_vec4(n, x_bs, out_u, out_c, x), [&](auto V) {
+        hipLaunchKernelGGL(ddim_invert_kernel<decltype(V)::value>, dim3(ew_blocks(B * (n / decltype(V)::value))), dim3(256), 0, st, cx,
+                           ce, out_u, out_c, scale, x, B, n, x_bs);
+    });
     check_launch("ddim_invert");
 }
 
@@ -655,23 +588,18 @@ void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
     DSD_CHECK(n <= (int64_t)1 << 30, "PLMS update: one sample has %lld elements; up to 2^30 are taken", (long long)n);
     DSD_CHECK(B <= 65535, "PLMS update: %d samples; up to 65535 are taken", B);
     if (a.x_bs <= 0) a.x_bs = n;
-    const bool v4 = n % 4 == 0 && a.x_bs % 4 == 0 && aligned16(a.out_u) && aligned16(a.out_c) && aligned16(a.h_new) &&
-                    aligned16(a.o1) && aligned16(a.o2) && aligned16(a.x_saved) && aligned16(a.x);
+    const bool v4 = can_vec4(n, a.x_bs, a.out_u, a.out_c, a.h_new, a.o1, a.o2, a.x_saved, a.x);
     const int64_t blocks = (n / (v4 ? 4 : 1) + 255) / 256;
     const int nblk = (int)std::min<int64_t>(blocks, kPlmsNormBlocks);
     if (a.thr > 0.f) {
         DSD_CHECK(a.part, "PLMS update: the threshold needs its scratch");
-        if (v4)
-            hipLaunchKernelGGL(plms_x0_norm_kernel<4>, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
-        else
-            hipLaunchKernelGGL(plms_x0_norm_kernel<1>, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
+        launch_vec(v4, [&](auto V) {
+            hipLaunchKernelGGL(plms_x0_norm_kernel<decltype(V)::value>, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
+        });
         check_launch("plms_x0_norm");
     }
     const dim3 grid((unsigned)std::min<int64_t>(blocks, 2048), (unsigned)B);
-    if (v4)
-        hipLaunchKernelGGL(plms_update_kernel<4>, grid, dim3(256), 0, s, a, B, (int)n, nblk);
-    else
-        hipLaunchKernelGGL(plms_update_kernel<1>, grid, dim3(256), 0, s, a, B, (int)n, nblk);
+    launch_vec(v4, [&](auto V) { hipLaunchKernelGGL(plms_update_kernel<decltype(V)::value>, grid, dim3(256), 0, s, a, B, (int)n, nblk); });
     check_launch("plms_update");
 }
 
