@@ -15,7 +15,7 @@ import numpy as np
 import torch as th
 
 from ... import _lib
-from ..._sched import Schedule, find_unet, run_device_loop, sampler_update, _seed_from_torch
+from ..._sched import Schedule, is_dit, loop_denoiser, run_device_loop, sampler_update, _seed_from_torch
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
@@ -141,7 +141,7 @@ class GaussianDiffusion:
         sched = self._schedule(ddim, eta, clip_denoised)
         hooks = denoised_fn is not None or cond_fn is not None
         self._check_hooks(ddim, denoised_fn, cond_fn)
-        unet = find_unet(model)
+        unet = loop_denoiser(model, model_kwargs)        # None for a DiT that is to receive labels / its own cond=
         if hooks and unet is not None:
             # a Python hook sits between network and update: per-step host loop; a bare native U-Net does not concatenate
             # c_concat itself (DiffusionWrapper.forward does, ddpm.py:1328-1333)
@@ -155,6 +155,8 @@ class GaussianDiffusion:
         img = noise if noise is not None else th.randn(*shape, device=device)      # :591-594
         img = img.to(device)
         c_concat = model_kwargs.get("c_concat")
+        if unet is not None and c_concat is None and is_dit(unet):
+            c_concat = [img.new_zeros((img.shape[0], 0) + tuple(img.shape[2:]))]      # an unconditional DiT: all input is state
         if unet is not None and c_concat is not None:
             cond = th.cat([c.to(device) for c in c_concat], 1)
             return run_device_loop(unet, sched, img, cond, step_noise=step_noise, seed=seed)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ..._lib import DSD_NCOEF, DsdDpmSchedule, check, dptr, lib, stream_ptr
-from ..._sched import Guidance, cat_unconditional, check_latent_io, find_unet, is_latent_denoiser
+from ..._sched import Guidance, cat_unconditional, check_latent_io, is_dit, is_latent_denoiser, loop_denoiser
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
 
@@ -303,7 +303,7 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
     """The multistep loop on the device.  ``guidance`` (default: what ``fn`` carries from model_wrapper): classifier-free
     guidance, dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided; its unconditional conditioning must have the shape, dtype
     and device of the concatenated condition."""
-    unet, cc = find_unet(fn.model), fn.c_concat()
+    unet, cc = loop_denoiser(fn.model, fn.model_kwargs), fn.c_concat()   # None for a DiT that is to receive labels / cond=
     if guidance is None and fn.unconditional_condition is not None:
         u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device).detach().float()
         guidance = Guidance(u, fn.guidance_scale, sched.steps)
@@ -314,15 +314,17 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
         guidance.check(torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), sched.steps)
         if unet is None:
             raise NotImplementedError("classifier-free guidance runs in the device loop only: it needs a native DSUnetModel / "
-                                      "UNetModel behind the model")
+                                      "UNetModel / DiT behind the model")
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
     B, Cx, H, W = x.shape
     if guided:
         g = guidance.bind()
+    if unet is not None and cc is None and is_dit(unet):
+        cc = [x.new_zeros((B, 0, H, W))]                           # an unconditional DiT: all input is state
     if unet is not None and cc is not None and is_latent_denoiser(unet):
-        # latent state [B,Cz,h,w] under the plain UNetModel: dsd_sample_dpm_latent
+        # latent state [B,Cz,h,w] under the plain UNetModel or the DiT: dsd_sample_dpm_latent
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
         check_latent_io(unet, x, cond)

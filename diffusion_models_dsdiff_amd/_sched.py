@@ -143,11 +143,13 @@ def cat_unconditional(c, u, device):
 
 def find_unet(model):
     """Locate the native denoiser behind the object the reference passes as ``model``
-    (DiffusionWrapper.diffusion_model, ddpm.py:1323; or the network itself): the four-stream DSUnetModel, or the plain
-    UNetModel that denoises VAE latents (run by the latent loops, dsd_sample_latent / dsd_sample_dpm_latent)."""
+    (DiffusionWrapper.diffusion_model, ddpm.py:1323; or the network itself): the four-stream DSUnetModel, or one of the two
+    that read the state from their own input — the plain UNetModel that denoises VAE latents and the DiT the reference's
+    trainer swaps in for the U-Net (both run by the latent loops, dsd_sample_latent / dsd_sample_dpm_latent)."""
+    from .UNet_DS_Diff.DiT_models import DiT
     from .UNet_DS_Diff.model import DSUnetModel
     from .ldm.modules.diffusionmodules.openaimodel import UNetModel
-    kinds = (DSUnetModel, UNetModel)
+    kinds = (DSUnetModel, UNetModel, DiT)
     if isinstance(model, kinds):
         return model
     inner = getattr(model, "diffusion_model", None)
@@ -159,14 +161,60 @@ def find_unet(model):
     return None
 
 
+def loop_denoiser(model, model_kwargs=None):
+    """find_unet for a sampler call that carries ``model_kwargs``: the denoiser the device loop may run, or None for the per-step
+    path.  The device loops hand a DiT its input and t and nothing else, so a call whose ``model_kwargs`` hold anything beside
+    ``c_concat`` — labels ``y``, DiT.forward's own ``cond`` — keeps the per-step path, where the network receives them as
+    ``model(x, t, **model_kwargs)``."""
+    unet = find_unet(model)
+    if unet is not None and is_dit(unet) and set(model_kwargs or {}) - {"c_concat"}:
+        return None
+    return unet
+
+
+def is_dit(unet) -> bool:
+    from .UNet_DS_Diff.DiT_models import DiT
+    return isinstance(unet, DiT)
+
+
 def is_latent_denoiser(unet) -> bool:
-    """True for the plain UNetModel (multi-channel latent state, DSD_BLOCK_UNET handle)."""
+    """True for the denoisers whose state is the first channels of their own input (multi-channel latent state): the plain
+    UNetModel (DSD_BLOCK_UNET handle) and the DiT (DSD_BLOCK_DIT)."""
     from .ldm.modules.diffusionmodules.openaimodel import UNetModel
-    return isinstance(unet, UNetModel)
+    return isinstance(unet, UNetModel) or is_dit(unet)
+
+
+def dit_state_channels(in_channels: int, learn_sigma: bool, cond_channels: int):
+    """(Cz, out_ch) of a DiT under a sampler: the state is what the 'concat' conditioning leaves of the input, Cz = in_channels -
+    Cc, and the output has in_channels // 3 * 2 channels with learn_sigma (DiT_models.py:163, sic), else in_channels.  The
+    samplers read the prediction from the first Cz of them and a learned variance from the next Cz, so out_ch must be Cz or
+    2*Cz: 4 input channels with 3 of conditioning (the shipped yaml) give (1, 2), 6 with 4 give (2, 4), 5 with 4 give (1, 2),
+    3 unconditional without learn_sigma give (3, 3)."""
+    in_channels, cond_channels = int(in_channels), int(cond_channels)
+    out_ch = in_channels // 3 * 2 if learn_sigma else in_channels
+    cz = in_channels - cond_channels
+    if cond_channels < 0 or cz < 1:
+        raise ValueError(f"a DiT of {in_channels} input channels leaves no state beside {cond_channels} conditioning channels")
+    if out_ch not in (cz, 2 * cz):
+        raise ValueError(f"a DiT of {in_channels} input channels (learn_sigma={bool(learn_sigma)}) has {out_ch} output channels; "
+                         f"with {cond_channels} conditioning channels the state has {cz}, which needs {cz} or {2 * cz}")
+    return cz, out_ch
 
 
 def check_latent_io(unet, x: torch.Tensor, cond: torch.Tensor) -> None:
     """Shape checks of the latent loops that the C entry points cannot see (they take one H, W)."""
+    if is_dit(unet):
+        if cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:]):
+            raise ValueError(f"conditioning {tuple(cond.shape)} does not match the state {tuple(x.shape)} "
+                             "(same batch and spatial size needed for the 'concat' conditioning)")
+        if tuple(x.shape[2:]) != (unet.input_size, unet.input_size):
+            raise ValueError(f"the DiT takes {unet.input_size}x{unet.input_size} inputs (input_size) but the state is "
+                             f"{tuple(x.shape)}")
+        cz, _ = dit_state_channels(unet.in_channels, unet.learn_sigma, cond.shape[1])
+        if cz != x.shape[1]:
+            raise ValueError(f"the DiT takes {unet.in_channels} input channels but state + conditioning have {x.shape[1]} + "
+                             f"{cond.shape[1]}")
+        return
     if unet.use_spatial_transformer:
         raise ValueError("the latent loops take 'concat' conditioning only; this UNetModel has a spatial transformer")
     if cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:]):
@@ -193,7 +241,7 @@ def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidan
     if inpaint is not None:
         inpaint.check(x_T, steps)
     if unet is None:
-        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel) behind the model handed to the sampler")
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel / DiT) behind the model handed to the sampler")
     if not x_T.is_cuda:
         raise RuntimeError(cpu_message)
     unet.sync_params()
@@ -297,9 +345,9 @@ def plms_step(order: int, a_t: float, a_prev: float, sqrt_1m_at: float, out_cond
     assert cz == Cz and x.shape[0] == (2 * B if out_uncond is not None else B) and tuple(x.shape[2:]) == (H, W)
     for t in (h_new, o1, o2, x_saved):
         assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, Cz, H, W))
-    check(lib().dsd_op_plms_step(int(order), float(a_t), float(a_prev), float(sqrt_1m_at),
-                                 dptr(out_uncond.float().contiguous()) if out_uncond is not None else None,
-                                 dptr(out_cond.float().contiguous()), float(scale), dptr(h_new), dptr(o1), dptr(o2), dptr(x_saved),
+    ou, oc = _f32c(out_uncond), _f32c(out_cond)
+    check(lib().dsd_op_plms_step(int(order), float(a_t), float(a_prev), float(sqrt_1m_at), dptr(ou),
+                                 dptr(oc), float(scale), dptr(h_new), dptr(o1), dptr(o2), dptr(x_saved),
                                  dptr(x), stride, float(threshold) if threshold is not None else 0.0, B, Cz, H, W, stream_ptr()))
 
 
@@ -308,16 +356,20 @@ def sampler_update(sched: Schedule, k: int, model_out: torch.Tensor, x: torch.Te
                    noise: Optional[torch.Tensor], seed: int = 0, want_x0: bool = False):
     """One fused update (dsd_op_sampler_update); x is updated in place."""
     B, Cx, H, W = x.shape
+    if not sched.c.learned_range and model_out.shape[1] == 2 * Cx:
+        model_out = model_out[:, :Cx]          # a variance half the schedule does not use (gaussian_diffusion.py:484-485)
     if Cx > 1:
-        # multi-channel states (latents): the update is elementwise, so [B,C,H,W] is B*C one-channel images — except for
-        # the learned-range variance, whose model output interleaves mean and variance channels per sample
+        # multi-channel states (latents): the update is elementwise, so [B,C,H,W] is B*C one-channel images.  With a
+        # learned-range variance a sample's output is [mean(Cx), variance(Cx)] planes, which is the one-channel layout of a
+        # (Cx*H) x W image: element (b, c, p) keeps its variance partner and its Philox counter b*Cx*H*W + c*H*W + p
         if sched.c.learned_range:
-            raise NotImplementedError("learned-range variance on multi-channel states is not on the sampling hot path")
-        B = B * Cx
+            H = Cx * H
+        else:
+            B = B * Cx
     x0 = torch.empty_like(x) if want_x0 else None
-    check(lib().dsd_op_sampler_update(C.byref(sched.c), k, dptr(model_out.float().contiguous()), dptr(x),
-                                      dptr(noise.float().contiguous()) if noise is not None else None,
-                                      C.c_uint64(seed), B, H, W, dptr(x0), stream_ptr()))
+    mo, z = _f32c(model_out), _f32c(noise)
+    check(lib().dsd_op_sampler_update(C.byref(sched.c), k, dptr(mo), dptr(x), dptr(z), C.c_uint64(seed), B, H, W, dptr(x0),
+                                      stream_ptr()))
     return x0
 
 
@@ -332,10 +384,9 @@ def sampler_update_guided(sched: Schedule, k: int, out_uncond: torch.Tensor, out
     assert x2.shape[0] == 2 * B and x2.is_contiguous() and tuple(x2.shape[2:]) == (H, W)
     assert (state_channels or x2.shape[1]) == Cz
     x0 = torch.empty_like(out_cond, dtype=torch.float32) if want_x0 else None
-    check(lib().dsd_op_sampler_update_guided(C.byref(sched.c), k, dptr(out_uncond.float().contiguous()),
-                                             dptr(out_cond.float().contiguous()), float(scale), dptr(x2),
-                                             x2.shape[1] * H * W, dptr(noise.float().contiguous()) if noise is not None else None,
-                                             C.c_uint64(seed), B, Cz, H, W, dptr(x0), stream_ptr()))
+    ou, oc, z = _f32c(out_uncond), _f32c(out_cond), _f32c(noise)
+    check(lib().dsd_op_sampler_update_guided(C.byref(sched.c), k, dptr(ou), dptr(oc), float(scale), dptr(x2), x2.shape[1] * H * W,
+                                             dptr(z), C.c_uint64(seed), B, Cz, H, W, dptr(x0), stream_ptr()))
     return x0
 
 
@@ -382,6 +433,13 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     return x
 
 
+def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """``t`` as a contiguous fp32 tensor (None stays None).  The caller keeps the result in a local until its launch is queued:
+    the copy a channel slice needs would otherwise be freed as soon as its pointer is taken, and the next copy could be handed
+    the same memory — two arguments of one launch aliasing each other."""
+    return None if t is None else t.float().contiguous()
+
+
 def _rows(x: torch.Tensor, state_channels: Optional[int]):
     """(Cz, row stride) of a contiguous [rows,C,H,W] tensor whose first ``state_channels`` (default: all) channels are the state."""
     assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
@@ -396,10 +454,9 @@ def mask_blend(a: float, s: float, x0: torch.Tensor, mask: torch.Tensor, x: torc
     B, Cz, H, W = x0.shape
     cz, stride = _rows(x, state_channels)
     assert cz == Cz and x.shape[0] == (2 * B if guided else B) and tuple(x.shape[2:]) == (H, W)
-    check(lib().dsd_op_mask_blend(float(a), float(s), dptr(x0.float().contiguous()), dptr(mask.float().contiguous()),
-                                  int(mask.shape[1]), dptr(x), stride, int(guided),
-                                  dptr(noise.float().contiguous()) if noise is not None else None, C.c_uint64(seed),
-                                  C.c_uint64(step), B, Cz, H, W, stream_ptr()))
+    x0c, mc, z = _f32c(x0), _f32c(mask), _f32c(noise)
+    check(lib().dsd_op_mask_blend(float(a), float(s), dptr(x0c), dptr(mc), int(mask.shape[1]), dptr(x), stride, int(guided), dptr(z),
+                                  C.c_uint64(seed), C.c_uint64(step), B, Cz, H, W, stream_ptr()))
 
 
 @torch.no_grad()
@@ -408,9 +465,9 @@ def q_sample_rows(a: torch.Tensor, s: torch.Tensor, x0: torch.Tensor, noise: Opt
     """a[b]*x0_b + s[b]*z_b (dsd_op_q_sample): a, s device fp32 [B] (coefficient tables gathered by t); z fed or Philox."""
     B, Cz, H, W = x0.shape
     out = torch.empty((B, Cz, H, W), device=x0.device, dtype=torch.float32)
-    check(lib().dsd_op_q_sample(dptr(a.float().contiguous()), dptr(s.float().contiguous()), dptr(x0.float().contiguous()),
-                                dptr(noise.float().contiguous()) if noise is not None else None, C.c_uint64(seed),
-                                C.c_uint64(step), dptr(out), 0, B, Cz, H, W, stream_ptr()))
+    ac, sc, x0c, z = _f32c(a), _f32c(s), _f32c(x0), _f32c(noise)
+    check(lib().dsd_op_q_sample(dptr(ac), dptr(sc), dptr(x0c), dptr(z), C.c_uint64(seed), C.c_uint64(step), dptr(out), 0, B, Cz, H,
+                                W, stream_ptr()))
     return out
 
 
@@ -421,6 +478,6 @@ def ddim_invert_step(cx: float, ce: float, out_cond: torch.Tensor, x: torch.Tens
     B, Cz, H, W = out_cond.shape
     cz, stride = _rows(x, state_channels)
     assert cz == Cz and x.shape[0] == (2 * B if out_uncond is not None else B) and tuple(x.shape[2:]) == (H, W)
-    check(lib().dsd_op_ddim_invert_step(float(cx), float(ce), dptr(out_uncond.float().contiguous()) if out_uncond is not None else None,
-                                        dptr(out_cond.float().contiguous()), float(scale), dptr(x), stride, B, Cz, H, W,
+    ou, oc = _f32c(out_uncond), _f32c(out_cond)
+    check(lib().dsd_op_ddim_invert_step(float(cx), float(ce), dptr(ou), dptr(oc), float(scale), dptr(x), stride, B, Cz, H, W,
                                         stream_ptr()))

@@ -292,7 +292,8 @@ int dsd_graph_stats(dsd_handle* h, int* captures, int* launches) {
 
 int dsd_set_slice_ids(dsd_handle* h, const int64_t* ids_host, int n) {
     DSD_TRY
-    DSD_CHECK(h && (!h->is_block || h->block_kind == DSD_BLOCK_UNET) && n >= 0 && (ids_host || n == 0), "bad argument");
+    DSD_CHECK(h && (!h->is_block || h->block_kind == DSD_BLOCK_UNET || h->block_kind == DSD_BLOCK_DIT) && n >= 0 &&
+                  (ids_host || n == 0), "bad argument");
     set_device(h->device);
     if (h->slice_ids) {
         DSD_HIP(hipDeviceSynchronize());
@@ -427,9 +428,32 @@ void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x,
     check_slice_ids(h, B);
 }
 
-// the plain UNetModel (DSD_BLOCK_UNET) on a Cz-channel latent state with a 'concat' conditioning of Cc channels
-void check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W,
-                  int out_ch) {
+// the state-in-input denoisers on a Cz-channel latent state with a 'concat' conditioning of Cc channels: the plain UNetModel
+// (DSD_BLOCK_UNET) or the DiT (DSD_BLOCK_DIT: square input of input_size, no labels — through DiffusionWrapper none reaches it,
+// DiT_models.py:245-249 — and Cc = 0 for an unconditional one).  want_ch: the output channels the sampler reads, Cz or (learned
+// range) 2*Cz.  Returns the handle's output channel count, the row stride of mout in planes: the UNetModel's equals want_ch; the
+// DiT's (in_channels // 3 * 2 with learn_sigma, sic) is Cz or 2*Cz, and a sampler without learned variance ignores the second
+// half (gaussian_diffusion.py:484-485).
+bool is_dit(const dsd_handle* h) { return h && h->is_block && h->block_kind == DSD_BLOCK_DIT; }
+
+int check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W,
+                 int want_ch) {
+    if (is_dit(h)) {
+        DSD_CHECK(x && (cond || Cc == 0), "null argument");
+        const std::vector<int32_t>& a = h->iargs;   // input_size, patch_size, in_channels, ..., learn_sigma at [8] (net.cpp DitCfg)
+        const int out_ch = a[8] ? a[2] / 3 * 2 : a[2];
+        DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
+        DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+        DSD_CHECK(a[2] == Cz + Cc, "the DiT takes %d input channels but state + conditioning have %d + %d", a[2], Cz, Cc);
+        DSD_CHECK(H == a[0] && W == a[0], "the DiT takes %dx%d inputs (input_size) but the state is %dx%d", a[0], a[0], H, W);
+        DSD_CHECK(out_ch == Cz || out_ch == 2 * Cz,
+                  "the DiT has %d output channels but a state of %d channels needs %d, or %d with a learned variance", out_ch, Cz, Cz,
+                  2 * Cz);
+        DSD_CHECK(want_ch <= out_ch, "a learned-range variance needs %d output channels (2 per state channel) but the DiT has %d",
+                  want_ch, out_ch);
+        check_slice_ids(h, B);
+        return out_ch;
+    }
     DSD_CHECK(h && cond && x, "null argument");
     DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
     DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
@@ -437,8 +461,9 @@ void check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int C
     DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
     DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
     DSD_CHECK(a[0] == Cz + Cc, "the UNetModel takes %d input channels but state + conditioning have %d + %d", a[0], Cz, Cc);
-    DSD_CHECK(a[2] == out_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], out_ch);
+    DSD_CHECK(a[2] == want_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], want_ch);
     check_slice_ids(h, B);
+    return want_ch;
 }
 
 LoopBinding make_binding(dsd_handle* h, const dsd_guidance* g, float* xs, int64_t x_bs, float* x, int Cz, int B, int64_t hw,
@@ -524,11 +549,13 @@ LoopBinding bind_latent(dsd_handle* h, const dsd_guidance* g, const float* cond,
     return b;
 }
 
-// `latent` selects the denoiser: the plain UNetModel on a Cz-channel state, or the four-stream model (Cz = 1)
-void check_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B,
-                    int H, int W, int out_ch) {
-    if (latent) check_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch);
-    else check_four_stream(h, cond, Cc, x, B, H, W);
+// `latent` selects the denoiser: a state-in-input one (UNetModel / DiT) on a Cz-channel state, or the four-stream model (Cz = 1).
+// want_ch: the output channels the sampler reads; returns the channels one output row holds (the four-stream callers check theirs).
+int check_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B,
+                   int H, int W, int want_ch) {
+    if (latent) return check_latent(h, g, cond, Cc, x, Cz, B, H, W, want_ch);
+    check_four_stream(h, cond, Cc, x, B, H, W);
+    return want_ch;
 }
 
 LoopBinding bind_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B,
@@ -626,10 +653,10 @@ static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd
         check_guided_schedule(sc);
         check_guidance(g, sc->steps);
     }
-    DSD_CHECK(!(sc->learned_range && Cz > 1),
+    DSD_CHECK(!(sc->learned_range && Cz > 1) || is_dit(h),
               "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
-    const int out_ch = (sc->learned_range ? 2 : 1) * Cz;
-    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch);
+    const int want_ch = (sc->learned_range ? 2 : 1) * Cz;
+    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, want_ch);
     DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d", h->cfg.out_channels,
               out_ch);
     set_device(h->device);
@@ -643,7 +670,7 @@ static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd
              [&](int k) {
                  sampler_update(step_coef(sc, k), b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs,
                                 noise ? noise + (size_t)k * B * b.n() : nullptr, seed, (uint64_t)k, B, (int)b.hw, s, nullptr, b.ids, Cz,
-                                b.x_bs);
+                                b.x_bs, out_ch * b.hw);
                  if (blend_last) blend_step(sc, k, inp, b, seed, s);
              });
     finish(h, b, s);
@@ -751,13 +778,13 @@ static DpmCoef dpm_coef(const dsd_dpm_schedule* sc, int k) {
 }
 
 // One sample = all Cz*h*w elements: the dynamic-thresholding quantile is per sample over C*h*w (sampler.py:379-388).  The
-// four-stream model may carry a learned sigma in a second output channel, which the solver ignores.
+// four-stream model and the DiT may carry a learned sigma in a second half of the output channels, which the solver ignores.
 static void sample_dpm(bool latent, dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
                        float* x, int Cz, int B, int H, int W, void* stream) {
     check_dpm_schedule(sc);
     if (g) check_guidance(g, sc->steps);
-    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
-    const int Cm = latent ? 1 : h->cfg.out_channels;
+    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;   // an output row is Cm samples long; the solver reads the first
     DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
@@ -823,7 +850,6 @@ int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sc, int k, const float* out_u
     check_dpm_schedule(sc);
     DSD_CHECK(k >= 0 && k < sc->steps && out_uncond && out_cond && x && m_cur && (Cm == 1 || Cm == 2), "bad argument");
     check_op_state(B, Cz, H, W, x_row_stride);
-    DSD_CHECK(Cm == 1 || Cz == 1, "a two-channel (learned-sigma) output needs one state channel; Cz = %d", Cz);
     DSD_CHECK(sc->order[k] < 2 || m_prev, "a second-order update needs m_prev");
     Tmp sb((size_t)B * sizeof(float));
     dpm_step(dpm_coef(sc, k), out_uncond, out_cond, Cm, scale, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio,
@@ -854,7 +880,7 @@ static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, cons
     check_plms_schedule(sc);
     if (g) check_guidance(g, sc->steps);
     if (inp) check_mask(inp, Cz);
-    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
     const int64_t n = (int64_t)Cz * H * W, plane = (int64_t)B * n;
     const Range r = step_range(first_step, n_steps, sc->steps);
@@ -868,11 +894,12 @@ static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, cons
     hipStream_t s = (hipStream_t)stream;
     const size_t planes = ((size_t)3 * plane * sizeof(float) + 15) / 16 * 16;   // nothing is allocated once the planes have their size
     ensure_buf(&h->plms_hist, &h->plms_hist_cap, planes + plms_norm_doubles(B, n) * sizeof(double));
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz, s);
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     PlmsStep a;
     a.thr = thr > 0.f ? thr : 0.f;
     a.out_u = b.out_u;
     a.out_c = b.out_c;
+    a.o_bs = out_ch * b.hw;
     a.x = b.xs;
     a.x_bs = b.x_bs;
     a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->plms_hist) + planes);
@@ -951,13 +978,14 @@ static void invert(bool latent, dsd_handle* h, const dsd_invert_schedule* sc, co
                    int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
     if (g) check_guidance(g, sc->steps);
-    check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz, s);
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s, [](int) {}, [&](int k) {
-        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs, B, Cz, (int)b.hw, s, b.x_bs);
+        ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs, B, Cz, (int)b.hw, s, b.x_bs,
+                         out_ch * b.hw);
     });
     finish(h, b, s);
 }

@@ -243,8 +243,9 @@ struct StepCoef {
     int mode, pred, learned_range, clip, nonzero;
     float eta;
 };
-// out_c: the model output [B,Cm*Cz,HW] (Cm = 1, or 2 with learned_range and Cz = 1); x in/out [B,Cz,HW] with row stride x_bs
-// (0 = Cz*HW); noise [B,Cz,HW] or null (Philox)
+// out_c: the model output, row b at out_c + b*o_bs (0 = Cz*HW, or 2*Cz*HW with learned_range): channels [0,Cz) the prediction,
+// [Cz,2Cz) the learned-range variance (read with learned_range only); x in/out [B,Cz,HW] with row stride x_bs (0 = Cz*HW);
+// noise [B,Cz,HW] or null (Philox)
 // slice_ids (optional, device [B]): global slice index of every batch row — the Philox counter of element r = c*HW + p of row b
 // is slice_ids[b]*Cz*HW + r instead of b*Cz*HW + r, so a slice's noise does not depend on how the volume was sharded or batched
 // Classifier-free guidance (out_u != nullptr, DSD_MODE_B_DDIM): the network ran on 2B rows (uncond half first), out_u / out_c are
@@ -253,7 +254,7 @@ struct StepCoef {
 // logical sample.
 void sampler_update(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
                     uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out = nullptr,
-                    const int64_t* slice_ids = nullptr, int Cz = 1, int64_t x_bs = 0);
+                    const int64_t* slice_ids = nullptr, int Cz = 1, int64_t x_bs = 0, int64_t o_bs = 0);
 // DPM-Solver(++) multistep: coefficients of one network evaluation + update (host tables, include/dsdiff.h dsd_dpm_schedule)
 struct DpmCoef {
     float alpha, sigma;      // marginal alpha_t, sigma_t at the evaluation time
@@ -274,8 +275,9 @@ void q_sample_blend(float a, float s, const float* a_row, const float* s_row, co
                     float* x, const float* noise, uint64_t seed, uint64_t step, int B, int Cz, int HW, hipStream_t st,
                     int64_t x_bs = 0, bool dup = false, const int64_t* slice_ids = nullptr);
 // DDIM inversion step: x = cx*x + ce*e, e = out_c or (out_u != nullptr) out_u + scale*(out_c - out_u), then written to both rows
+// (output rows of o_bs elements, 0 = Cz*HW: the prediction is their first Cz*HW)
 void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c, float scale, float* x, int B, int Cz, int HW,
-                      hipStream_t st, int64_t x_bs = 0);
+                      hipStream_t st, int64_t x_bs = 0, int64_t o_bs = 0);
 // PLMS (sampler.hip): one update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:206-243) on B logical samples of
 // n = Cz*HW elements.  order (DSD_PLMS_*): 0 predict / 1 correct = the two halves of the first step around its second network
 // evaluation, 2..4 = Adams-Bashforth on 1..3 earlier noise predictions.  out_u == nullptr: e_t = out_c, else e_t = out_u +
@@ -295,6 +297,7 @@ struct PlmsStep {
     float* x_saved = nullptr;
     float* x = nullptr;
     int64_t x_bs = 0;
+    int64_t o_bs = 0;        // row stride of out_u / out_c (0 = n; 2n for a model with a variance half, left unread)
     double* part = nullptr;
 };
 size_t plms_norm_doubles(int B, int64_t n);

@@ -150,7 +150,10 @@ __device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float 
 
 // One sample is n = Cz*HW elements (r = c*HW + p inside it).  The state row b lives at x + b*x_bs: x_bs = n for a state of its
 // own, (Cz+Cc)*HW when the state is the first Cz channels of the denoiser's NCHW input (the latent loop writes x_{t-1} straight
-// into the buffer the network reads next).  The model output, noise and x0_out are contiguous [B,Cm*Cz,HW] / [B,Cz,HW].  The
+// into the buffer the network reads next).  Noise and x0_out are contiguous [B,Cz,HW].  The model output row b lives at
+// mo + b*o_bs: its first n elements are the prediction (channels [0,Cz)), the n after them the learned-range variance (channels
+// [Cz,2Cz): frac of (b, c, p) at o_bs*b + n + c*HW + p, gaussian_diffusion.py:280-294); o_bs = n, or 2n for a model with a
+// variance half, which every mode without learned variance leaves unread.  The
 // Philox counter of (row b, channel c, pixel p) is (slice_ids ? slice_ids[b] : b)*n + r: distinct channels never share a normal.
 // Classifier-free guidance (mo_u != nullptr; ddim.py:194-219): the network ran on 2B rows — x_in = cat([x]*2), c_in =
 // cat([uncond, cond]) — so its output arrives as the halves mo_u / mo_c and the state occupies 2B rows, logical sample b at rows
@@ -161,18 +164,18 @@ template <int V>
 __global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const float* __restrict__ mo_u,
                                                              const float* __restrict__ mo_c, float gs, float* __restrict__ x,
                                                              const float* __restrict__ noise, uint64_t seed, uint64_t step,
-                                                             int B, int64_t n, int64_t x_bs, float* __restrict__ x0_out,
+                                                             int B, int64_t n, int64_t x_bs, int64_t o_bs,
+                                                             float* __restrict__ x0_out,
                                                              const int64_t* __restrict__ slice_ids) {
     const int64_t nv = n / V;
     // One pack per thread and no grid-stride loop: out of a loop the compiler hoists the constants of the inlined logf / sinf /
     // cosf into scalar registers, more than there are once all four modes and both output halves are live (it spilled them).
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= B * nv) return;
-    const int Cm = sc.learned_range ? 2 : 1;                     // learned range: Cz == 1 (checked by the callers)
     const int64_t b = i / nv;
     const int64_t p = (i - b * nv) * V;
     const int64_t li = b * n + p;                                // in the [B,n] tensors
-    const int64_t oi = (b * Cm) * n + p;                         // in the model output
+    const int64_t oi = b * o_bs + p;                             // in the model output
     const int64_t xi = b * x_bs + p;
     Pack<V> out = ld_pack<V>(mo_c + oi);
     if (mo_u) {
@@ -194,14 +197,17 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(StepCoef sc, const 
 
 void sampler_update(const StepCoef& sc, const float* out_u, const float* out_c, float scale, float* x, const float* noise,
                     uint64_t seed, uint64_t step, int B, int HW, hipStream_t s, float* x0_out, const int64_t* slice_ids, int Cz,
-                    int64_t x_bs) {
+                    int64_t x_bs, int64_t o_bs) {
     const int64_t n = (int64_t)Cz * HW;
     if (!B || !n) return;
     if (x_bs <= 0) x_bs = n;
-    const bool v4 = can_vec4(n, x_bs, out_u, out_c, x, noise, x0_out);
+    if (o_bs <= 0) o_bs = (sc.learned_range ? 2 : 1) * n;
+    DSD_CHECK(o_bs >= (sc.learned_range ? 2 : 1) * n, "sampler update: output rows of %lld elements, the update reads %lld",
+              (long long)o_bs, (long long)((sc.learned_range ? 2 : 1) * n));
+    const bool v4 = can_vec4(n, x_bs, out_u, out_c, x, noise, x0_out) && o_bs % 4 == 0;
     launch_vec(v4, [&](auto V) {
         hipLaunchKernelGGL(sampler_update_kernel<decltype(V)::value>, dim3((unsigned)((B * (n / decltype(V)::value) + 255) / 256)),
-                           dim3(256), 0, s, sc, out_u, out_c, scale, x, noise, seed, step, B, n, x_bs, x0_out, slice_ids);
+                           dim3(256), 0, s, sc, out_u, out_c, scale, x, noise, seed, step, B, n, x_bs, o_bs, x0_out, slice_ids);
     });
     check_launch("sampler_update");
 }
@@ -448,16 +454,16 @@ void q_sample_blend(float a, float s, const float* a_row, const float* s_row, co
 template <int V>
 __global__ __launch_bounds__(256) void ddim_invert_kernel(float cx, float ce, const float* __restrict__ mo_u,
                                                           const float* __restrict__ mo_c, float gs, float* __restrict__ x, int B,
-                                                          int64_t n, int64_t x_bs) {
+                                                          int64_t n, int64_t x_bs, int64_t o_bs) {
     const int64_t nv = n / V, total = (int64_t)B * nv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / nv;
         const int64_t p = (i - b * nv) * V;
-        const int64_t li = b * n + p, xi = b * x_bs + p;
-        Pack<V> e = ld_pack<V>(mo_c + li);
+        const int64_t oi = b * o_bs + p, xi = b * x_bs + p;      // output rows of o_bs: the prediction is their first n elements
+        Pack<V> e = ld_pack<V>(mo_c + oi);
         const Pack<V> xt = ld_pack<V>(x + xi);
         if (mo_u) {
-            const Pack<V> eu = ld_pack<V>(mo_u + li);
+            const Pack<V> eu = ld_pack<V>(mo_u + oi);
 #pragma unroll
             for (int j = 0; j < V; ++j) e.v[j] = eu.v[j] + gs * (e.v[j] - eu.v[j]);
         }
@@ -470,31 +476,33 @@ __global__ __launch_bounds__(256) void ddim_invert_kernel(float cx, float ce, co
 }
 
 void ddim_invert_step(float cx, float ce, const float* out_u, const float* out_c, float scale, float* x, int B, int Cz, int HW,
-                      hipStream_t st, int64_t x_bs) {
+                      hipStream_t st, int64_t x_bs, int64_t o_bs) {
     const int64_t n = (int64_t)Cz * HW;
     if (!B || !n) return;
     if (x_bs <= 0) x_bs = n;
-    launch_vec(can_vec4(n, x_bs, out_u, out_c, x), [&](auto V) {
+    if (o_bs <= 0) o_bs = n;
+    launch_vec(can_vec4(n, x_bs, out_u, out_c, x) && o_bs % 4 == 0, [&](auto V) {
         hipLaunchKernelGGL(ddim_invert_kernel<decltype(V)::value>, dim3(ew_blocks(B * (n / decltype(V)::value))), dim3(256), 0, st, cx,
-                           ce, out_u, out_c, scale, x, B, n, x_bs);
+                           ce, out_u, out_c, scale, x, B, n, x_bs, o_bs);
     });
     check_launch("ddim_invert");
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // PLMS (ldm/models/diffusion/plms.py:206-243; PlmsStep in kernels.h).  Grid as the blend's: x over the packs of one sample, y =
-// the sample, so the threshold's scale is block-uniform.  The history planes, x_saved and the two output halves are contiguous
-// [B,n]; the state row b sits at x + b*x_bs and, guided, the result also goes to row B+b.
+// the sample, so the threshold's scale is block-uniform.  The history planes and x_saved are contiguous [B,n]; row b of the two
+// output halves sits at out + b*o_bs (o_bs = n, or 2n for a model with a variance half, which PLMS leaves unread); the state row
+// b sits at x + b*x_bs and, guided, the result also goes to row B+b.
 // plms_form: e_t, e' and the pred_x0 before thresholding of one pack — the one place both kernels take them from, so the norm
 // kernel sums exactly the values the update kernel scales.  The combinations are the reference's expressions, left to right,
 // every product and sum rounded on its own (file-wide contract(off)), the divisors literals with an IEEE division.
 template <int V>
 __device__ __forceinline__ void plms_form(const PlmsStep& a, int b, int p, int n, Pack<V>& et, Pack<V>& ep, Pack<V>& xt,
                                           Pack<V>& x0) {
-    const int64_t li = (int64_t)b * n + p;
-    Pack<V> e = ld_pack<V>(a.out_c + li);
+    const int64_t li = (int64_t)b * n + p, oi = b * a.o_bs + p;               // output rows of o_bs, the prediction first
+    Pack<V> e = ld_pack<V>(a.out_c + oi);
     if (a.out_u) {                                                            // plms.py:189-193
-        const Pack<V> eu = ld_pack<V>(a.out_u + li);
+        const Pack<V> eu = ld_pack<V>(a.out_u + oi);
 #pragma unroll
         for (int j = 0; j < V; ++j) e.v[j] = eu.v[j] + a.scale * (e.v[j] - eu.v[j]);
     }
@@ -588,7 +596,8 @@ void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
     DSD_CHECK(n <= (int64_t)1 << 30, "PLMS update: one sample has %lld elements; up to 2^30 are taken", (long long)n);
     DSD_CHECK(B <= 65535, "PLMS update: %d samples; up to 65535 are taken", B);
     if (a.x_bs <= 0) a.x_bs = n;
-    const bool v4 = can_vec4(n, a.x_bs, a.out_u, a.out_c, a.h_new, a.o1, a.o2, a.x_saved, a.x);
+    if (a.o_bs <= 0) a.o_bs = n;
+    const bool v4 = can_vec4(n, a.x_bs, a.out_u, a.out_c, a.h_new, a.o1, a.o2, a.x_saved, a.x) && a.o_bs % 4 == 0;
     const int64_t blocks = (n / (v4 ? 4 : 1) + 255) / 256;
     const int nblk = (int)std::min<int64_t>(blocks, kPlmsNormBlocks);
     if (a.thr > 0.f) {

@@ -245,11 +245,13 @@ typedef struct dsd_schedule {
 int dsd_sample(dsd_handle* h, const dsd_schedule* sched, const float* cond, int Cc, float* x, const float* noise,
                uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
 /* The fused sampler update alone (iteration k): model_out [B,Cm,H,W]; x updated in place; pred_xstart
- * (optional, [B,1,H,W]) receives the clipped x_0 prediction (the reference's out["pred_xstart"]). */
+ * (optional, [B,1,H,W]) receives the clipped x_0 prediction (the reference's out["pred_xstart"]).  A state of Cz channels is B*Cz
+ * one-channel images; with a learned-range variance it is B images of (Cz*H) x W: the output row [mean(Cz), variance(Cz)] is
+ * the one-channel layout at that height, and element (b, c, p) keeps its Philox counter b*Cz*H*W + c*H*W + p. */
 int dsd_op_sampler_update(const dsd_schedule* sched, int k, const float* model_out, float* x, const float* noise,
                           uint64_t philox_seed, int B, int H, int W, float* pred_xstart, void* stream);
 
-/* ---- latent sampling loops (DSD_BLOCK_UNET denoiser) -------------------------------------
+/* ---- latent sampling loops (DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser) --------------------
  * The loops of dsd_sample / dsd_sample_dpm on a multi-channel state: x [B,Cz,H,W] (VAE latents, in = x_T, out = sample, in
  * place) denoised by a DSD_BLOCK_UNET handle (the plain UNetModel, no spatial transformer) with in_channels = Cz + Cc and
  * out_channels = Cz (2 with a learned-range variance, which needs Cz = 1).  cond [B,Cc,H,W] is concatenated after the state
@@ -258,7 +260,16 @@ int dsd_op_sampler_update(const dsd_schedule* sched, int k, const float* model_o
  * dsd_set_slice_ids (Philox counter (seed, step, slice, channel, pixel)) and dsd_set_graph replay (one stream, no forks) work
  * as for the four-stream model.  noise: NULL -> Philox, else [steps,B,Cz,H,W].
  * Replaces DDIMSampler.sample / ddim_sampling (ldm/models/diffusion/ddim.py:57-261) and LatentDiffusion.p_sample_loop
- * (ddpm.py:1048-1115) as trainers/trainer_latent_diffusion.py:492-544 calls them. */
+ * (ddpm.py:1048-1115) as trainers/trainer_latent_diffusion.py:492-544 calls them.
+ * Every *_latent* entry (this one, _guided, _masked, dsd_sample_dpm_latent(_guided), dsd_sample_plms_latent, dsd_invert_latent)
+ * also takes a DSD_BLOCK_DIT handle, the network the reference's trainer swaps in for the U-Net behind the same DiffusionWrapper
+ * (trainers/trainer_use_gaussian_diff.py:84-86): in_channels = Cz + Cc (Cc = 0 and cond = NULL for an unconditional DiT),
+ * H = W = input_size, t as the handle's aux and no labels (none reaches the DiT through the wrapper).  Its output has Cz
+ * channels, or 2*Cz with learn_sigma (in_channels // 3 * 2, sic): the prediction is channels [0,Cz), the learned-range variance
+ * of (b, c, p) is channel Cz + c — read by DSD_MODE_A_DDPM with learned_range for any Cz, left unread by every other mode
+ * (gaussian_diffusion.py:484-485).  Each misfit (channels, size, output channels, learned_range without a variance half) is
+ * rejected with its numbers before any device work.  DSD_PREC_F16 / DSD_PREC_BF16 apply to the network only: the state, the
+ * updates and the model output stay fp32. */
 int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sched, const float* cond, int Cc, float* x, int Cz, const float* noise,
                       uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
 
@@ -290,8 +301,8 @@ typedef struct dsd_dpm_schedule {
  * contributes its first channel only (gaussian_diffusion.py:484-485). */
 int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int B, int H, int W,
                    void* stream);
-/* dsd_sample_dpm on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser (out_channels = Cz), set up as in
- * dsd_sample_latent.  Dynamic thresholding takes the quantile per sample over all Cz*H*W elements (dynamic_thresholding_fn,
+/* dsd_sample_dpm on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser (out_channels = Cz) or a DSD_BLOCK_DIT one
+ * (Cz or 2*Cz output channels, the first Cz read), set up as in dsd_sample_latent.  Dynamic thresholding takes the quantile per sample over all Cz*H*W elements (dynamic_thresholding_fn,
  * ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:418).  Replaces DPMSolverSampler.sample (sampler.py:35-103). */
 int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int Cz, int B, int H,
                           int W, void* stream);
@@ -377,7 +388,7 @@ typedef struct dsd_invert_schedule {
     const float* coef;      /* host, steps*2: cx, ce */
     const float* t_model;   /* host, steps */
 } dsd_invert_schedule;
-/* x: [B,1,H,W] (four-stream model) / [B,Cz,H,W] (DSD_BLOCK_UNET) in = x0, out = the encoded state, in place.  g: NULL or the
+/* x: [B,1,H,W] (four-stream model) / [B,Cz,H,W] (DSD_BLOCK_UNET, DSD_BLOCK_DIT) in = x0, out = the encoded state, in place.  g: NULL or the
  * guidance (2B network rows per step, as in the guided sampling loops). */
 int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
                int H, int W, int first_step, int n_steps, void* stream);
@@ -417,7 +428,7 @@ int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const f
 int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
                     float dynamic_threshold, const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W,
                     int first_step, int n_steps, void* stream);
-/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser, set up as in dsd_sample_latent. */
+/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, set up as in dsd_sample_latent. */
 int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
                            float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B,
                            int H, int W, int first_step, int n_steps, void* stream);
