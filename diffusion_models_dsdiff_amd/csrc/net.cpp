@@ -446,12 +446,19 @@ void p_vae_decoder(dsd_handle* h, const VaeCfg& c) {   // model.py:546-616
 float* dsd_handle::P(const std::string& name) const {
     auto it = pidx.find(name);
     DSD_CHECK(it != pidx.end(), "unknown parameter %s", name.c_str());
-    return reinterpret_cast<float*>(slab + params[it->second].off);
+    return slab_at(params[it->second].off);
 }
 const Param& dsd_handle::PP(const std::string& name) const {
     auto it = pidx.find(name);
     DSD_CHECK(it != pidx.end(), "unknown parameter %s", name.c_str());
     return params[it->second];
+}
+int* dsd_handle::ensure_ovf() {
+    if (!ovf) {
+        DSD_HIP(hipMalloc((void**)&ovf, sizeof(int)));
+        DSD_HIP(hipMemset(ovf, 0, sizeof(int)));
+    }
+    return ovf;
 }
 
 void dsd::net_declare_params(dsd_handle* h) {
@@ -548,7 +555,7 @@ void dsd::net_set_param(dsd_handle* h, const char* name, const float* src, const
         for (int i = 0; i < ndim; ++i) got += std::to_string(shape[i]) + ",";
         fail("size mismatch for %s: expected [%s] got [%s]", name, want.c_str(), got.c_str());
     }
-    float* dst = reinterpret_cast<float*>(h->slab + p.off);
+    float* dst = h->slab_at(p.off);
     const size_t bytes = (size_t)p.numel * sizeof(float);
     const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     // the repack staging buffer is shared by every upload: an upload on ANOTHER stream than the previous one first waits for it
@@ -581,17 +588,17 @@ void dsd::net_set_param(dsd_handle* h, const char* name, const float* src, const
         h->last_param_stream = s;
         h->any_param_upload = true;
     }
-    const std::string conv_name = p.name.size() > 7 ? p.name.substr(0, p.name.size() - 7) : p.name;   // "<conv>.weight" -> "<conv>"
-    for (const std::string& key : {conv_name, conv_name + "#f16", conv_name + "#wino", conv_name + "#sub", p.name + "#h16", p.name + "#b16"}) {
-        auto sp = h->wsplit.find(key);
-        if (sp != h->wsplit.end()) {
-            DSD_HIP(hipDeviceSynchronize());
-            (void)hipFree(sp->second);
-            h->wsplit.erase(sp);
-            h->wsplit_bytes.erase(key);
-            h->plan.valid = false;
-            net_drop_graph(h);
+    // every derived form of this parameter is stale now
+    for (auto it = h->derived.begin(); it != h->derived.end();) {
+        if (it->second.source != p.name) {
+            ++it;
+            continue;
         }
+        DSD_HIP(hipDeviceSynchronize());
+        (void)hipFree(it->second.ptr);
+        it = h->derived.erase(it);
+        h->plan.valid = false;
+        net_drop_graph(h);
     }
 }
 
@@ -610,33 +617,31 @@ void dsd::net_drop_graph(dsd_handle* h) {
 
 void dsd::net_drop_other_pieces(dsd_handle* h, int precision) {
     if (precision == PREC_F32) return;   // the exact mode needs none, but switching back should not re-split everything
-    // which family a cached entry belongs to, by the suffix of its key: "#f16" two fp16 pieces (f16x3), "#h16" / "#b16" the
-    // single fp16 / bf16 copy of the half-precision modes, anything else the bf16 pieces (bf16x3 / bf16x6, also what the
-    // half-precision modes keep for the layers that stay fp32-grade)
-    auto ends = [](const std::string& k, const char* sfx) { return k.size() > 4 && k.compare(k.size() - 4, 4, sfx) == 0; };
-    bool any = false;
-    for (auto it = h->wsplit.begin(); it != h->wsplit.end();) {
-        bool keep;
-        if (ends(it->first, "#f16")) keep = precision == PREC_F16X3;
-        else if (ends(it->first, "#h16")) keep = precision == PREC_F16;
-        else if (ends(it->first, "#b16")) keep = precision == PREC_BF16;
-        else keep = precision != PREC_F16X3;
-        if (!keep) {
-            if (!any) DSD_HIP(hipDeviceSynchronize());
-            any = true;
-            (void)hipFree(it->second);
-            h->wsplit_bytes.erase(it->first);
-            it = h->wsplit.erase(it);
-        } else {
-            ++it;
+    auto keep = [&](WeightFamily f) {
+        switch (f) {
+            case WF_F16_PIECES: return precision == PREC_F16X3;
+            case WF_F16_COPY: return precision == PREC_F16;
+            case WF_BF16_COPY: return precision == PREC_BF16;
+            default: return precision != PREC_F16X3;   // (the half-precision modes keep the bf16 pieces of their fp32-grade layers)
         }
+    };
+    bool any = false;
+    for (auto it = h->derived.begin(); it != h->derived.end();) {
+        if (keep(it->second.family)) {
+            ++it;
+            continue;
+        }
+        if (!any) DSD_HIP(hipDeviceSynchronize());
+        any = true;
+        (void)hipFree(it->second.ptr);
+        it = h->derived.erase(it);
     }
     if (any) net_drop_graph(h);
 }
 
 size_t dsd::net_piece_bytes(const dsd_handle* h) {
     size_t b = 0;
-    for (const auto& kv : h->wsplit_bytes) b += kv.second;
+    for (const auto& kv : h->derived) b += kv.second.bytes;
     return b;
 }
 
@@ -663,9 +668,8 @@ void dsd::net_free(dsd_handle* h) {
         if (h->lane_join[l]) (void)hipEventDestroy(h->lane_join[l]);
         if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
     }
-    for (auto& kv : h->wsplit) (void)hipFree(kv.second);
-    h->wsplit.clear();
-    h->wsplit_bytes.clear();
+    for (auto& kv : h->derived) (void)hipFree(kv.second.ptr);
+    h->derived.clear();
     for (auto e : h->ev) (void)hipEventDestroy(e);
     h->ev.clear();
 }
@@ -678,6 +682,27 @@ struct EmbRef {
     int64_t col = 0;       // first column of this block
     int stride = 0;
     bool valid = false;
+};
+
+// What Builder::conv can do besides the plain convolution, by name (every field at its default = conv(name, x, cout, ks)).
+struct ConvOpt {
+    int stride = 1;
+    bool ups = false;             // nearest-x2 upsample folded into the gather (Upsample.forward)
+    const EmbRef* emb = nullptr;  // + emb_out[:, :, None, None] in the epilogue
+    const Tn* res = nullptr;      // + residual in the epilogue
+    int plane = -1;               // >= 0: x is the caller's input plane io.plane[plane], not an arena tensor
+    bool to_out = false;          // write to io.out (NCHW) instead of an arena tensor
+    bool bias = true;
+    const Tn* dst = nullptr;      // write into channels [0, cout) of this wider tensor (see conv)
+    bool want_stats = false;      // a GroupNorm reads the result: emit its statistics from the epilogue where the kernel can
+    int pad_lo = -1, pad_total = -1;   // asymmetric padding (the KL-VAE's Downsample); -1: ks / 2 on every side
+    const GnRef* gn = nullptr;    // apply this GroupNorm + SiLU to x while staging it (ask can_fuse_gn first)
+};
+// norm_conv3x3 beyond the fused-or-apply decision
+struct NormOpt {
+    bool small_first = false;     // ResBlock: a map small enough for the one-launch GroupNorm takes that, never the fused form
+    bool consume = false;         // release x as soon as the convolution no longer needs it
+    std::function<void(Tn&)> rework;   // reworks the normalised tensor before the convolution (ResBlock up / down): never fused
 };
 
 struct Builder {
@@ -721,20 +746,26 @@ struct Builder {
     int conv_prec() const { return hd->precision >= PREC_F16 ? PREC_BF16X6 : hd->precision; }
     bool half_mode() const { return hd->precision == PREC_F16 || hd->precision == PREC_BF16; }
     // 16-bit copy of a Linear weight [N][K] (made once per mode at plan time, on the caller's stream)
+    // the device-resident form `key` of parameter `source`, from the handle's cache; made on first use: make(buffer) enqueues
+    // the work on the caller's stream, ordered after the dsd_set_param copies / repacks enqueued there
+    template <class Make>
+    void* derived(const std::string& key, const std::string& source, WeightFamily family, size_t bytes, Make make) {
+        auto it = hd->derived.find(key);
+        if (it == hd->derived.end()) {
+            DerivedWeight d;
+            DSD_HIP(hipMalloc(&d.ptr, bytes));
+            make(d.ptr);
+            split_any = true;
+            d.bytes = bytes; d.source = source; d.family = family;
+            it = hd->derived.emplace(key, d).first;
+        }
+        return it->second.ptr;
+    }
     const void* w16(const std::string& name) {
         const bool bf = hd->precision == PREC_BF16;
-        const std::string key = name + (bf ? "#b16" : "#h16");
-        auto it = hd->wsplit.find(key);
-        if (it == hd->wsplit.end()) {
-            const Param& pw = hd->PP(name);
-            void* buf = nullptr;
-            DSD_HIP(hipMalloc(&buf, (size_t)pw.numel * 2));
-            cast16(W(name), pw.numel, buf, bf ? 1 : 0, ps);
-            split_any = true;
-            it = hd->wsplit.emplace(key, buf).first;
-            hd->wsplit_bytes[key] = (size_t)pw.numel * 2;
-        }
-        return it->second;
+        const int64_t n = hd->PP(name).numel;
+        return derived(name + (bf ? "#b16" : "#h16"), name, bf ? WF_BF16_COPY : WF_F16_COPY, (size_t)n * 2,
+                       [&](void* buf) { cast16(W(name), n, buf, bf ? 1 : 0, ps); });
     }
     // nn.Linear on 16-bit operands (gemm16.hip).  x: 16-bit tokens [n, h*w, K].  epi EPI16_STORE / EPI16_GELU: returns the
     // 16-bit result; EPI16_GATED: xres (fp32) += gate * result, returns xres.
@@ -767,8 +798,8 @@ struct Builder {
             Gemm16Args c = a;
             c.x = h->arena + xoff;
             if (epi == EPI16_GATED) {
-                c.x32 = reinterpret_cast<float*>(h->arena + yoff);
-                c.gate = reinterpret_cast<const float*>(h->arena + gate_off) + gate_col;
+                c.x32 = h->at<float>(yoff);
+                c.gate = h->at<float>(gate_off) + gate_col;
             } else {
                 c.y16 = h->arena + yoff;
             }
@@ -814,36 +845,37 @@ struct Builder {
     // ---- convolution: src is an arena tensor, or (plane >= 0) one of the caller's input planes
     // dst != nullptr: the result is written into channels [0, cout) of the wider NHWC tensor *dst (row stride dst->c) instead
     // of a tensor of its own — the decoder's cat([h, skip]) without the copy of h; the returned Tn is then a view of *dst.
-    Tn conv(const std::string& name, const Tn& x, int cout, int ks, int stride = 1, bool ups = false,
-            const EmbRef* emb = nullptr, const Tn* res = nullptr, int plane = -1, bool to_out = false, bool bias = true,
-            const Tn* dst = nullptr, bool want_stats = false, int pad_lo = -1, int pad_total = -1, const GnRef* gn = nullptr) {
+    Tn conv(const std::string& name, const Tn& x, int cout, int ks, const ConvOpt& o = {}) {
+        const int plane = o.plane;
+        const bool to_out = o.to_out;
         ConvArgs a;
-        a.N = x.n; a.H = x.h; a.W = x.w; a.Cin = x.c; a.Cout = cout; a.ks = ks; a.stride = stride; a.ups = ups ? 1 : 0;
-        a.pad_lo = pad_lo; a.pad_total = pad_total;
+        a.N = x.n; a.H = x.h; a.W = x.w; a.Cin = x.c; a.Cout = cout; a.ks = ks; a.stride = o.stride; a.ups = o.ups ? 1 : 0;
+        a.pad_lo = o.pad_lo; a.pad_total = o.pad_total;
         {
             int oh_, ow_;
             conv_out_hw(a, &oh_, &ow_);
             a.lanes = plan_lanes((int64_t)x.n * oh_ * ow_);
         }
-        a.w = W(name + ".weight");
-        a.bias = bias ? W(name + ".bias") : nullptr;
-        const Param& pw = hd->PP(name + ".weight");
+        const std::string wname = name + ".weight";
+        a.w = W(wname);
+        a.bias = o.bias ? W(name + ".bias") : nullptr;
+        const Param& pw = hd->PP(wname);
         DSD_CHECK(pw.numel == (int64_t)cout * x.c * ks * ks, "conv %s: weight has %lld elements, graph expects %dx%dx%dx%d",
                   name.c_str(), (long long)pw.numel, cout, x.c, ks, ks);
         int OH, OW;
         conv_out_hw(a, &OH, &OW);
         Tn y;
-        if (dst) {
-            DSD_CHECK(!to_out && dst->n == x.n && dst->h == OH && dst->w == OW && dst->c >= cout && dst->c % 4 == 0,
+        if (o.dst) {
+            DSD_CHECK(!to_out && o.dst->n == x.n && o.dst->h == OH && o.dst->w == OW && o.dst->c >= cout && o.dst->c % 4 == 0,
                       "conv %s: destination view does not fit", name.c_str());
-            y = *dst;
+            y = *o.dst;
             y.c = cout;
             y.st[0] = y.st[1] = StatRef{};
         } else if (!to_out) {
             y = alloc(x.n, OH, OW, cout);
         }
-        const int y_ld = dst ? dst->c : 0;
-        if (res) DSD_CHECK(res->n == x.n && res->h == OH && res->w == OW && res->c == cout, "conv %s: residual shape mismatch", name.c_str());
+        const int y_ld = o.dst ? o.dst->c : 0;
+        if (o.res) DSD_CHECK(o.res->n == x.n && o.res->h == OH && o.res->w == OW && o.res->c == cout, "conv %s: residual shape mismatch", name.c_str());
         const int prec = conv_prec();
         a.precision = prec;
         // nearest-x2 upsample + 3x3 in bf16x6: four 2x2 phase convolutions on the low-resolution map (conv2d_subpixel_ok),
@@ -851,67 +883,33 @@ struct Builder {
         const bool subpixel = prec != PREC_F32 && plane < 0 && !hd->use_winograd && conv2d_subpixel_ok(a);
         a.precision = PREC_F32;
         if (subpixel) {
-            const std::string skey = name + "#sub";
-            auto it = hd->wsplit.find(skey);
-            if (it == hd->wsplit.end()) {
-                void* planes = nullptr;
-                const size_t sb = subpixel_weight_bytes(cout, x.c);
-                DSD_HIP(hipMalloc(&planes, sb));
-                subpixel_weights(a.w, cout, x.c, planes, ps);   // (on the caller's stream, as split_weights below)
-                split_any = true;
-                it = hd->wsplit.emplace(skey, planes).first;
-                hd->wsplit_bytes[skey] = sb;
-            }
-            a.w_subpixel = it->second;
+            a.w_subpixel = derived(name + "#sub", wname, WF_BF16_PIECES, subpixel_weight_bytes(cout, x.c),
+                                   [&](void* buf) { subpixel_weights(a.w, cout, x.c, buf, ps); });
             a.precision = prec;
         } else if (prec != PREC_F32 && x.c % 32 == 0 && plane < 0) {   // split-bf16 arithmetic: pieces of the (packed) weight
             const bool f16 = prec == PREC_F16X3;
-            const std::string key = f16 ? name + "#f16" : name;
-            auto it = hd->wsplit.find(key);
-            if (it == hd->wsplit.end()) {
-                void* planes = nullptr;
-                DSD_HIP(hipMalloc(&planes, (size_t)pw.numel * 2 * 3));
-                if (f16 && !hd->ovf) {
-                    DSD_HIP(hipMalloc((void**)&hd->ovf, sizeof(int)));
-                    DSD_HIP(hipMemset(hd->ovf, 0, sizeof(int)));
-                }
-                // on the caller's stream: ordered after the dsd_set_param copies / repacks enqueued there
-                split_weights(a.w, pw.numel, 3, planes, ps, f16, hd->ovf);
-                split_any = true;
-                it = hd->wsplit.emplace(key, planes).first;
-                hd->wsplit_bytes[key] = (size_t)pw.numel * 2 * 3;
-            }
-            a.w_split = it->second;
+            if (f16) hd->ensure_ovf();
+            a.w_split = derived(f16 ? name + "#f16" : name, wname, f16 ? WF_F16_PIECES : WF_BF16_PIECES, (size_t)pw.numel * 2 * 3,
+                                [&](void* buf) { split_weights(a.w, pw.numel, 3, buf, ps, f16, hd->ovf); });
             a.precision = prec;
             a.ovf = f16 ? hd->ovf : nullptr;
             // 3x3 stride-1 layers with enough tiles: F(2,3)-along-W kernel (conv_wino.hip), transformed weights packed once
-            if (hd->use_winograd && conv2d_wino_worthwhile(a)) {
-                const std::string wkey = name + "#wino";
-                auto wi = hd->wsplit.find(wkey);
-                if (wi == hd->wsplit.end()) {
-                    void* packed = nullptr;
-                    const size_t wb = wino_packed_bytes(cout, x.c);
-                    DSD_HIP(hipMalloc(&packed, wb));
-                    wino_pack_weights(a.w, cout, x.c, packed, ps);
-                    split_any = true;
-                    wi = hd->wsplit.emplace(wkey, packed).first;
-                    hd->wsplit_bytes[wkey] = wb;
-                }
-                a.w_wino = wi->second;
-            }
+            if (hd->use_winograd && conv2d_wino_worthwhile(a))
+                a.w_wino = derived(name + "#wino", wname, WF_BF16_PIECES, wino_packed_bytes(cout, x.c),
+                                   [&](void* buf) { wino_pack_weights(a.w, cout, x.c, buf, ps); });
         }
-        if (gn) {   // the kernel applies GroupNorm + SiLU to x itself (the caller asked can_fuse_gn first)
+        if (o.gn) {   // the kernel applies GroupNorm + SiLU to x itself (the caller asked can_fuse_gn first)
             a.gn_scale = a.gn_shift = reinterpret_cast<const float*>(this);   // non-null placeholders for the plan-time queries
-            DSD_CHECK(gn->act == ACT_SILU && conv2d_fuses_gn(a), "conv %s: cannot take the GroupNorm of its input", name.c_str());
+            DSD_CHECK(o.gn->act == ACT_SILU && conv2d_fuses_gn(a), "conv %s: cannot take the GroupNorm of its input", name.c_str());
         }
-        const size_t gsc = gn ? gn->scoff : 0, gsh = gn ? gn->shoff : 0;
-        const bool has_gn = gn != nullptr;
+        const size_t gsc = o.gn ? o.gn->scoff : 0, gsh = o.gn ? o.gn->shoff : 0;
+        const bool has_gn = o.gn != nullptr;
         const size_t skb = conv2d_scratch_bytes(a);            // split-K partial tiles of the small-grid layers
         const size_t skoff = skb ? alloc_raw(skb) : 0;
         // GroupNorm statistics of the output from the epilogue, when the kernel this problem gets can emit them
         size_t stoff = 0;
         int stchunks = 0;
-        if (want_stats && !to_out && hd->fuse_gn_stats) {
+        if (o.want_stats && !to_out && hd->fuse_gn_stats) {
             ConvArgs q = a;
             q.x_bs = -1;
             stchunks = conv2d_stats_chunks(q);
@@ -922,10 +920,10 @@ struct Builder {
                 y.st[0] = sr;
             }
         }
-        const size_t xoff = x.off, yoff = y.off, roff = res ? res->off : 0;
-        const bool has_res = res != nullptr;
+        const size_t xoff = x.off, yoff = y.off, roff = o.res ? o.res->off : 0;
+        const bool has_res = o.res != nullptr;
         EmbRef e;
-        if (emb) e = *emb;
+        if (o.emb) e = *o.emb;
         dsd_handle* h = hd;
         const bool nchw = to_out && cout > 1;
         plan.flops += conv2d_flops(a);
@@ -935,28 +933,28 @@ struct Builder {
                 c.x = h->io.plane[plane];
                 c.x_bs = h->io.plane_bs[plane];
             } else {
-                c.x = reinterpret_cast<const float*>(h->arena + xoff);
+                c.x = h->at<float>(xoff);
                 c.x_bs = -1;
             }
-            c.y = to_out ? h->io.out : reinterpret_cast<float*>(h->arena + yoff);
+            c.y = to_out ? h->io.out : h->at<float>(yoff);
             c.y_ld = y_ld;
             c.out_nchw = nchw ? 1 : 0;
             if (e.valid) {
-                c.emb = reinterpret_cast<const float*>(h->arena + e.arena_off) + e.col;
+                c.emb = h->at<float>(e.arena_off) + e.col;
                 c.emb_stride = e.stride;
             }
-            if (has_res) c.res = reinterpret_cast<const float*>(h->arena + roff);
+            if (has_res) c.res = h->at<float>(roff);
             if (skb) {
-                c.scratch = reinterpret_cast<float*>(h->arena + skoff);
+                c.scratch = h->at<float>(skoff);
                 c.scratch_bytes = skb;
             }
             if (stchunks > 0) {
-                c.stats = reinterpret_cast<double*>(h->arena + stoff);
+                c.stats = h->at<double>(stoff);
                 c.stats_chunks = stchunks;
             }
             if (has_gn) {
-                c.gn_scale = reinterpret_cast<const float*>(h->arena + gsc);
-                c.gn_shift = reinterpret_cast<const float*>(h->arena + gsh);
+                c.gn_scale = h->at<float>(gsc);
+                c.gn_shift = h->at<float>(gsh);
             }
             conv2d(c, s);
         }, skb ? 2 : 1, conv2d_variant(a), conv2d_exec_flops(a),
@@ -979,9 +977,9 @@ struct Builder {
             if (film) e = *film;
             dsd_handle* h = hd;
             op([=](hipStream_t s) {
-                const float* fp = e.valid ? reinterpret_cast<const float*>(h->arena + e.arena_off) + e.col : nullptr;
-                gn_small(reinterpret_cast<const float*>(h->arena + xoff), N, HW, C, gamma, beta, eps, fp, e.stride, act,
-                         reinterpret_cast<float*>(h->arena + yoff), s);
+                const float* fp = e.valid ? h->at<float>(e.arena_off) + e.col : nullptr;
+                gn_small(h->at<float>(xoff), N, HW, C, gamma, beta, eps, fp, e.stride, act,
+                         h->at<float>(yoff), s);
             }, 1, act == ACT_SILU ? "gn_silu_small" : "gn_small", 0.0, 12.0 * N * HW * C);
             return y;
         }
@@ -1013,21 +1011,21 @@ struct Builder {
         const double tbytes = 4.0 * N * HW * C;
         if (!have)
             op([=](hipStream_t s) {
-                gn_stats(reinterpret_cast<const float*>(h->arena + xoff), N, HW, C, reinterpret_cast<double*>(h->arena + poff), nchunk, s);
+                gn_stats(h->at<float>(xoff), N, HW, C, h->at<double>(poff), nchunk, s);
             }, 1, "gn_stats", 0.0, tbytes);
         op([=](hipStream_t s) {
-            const float* fp = e.valid ? reinterpret_cast<const float*>(h->arena + e.arena_off) + e.col : nullptr;
+            const float* fp = e.valid ? h->at<float>(e.arena_off) + e.col : nullptr;
             GnSrc s0, s1;
             if (have) {
-                s0.p = reinterpret_cast<const double*>(h->arena + r0.off); s0.chunks = r0.chunks; s0.c0 = 0; s0.c = r0.c;
+                s0.p = h->at<double>(r0.off); s0.chunks = r0.chunks; s0.c0 = 0; s0.c = r0.c;
                 if (r1.valid()) {
-                    s1.p = reinterpret_cast<const double*>(h->arena + r1.off); s1.chunks = r1.chunks; s1.c0 = r1.c0; s1.c = r1.c;
+                    s1.p = h->at<double>(r1.off); s1.chunks = r1.chunks; s1.c0 = r1.c0; s1.c = r1.c;
                 }
             } else {
-                s0.p = reinterpret_cast<const double*>(h->arena + poff); s0.chunks = nchunk; s0.c0 = 0; s0.c = C;
+                s0.p = h->at<double>(poff); s0.chunks = nchunk; s0.c0 = 0; s0.c = C;
             }
             gn_finalize(s0, s1, N, HW, C, gamma, beta, eps, fp, e.stride,
-                        reinterpret_cast<float*>(h->arena + scoff), reinterpret_cast<float*>(h->arena + shoff), s);
+                        h->at<float>(scoff), h->at<float>(shoff), s);
         }, 1, "gn_finalize");
         if (!have) release_raw(poff, pbytes);
         GnRef g;
@@ -1042,8 +1040,8 @@ struct Builder {
         const size_t xoff = x.off, yoff = y.off, scoff = g.scoff, shoff = g.shoff;
         dsd_handle* h = hd;
         op([=](hipStream_t s) {
-            affine_act(reinterpret_cast<const float*>(h->arena + xoff), N, HW, C, reinterpret_cast<float*>(h->arena + scoff),
-                       reinterpret_cast<float*>(h->arena + shoff), act, reinterpret_cast<float*>(h->arena + yoff), s);
+            affine_act(h->at<float>(xoff), N, HW, C, h->at<float>(scoff),
+                       h->at<float>(shoff), act, h->at<float>(yoff), s);
         }, 1, act == ACT_SILU ? "gn_silu_apply" : "gn_apply", 0.0, 8.0 * N * HW * C);
         return y;
     }
@@ -1056,7 +1054,7 @@ struct Builder {
     void out_conv1(const std::string& norm, const std::string& cv, const Tn& x, int cout) {
         if (!(hd->fuse_gn_apply && conv_out1_ok(x.c, cout, 3, 1) && !gn_small_ok(x.hw(), x.c))) {
             Tn a = gn_act(norm, x, ACT_SILU);
-            conv(cv, a, cout, 3, 1, false, nullptr, nullptr, -1, /*to_out=*/true);
+            conv(cv, a, cout, 3, {.to_out = true});
             release(a);
             return;
         }
@@ -1073,10 +1071,10 @@ struct Builder {
         plan.flops += fl;
         op([=](hipStream_t s) {
             ConvOut1Args a;
-            a.x = reinterpret_cast<const float*>(h->arena + xoff);
+            a.x = h->at<float>(xoff);
             a.N = N; a.H = H; a.W = Wd; a.C = C;
-            a.scale = reinterpret_cast<const float*>(h->arena + scoff);
-            a.shift = reinterpret_cast<const float*>(h->arena + shoff);
+            a.scale = h->at<float>(scoff);
+            a.shift = h->at<float>(shoff);
             a.w = w;
             a.bias = bias;
             a.y = h->io.out;
@@ -1103,10 +1101,32 @@ struct Builder {
         dsd_handle* h = hd;
         const Tn xx = x;
         op([=](hipStream_t s) {
-            const float* xp = reinterpret_cast<const float*>(h->arena + xoff);
-            float* yp = reinterpret_cast<float*>(h->arena + yoff);
+            const float* xp = h->at<float>(xoff);
+            float* yp = h->at<float>(yoff);
             if (up) upsample2(xp, xx.n, xx.h, xx.w, xx.c, yp, s); else avgpool2(xp, xx.n, xx.h, xx.w, xx.c, yp, s);
         });
+        return y;
+    }
+
+    // y = Conv3x3(SiLU(GroupNorm(x))) [FiLM by `film`].  Where the tap-reuse kernel takes the convolution (can_fuse_gn) it
+    // applies the GroupNorm + SiLU while it stages its input and no apply pass runs; else apply pass, then convolution.
+    Tn norm_conv3x3(const std::string& norm, const std::string& cv, const Tn& x, int cout, float eps, const EmbRef* film,
+                    ConvOpt o, const NormOpt& n = {}) {
+        Tn xr = x;
+        const bool small = n.small_first && hd->fuse_gn_stats && gn_small_ok(x.hw(), x.c);
+        if (!n.rework && !small && can_fuse_gn(x, cout)) {
+            GnRef g = gn_prepare(norm, x, ACT_SILU, eps, film);
+            o.gn = &g;
+            Tn y = conv(cv, x, cout, 3, o);
+            gn_release(g);
+            if (n.consume) release(xr);
+            return y;
+        }
+        Tn a = gn_act(norm, x, ACT_SILU, eps, film);
+        if (n.consume) release(xr);
+        if (n.rework) n.rework(a);
+        Tn y = conv(cv, a, cout, 3, o);
+        release(a);
         return y;
     }
 
@@ -1118,45 +1138,26 @@ struct Builder {
         // GroupNorm + SiLU in front of a 3x3 convolution: the large layers apply it while they stage their input (no apply pass)
         Tn xs = x;
         bool xs_owned = false;
-        Tn h;
-        const bool gn_small_in = hd->fuse_gn_stats && gn_small_ok(x.hw(), x.c);
-        if (!up && !down && !gn_small_in && can_fuse_gn(x, cout)) {
-            GnRef g = gn_prepare(pre(p, "in_layers.0"), x, ACT_SILU);
-            h = conv(pre(p, "in_layers.2"), x, cout, 3, 1, false, film ? nullptr : &emb, nullptr, -1, false, true, nullptr,
-                     /*want_stats=*/true, -1, -1, &g);
-            gn_release(g);
-        } else {
-            Tn a = gn_act(pre(p, "in_layers.0"), x, ACT_SILU);
-            if (up || down) {
+        NormOpt in;
+        in.small_first = true;
+        if (up || down)   // h = h_upd(in_rest(x)); x = x_upd(x)  (:266-270)
+            in.rework = [&](Tn& a) {
                 Tn a2 = resample(a, up);
                 release(a);
                 a = a2;
                 xs = resample(x, up);
                 xs_owned = true;
-            }
-            h = conv(pre(p, "in_layers.2"), a, cout, 3, 1, false, film ? nullptr : &emb, nullptr, -1, false, true, nullptr,
-                     /*want_stats=*/true);   // out_layers.0 normalises exactly this tensor
-            release(a);
-        }
+            };
+        Tn h = norm_conv3x3(pre(p, "in_layers.0"), pre(p, "in_layers.2"), x, cout, 1e-5f, nullptr,
+                            {.emb = film ? nullptr : &emb, .want_stats = true}, in);   // out_layers.0 normalises exactly this tensor
         Tn skip = xs;
         bool skip_owned = false;
         if (cin != cout) {
             skip = conv(pre(p, "skip_connection"), xs, cout, 1);
             skip_owned = true;
         }
-        Tn out;
-        const bool gn_small_out = hd->fuse_gn_stats && gn_small_ok(h.hw(), h.c);
-        if (!gn_small_out && can_fuse_gn(h, cout)) {
-            GnRef g = gn_prepare(pre(p, "out_layers.0"), h, ACT_SILU, 1e-5f, film ? &emb : nullptr);
-            out = conv(pre(p, "out_layers.3"), h, cout, 3, 1, false, nullptr, &skip, -1, false, true, dst, true, -1, -1, &g);
-            gn_release(g);
-            release(h);
-        } else {
-            Tn a3 = gn_act(pre(p, "out_layers.0"), h, ACT_SILU, 1e-5f, film ? &emb : nullptr);
-            release(h);
-            out = conv(pre(p, "out_layers.3"), a3, cout, 3, 1, false, nullptr, &skip, -1, false, true, dst, true);
-            release(a3);
-        }
+        Tn out = norm_conv3x3(pre(p, "out_layers.0"), pre(p, "out_layers.3"), h, cout, 1e-5f, film ? &emb : nullptr,
+                              {.res = &skip, .dst = dst, .want_stats = true}, {.small_first = true, .consume = true});
         if (skip_owned) release(skip);
         if (xs_owned) release(xs);
         return out;
@@ -1191,14 +1192,14 @@ struct Builder {
             plan.flops += 4.0 * x.n * heads * (double)T * T * d;
             op([=](hipStream_t s) {
                 AttnArgs r = aa;
-                const float* base = reinterpret_cast<const float*>(h->arena + qoff);
+                const float* base = h->at<float>(qoff);
                 r.q = base + qo; r.k = base + ko; r.v = base + vo;
-                r.out = reinterpret_cast<float*>(h->arena + aoff);
+                r.out = h->at<float>(aoff);
                 attention(r, s);
             }, 1, "attention", 4.0 * x.n * heads * (double)T * T * d);
         }
         release(qkv);
-        Tn out = conv(pre(p, "proj_out"), a, C, 1, 1, false, nullptr, &x, -1, false, true, dst, true);
+        Tn out = conv(pre(p, "proj_out"), a, C, 1, {.res = &x, .dst = dst, .want_stats = true});
         release(a);
         return out;
     }
@@ -1206,7 +1207,7 @@ struct Builder {
     // FeatureDisentangle.forward, model.py:165-168
     Tn disentangle(const std::string& p, const Tn& x, int half) {
         Tn a = gn_act(pre(p, "conv_1.0"), x, ACT_SILU);
-        Tn o = conv(pre(p, "conv_1.2"), a, x.c, 3, 1, false, nullptr, &x, -1, false, true, nullptr, true);
+        Tn o = conv(pre(p, "conv_1.2"), a, x.c, 3, {.res = &x, .want_stats = true});
         release(a);
         Tn a2 = gn_act(pre(p, "conv_2.0"), o, ACT_SILU);
         release(o);
@@ -1224,8 +1225,8 @@ struct Builder {
         const Tn xx = x;
         dsd_handle* h = hd;
         op([=](hipStream_t s) {
-            se_scale(reinterpret_cast<const float*>(h->arena + xoff), xx.n, xx.hw(), xx.c, w1, w2, Cr,
-                     reinterpret_cast<float*>(h->arena + yoff), s);
+            se_scale(h->at<float>(xoff), xx.n, xx.hw(), xx.c, w1, w2, Cr,
+                     h->at<float>(yoff), s);
         });
         return y;
     }
@@ -1255,16 +1256,16 @@ struct Builder {
             const size_t soff = sr.off;
             op([=](hipStream_t s) {
                 const float* p[4] = {nullptr, nullptr, nullptr, nullptr};
-                for (int i = 0; i < nsrc; ++i) p[i] = reinterpret_cast<const float*>(h->arena + o[i]);
-                avg_into_stats(p[0], p[1], p[2], p[3], div, N, HW, C, reinterpret_cast<float*>(h->arena + doff), dstC, coff, act,
-                               bmask, reinterpret_cast<double*>(h->arena + soff), nchunk, s);
+                for (int i = 0; i < nsrc; ++i) p[i] = h->at<float>(o[i]);
+                avg_into_stats(p[0], p[1], p[2], p[3], div, N, HW, C, h->at<float>(doff), dstC, coff, act,
+                               bmask, h->at<double>(soff), nchunk, s);
             }, 1, nsrc == 4 ? "skip_avg4_concat+stats" : "concat_copy+stats", 0.0, 4.0 * pixels * C * (nsrc + 1));
             return;
         }
         op([=](hipStream_t s) {
             const float* p[4] = {nullptr, nullptr, nullptr, nullptr};
-            for (int i = 0; i < nsrc; ++i) p[i] = reinterpret_cast<const float*>(h->arena + o[i]);
-            avg_into(p[0], p[1], p[2], p[3], div, pixels, C, reinterpret_cast<float*>(h->arena + doff), dstC, coff, act, s,
+            for (int i = 0; i < nsrc; ++i) p[i] = h->at<float>(o[i]);
+            avg_into(p[0], p[1], p[2], p[3], div, pixels, C, h->at<float>(doff), dstC, coff, act, s,
                      per_sample, bmask);
         }, 1, nsrc == 4 ? "skip_avg4_concat" : "concat_copy", 0.0, 4.0 * pixels * C * (nsrc + 1));
     }
@@ -1280,14 +1281,14 @@ struct Builder {
             Tn nxt;
             const Tn* d = li + 1 == layers.size() ? dst : nullptr;   // only the block's last layer writes into the view
             switch (L.kind) {
-                case L_CONV: nxt = conv(nm, cur, L.cout, 3, 1, false, nullptr, nullptr, plane, false, true, d, true); break;
+                case L_CONV: nxt = conv(nm, cur, L.cout, 3, {.plane = plane, .dst = d, .want_stats = true}); break;
                 case L_RES: nxt = res_block(nm, cur, L.cin, L.cout, L.up, L.down, embs.at(emb_i++), d); break;
                 case L_ATTN:
                     nxt = L.dh > 0 ? spatial_transformer(nm + ".", cur, L.heads, L.dh, 1, &st_ctx, d)
                                    : attn_block(nm, cur, L.heads, hd->cfg.use_new_attention_order != 0, d);
                     break;
-                case L_DOWN: nxt = conv(nm + ".op", cur, L.ch, 3, 2, false, nullptr, nullptr, -1, false, true, d, true); break;
-                case L_UP: nxt = conv(nm + ".conv", cur, L.ch, 3, 1, true, nullptr, nullptr, -1, false, true, d, true); break;
+                case L_DOWN: nxt = conv(nm + ".op", cur, L.ch, 3, {.stride = 2, .dst = d, .want_stats = true}); break;
+                case L_UP: nxt = conv(nm + ".conv", cur, L.ch, 3, {.ups = true, .dst = d, .want_stats = true}); break;
             }
             if (cur_owned && plane < 0) release(cur);
             plane = -1;
@@ -1299,7 +1300,7 @@ struct Builder {
 
     // ---------------------------------------------------------------- token blocks (cross-attention variant)
     Tn linear_tok(const std::string& name, const Tn& x, int cout, bool bias, const Tn* res = nullptr) {
-        return conv(name, x, cout, 1, 1, false, nullptr, res, -1, false, bias);
+        return conv(name, x, cout, 1, {.res = res, .bias = bias});
     }
     Tn lnorm(const std::string& name, const Tn& x) {
         Tn y = alloc(x.n, x.h, x.w, x.c);
@@ -1310,8 +1311,8 @@ struct Builder {
         const int C = x.c;
         dsd_handle* h = hd;
         op([=](hipStream_t s) {
-            layer_norm(reinterpret_cast<const float*>(h->arena + xoff), rows, C, g, b, 1e-5f,
-                       reinterpret_cast<float*>(h->arena + yoff), s);
+            layer_norm(h->at<float>(xoff), rows, C, g, b, 1e-5f,
+                       h->at<float>(yoff), s);
         });
         return y;
     }
@@ -1335,10 +1336,10 @@ struct Builder {
         plan.flops += 4.0 * x.n * heads * (double)aa.Tq * aa.Tk * d;
         op([=](hipStream_t s) {
             AttnArgs r = aa;
-            r.q = reinterpret_cast<const float*>(h->arena + qo);
-            r.k = reinterpret_cast<const float*>(h->arena + ko);
-            r.v = reinterpret_cast<const float*>(h->arena + vo);
-            r.out = reinterpret_cast<float*>(h->arena + ao);
+            r.q = h->at<float>(qo);
+            r.k = h->at<float>(ko);
+            r.v = h->at<float>(vo);
+            r.out = h->at<float>(ao);
             attention(r, s);
         });
         release(q); release(k); release(v);
@@ -1354,7 +1355,7 @@ struct Builder {
         const int64_t rows = (int64_t)x.n * x.hw();
         dsd_handle* h = hd;
         op([=](hipStream_t s) {
-            geglu(reinterpret_cast<const float*>(h->arena + ho), rows, inner2 / 2, reinterpret_cast<float*>(h->arena + go), s);
+            geglu(h->at<float>(ho), rows, inner2 / 2, h->at<float>(go), s);
         });
         release(hh);
         Tn y = linear_tok(pre(p, "net.2"), g, x.c, true, res);
@@ -1374,7 +1375,7 @@ struct Builder {
             release(t);
             t = t2;
         }
-        Tn y = conv(p + "proj_out", t, x.c, 1, 1, false, nullptr, &x, -1, false, true, dst, dst != nullptr);
+        Tn y = conv(p + "proj_out", t, x.c, 1, {.res = &x, .dst = dst, .want_stats = dst != nullptr});
         release(t);
         return y;
     }
@@ -1396,31 +1397,12 @@ struct Builder {
     Tn vae_res(const std::string& p, const Tn& x, int cout) {
         // (as in res_block: where the tap-reuse kernel takes the 3x3 convolution — 128- and 160-column tiles — it applies the
         // GroupNorm + swish of its input itself and the apply pass disappears)
-        Tn h;
-        if (can_fuse_gn(x, cout)) {
-            GnRef g = gn_prepare(p + ".norm1", x, ACT_SILU, 1e-6f);
-            h = conv(p + ".conv1", x, cout, 3, 1, false, nullptr, nullptr, -1, false, true, nullptr, true, -1, -1, &g);
-            gn_release(g);
-        } else {
-            Tn a = gn_act(p + ".norm1", x, ACT_SILU, 1e-6f);
-            h = conv(p + ".conv1", a, cout, 3, 1, false, nullptr, nullptr, -1, false, true, nullptr, true);
-            release(a);
-        }
+        Tn h = norm_conv3x3(p + ".norm1", p + ".conv1", x, cout, 1e-6f, nullptr, {.want_stats = true});
         Tn skip = x;
         const bool proj = x.c != cout;
         if (proj) skip = conv(p + ".nin_shortcut", x, cout, 1);
-        Tn out;
-        if (can_fuse_gn(h, cout)) {
-            GnRef g = gn_prepare(p + ".norm2", h, ACT_SILU, 1e-6f);
-            out = conv(p + ".conv2", h, cout, 3, 1, false, nullptr, &skip, -1, false, true, nullptr, true, -1, -1, &g);
-            gn_release(g);
-            release(h);
-        } else {
-            Tn a2 = gn_act(p + ".norm2", h, ACT_SILU, 1e-6f);
-            release(h);
-            out = conv(p + ".conv2", a2, cout, 3, 1, false, nullptr, &skip, -1, false, true, nullptr, true);
-            release(a2);
-        }
+        Tn out = norm_conv3x3(p + ".norm2", p + ".conv2", h, cout, 1e-6f, nullptr, {.res = &skip, .want_stats = true},
+                              {.consume = true});
         if (proj) release(skip);
         return out;
     }
@@ -1437,10 +1419,7 @@ struct Builder {
         const bool f16 = hd->precision == PREC_F16X3;
         const size_t sb = (size_t)T * T * sizeof(float), vb = (size_t)C * T * sizeof(float), pb = split ? (size_t)T * C * 6 : 0;
         const size_t soff = alloc_raw(sb), vtoff = alloc_raw(vb), poff = pb ? alloc_raw(pb) : 0;
-        if (split && f16 && !hd->ovf) {
-            DSD_HIP(hipMalloc((void**)&hd->ovf, sizeof(int)));
-            DSD_HIP(hipMemset(hd->ovf, 0, sizeof(int)));
-        }
+        if (split && f16) hd->ensure_ovf();
         const size_t qo = q.off, ko = k.off, vo = v.off, ao = a.off;
         const int prec = hd->precision;
         const float scale = 1.f / std::sqrt((float)C);   // int(c)**(-0.5), :196
@@ -1448,8 +1427,8 @@ struct Builder {
         const double fl = 4.0 * Bn * (double)T * T * C;
         plan.flops += fl;
         op([=](hipStream_t s) {
-            float* S = reinterpret_cast<float*>(h->arena + soff);
-            float* vt = reinterpret_cast<float*>(h->arena + vtoff);
+            float* S = h->at<float>(soff);
+            float* vt = h->at<float>(vtoff);
             void* planes = pb ? static_cast<void*>(h->arena + poff) : nullptr;
             auto gemm_nt = [&](const float* A, const float* Bm, float* Y, int M, int N, int K) {
                 ConvArgs c;
@@ -1463,10 +1442,10 @@ struct Builder {
                 conv2d(c, s);
             };
             for (int b = 0; b < Bn; ++b) {
-                const float* qb = reinterpret_cast<const float*>(h->arena + qo) + (size_t)b * T * C;
-                const float* kb = reinterpret_cast<const float*>(h->arena + ko) + (size_t)b * T * C;
-                const float* vb_ = reinterpret_cast<const float*>(h->arena + vo) + (size_t)b * T * C;
-                float* ab = reinterpret_cast<float*>(h->arena + ao) + (size_t)b * T * C;
+                const float* qb = h->at<float>(qo) + (size_t)b * T * C;
+                const float* kb = h->at<float>(ko) + (size_t)b * T * C;
+                const float* vb_ = h->at<float>(vo) + (size_t)b * T * C;
+                float* ab = h->at<float>(ao) + (size_t)b * T * C;
                 gemm_nt(qb, kb, S, T, T, C);            // w_[i][j] = sum_c q[i][c] k[j][c]                     :194-195
                 softmax_rows(S, T, T, scale, s);         // * C^-1/2, softmax over j                             :196-197
                 nhwc_to_nchw(vb_, 1, C, T, vt, s);       // v^T [C][T]
@@ -1477,7 +1456,7 @@ struct Builder {
         release_raw(vtoff, vb);
         if (pb) release_raw(poff, pb);
         release(q); release(k); release(v);
-        Tn out = conv(p + ".proj_out", a, C, 1, 1, false, nullptr, &x, -1, false, true, nullptr, true);
+        Tn out = conv(p + ".proj_out", a, C, 1, {.res = &x, .want_stats = true});
         release(a);
         return out;
     }
@@ -1489,7 +1468,7 @@ struct Builder {
         dsd_handle* hh = hd;
         op([=](hipStream_t s) {
             const float* src = which == 0 ? hh->io.x_nchw : (which == 1 ? hh->io.aux : hh->io.aux2);
-            float* dst = reinterpret_cast<float*>(hh->arena + off);
+            float* dst = hh->at<float>(off);
             if (from_nchw && c > 1 && h * w > 1)
                 nchw_to_nhwc(src, n, c, h * w, dst, s);
             else
@@ -1503,7 +1482,7 @@ struct Builder {
         dsd_handle* hh = hd;
         op([=](hipStream_t s) {
             float* dst = feat_idx >= 0 ? hh->io.feats[feat_idx] : hh->io.out;
-            const float* src = reinterpret_cast<const float*>(hh->arena + off);
+            const float* src = hh->at<float>(off);
             if (to_nchw && tt.c > 1 && tt.hw() > 1)
                 nhwc_to_nchw(src, tt.n, tt.c, tt.hw(), dst, s);
             else
@@ -1511,6 +1490,114 @@ struct Builder {
         });
     }
 };
+
+// --------------------------------------------------------------------------------- what the two U-Nets share
+// The timestep conditioning of a forward: emb_all holds the output of EVERY ResBlock's emb_layers.
+struct TimeEmb {
+    Tn all;                                          // [B, emb_total]
+    std::unordered_map<std::string, int64_t> col;    // ResBlock name -> its first column
+    // one EmbRef per ResBlock of a TimestepEmbedSequential, in layer order
+    std::vector<EmbRef> of(const std::string& prefix, const std::vector<Layer>& layers) const {
+        std::vector<EmbRef> out;
+        for (size_t li = 0; li < layers.size(); ++li)
+            if (layers[li].kind == L_RES) {
+                EmbRef e;
+                e.arena_off = all.off;
+                e.col = col.at(prefix + "." + std::to_string(li));
+                e.stride = all.c;
+                e.valid = true;
+                out.push_back(e);
+            }
+        return out;
+    }
+};
+
+// ---- timestep embedding MLP + all emb_layers (68 of them in the headline network) as ONE GEMM (model.py:645-646,
+// openaimodel.py:939-940; :222-228,273).  t_from_aux: the timesteps are the fp32 vector io.aux (block handles), else io.t
+TimeEmb time_embed(Builder& b, const Spec& sp, bool t_from_aux) {
+    dsd_handle* hd = b.hd;
+    const int B = b.B, mc = hd->cfg.model_channels, ted = sp.ted, etot = (int)hd->emb_total;
+    Tn temb = b.alloc(B, 1, 1, mc), e1 = b.alloc(B, 1, 1, ted), emb = b.alloc(B, 1, 1, ted);
+    TimeEmb te;
+    te.all = b.alloc(B, 1, 1, etot);
+    {
+        const size_t to = temb.off, e1o = e1.off, eo = emb.off, ao = te.all.off;
+        const float *w0 = b.W("time_embed.0.weight"), *b0 = b.W("time_embed.0.bias");
+        const float *w2 = b.W("time_embed.2.weight"), *b2 = b.W("time_embed.2.bias");
+        const float *wall = hd->slab_at(hd->emb_w_off), *ball = hd->slab_at(hd->emb_b_off);
+        const double fl = 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot);
+        b.plan.flops += fl;
+        b.op([=](hipStream_t s) {
+            float *tp = hd->at<float>(to), *e1p = hd->at<float>(e1o), *ep = hd->at<float>(eo), *ap = hd->at<float>(ao);
+            if (t_from_aux)
+                timestep_embedding(hd->io.aux, 1, B, mc, tp, s, hd->freqs);
+            else
+                timestep_embedding(hd->io.t, hd->io.t_is_float, B, mc, tp, s, hd->freqs);
+            linear(tp, B, mc, mc, w0, b0, ted, ACT_NONE, e1p, ted, s);
+            linear(e1p, B, ted, ted, w2, b2, ted, ACT_SILU, ep, ted, s);
+            linear(ep, B, ted, ted, wall, ball, etot, ACT_SILU, ap, etot, s);
+        }, 4, "time_embed_mlp", fl);
+    }
+    b.release(temb); b.release(e1); b.release(emb);
+    // column of each ResBlock inside emb_all = position of its bias in the contiguous bias region (declaration order)
+    int64_t col = 0;
+    for (const auto& p : hd->params)
+        if (p.region == 2) {
+            te.col[p.name.substr(0, p.name.size() - std::strlen(".emb_layers.1.bias"))] = col;
+            col += p.numel;
+        }
+    return te;
+}
+
+// channels and size of what a TimestepEmbedSequential makes of a [c, hh, ww] input
+void block_out(const std::vector<Layer>& layers, int c, int hh, int ww, int* oc, int* oh, int* ow) {
+    *oc = c; *oh = hh; *ow = ww;
+    for (const Layer& L : layers) {
+        if (L.kind == L_RES || L.kind == L_CONV) *oc = L.cout;
+        if (L.kind == L_UP || (L.kind == L_RES && L.up)) { *oh *= 2; *ow *= 2; }
+        if (L.kind == L_DOWN || (L.kind == L_RES && L.down)) { *oh /= 2; *ow /= 2; }
+    }
+}
+
+// ---- decoder: h = cat([h, skip]); h = module(h, emb), where skip is the mean of what the ns encoder streams pushed
+// (model.py:743-746: (hs+hs_a+hs_al+hs_l)/4; openaimodel.py:950-952: hs.pop() itself).  Consumes h and every hs entry.
+// The concat buffer of block bi+1 is allocated before block bi runs, and block bi's last convolution writes h straight
+// into its first channels (row stride = concat width): torch.cat([h, skip]) costs no copy of h.
+Tn decode(Builder& b, const Spec& sp, const TimeEmb& te, Tn h, std::vector<Tn>* hs, int ns) {
+    const int B = b.B;
+    Tn c2 = b.alloc(B, h.h, h.w, h.c + hs[0].back().c);
+    b.avg(&h, 1, 1.f, c2, 0, ACT_NONE, /*want_stats=*/true);
+    b.release(h);
+    for (size_t bi = 0; bi < sp.output_blocks.size(); ++bi) {
+        Tn sk[4];
+        for (int s = 0; s < ns; ++s) {
+            sk[s] = hs[s].back();
+            hs[s].pop_back();
+        }
+        DSD_CHECK(sk[0].h == c2.h && sk[0].w == c2.w, "decoder skip shape mismatch at output_blocks.%zu", bi);
+        const int hc = c2.c - sk[0].c;
+        b.avg(sk, ns, (float)ns, c2, hc, ACT_NONE, /*want_stats=*/true);   // only taken when the h part brought its statistics
+        for (int s = 0; s < ns; ++s) b.release(sk[s]);
+        const bool last = bi + 1 == sp.output_blocks.size();
+        Tn next;
+        if (!last) {
+            int oc, oh, ow;
+            block_out(sp.output_blocks[bi], c2.c, c2.h, c2.w, &oc, &oh, &ow);
+            next = b.alloc(B, oh, ow, oc + hs[0].back().c);
+        }
+        const std::string pre_ = "output_blocks." + std::to_string(bi);
+        size_t ei = 0;
+        Tn out = b.block(pre_, sp.output_blocks[bi], c2, /*keep_input=*/false, te.of(pre_, sp.output_blocks[bi]), ei, -1,
+                         last ? nullptr : &next);
+        if (last) {
+            h = out;
+        } else {
+            next.st[0] = out.st[0];   // the block's last convolution wrote h (and its statistics) into the next concat buffer
+            c2 = next;
+        }
+    }
+    return h;
+}
 
 // --------------------------------------------------------------------------------- DSUnetModel.forward
 void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool share) {
@@ -1522,55 +1609,7 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
     DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
     // share: the al / l streams see the same (all-zero) plane and the same timestep for every slice -> batch of ONE
     DSD_CHECK(!share || (zero_al_l && !want_feats), "zero-stream sharing needs the 2-channel branch and no feature outputs");
-
-    // ---- timestep embedding MLP + all 68 emb_layers as ONE GEMM (model.py:645-646; openaimodel.py:222-228,273)
-    const int mc = cfg.model_channels, ted = sp.ted;
-    Tn temb = b.alloc(B, 1, 1, mc), e1 = b.alloc(B, 1, 1, ted), emb = b.alloc(B, 1, 1, ted);
-    Tn emb_all = b.alloc(B, 1, 1, (int)hd->emb_total);
-    {
-        const size_t to = temb.off, e1o = e1.off, eo = emb.off, ao = emb_all.off;
-        const float *w0 = b.W("time_embed.0.weight"), *b0 = b.W("time_embed.0.bias");
-        const float *w2 = b.W("time_embed.2.weight"), *b2 = b.W("time_embed.2.bias");
-        const float* wall = reinterpret_cast<const float*>(hd->slab + hd->emb_w_off);
-        const float* ball = reinterpret_cast<const float*>(hd->slab + hd->emb_b_off);
-        const int etot = (int)hd->emb_total;
-        b.plan.flops += 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot);
-        b.op([=](hipStream_t s) {
-            float* tp = reinterpret_cast<float*>(hd->arena + to);
-            float* e1p = reinterpret_cast<float*>(hd->arena + e1o);
-            float* ep = reinterpret_cast<float*>(hd->arena + eo);
-            float* ap = reinterpret_cast<float*>(hd->arena + ao);
-            timestep_embedding(hd->io.t, hd->io.t_is_float, B, mc, tp, s, hd->freqs);
-            linear(tp, B, mc, mc, w0, b0, ted, ACT_NONE, e1p, ted, s);
-            linear(e1p, B, ted, ted, w2, b2, ted, ACT_SILU, ep, ted, s);
-            linear(ep, B, ted, ted, wall, ball, etot, ACT_SILU, ap, etot, s);
-        }, 4, "time_embed_mlp", 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot));
-    }
-    b.release(temb); b.release(e1); b.release(emb);
-    // column of each ResBlock inside emb_all = position of its bias in the contiguous bias region (declaration order)
-    std::unordered_map<std::string, int64_t> emb_col;
-    {
-        int64_t col = 0;
-        for (const auto& p : hd->params)
-            if (p.region == 2) {
-                emb_col[p.name.substr(0, p.name.size() - std::strlen(".emb_layers.1.bias"))] = col;
-                col += p.numel;
-            }
-    }
-    auto embs_for = [&](const std::string& prefix, const std::vector<std::vector<Layer>>& blocks) {
-        std::vector<std::vector<EmbRef>> out(blocks.size());
-        for (size_t bi = 0; bi < blocks.size(); ++bi)
-            for (size_t li = 0; li < blocks[bi].size(); ++li)
-                if (blocks[bi][li].kind == L_RES) {
-                    EmbRef e;
-                    e.arena_off = emb_all.off;
-                    e.col = emb_col.at(prefix + "." + std::to_string(bi) + "." + std::to_string(li));
-                    e.stride = (int)hd->emb_total;
-                    e.valid = true;
-                    out[bi].push_back(e);
-                }
-        return out;
-    };
+    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/false);
 
     // ---- four encoder streams (model.py:674-686): stream order n, a, al, l ; planes io.plane[0..3]
     const char* sfx[4] = {"", "_a", "_al", "_l"};
@@ -1589,11 +1628,10 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
         }
     }
     auto run_blocks = [&](int s, size_t from, size_t to) {
-        const std::string base = std::string("input_blocks") + sfx[s];
-        auto embs = embs_for(base, sp.input_blocks);
         for (size_t bi = from; bi < to; ++bi) {
+            const std::string pre_ = std::string("input_blocks") + sfx[s] + "." + std::to_string(bi);
             size_t ei = 0;
-            Tn nxt = b.block(base + "." + std::to_string(bi), sp.input_blocks[bi], cur4[s], /*keep_input=*/true, embs[bi], ei,
+            Tn nxt = b.block(pre_, sp.input_blocks[bi], cur4[s], /*keep_input=*/true, te.of(pre_, sp.input_blocks[bi]), ei,
                              bi == 0 ? s : -1);
             hs[s].push_back(nxt);
             cur4[s] = nxt;
@@ -1612,21 +1650,8 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
         b.end_parallel();
     }
     // ---- middle block on the noise stream only (model.py:688)
-    Tn h_n;
-    {
-        std::vector<EmbRef> me;
-        for (size_t li = 0; li < sp.middle.size(); ++li)
-            if (sp.middle[li].kind == L_RES) {
-                EmbRef e;
-                e.arena_off = emb_all.off;
-                e.col = emb_col.at("middle_block." + std::to_string(li));
-                e.stride = (int)hd->emb_total;
-                e.valid = true;
-                me.push_back(e);
-            }
-        size_t ei = 0;
-        h_n = b.block("middle_block", sp.middle, hs[0].back(), /*keep_input=*/true, me, ei);
-    }
+    size_t mei = 0;
+    Tn h_n = b.block("middle_block", sp.middle, hs[0].back(), /*keep_input=*/true, te.of("middle_block", sp.middle), mei);
     // ---- disentangle heads (model.py:695-725)
     const Tn &h_a = hs[1].back(), &h_al = hs[2].back(), &h_l = hs[3].back();
     const int half = sp.half;
@@ -1680,52 +1705,11 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
     b.release(h_n); b.release(h_share); b.release(h_style); b.release(h_anat); b.release(h_les);
     Tn h = b.conv("all_proj.1", cat, sp.conv_ch, 1);
     b.release(cat);
-    // ---- decoder (model.py:743-746): cat[h, (hs+hs_a+hs_al+hs_l)/4]
-    auto dembs = embs_for("output_blocks", sp.output_blocks);
-    // The concat buffer of block bi+1 is allocated before block bi runs, and block bi's last convolution writes h straight
-    // into its first channels (row stride = concat width): torch.cat([h, skip]) costs no copy of h.
-    auto block_out = [&](const std::vector<Layer>& layers, int c, int hh, int ww, int* oc, int* oh, int* ow) {
-        *oc = c; *oh = hh; *ow = ww;
-        for (const Layer& L : layers) {
-            if (L.kind == L_RES || L.kind == L_CONV) *oc = L.cout;
-            if (L.kind == L_UP || (L.kind == L_RES && L.up)) { *oh *= 2; *ow *= 2; }
-            if (L.kind == L_DOWN || (L.kind == L_RES && L.down)) { *oh /= 2; *ow /= 2; }
-        }
-    };
-    Tn c2 = b.alloc(B, h.h, h.w, h.c + hs[0].back().c);
-    b.avg(&h, 1, 1.f, c2, 0, ACT_NONE, /*want_stats=*/true);
-    b.release(h);
-    for (size_t bi = 0; bi < sp.output_blocks.size(); ++bi) {
-        Tn sk[4];
-        for (int s = 0; s < 4; ++s) {
-            sk[s] = hs[s].back();
-            hs[s].pop_back();
-        }
-        DSD_CHECK(sk[0].h == c2.h && sk[0].w == c2.w, "decoder skip shape mismatch at output_blocks.%zu", bi);
-        const int hc = c2.c - sk[0].c;
-        b.avg(sk, 4, 4.f, c2, hc, ACT_NONE, /*want_stats=*/true);   // only taken when the h part brought its statistics
-        for (auto& t : sk) b.release(t);
-        const bool last = bi + 1 == sp.output_blocks.size();
-        Tn next;
-        if (!last) {
-            int oc, oh, ow;
-            block_out(sp.output_blocks[bi], c2.c, c2.h, c2.w, &oc, &oh, &ow);
-            next = b.alloc(B, oh, ow, oc + hs[0].back().c);
-        }
-        size_t ei = 0;
-        Tn out = b.block("output_blocks." + std::to_string(bi), sp.output_blocks[bi], c2, /*keep_input=*/false, dembs[bi], ei,
-                         -1, last ? nullptr : &next);
-        if (last) {
-            h = out;
-        } else {
-            next.st[0] = out.st[0];   // the block's last convolution wrote h (and its statistics) into the next concat buffer
-            c2 = next;
-        }
-    }
+    h = decode(b, sp, te, h, hs, 4);
     // ---- out = Conv3x3(SiLU(GN(h)))  (model.py:511-515,751)
     b.out_conv1("out.0", "out.2", h, cfg.out_channels);
     b.release(h);
-    b.release(emb_all);
+    b.release(te.all);
 }
 
 // --------------------------------------------------------------------------------- UNetModel.forward (openaimodel.py:926-958)
@@ -1742,51 +1726,7 @@ void build_plain_unet(Builder& b, int C, int H, int W, int aux_len, int aux_len2
     DSD_CHECK(C == cfg.in_channels, "UNetModel: input has %d channels, expected %d", C, cfg.in_channels);
     DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
     DSD_CHECK(aux_len == 1, "UNetModel: timesteps missing");
-    // ---- timestep embedding MLP + all emb_layers as ONE GEMM (openaimodel.py:939-940; :222-228,273)
-    const int mc = cfg.model_channels, ted = sp.ted, etot = (int)hd->emb_total;
-    Tn temb = b.alloc(B, 1, 1, mc), e1 = b.alloc(B, 1, 1, ted), emb = b.alloc(B, 1, 1, ted), emb_all = b.alloc(B, 1, 1, etot);
-    {
-        const size_t to = temb.off, e1o = e1.off, eo = emb.off, ao = emb_all.off;
-        const float *w0 = b.W("time_embed.0.weight"), *b0 = b.W("time_embed.0.bias");
-        const float *w2 = b.W("time_embed.2.weight"), *b2 = b.W("time_embed.2.bias");
-        const float* wall = reinterpret_cast<const float*>(hd->slab + hd->emb_w_off);
-        const float* ball = reinterpret_cast<const float*>(hd->slab + hd->emb_b_off);
-        const double fl = 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot);
-        b.plan.flops += fl;
-        b.op([=](hipStream_t s) {
-            float* tp = reinterpret_cast<float*>(hd->arena + to);
-            float* e1p = reinterpret_cast<float*>(hd->arena + e1o);
-            float* ep = reinterpret_cast<float*>(hd->arena + eo);
-            float* ap = reinterpret_cast<float*>(hd->arena + ao);
-            timestep_embedding(hd->io.aux, 1, B, mc, tp, s, hd->freqs);
-            linear(tp, B, mc, mc, w0, b0, ted, ACT_NONE, e1p, ted, s);
-            linear(e1p, B, ted, ted, w2, b2, ted, ACT_SILU, ep, ted, s);
-            linear(ep, B, ted, ted, wall, ball, etot, ACT_SILU, ap, etot, s);
-        }, 4, "time_embed_mlp", fl);
-    }
-    b.release(temb); b.release(e1); b.release(emb);
-    std::unordered_map<std::string, int64_t> emb_col;
-    {
-        int64_t col = 0;
-        for (const auto& p : hd->params)
-            if (p.region == 2) {
-                emb_col[p.name.substr(0, p.name.size() - std::strlen(".emb_layers.1.bias"))] = col;
-                col += p.numel;
-            }
-    }
-    auto embs_of = [&](const std::string& prefix, const std::vector<Layer>& layers) {
-        std::vector<EmbRef> out;
-        for (size_t li = 0; li < layers.size(); ++li)
-            if (layers[li].kind == L_RES) {
-                EmbRef e;
-                e.arena_off = emb_all.off;
-                e.col = emb_col.at(prefix + "." + std::to_string(li));
-                e.stride = etot;
-                e.valid = true;
-                out.push_back(e);
-            }
-        return out;
-    };
+    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/true);
     // ---- encoder: h = module(h, emb, context); hs.append(h)   (:946-948)
     Tn x = b.import_ext(0, B, H, W, C, /*from_nchw=*/true);
     if (so.on) b.st_ctx = b.import_ext(2, B, aux_len2, 1, so.ctx_dim, false);
@@ -1794,58 +1734,16 @@ void build_plain_unet(Builder& b, int C, int H, int W, int aux_len, int aux_len2
     Tn cur = x;
     for (size_t bi = 0; bi < sp.input_blocks.size(); ++bi) {
         const std::string pre_ = "input_blocks." + std::to_string(bi);
-        auto embs = embs_of(pre_, sp.input_blocks[bi]);
         size_t ei = 0;
-        Tn nxt = b.block(pre_, sp.input_blocks[bi], cur, /*keep_input=*/true, embs, ei);
+        Tn nxt = b.block(pre_, sp.input_blocks[bi], cur, /*keep_input=*/true, te.of(pre_, sp.input_blocks[bi]), ei);
         hs.push_back(nxt);
         cur = nxt;
     }
     b.release(x);
-    // ---- middle (:949)
-    Tn h;
-    {
-        auto me = embs_of("middle_block", sp.middle);
-        size_t ei = 0;
-        h = b.block("middle_block", sp.middle, hs.back(), /*keep_input=*/true, me, ei);
-    }
-    // ---- decoder: h = cat([h, hs.pop()]); h = module(h, emb)   (:950-952); a block's last convolution writes h straight into
-    // the first channels of the next concat buffer
-    auto block_out = [&](const std::vector<Layer>& layers, int c, int hh, int ww, int* oc, int* oh, int* ow) {
-        *oc = c; *oh = hh; *ow = ww;
-        for (const Layer& L : layers) {
-            if (L.kind == L_RES || L.kind == L_CONV) *oc = L.cout;
-            if (L.kind == L_UP || (L.kind == L_RES && L.up)) { *oh *= 2; *ow *= 2; }
-            if (L.kind == L_DOWN || (L.kind == L_RES && L.down)) { *oh /= 2; *ow /= 2; }
-        }
-    };
-    Tn c2 = b.alloc(B, h.h, h.w, h.c + hs.back().c);
-    b.avg(&h, 1, 1.f, c2, 0, ACT_NONE, /*want_stats=*/true);
-    b.release(h);
-    for (size_t bi = 0; bi < sp.output_blocks.size(); ++bi) {
-        Tn sk = hs.back();
-        hs.pop_back();
-        DSD_CHECK(sk.h == c2.h && sk.w == c2.w, "decoder skip shape mismatch at output_blocks.%zu", bi);
-        const int hc = c2.c - sk.c;
-        b.avg(&sk, 1, 1.f, c2, hc, ACT_NONE, /*want_stats=*/true);
-        b.release(sk);
-        const bool last = bi + 1 == sp.output_blocks.size();
-        Tn next;
-        if (!last) {
-            int oc, oh, ow;
-            block_out(sp.output_blocks[bi], c2.c, c2.h, c2.w, &oc, &oh, &ow);
-            next = b.alloc(B, oh, ow, oc + hs.back().c);
-        }
-        const std::string pre_ = "output_blocks." + std::to_string(bi);
-        auto de = embs_of(pre_, sp.output_blocks[bi]);
-        size_t ei = 0;
-        Tn out = b.block(pre_, sp.output_blocks[bi], c2, /*keep_input=*/false, de, ei, -1, last ? nullptr : &next);
-        if (last) {
-            h = out;
-        } else {
-            next.st[0] = out.st[0];
-            c2 = next;
-        }
-    }
+    // ---- middle (:949), decoder (:950-952)
+    size_t mei = 0;
+    Tn h = b.block("middle_block", sp.middle, hs.back(), /*keep_input=*/true, te.of("middle_block", sp.middle), mei);
+    h = decode(b, sp, te, h, &hs, 1);
     // ---- out = Conv3x3(SiLU(GN(h)))   (:901-905,957)
     Tn a = b.gn_act("out.0", h, ACT_SILU);
     b.release(h);
@@ -1854,7 +1752,7 @@ void build_plain_unet(Builder& b, int C, int H, int W, int aux_len, int aux_len2
     b.export_out(y, /*to_nchw=*/true);
     b.release(y);
     if (so.on) b.release(b.st_ctx);
-    b.release(emb_all);
+    b.release(te.all);
 }
 
 // --------------------------------------------------------------------------------- DiT.forward (DiT_models.py:224-243)
@@ -1872,14 +1770,14 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
     Tn tok = b.alloc(B, T, 1, K);
     {
         const size_t to = tok.off;
-        b.op([=](hipStream_t s) { patchify(hd->io.x_nchw, B, C, H, W, p, reinterpret_cast<float*>(hd->arena + to), s); }, 1, "patchify");
+        b.op([=](hipStream_t s) { patchify(hd->io.x_nchw, B, C, H, W, p, hd->at<float>(to), s); }, 1, "patchify");
     }
     Tn x = b.conv("x_embedder.proj", tok, D, 1);
     b.release(tok);
     {
         const size_t xo = x.off;
         const float* pos = b.W("pos_embed");
-        b.op([=](hipStream_t s) { add_rows_broadcast(reinterpret_cast<float*>(hd->arena + xo), pos, B, (int64_t)T * D, s); }, 1, "pos_embed_add");
+        b.op([=](hipStream_t s) { add_rows_broadcast(hd->at<float>(xo), pos, B, (int64_t)T * D, s); }, 1, "pos_embed_add");
     }
     // ---- conditioning vector c = t_embedder(t) [+ y_embedder(y)] and ALL adaLN modulations as one GEMM (:233-238, :113-116)
     Tn tf = b.alloc(B, 1, 1, 256), e1 = b.alloc(B, 1, 1, D), cvec = b.alloc(B, 1, 1, D), mod = b.alloc(B, 1, 1, etot);
@@ -1888,16 +1786,15 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
         const float *w0 = b.W("t_embedder.mlp.0.weight"), *b0 = b.W("t_embedder.mlp.0.bias");
         const float *w2 = b.W("t_embedder.mlp.2.weight"), *b2 = b.W("t_embedder.mlp.2.bias");
         const float* table = c.classes > 0 ? b.W("y_embedder.embedding_table.weight") : nullptr;
-        const float* wall = reinterpret_cast<const float*>(hd->slab + hd->emb_w_off);
-        const float* ball = reinterpret_cast<const float*>(hd->slab + hd->emb_b_off);
+        const float *wall = hd->slab_at(hd->emb_w_off), *ball = hd->slab_at(hd->emb_b_off);
         const bool labels = aux_len2 > 0;
         const double fl = 2.0 * B * (256.0 * D + (double)D * D + (double)D * etot);
         b.plan.flops += fl;
         b.op([=](hipStream_t s) {
-            float* tfp = reinterpret_cast<float*>(hd->arena + tfo);
-            float* e1p = reinterpret_cast<float*>(hd->arena + e1o);
-            float* cp = reinterpret_cast<float*>(hd->arena + co);
-            float* mp = reinterpret_cast<float*>(hd->arena + mo);
+            float* tfp = hd->at<float>(tfo);
+            float* e1p = hd->at<float>(e1o);
+            float* cp = hd->at<float>(co);
+            float* mp = hd->at<float>(mo);
             timestep_embedding(hd->io.aux, 1, B, 256, tfp, s, hd->freqs);
             linear(tfp, B, 256, 256, w0, b0, D, ACT_NONE, e1p, D, s);
             linear(e1p, B, D, D, w2, b2, D, ACT_SILU, cp, D, s);
@@ -1927,22 +1824,22 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
         const size_t so = src.off, yo = y.off, mo = mod.off;
         if (out16) {
             b.op([=](hipStream_t s) {
-                ln_modulate16(reinterpret_cast<const float*>(hd->arena + so), B, T, D, reinterpret_cast<const float*>(hd->arena + mo) + mcol,
+                ln_modulate16(hd->at<float>(so), B, T, D, hd->at<float>(mo) + mcol,
                               etot, shift_off, scale_off, 1e-6f, hd->arena + yo, bf, s);
             }, 1, "ln_modulate16", 0.0, 6.0 * B * T * D);
             return y;
         }
         b.op([=](hipStream_t s) {
-            ln_modulate(reinterpret_cast<const float*>(hd->arena + so), B, T, D, reinterpret_cast<const float*>(hd->arena + mo) + mcol, etot,
-                        shift_off, scale_off, 1e-6f, reinterpret_cast<float*>(hd->arena + yo), s);
+            ln_modulate(hd->at<float>(so), B, T, D, hd->at<float>(mo) + mcol, etot,
+                        shift_off, scale_off, 1e-6f, hd->at<float>(yo), s);
         }, 1, "ln_modulate", 0.0, 8.0 * B * T * D);
         return y;
     };
     auto gated = [&](const Tn& xx, const Tn& yy, int mcol, int gate_off) {
         const size_t xo = xx.off, yo = yy.off, mo = mod.off;
         b.op([=](hipStream_t s) {
-            gated_residual(reinterpret_cast<float*>(hd->arena + xo), reinterpret_cast<const float*>(hd->arena + yo), B, T, D,
-                           reinterpret_cast<const float*>(hd->arena + mo) + mcol, etot, gate_off, s);
+            gated_residual(hd->at<float>(xo), hd->at<float>(yo), B, T, D,
+                           hd->at<float>(mo) + mcol, etot, gate_off, s);
         }, 1, "gated_residual", 0.0, 12.0 * B * T * D);
     };
     const int hdim = D / c.heads;
@@ -2000,9 +1897,9 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
             b.plan.flops += fl;
             b.op([=](hipStream_t s) {
                 AttnArgs r = aa;
-                const float* base = reinterpret_cast<const float*>(hd->arena + qo);
+                const float* base = hd->at<float>(qo);
                 r.q = base; r.k = base + D; r.v = base + 2 * D;
-                r.out = reinterpret_cast<float*>(hd->arena + ao);
+                r.out = hd->at<float>(ao);
                 attention(r, s);
             }, 1, "attention", fl);
         }
@@ -2017,7 +1914,7 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
         {
             const size_t ho = h1.off;
             const int64_t cnt = (int64_t)B * T * c.mlp;
-            b.op([=](hipStream_t s) { gelu_tanh(reinterpret_cast<float*>(hd->arena + ho), cnt, s); }, 1, "gelu_tanh", 0.0, 8.0 * cnt);
+            b.op([=](hipStream_t s) { gelu_tanh(hd->at<float>(ho), cnt, s); }, 1, "gelu_tanh", 0.0, 8.0 * cnt);
         }
         Tn y2 = b.conv(bp + ".mlp.fc2", h1, D, 1);
         b.release(h1);
@@ -2033,7 +1930,7 @@ void build_dit(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
     {
         const size_t oo = o.off;
         const int hw = c.input / p;
-        b.op([=](hipStream_t s) { unpatchify(reinterpret_cast<const float*>(hd->arena + oo), B, co, hw, hw, p, hd->io.out, s); }, 1, "unpatchify");
+        b.op([=](hipStream_t s) { unpatchify(hd->at<float>(oo), B, co, hw, hw, p, hd->io.out, s); }, 1, "unpatchify");
     }
     b.release(o);
     b.release(mod);
@@ -2065,8 +1962,8 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
             const size_t ei = e.off, oo = eout.off;
             const float *w = b.W("emb_layers.1.weight"), *bb = b.W("emb_layers.1.bias");
             b.op([=](hipStream_t s) {
-                linear(reinterpret_cast<const float*>(hd->arena + ei), B, aux_len, aux_len, w, bb, eo, ACT_SILU,
-                       reinterpret_cast<float*>(hd->arena + oo), eo, s);
+                linear(hd->at<float>(ei), B, aux_len, aux_len, w, bb, eo, ACT_SILU,
+                       hd->at<float>(oo), eo, s);
             });
             EmbRef er;
             er.arena_off = eout.off; er.col = 0; er.stride = eo; er.valid = true;
@@ -2075,8 +1972,8 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
             break;
         }
         case DSD_BLOCK_ATTN: y = b.attn_block("", x, a[1], a[2] != 0); break;
-        case DSD_BLOCK_UPSAMPLE: y = b.conv("conv", x, a[0], 3, 1, true); break;
-        case DSD_BLOCK_DOWNSAMPLE: y = b.conv("op", x, a[0], 3, 2); break;
+        case DSD_BLOCK_UPSAMPLE: y = b.conv("conv", x, a[0], 3, {.ups = true}); break;
+        case DSD_BLOCK_DOWNSAMPLE: y = b.conv("op", x, a[0], 3, {.stride = 2}); break;
         case DSD_BLOCK_DISENTANGLE: y = b.disentangle("", x, a[1]); break;
         case DSD_BLOCK_SE: y = b.se("", x); break;
         case DSD_BLOCK_CROSSATTN: {
@@ -2110,7 +2007,7 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
             DSD_CHECK(C == c.in_ch, "VAE encoder: input has %d channels, expected %d", C, c.in_ch);
             DSD_CHECK(H % (1 << (L - 1)) == 0 && W % (1 << (L - 1)) == 0, "VAE encoder: H=%d, W=%d must be multiples of %d", H, W, 1 << (L - 1));
             const std::string e = "encoder";
-            Tn hcur = b.conv(e + ".conv_in", x, c.ch, 3, 1, false, nullptr, nullptr, -1, false, true, nullptr, true);
+            Tn hcur = b.conv(e + ".conv_in", x, c.ch, 3, {.want_stats = true});
             int res = c.resolution;
             for (int l = 0; l < L; ++l) {
                 for (int j = 0; j < c.nrb; ++j) {
@@ -2124,8 +2021,8 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
                     }
                 }
                 if (l != L - 1) {   // Downsample :78-83: zero row/column AFTER the last one, stride 2, no padding before
-                    Tn t = b.conv(e + ".down." + std::to_string(l) + ".downsample.conv", hcur, hcur.c, 3, 2, false, nullptr, nullptr,
-                                  -1, false, true, nullptr, true, /*pad_lo=*/0, /*pad_total=*/1);
+                    Tn t = b.conv(e + ".down." + std::to_string(l) + ".downsample.conv", hcur, hcur.c, 3,
+                                  {.stride = 2, .want_stats = true, .pad_lo = 0, .pad_total = 1});
                     b.release(hcur);
                     hcur = t;
                     res /= 2;
@@ -2159,7 +2056,7 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
                 zin = b.conv("post_quant_conv", x, c.z, 1);
                 zin_owned = true;
             }
-            Tn hcur = b.conv(d + ".conv_in", zin, c.ch * c.mult[L - 1], 3, 1, false, nullptr, nullptr, -1, false, true, nullptr, true);
+            Tn hcur = b.conv(d + ".conv_in", zin, c.ch * c.mult[L - 1], 3, {.want_stats = true});
             if (zin_owned) b.release(zin);
             Tn t = b.vae_res(d + ".mid.block_1", hcur, hcur.c);
             b.release(hcur);
@@ -2180,8 +2077,7 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
                     }
                 }
                 if (l != 0) {
-                    Tn r = b.conv(d + ".up." + std::to_string(l) + ".upsample.conv", hcur, hcur.c, 3, 1, true, nullptr, nullptr, -1,
-                                  false, true, nullptr, true);
+                    Tn r = b.conv(d + ".up." + std::to_string(l) + ".upsample.conv", hcur, hcur.c, 3, {.ups = true, .want_stats = true});
                     b.release(hcur);
                     hcur = r;
                     res *= 2;

@@ -103,6 +103,21 @@ struct GraphKey {
     }
 };
 
+// Device-resident forms made from a parameter at plan time.  The family says which arithmetic modes read an entry
+// (net_drop_other_pieces keeps or frees by it); the source says which upload makes it stale (net_set_param).
+enum WeightFamily {
+    WF_BF16_PIECES,   // three bf16 pieces: bf16x3 / bf16x6, the fp32-grade layers of the half modes, sub-pixel and Winograd forms
+    WF_F16_PIECES,    // three fp16 pieces (f16x3)
+    WF_F16_COPY,      // one fp16 copy of a Linear weight (f16)
+    WF_BF16_COPY,     // one bf16 copy of a Linear weight (bf16)
+};
+struct DerivedWeight {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    std::string source;   // name of the parameter it was made from
+    WeightFamily family = WF_BF16_PIECES;
+};
+
 struct dsd_net;
 using Net = dsd_net;
 
@@ -174,9 +189,11 @@ struct dsd_handle {
     // dsd_sample only: evaluate the two all-zero-input streams of the C_in = 2 branch ONCE per step instead of once per
     // slice (same input, same timestep for every slice of the batch -> same result).  Off by default.
     int share_zero_streams = 0;
-    std::unordered_map<std::string, void*> wsplit;   // parameter name (+"#f16") -> [3][numel] bf16 / fp16 planes
-    std::unordered_map<std::string, size_t> wsplit_bytes;
-    int* ovf = nullptr;                              // device flag: fp16 range exceeded in f16x3 mode
+    // every derived form of a weight, made lazily at plan time (Builder::derived), keyed by layer name + form:
+    // "<conv>" [3][numel] bf16 pieces, "<conv>#f16" the fp16 ones, "<conv>#sub" sub-pixel phase weights, "<conv>#wino" packed
+    // Winograd weights, "<linear>.weight#h16" / "#b16" the 16-bit copy of the half-precision modes
+    std::unordered_map<std::string, dsd::DerivedWeight> derived;
+    int* ovf = nullptr;                              // device flag: fp16 range exceeded in f16x3 mode (ensure_ovf)
     // per-kernel profiling (dsd_profile_*): hipEvents around every op of the plan on the caller's stream
     bool profiling = false;
     std::vector<hipEvent_t> ev;
@@ -188,6 +205,10 @@ struct dsd_handle {
     size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0;
 
     float* P(const std::string& name) const;
+    float* slab_at(size_t off) const { return reinterpret_cast<float*>(slab + off); }
+    // typed view of the workspace arena at a planned offset (read when a closure runs: the arena may have been regrown since)
+    template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(arena + off); }
+    int* ensure_ovf();
     const dsd::Param& PP(const std::string& name) const;
 };
 
@@ -207,7 +228,7 @@ void net_run_cached(dsd_handle* h, hipStream_t s);
 void net_drop_graph(dsd_handle* h);
 // DSD_BLOCK_UNET handles: built with use_spatial_transformer (a SpatialTransformer on `context` in every attention slot)
 bool net_unet_has_spatial_transformer(const dsd_handle* h);
-// frees the weight pieces of the arithmetic family (bf16 / fp16) that `precision` does not use
+// frees the derived weights whose family (WeightFamily) `precision` does not read
 void net_drop_other_pieces(dsd_handle* h, int precision);
 size_t net_piece_bytes(const dsd_handle* h);
 // f16x3 only: synchronises the stream and throws if an operand left the fp16 range during the work enqueued so far
