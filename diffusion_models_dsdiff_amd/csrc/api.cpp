@@ -1267,6 +1267,78 @@ int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float
     DSD_CATCH
 }
 
+int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
+                     int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex, float* y,
+                     void* stream) {
+    DSD_TRY
+    hipStream_t s = (hipStream_t)stream;
+    // every argument is checked before the first launch (the rules of the planner's destination views, net.cpp conv())
+    DSD_CHECK(x && w_oihw && y && ex, "conv2d_ex: null argument");
+    DSD_CHECK(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && (ks == 1 || ks == 3) && (stride == 1 || stride == 2),
+              "conv2d_ex: bad problem size");
+    const int64_t plane = (int64_t)H * W * Cin;
+    DSD_CHECK(ex->x_batch_stride == -1 || ex->x_batch_stride == 0 || ex->x_batch_stride >= plane,
+              "conv2d_ex: x_batch_stride %lld is neither -1, 0 nor at least one plane (%lld)", (long long)ex->x_batch_stride, (long long)plane);
+    DSD_CHECK((ex->pad_lo < 0) == (ex->pad_total < 0) && ex->pad_lo < ks && ex->pad_total < 2 * ks && ex->pad_lo <= std::max(ex->pad_total, 0),
+              "conv2d_ex: pad_lo %d / pad_total %d", ex->pad_lo, ex->pad_total);
+    const int y_ld = ex->y_ld > 0 ? ex->y_ld : Cout, emb_stride = ex->emb_stride > 0 ? ex->emb_stride : Cout;
+    DSD_CHECK(ex->y_ld >= 0 && y_ld >= Cout, "conv2d_ex: y_ld %d is smaller than Cout %d", ex->y_ld, Cout);
+    DSD_CHECK(y_ld == Cout || y_ld % 4 == 0, "conv2d_ex: y_ld %d of a channel slice is not a multiple of 4", y_ld);
+    DSD_CHECK(reinterpret_cast<uintptr_t>(y) % 16 == 0, "conv2d_ex: y is not 16-byte aligned");
+    DSD_CHECK(!ex->out_nchw || y_ld == Cout, "conv2d_ex: an NCHW output has no row stride");
+    DSD_CHECK(ex->emb_stride >= 0 && emb_stride >= Cout, "conv2d_ex: emb_stride %d is smaller than Cout %d", ex->emb_stride, Cout);
+    DSD_CHECK(emb_stride == Cout || emb_stride % 4 == 0, "conv2d_ex: emb_stride %d of a column range is not a multiple of 4", emb_stride);
+    DSD_CHECK(reinterpret_cast<uintptr_t>(emb) % 16 == 0, "conv2d_ex: emb is not 16-byte aligned");
+    const size_t nw = (size_t)Cout * Cin * ks * ks;
+    Tmp wp(nw * sizeof(float)), planes(nw * 2 * 3);
+    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
+    ConvArgs a;
+    a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = wp.as<float>(); a.bias = bias; a.Cout = Cout; a.ks = ks;
+    a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = emb_stride; a.res = res; a.y = y;
+    a.x_bs = ex->x_batch_stride; a.pad_lo = ex->pad_lo; a.pad_total = ex->pad_total; a.y_ld = ex->y_ld;
+    Tmp ovf(sizeof(int));
+    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
+    if ((precision & 3) != PREC_F32) {
+        const bool f16 = (precision & 3) == PREC_F16X3;
+        split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
+        a.w_split = planes.p;
+        a.precision = precision & 3;
+        a.ovf = f16 ? ovf.as<int>() : nullptr;
+        if (precision & 16) a.variant = 30;
+        if (precision & 32) a.variant = 31;
+        if (precision & 64) a.variant = 32;
+    }
+    Tmp wpk((precision & 128) ? wino_packed_bytes(Cout, Cin) + 256 : 256);
+    if (precision & 128) {   // packed as the planner does, before the output layout is known: an NCHW launch then diverts
+        DSD_CHECK(conv2d_wino_shape_ok(a), "conv2d: this problem cannot run on the F(2,3) kernel (3x3, stride 1, even width, "
+                                           "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
+        wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
+        a.w_wino = wpk.p;
+    }
+    a.out_nchw = ex->out_nchw ? 1 : 0;
+    const bool sub = conv2d_subpixel_ok(a);
+    Tmp wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0);
+    if (sub) {
+        subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
+        a.w_subpixel = wsub.p;
+    }
+    const size_t sbytes = ex->no_scratch ? 0 : conv2d_scratch_bytes(a);
+    Tmp scratch(sbytes);
+    a.scratch = ex->no_scratch ? nullptr : scratch.as<float>();
+    a.scratch_bytes = sbytes;
+    // what runs: the name of these very arguments, and the split-K factor conv2d() takes with / without scratch
+    snprintf(ex->kernel, sizeof(ex->kernel), "%s", conv2d_variant(a));
+    int st = -1, nt = 0, ksp = 1;
+    if (Cin % 4 == 0 && ks * ks * Cin >= 32 && !a.w_subpixel && !conv2d_wino_eligible(a)) conv2d_plan_query(a, &st, &nt, &ksp, a.scratch != nullptr);
+    ex->ksplit = ksp;
+    conv2d(a, s);
+    int flag = 0;
+    DSD_HIP(hipMemcpyAsync(&flag, ovf.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    DSD_HIP(hipStreamSynchronize(s));
+    DSD_CHECK(!flag, "f16x3: a convolution operand exceeded the fp16 range (|x| > 65504); the result is invalid - use bf16x6 or f32");
+    DSD_CATCH
+}
+
 int dsd_op_group_norm(const float* x, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
                       float* y, void* stream) {
     DSD_TRY
@@ -1319,6 +1391,26 @@ int dsd_op_qkv_attention(const float* qkv, int N, int T, int C, int heads, int n
         a.q_hs = a.k_hs = a.v_hs = 3 * d;
     }
     a.out = out;
+    a.split = split != 0;
+    attention(a, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_attention(const float* q, const float* k, const float* v, int N, int Tq, int Tk, int heads, int d, int ldq, int ldk,
+                     int ldv, int ldo, int q_hs, int k_hs, int v_hs, float scale_q, float scale_k, float scale_s, int split,
+                     float* out, void* stream) {
+    DSD_TRY
+    DSD_CHECK(q && k && v && out, "attention: null argument");
+    DSD_CHECK(N >= 1 && heads >= 1 && d >= 1 && q_hs >= 0 && k_hs >= 0 && v_hs >= 0, "attention: bad problem size");
+    DSD_CHECK(ldq >= d && ldk >= d && ldv >= d && ldo >= heads * d && ldo % 4 == 0, "attention: row strides do not hold the heads");
+    DSD_CHECK(reinterpret_cast<uintptr_t>(q) % 16 == 0 && reinterpret_cast<uintptr_t>(k) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(v) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0, "attention: pointers must be 16-byte aligned");
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.out = out;
+    a.N = N; a.Tq = Tq; a.Tk = Tk; a.heads = heads; a.d = d;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.q_hs = q_hs; a.k_hs = k_hs; a.v_hs = v_hs;
+    a.scale_q = scale_q; a.scale_k = scale_k; a.scale_s = scale_s;
     a.split = split != 0;
     attention(a, (hipStream_t)stream);
     DSD_CATCH

@@ -724,13 +724,13 @@ bool conv2d_fuses_gn(const ConvArgs& a) {
     return conv2d_split_tr(a, nt, ks, ad);
 }
 
-void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt_out, int* ks_out) {
+void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt_out, int* ks_out, bool allow_split) {
     int OH, OW;
     conv_out_hw(a, &OH, &OW);
     const int tm = cdiv((int64_t)a.N * OH * OW, BM);
     const int pr = effective_precision(a, tm);
     int nt = pick_nt(a.Cout, tm, pr, a.lanes), ks = 1, ad = -1;
-    if (pr != PREC_F32) conv2d_split_plan(a, nt, &nt, &ks, &ad);
+    if (pr != PREC_F32) conv2d_split_plan(a, nt, &nt, &ks, &ad, allow_split);
     *structure = ad;
     *nt_out = nt;
     *ks_out = ks;

@@ -103,7 +103,7 @@ size_t conv2d_scratch_bytes(const ConvArgs& a);   // workspace conv2d() can use 
 // width the generic cost model (conv.hip pick_nt) would take
 void conv2d_split_plan(const ConvArgs& a, int nt_default, int* nt, int* ksplit, int* structure = nullptr, bool allow_split = true);
 const char* conv2d_variant(const ConvArgs& a);
-void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt, int* ksplit);   // what conv2d() would launch   // name of the kernel conv2d() will launch for these arguments
+void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt, int* ksplit, bool allow_split = true);   // what conv2d() would launch (allow_split: scratch present)   // name of the kernel conv2d() will launch for these arguments
 void pack_ohwi(const float* w_oihw, float* w_ohwi, int Cout, int Cin, int ks, hipStream_t s);
 // conv_wino.hip: 3x3 stride-1 convolution as F(2,3) along the width (1.5x fewer MFMAs), bf16x6 arithmetic
 bool conv2d_wino_shape_ok(const ConvArgs& a);      // could run there if it had packed weights

@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, dptr, stream_ptr
+from ._lib import lib, check, dptr, stream_ptr, DsdConvEx
 
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -38,6 +38,41 @@ def conv2d(x_nhwc, w_oihw, bias, stride=1, upsample=False, emb=None, res=None, p
     return y
 
 
+def conv_out_hw(H, W, ks, stride=1, upsample=False, pad_total=-1):
+    IH, IW = (H * 2, W * 2) if upsample else (H, W)
+    pt = pad_total if pad_total >= 0 else 2 * (ks // 2)
+    return (IH + pt - ks) // stride + 1, (IW + pt - ks) // stride + 1
+
+
+def conv2d_ex(x, shape, w_oihw, bias, y, stride=1, upsample=False, emb=None, res=None, precision="f32", structure="auto",
+              x_batch_stride=-1, pad_lo=-1, pad_total=-1, y_ld=0, out_nchw=False, emb_stride=0, no_scratch=False):
+    """The convolution with the launch arguments only the networks set (dsd_op_conv2d_ex).  x: any contiguous fp32 CUDA tensor
+    holding the planes (`shape` = (N, H, W, Cin) says how it is read, x_batch_stride how far the samples lie apart); y: the
+    caller's output buffer, written in place — a channel slice of a wider NHWC tensor is passed as the (non-contiguous) view
+    buf[..., c0:c0 + Cout] with y_ld = buf.shape[-1], emb likewise as a column view with emb_stride.  Returns (kernel name,
+    split-K factor) of the launch."""
+    N, H, W, Cin = shape
+    Cout, _, ks, _ = w_oihw.shape
+    ex = DsdConvEx(x_batch_stride=int(x_batch_stride), pad_lo=pad_lo, pad_total=pad_total, y_ld=int(y_ld), out_nchw=int(out_nchw),
+                   emb_stride=int(emb_stride), no_scratch=int(no_scratch), ksplit=0)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # views: the pointer of the first element
+    assert x.is_cuda and x.is_contiguous() and y.is_cuda and (res is None or res.is_contiguous())
+    check(lib().dsd_op_conv2d_ex(ptr(x), N, H, W, Cin, dptr(w_oihw.contiguous()), dptr(bias), Cout, ks, stride, int(upsample),
+                                 ptr(emb), dptr(res), PRECISIONS[precision] | STRUCTURES[structure], C.byref(ex), ptr(y),
+                                 stream_ptr()))
+    return ex.kernel.decode(), ex.ksplit
+
+
+def conv_mfma16(on=None):
+    """MFMA shape of the tap-reuse convolution kernel (dsd_set_conv_mfma16: 0 = 32x32x16, 1 = 16x16x32), process-wide.  Sets it
+    and returns the previous setting; on=None only reads it."""
+    L = lib()
+    prev = L.dsd_set_conv_mfma16(int(bool(on)))
+    if on is None:
+        L.dsd_set_conv_mfma16(prev)
+    return prev
+
+
 def group_norm(x_nhwc, gamma, beta, eps=1e-5, silu=False):
     N, H, W, Cc = x_nhwc.shape
     y = torch.empty_like(x_nhwc)
@@ -61,6 +96,16 @@ def qkv_attention(qkv_ntc, heads, new_order=True, split=False):
     a = torch.empty((N, T, C3 // 3), device=qkv_ntc.device, dtype=torch.float32)
     check(lib().dsd_op_qkv_attention(dptr(qkv_ntc), N, T, C3 // 3, heads, int(new_order), int(split), dptr(a), stream_ptr()))
     return a
+
+
+def attention(q, k, v, out, N, Tq, Tk, heads, d, ldq, ldk, ldv, ldo, q_hs, k_hs, v_hs, scale_q=1.0, scale_k=1.0, scale_s=1.0,
+              split=False):
+    """softmax((q scale_q)(k scale_k)^T scale_s) v per head with every launch argument of the kernel (dsd_op_attention).
+    q / k / v / out: fp32 CUDA tensors or views; only their first element's address and the strides given here are used."""
+    check(lib().dsd_op_attention(C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), N, Tq, Tk, heads, d,
+                                 ldq, ldk, ldv, ldo, q_hs, k_hs, v_hs, float(scale_q), float(scale_k), float(scale_s), int(split),
+                                 C.c_void_p(out.data_ptr()), stream_ptr()))
+    return out
 
 
 def gemm_half(x, w, bias=None, dtype="f16", epi="store", gate=None, T=1, y=None):

@@ -501,6 +501,33 @@ int dsd_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w_o
 int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
                        int ks, int stride, int upsample, const float* emb, const float* res, int precision, float* y,
                        void* stream);
+/* The launch arguments the networks set and dsd_op_conv2d_prec cannot express (ConvArgs, csrc/kernels.h); everything else as
+ * in dsd_op_conv2d_prec, including the precision | structure bits, the F(2,3) / sub-pixel weight preparation and the f16x3
+ * overflow flag.  Inputs:
+ *   x_batch_stride  elements between the samples of x: -1 = H*W*Cin, 0 = ONE plane shared by the batch, else >= H*W*Cin
+ *   pad_lo, pad_total  zero rows / columns before the first one and in total per axis (-1, -1 = ks/2 on every side;
+ *                   0, 1 = the VAE's Downsample)
+ *   y_ld            row stride of y in elements (0 = Cout): y is a channel slice of a wider NHWC tensor; y itself points
+ *                   at the slice's first channel (16-byte aligned; y_ld % 4 == 0 unless y_ld == Cout)
+ *   out_nchw        y is [N,Cout,OH,OW] (needs y_ld == Cout)
+ *   emb_stride      row stride of emb in elements (0 = Cout): emb[n*emb_stride + co], emb pointing at the layer's first column
+ *   no_scratch      launch without split-K workspace (what a caller outside the planned graph does)
+ * Outputs: kernel = conv2d_variant() of the arguments that were launched, ksplit = the split-K factor that ran (1 without
+ * scratch, whatever the name says).  y is caller-allocated; arguments are validated before anything is launched. */
+typedef struct dsd_conv_ex {
+    int64_t x_batch_stride;
+    int32_t pad_lo, pad_total;
+    int32_t y_ld;
+    int32_t out_nchw;
+    int32_t emb_stride;
+    int32_t no_scratch;
+    int32_t ksplit;
+    int32_t reserved;
+    char kernel[64];
+} dsd_conv_ex;
+int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
+                     int ks, int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex,
+                     float* y, void* stream);
 /* Micro-benchmark of the convolution kernel on random data (library-owned buffers): average ms per launch over
  * `iters` back-to-back launches (hipEvents) and the algorithmic FLOPs of one launch.  variant: -1/0 default fp32
  * kernel, 1 flat-load fp32 kernel, 10 bf16x3, 11 bf16x6, 12 f16x3 (library's choice of structure), 20/21 both operands staged
@@ -554,6 +581,13 @@ int dsd_op_gn_silu_conv_out1(const float* x, int N, int H, int W, int C, const f
  * the fp32 matrix cores (what DSD_PREC_F32 runs); 1: operands split exactly into three bf16 pieces, six bf16 MFMA products
  * each (what every other mode runs); the softmax is fp32 either way. */
 int dsd_op_qkv_attention(const float* qkv, int N, int T, int C, int heads, int new_order, int split, float* a, void* stream);
+/* The fp32-grade attention kernels with every launch argument of AttnArgs (csrc/kernels.h): out[n,t,h*d + :] =
+ * softmax((q scale_q)(k scale_k)^T scale_s) v per head.  q rows [N*Tq] of ldq floats with head h at +h*q_hs (k, v alike over
+ * N*Tk rows), out rows of ldo floats with head h at +h*d.  Strides and pointers must keep rows 16-byte aligned.  split as in
+ * dsd_op_qkv_attention. */
+int dsd_op_attention(const float* q, const float* k, const float* v, int N, int Tq, int Tk, int heads, int d, int ldq, int ldk,
+                     int ldv, int ldo, int q_hs, int k_hs, int v_hs, float scale_q, float scale_k, float scale_s, int split,
+                     float* out, void* stream);
 /* The half-precision kernels of DSD_PREC_F16 / DSD_PREC_BF16 on fp32 device buffers (the entry rounds the inputs to 16 bits
  * once, runs the kernel, and widens the 16-bit result): y[M,N] = x[M,K] w[N,K]^T + bias (nn.Linear; timm Mlp / Attention
  * projections, DiT_models.py:101-122).  epi 0: y = round16(acc + bias); 1: y = round16(gelu_tanh(round16(acc + bias)));
