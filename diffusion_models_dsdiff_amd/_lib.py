@@ -27,7 +27,7 @@ PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 
 EXPORTS = [
     "dsd_last_error", "dsd_device_info", "dsd_create", "dsd_destroy", "dsd_param_count", "dsd_param_info",
     "dsd_set_param", "dsd_set_timestep_freqs", "dsd_set_precision", "dsd_get_precision", "dsd_set_share_zero_streams", "dsd_params_ready", "dsd_plan", "dsd_workspace_bytes", "dsd_device_bytes", "dsd_set_graph", "dsd_graph_stats", "dsd_set_fuse_gn_stats", "dsd_set_fuse_gn_apply", "dsd_set_stream_lanes", "dsd_set_winograd", "dsd_set_slice_ids", "dsd_plan_launches", "dsd_plan_flops",
-    "dsd_profile_enable", "dsd_profile_count", "dsd_profile_get", "dsd_profile_op_count", "dsd_profile_op_get", "dsd_profile_op_name", "dsd_forward", "dsd_sample", "dsd_op_sampler_update", "dsd_sample_dpm", "dsd_op_dpm_step", "dsd_op_dpm_threshold", "dsd_block_create", "dsd_block_forward", "dsd_bench_conv2d", "dsd_bench_conv2d_stamps", "dsd_bench_mfma_peak", "dsd_conv_plan", "dsd_subpixel_weights_host", "dsd_set_conv_mfma16", "dsd_op_conv2d", "dsd_op_conv2d_prec", "dsd_op_conv2d_ex", "dsd_op_gn_silu_conv_out1",
+    "dsd_profile_enable", "dsd_profile_count", "dsd_profile_get", "dsd_profile_op_count", "dsd_profile_op_get", "dsd_profile_op_name", "dsd_forward", "dsd_sample", "dsd_op_sampler_update", "dsd_sample_dpm", "dsd_op_dpm_step", "dsd_op_dpm_threshold", "dsd_block_create", "dsd_block_forward", "dsd_bench_conv2d", "dsd_bench_conv2d_stamps", "dsd_bench_mfma_peak", "dsd_conv_plan", "dsd_subpixel_weights_host", "dsd_set_conv_mfma16", "dsd_op_conv2d", "dsd_op_conv2d_prec", "dsd_op_conv2d_ex", "dsd_op_conv2d_gn", "dsd_op_gn_finalize", "dsd_op_avg_into_stats", "dsd_op_gn_small", "dsd_op_gn_silu_conv_out1",
     "dsd_op_gaussian_sample", "dsd_op_group_norm", "dsd_op_qkv_attention", "dsd_op_attention", "dsd_op_gemm_half", "dsd_bench_gemm_half", "dsd_bench_attention_half", "dsd_op_attention_half", "dsd_op_timestep_embedding", "dsd_op_linear", "dsd_op_philox_normal",
     "dsd_sample_latent", "dsd_sample_dpm_latent", "dsd_op_posterior_sample_scaled",
     "dsd_sample_guided", "dsd_sample_latent_guided", "dsd_sample_dpm_guided", "dsd_sample_dpm_latent_guided",
@@ -81,6 +81,11 @@ class DsdConvEx(C.Structure):
     _fields_ = [("x_batch_stride", C.c_int64), ("pad_lo", C.c_int32), ("pad_total", C.c_int32), ("y_ld", C.c_int32),
                 ("out_nchw", C.c_int32), ("emb_stride", C.c_int32), ("no_scratch", C.c_int32), ("ksplit", C.c_int32),
                 ("reserved", C.c_int32), ("kernel", C.c_char * 64)]
+
+
+class DsdConvGn(C.Structure):
+    _fields_ = [("gn_scale", C.c_void_p), ("gn_shift", C.c_void_p), ("stats", C.c_void_p), ("stats_doubles", C.c_int64),
+                ("stats_chunks", C.c_int32), ("query", C.c_int32)]
 
 
 class DsdError(RuntimeError):
@@ -165,6 +170,12 @@ def lib() -> C.CDLL:
     L.dsd_op_conv2d_prec.argtypes = [f32p, i32, i32, i32, i32, f32p, f32p, i32, i32, i32, i32, f32p, f32p, i32, f32p, vp]
     L.dsd_op_conv2d_ex.argtypes = [f32p, i32, i32, i32, i32, f32p, f32p, i32, i32, i32, i32, f32p, f32p, i32, C.POINTER(DsdConvEx),
                                    f32p, vp]
+    L.dsd_op_conv2d_gn.argtypes = [f32p, i32, i32, i32, i32, f32p, f32p, i32, i32, i32, i32, f32p, f32p, i32, C.POINTER(DsdConvEx),
+                                   C.POINTER(DsdConvGn), f32p, vp]
+    L.dsd_op_gn_finalize.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, f32p, f32p, C.c_float, f32p, i32, f32p, f32p, vp]
+    L.dsd_op_avg_into_stats.argtypes = [f32p, f32p, f32p, f32p, C.c_float, i32, i32, i32, f32p, i32, i32, i32, i32, vp, i64,
+                                        C.POINTER(C.c_int), vp]
+    L.dsd_op_gn_small.argtypes = [f32p, i32, i32, i32, f32p, f32p, C.c_float, f32p, i32, i32, f32p, vp]
     L.dsd_op_attention.argtypes = [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float,
                                    C.c_float, i32, f32p, vp]
     L.dsd_op_group_norm.argtypes = [f32p, i32, i32, i32, f32p, f32p, C.c_float, i32, f32p, vp]

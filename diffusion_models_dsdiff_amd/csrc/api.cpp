@@ -1267,11 +1267,10 @@ int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float
     DSD_CATCH
 }
 
-int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
-                     int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex, float* y,
-                     void* stream) {
-    DSD_TRY
-    hipStream_t s = (hipStream_t)stream;
+// dsd_op_conv2d_ex and dsd_op_conv2d_gn: gn == nullptr is the former (no GroupNorm arguments, always launched)
+static void conv2d_ex_run(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
+                          int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex,
+                          dsd_conv_gn* gn, float* y, hipStream_t s) {
     // every argument is checked before the first launch (the rules of the planner's destination views, net.cpp conv())
     DSD_CHECK(x && w_oihw && y && ex, "conv2d_ex: null argument");
     DSD_CHECK(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && (ks == 1 || ks == 3) && (stride == 1 || stride == 2),
@@ -1289,18 +1288,17 @@ int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* 
     DSD_CHECK(ex->emb_stride >= 0 && emb_stride >= Cout, "conv2d_ex: emb_stride %d is smaller than Cout %d", ex->emb_stride, Cout);
     DSD_CHECK(emb_stride == Cout || emb_stride % 4 == 0, "conv2d_ex: emb_stride %d of a column range is not a multiple of 4", emb_stride);
     DSD_CHECK(reinterpret_cast<uintptr_t>(emb) % 16 == 0, "conv2d_ex: emb is not 16-byte aligned");
+    // the whole ConvArgs first, on buffers that are allocated but not yet filled: the queries below only look at which pointers
+    // are present, so every refusal comes before the first launch
     const size_t nw = (size_t)Cout * Cin * ks * ks;
     Tmp wp(nw * sizeof(float)), planes(nw * 2 * 3);
-    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
     ConvArgs a;
     a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = wp.as<float>(); a.bias = bias; a.Cout = Cout; a.ks = ks;
     a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = emb_stride; a.res = res; a.y = y;
     a.x_bs = ex->x_batch_stride; a.pad_lo = ex->pad_lo; a.pad_total = ex->pad_total; a.y_ld = ex->y_ld;
     Tmp ovf(sizeof(int));
-    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
-    if ((precision & 3) != PREC_F32) {
-        const bool f16 = (precision & 3) == PREC_F16X3;
-        split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
+    const bool split = (precision & 3) != PREC_F32, f16 = (precision & 3) == PREC_F16X3;
+    if (split) {
         a.w_split = planes.p;
         a.precision = precision & 3;
         a.ovf = f16 ? ovf.as<int>() : nullptr;
@@ -1312,16 +1310,16 @@ int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* 
     if (precision & 128) {   // packed as the planner does, before the output layout is known: an NCHW launch then diverts
         DSD_CHECK(conv2d_wino_shape_ok(a), "conv2d: this problem cannot run on the F(2,3) kernel (3x3, stride 1, even width, "
                                            "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
-        wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
         a.w_wino = wpk.p;
     }
     a.out_nchw = ex->out_nchw ? 1 : 0;
+    if (gn) {
+        a.gn_scale = gn->gn_scale;
+        a.gn_shift = gn->gn_shift;
+    }
     const bool sub = conv2d_subpixel_ok(a);
     Tmp wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0);
-    if (sub) {
-        subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
-        a.w_subpixel = wsub.p;
-    }
+    if (sub) a.w_subpixel = wsub.p;
     const size_t sbytes = ex->no_scratch ? 0 : conv2d_scratch_bytes(a);
     Tmp scratch(sbytes);
     a.scratch = ex->no_scratch ? nullptr : scratch.as<float>();
@@ -1331,11 +1329,106 @@ int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* 
     int st = -1, nt = 0, ksp = 1;
     if (Cin % 4 == 0 && ks * ks * Cin >= 32 && !a.w_subpixel && !conv2d_wino_eligible(a)) conv2d_plan_query(a, &st, &nt, &ksp, a.scratch != nullptr);
     ex->ksplit = ksp;
+    if (gn) {
+        gn->stats_chunks = conv2d_stats_chunks(a);
+        DSD_CHECK((gn->gn_scale == nullptr) == (gn->gn_shift == nullptr), "conv2d_gn: gn_scale and gn_shift come together");
+        DSD_CHECK(gn->gn_scale == nullptr || conv2d_fuses_gn(a), "conv2d_gn: GroupNorm coefficients given, but %s does not apply them "
+                                                                  "(conv2d_fuses_gn)", ex->kernel);
+        DSD_CHECK(gn->gn_scale == nullptr || (reinterpret_cast<uintptr_t>(gn->gn_scale) % 16 == 0 && reinterpret_cast<uintptr_t>(gn->gn_shift) % 16 == 0),
+                  "conv2d_gn: gn_scale / gn_shift are not 16-byte aligned");
+        if (gn->stats) {
+            DSD_CHECK(gn->stats_chunks > 0, "conv2d_gn: output statistics requested, but %s cannot emit them for these arguments "
+                                            "(conv2d_stats_chunks = 0)", ex->kernel);
+            DSD_CHECK(gn->stats_doubles >= (int64_t)N * gn->stats_chunks * Cout * 2, "conv2d_gn: the statistics buffer holds %lld doubles, "
+                      "%d chunks need %lld", (long long)gn->stats_doubles, gn->stats_chunks, (long long)N * gn->stats_chunks * Cout * 2);
+            DSD_CHECK(reinterpret_cast<uintptr_t>(gn->stats) % 8 == 0, "conv2d_gn: stats is not 8-byte aligned");
+            a.stats = gn->stats;
+            a.stats_chunks = gn->stats_chunks;
+        }
+        if (gn->query) return;
+    }
+    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
+    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
+    if (split) split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
+    if (a.w_wino) wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
+    if (sub) subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
     conv2d(a, s);
     int flag = 0;
     DSD_HIP(hipMemcpyAsync(&flag, ovf.p, sizeof(int), hipMemcpyDeviceToHost, s));
     DSD_HIP(hipStreamSynchronize(s));
     DSD_CHECK(!flag, "f16x3: a convolution operand exceeded the fp16 range (|x| > 65504); the result is invalid - use bf16x6 or f32");
+}
+
+int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
+                     int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex, float* y,
+                     void* stream) {
+    DSD_TRY
+    conv2d_ex_run(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, nullptr, y, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_conv2d_gn(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
+                     int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex, dsd_conv_gn* gn,
+                     float* y, void* stream) {
+    DSD_TRY
+    DSD_CHECK(gn, "conv2d_gn: null argument");
+    conv2d_ex_run(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, gn, y, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_gn_finalize(const double* p0, int chunks0, int c0, const double* p1, int chunks1, int c1, int N, int HW, int C,
+                       const float* gamma, const float* beta, float eps, const float* film, int film_stride, float* scale,
+                       float* shift, void* stream) {
+    DSD_TRY
+    hipStream_t s = (hipStream_t)stream;
+    DSD_CHECK(p0 && gamma && beta && scale && shift, "gn_finalize: null argument");
+    DSD_CHECK(N >= 1 && HW >= 1 && C >= 32 && C % 32 == 0, "gn_finalize: bad problem size (GroupNorm32: C %% 32 == 0)");
+    DSD_CHECK(chunks0 >= 1 && c0 >= 1 && (!p1 || (chunks1 >= 1 && c1 >= 1)), "gn_finalize: a source needs chunks >= 1 and channels >= 1");
+    DSD_CHECK(c0 + (p1 ? c1 : 0) == C, "gn_finalize: the statistic sources (%d + %d channels) do not cover the %d channels", c0,
+              p1 ? c1 : 0, C);
+    DSD_CHECK(!film || film_stride >= 2 * C, "gn_finalize: film_stride %d is smaller than 2 C = %d", film_stride, 2 * C);
+    GnSrc s0, s1;
+    s0.p = p0; s0.chunks = chunks0; s0.c0 = 0; s0.c = c0;
+    if (p1) {
+        s1.p = p1; s1.chunks = chunks1; s1.c0 = c0; s1.c = c1;
+    }
+    gn_finalize(s0, s1, N, HW, C, gamma, beta, eps, film, film_stride, scale, shift, s);
+    DSD_HIP(hipStreamSynchronize(s));
+    DSD_CATCH
+}
+
+int dsd_op_avg_into_stats(const float* a, const float* b, const float* c, const float* d, float div, int N, int HW, int C, float* dst,
+                          int dstC, int coff, int act, int bmask, double* partial, int64_t partial_doubles, int* nchunk,
+                          void* stream) {
+    DSD_TRY
+    hipStream_t s = (hipStream_t)stream;
+    DSD_CHECK(a && dst && partial && nchunk, "avg_into_stats: null argument");
+    DSD_CHECK((b || !c) && (c || !d), "avg_into_stats: sources are given in order (a, b, c, d)");
+    DSD_CHECK(N >= 1 && HW >= 1 && C >= 4 && C % 4 == 0 && dstC % 4 == 0 && coff % 4 == 0 && coff >= 0 && coff + C <= dstC,
+              "avg_into_stats: channels [%d, %d) of %d: counts must be multiples of 4 and the slice inside the row", coff, coff + C, dstC);
+    DSD_CHECK(div > 0.f && (act == ACT_NONE || act == ACT_SILU) && bmask >= 0 && bmask < 16, "avg_into_stats: bad div / act / bmask");
+    for (const void* q : {(const void*)a, (const void*)b, (const void*)c, (const void*)d, (const void*)dst})
+        DSD_CHECK(reinterpret_cast<uintptr_t>(q) % 16 == 0, "avg_into_stats: pointers must be 16-byte aligned");
+    *nchunk = gn_nchunks(HW, C);
+    DSD_CHECK(partial_doubles >= (int64_t)N * *nchunk * C * 2, "avg_into_stats: the statistics buffer holds %lld doubles, %d chunks need %lld",
+              (long long)partial_doubles, *nchunk, (long long)N * *nchunk * C * 2);
+    avg_into_stats(a, b, c, d, div, N, HW, C, dst, dstC, coff, act, bmask, partial, *nchunk, s);
+    DSD_HIP(hipStreamSynchronize(s));
+    DSD_CATCH
+}
+
+int dsd_op_gn_small(const float* x, int N, int HW, int C, const float* gamma, const float* beta, float eps, const float* film,
+                    int film_stride, int act, float* y, void* stream) {
+    DSD_TRY
+    hipStream_t s = (hipStream_t)stream;
+    DSD_CHECK(x && gamma && beta && y, "gn_small: null argument");
+    DSD_CHECK(N >= 1 && HW >= 1 && C >= 32 && C % 32 == 0, "gn_small: bad problem size (GroupNorm32: C %% 32 == 0)");
+    DSD_CHECK((int64_t)HW * (C / 32) <= 32768, "gn_small: a group of %d x %d values is beyond the kernel's reach (32768)", HW, C / 32);
+    DSD_CHECK(act == ACT_NONE || act == ACT_SILU, "gn_small: bad activation %d", act);
+    DSD_CHECK(!film || film_stride >= 2 * C, "gn_small: film_stride %d is smaller than 2 C = %d", film_stride, 2 * C);
+    DSD_CHECK(reinterpret_cast<uintptr_t>(x) % 8 == 0 && reinterpret_cast<uintptr_t>(y) % 8 == 0, "gn_small: x / y must be 8-byte aligned");
+    gn_small(x, N, HW, C, gamma, beta, eps, film, film_stride, act, y, s);
+    DSD_HIP(hipStreamSynchronize(s));
     DSD_CATCH
 }
 

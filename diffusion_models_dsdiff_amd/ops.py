@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, dptr, stream_ptr, DsdConvEx
+from ._lib import lib, check, dptr, stream_ptr, DsdConvEx, DsdConvGn
 
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -61,6 +61,72 @@ def conv2d_ex(x, shape, w_oihw, bias, y, stride=1, upsample=False, emb=None, res
                                  ptr(emb), dptr(res), PRECISIONS[precision] | STRUCTURES[structure], C.byref(ex), ptr(y),
                                  stream_ptr()))
     return ex.kernel.decode(), ex.ksplit
+
+
+def conv2d_gn(x, shape, w_oihw, bias, y, gn_scale=None, gn_shift=None, stats=None, query=False, stride=1, upsample=False, emb=None,
+              res=None, precision="f32", structure="auto", x_batch_stride=-1, pad_lo=-1, pad_total=-1, y_ld=0, out_nchw=False,
+              emb_stride=0, no_scratch=False):
+    """conv2d_ex with the GroupNorm arguments (dsd_op_conv2d_gn): gn_scale / gn_shift [N, Cin] fp32 — the kernel then computes
+    conv(silu(x * scale + shift)) —, stats: a float64 CUDA tensor (or view) that receives [N, chunks, Cout, 2] (sum, sum of
+    squares) of the output; query=True launches nothing.  Returns (kernel name, split-K factor, chunks per sample the kernel
+    of these arguments emits: size stats from a query)."""
+    N, H, W, Cin = shape
+    Cout, _, ks, _ = w_oihw.shape
+    ex = DsdConvEx(x_batch_stride=int(x_batch_stride), pad_lo=pad_lo, pad_total=pad_total, y_ld=int(y_ld), out_nchw=int(out_nchw),
+                   emb_stride=int(emb_stride), no_scratch=int(no_scratch), ksplit=0)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    assert x.is_cuda and x.is_contiguous() and y.is_cuda and (res is None or res.is_contiguous())
+    assert stats is None or (stats.is_cuda and stats.dtype == torch.float64 and stats.is_contiguous())
+    for t in (gn_scale, gn_shift):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (N, Cin))
+    gn = DsdConvGn(gn_scale=None if gn_scale is None else gn_scale.data_ptr(), gn_shift=None if gn_shift is None else gn_shift.data_ptr(),
+                   stats=None if stats is None else stats.data_ptr(), stats_doubles=0 if stats is None else stats.numel(),
+                   stats_chunks=0, query=int(query))
+    check(lib().dsd_op_conv2d_gn(ptr(x), N, H, W, Cin, dptr(w_oihw.contiguous()), dptr(bias), Cout, ks, stride, int(upsample),
+                                 ptr(emb), dptr(res), PRECISIONS[precision] | STRUCTURES[structure], C.byref(ex), C.byref(gn), ptr(y),
+                                 stream_ptr()))
+    return ex.kernel.decode(), ex.ksplit, gn.stats_chunks
+
+
+def gn_finalize(srcs, N, HW, C_, gamma, beta, eps=1e-5, film=None, film_stride=0):
+    """gn_finalize on caller-supplied statistics (dsd_op_gn_finalize).  srcs: one or two float64 CUDA tensors [N, chunks, c, 2]
+    (sum, sum of squares per chunk and column), the second covering the channels behind the first; film: [N, film_stride] fp32
+    (scale in columns [0, C), shift in [C, 2C)).  Returns (scale, shift), [N, C] each."""
+    assert 1 <= len(srcs) <= 2
+    for t in srcs:
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 4 and t.shape[0] == N and t.shape[3] == 2
+    p1 = srcs[1] if len(srcs) == 2 else None
+    scale = torch.empty((N, C_), device=srcs[0].device, dtype=torch.float32)
+    shift = torch.empty_like(scale)
+    check(lib().dsd_op_gn_finalize(C.c_void_p(srcs[0].data_ptr()), srcs[0].shape[1], srcs[0].shape[2],
+                                   None if p1 is None else C.c_void_p(p1.data_ptr()), 0 if p1 is None else p1.shape[1],
+                                   0 if p1 is None else p1.shape[2], N, HW, C_, dptr(gamma), dptr(beta), eps, dptr(film),
+                                   int(film_stride), dptr(scale), dptr(shift), stream_ptr()))
+    return scale, shift
+
+
+def avg_into_stats(srcs, div, N, HW, C_, dst, dstC, coff, act, bmask, partial):
+    """dst[..., coff:coff + C] = act(sum(srcs) / div) and the statistics of what was written (dsd_op_avg_into_stats).  srcs: 1 to
+    4 contiguous fp32 CUDA tensors [N, HW, C] ([HW, C] where bit k of bmask is set); dst: the tensor (or view) whose first element
+    is row 0, column 0 of the [N * HW, dstC] destination; partial: a float64 CUDA tensor (or view) with room for
+    [N, chunks, C, 2].  Returns the chunk count the statistics were written with."""
+    assert 1 <= len(srcs) <= 4 and dst.is_cuda and partial.is_cuda and partial.dtype == torch.float64 and partial.is_contiguous()
+    p = [dptr(t) for t in srcs] + [None] * (4 - len(srcs))
+    n = C.c_int(0)
+    check(lib().dsd_op_avg_into_stats(p[0], p[1], p[2], p[3], float(div), N, HW, C_, C.c_void_p(dst.data_ptr()), dstC, coff,
+                                      int(act), int(bmask), C.c_void_p(partial.data_ptr()), partial.numel(), C.byref(n),
+                                      stream_ptr()))
+    return n.value
+
+
+def gn_small(x_nhwc, gamma, beta, eps=1e-5, film=None, film_stride=0, silu=False):
+    """GroupNorm32 (+ FiLM, + SiLU) of a small map in one launch (dsd_op_gn_small), x [N, H, W, C] or [N, HW, C]."""
+    N, Cc = x_nhwc.shape[0], x_nhwc.shape[-1]
+    HW = x_nhwc.numel() // (N * Cc)
+    y = torch.empty_like(x_nhwc)
+    check(lib().dsd_op_gn_small(dptr(x_nhwc), N, HW, Cc, dptr(gamma), dptr(beta), eps, dptr(film), int(film_stride), int(silu),
+                                dptr(y), stream_ptr()))
+    return y
 
 
 def conv_mfma16(on=None):

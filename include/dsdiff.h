@@ -528,6 +528,47 @@ typedef struct dsd_conv_ex {
 int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
                      int ks, int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex,
                      float* y, void* stream);
+/* dsd_op_conv2d_ex with the remaining ConvArgs fields: GroupNorm + SiLU of the INPUT applied inside the kernel, and the GroupNorm
+ * statistics of the OUTPUT from the epilogue.  Inputs:
+ *   gn_scale, gn_shift  [N][Cin] per-(sample, channel) coefficients (dsd_op_gn_finalize's), both or neither; x is then the tensor
+ *                   BEFORE the normalisation and the layer computes conv(silu(x * scale + shift)) with zero padding of the
+ *                   activated tensor.  Refused unless the launch runs the tap-reuse kernel (kernel name ".../tr+gn")
+ *   stats           optional output, [N][stats_chunks][Cout][2] doubles: (sum, sum of squares) of every output column over a
+ *                   chunk = a run of OH*OW / stats_chunks consecutive output pixels of one sample (sub-pixel form: chunk =
+ *                   (2 py + px) * (H*W / 256) + run of 256 low-resolution pixels whose phase-(py, px) outputs it covers)
+ *   stats_doubles   doubles the stats buffer holds (checked against N * stats_chunks * Cout * 2)
+ *   query           1: fill ex->kernel, ex->ksplit and stats_chunks, launch nothing (y is not written)
+ * Output: stats_chunks = chunks per sample the kernel of exactly these arguments (no_scratch included) emits; 0 = it cannot,
+ * and a call with stats is then refused.  Every refusal comes before the first launch. */
+typedef struct dsd_conv_gn {
+    const float* gn_scale;
+    const float* gn_shift;
+    double* stats;
+    int64_t stats_doubles;
+    int32_t stats_chunks;
+    int32_t query;
+} dsd_conv_gn;
+int dsd_op_conv2d_gn(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
+                     int ks, int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex,
+                     dsd_conv_gn* gn, float* y, void* stream);
+/* gn_finalize on caller-supplied statistics: source 0 covers channels [0, c0) with chunks0 chunks per sample
+ * (p0[N][chunks0][c0][2] doubles), the optional source 1 (p1 != NULL) channels [c0, c0 + c1); c0 (+ c1) must equal C.  film
+ * (optional): [N][film_stride] rows holding the FiLM scale in columns [0, C) and the shift in [C, 2C).  scale / shift: [N][C],
+ * GroupNorm32(x) (* (1 + film scale) + film shift) = x * scale + shift. */
+int dsd_op_gn_finalize(const double* p0, int chunks0, int c0, const double* p1, int chunks1, int c1, int N, int HW, int C,
+                       const float* gamma, const float* beta, float eps, const float* film, int film_stride, float* scale,
+                       float* shift, void* stream);
+/* dst[n, p, coff:coff+C] = act((a [+ b] [+ c] [+ d]) / div) on [N][HW][C] sources (bit k of bmask: source k is ONE sample
+ * [HW][C] broadcast over the batch), dst rows of dstC floats, and the per-column statistics of what was written:
+ * partial[N][*nchunk][C][2] doubles (the chunking of the standalone statistics pass; *nchunk is an output, partial_doubles the
+ * room the caller gave).  act: 0 none, 1 SiLU. */
+int dsd_op_avg_into_stats(const float* a, const float* b, const float* c, const float* d, float div, int N, int HW, int C,
+                          float* dst, int dstC, int coff, int act, int bmask, double* partial, int64_t partial_doubles,
+                          int* nchunk, void* stream);
+/* The one-launch GroupNorm32 (+ FiLM, + activation) of small maps, called directly (the DSD_GN_SMALL switch of the networks is
+ * not consulted): x, y [N][HW][C], C % 32 == 0, HW * C / 32 <= 32768; film as in dsd_op_gn_finalize; act: 0 none, 1 SiLU. */
+int dsd_op_gn_small(const float* x, int N, int HW, int C, const float* gamma, const float* beta, float eps, const float* film,
+                    int film_stride, int act, float* y, void* stream);
 /* Micro-benchmark of the convolution kernel on random data (library-owned buffers): average ms per launch over
  * `iters` back-to-back launches (hipEvents) and the algorithmic FLOPs of one launch.  variant: -1/0 default fp32
  * kernel, 1 flat-load fp32 kernel, 10 bf16x3, 11 bf16x6, 12 f16x3 (library's choice of structure), 20/21 both operands staged
