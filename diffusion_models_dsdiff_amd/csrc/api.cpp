@@ -1,5 +1,6 @@
 // api.cpp — the extern "C" surface of libdsdiff.so (see include/dsdiff.h).
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "net.h"
@@ -1042,18 +1043,124 @@ int dsd_op_dpm_threshold(const float* x0, int B, int n, float ratio, float max_v
 }
 
 // ------------------------------------------------------------------------------------------- kernel-level ops
+// The `precision` argument of the convolution entry points -> ConvArgs: arithmetic in bits 0-1; 16 / 32 / 64 force the
+// A-direct / staged / 256-row A-direct structure of the split kernels; 256 plans as inside a stream-lane region (three launches
+// of the same shape run beside this one).  Bit 128 (the F(2,3) kernel) needs packed weights: conv2d_op.
+static void conv_option_bits(int bits, ConvArgs* a) {
+    a->precision = bits & 3;
+    if (a->precision != PREC_F32) a->variant = (bits & 64) ? 32 : (bits & 32) ? 31 : (bits & 16) ? 30 : -1;
+    if (bits & 256) a->lanes = 4;
+}
+
+static dsd_conv_ex conv_ex_defaults() {
+    dsd_conv_ex ex{};
+    ex.x_batch_stride = ex.pad_lo = ex.pad_total = -1;
+    return ex;
+}
+
+// The one body of the convolution entry points.  gn == nullptr: no GroupNorm arguments, always launched.  `launch` replaces the
+// single conv2d() call (dsd_bench_conv2d times its own).
+static void conv2d_op(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
+                      int stride, int upsample, const float* emb, const float* res, int bits, dsd_conv_ex* ex, dsd_conv_gn* gn,
+                      float* y, hipStream_t s, const std::function<void(ConvArgs&)>& launch = {}) {
+    // every argument is checked before the first launch (the rules of the planner's destination views, net.cpp conv())
+    DSD_CHECK(x && w_oihw && y && ex, "conv2d_ex: null argument");
+    DSD_CHECK(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && (ks == 1 || ks == 3) && (stride == 1 || stride == 2),
+              "conv2d_ex: bad problem size");
+    const int64_t plane = (int64_t)H * W * Cin;
+    DSD_CHECK(ex->x_batch_stride == -1 || ex->x_batch_stride == 0 || ex->x_batch_stride >= plane,
+              "conv2d_ex: x_batch_stride %lld is neither -1, 0 nor at least one plane (%lld)", (long long)ex->x_batch_stride, (long long)plane);
+    DSD_CHECK((ex->pad_lo < 0) == (ex->pad_total < 0) && ex->pad_lo < ks && ex->pad_total < 2 * ks && ex->pad_lo <= std::max(ex->pad_total, 0),
+              "conv2d_ex: pad_lo %d / pad_total %d", ex->pad_lo, ex->pad_total);
+    const int y_ld = ex->y_ld > 0 ? ex->y_ld : Cout, emb_stride = ex->emb_stride > 0 ? ex->emb_stride : Cout;
+    DSD_CHECK(ex->y_ld >= 0 && y_ld >= Cout, "conv2d_ex: y_ld %d is smaller than Cout %d", ex->y_ld, Cout);
+    DSD_CHECK(y_ld == Cout || y_ld % 4 == 0, "conv2d_ex: y_ld %d of a channel slice is not a multiple of 4", y_ld);
+    DSD_CHECK(reinterpret_cast<uintptr_t>(y) % 16 == 0, "conv2d_ex: y is not 16-byte aligned");
+    DSD_CHECK(!ex->out_nchw || y_ld == Cout, "conv2d_ex: an NCHW output has no row stride");
+    DSD_CHECK(ex->emb_stride >= 0 && emb_stride >= Cout, "conv2d_ex: emb_stride %d is smaller than Cout %d", ex->emb_stride, Cout);
+    DSD_CHECK(emb_stride == Cout || emb_stride % 4 == 0, "conv2d_ex: emb_stride %d of a column range is not a multiple of 4", emb_stride);
+    DSD_CHECK(reinterpret_cast<uintptr_t>(emb) % 16 == 0, "conv2d_ex: emb is not 16-byte aligned");
+    // the whole ConvArgs first, with a placeholder where a buffer will be: the queries below only look at which pointers are
+    // present, so every refusal — and all of query mode — comes before anything touches a device
+    const void* const present = ex;
+    const size_t nw = (size_t)Cout * Cin * ks * ks;
+    ConvArgs a;
+    a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = w_oihw; a.bias = bias; a.Cout = Cout; a.ks = ks;
+    a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = emb_stride; a.res = res; a.y = y;
+    a.x_bs = ex->x_batch_stride; a.pad_lo = ex->pad_lo; a.pad_total = ex->pad_total; a.y_ld = ex->y_ld;
+    conv_option_bits(bits, &a);
+    const bool split = a.precision != PREC_F32, f16 = a.precision == PREC_F16X3;
+    if (split) a.w_split = present;
+    if (bits & 128) {   // packed as the planner does, before the output layout is known: an NCHW launch then diverts
+        DSD_CHECK(conv2d_wino_shape_ok(a), "conv2d: this problem cannot run on the F(2,3) kernel (3x3, stride 1, even width, "
+                                           "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
+        a.w_wino = present;
+    }
+    a.out_nchw = ex->out_nchw ? 1 : 0;
+    if (gn) {
+        a.gn_scale = gn->gn_scale;
+        a.gn_shift = gn->gn_shift;
+    }
+    const bool sub = conv2d_subpixel_ok(a);
+    if (sub) a.w_subpixel = present;
+    // what runs: the route of the launch these very arguments get, with / without scratch
+    const ConvRoute route = conv2d_route(a, !ex->no_scratch);
+    snprintf(ex->kernel, sizeof(ex->kernel), "%s", conv2d_route_name(route, a.gn_scale != nullptr));
+    ex->ksplit = route.ksplit;
+    if (gn) {
+        gn->stats_chunks = route.stats_chunks;
+        DSD_CHECK((gn->gn_scale == nullptr) == (gn->gn_shift == nullptr), "conv2d_gn: gn_scale and gn_shift come together");
+        DSD_CHECK(gn->gn_scale == nullptr || route.fuses_gn, "conv2d_gn: GroupNorm coefficients given, but %s does not apply them "
+                                                                  "(ConvRoute.fuses_gn)", ex->kernel);
+        DSD_CHECK(gn->gn_scale == nullptr || (reinterpret_cast<uintptr_t>(gn->gn_scale) % 16 == 0 && reinterpret_cast<uintptr_t>(gn->gn_shift) % 16 == 0),
+                  "conv2d_gn: gn_scale / gn_shift are not 16-byte aligned");
+        if (gn->stats) {
+            DSD_CHECK(gn->stats_chunks > 0, "conv2d_gn: output statistics requested, but %s cannot emit them for these arguments "
+                                            "(ConvRoute.stats_chunks = 0)", ex->kernel);
+            DSD_CHECK(gn->stats_doubles >= (int64_t)N * gn->stats_chunks * Cout * 2, "conv2d_gn: the statistics buffer holds %lld doubles, "
+                      "%d chunks need %lld", (long long)gn->stats_doubles, gn->stats_chunks, (long long)N * gn->stats_chunks * Cout * 2);
+            DSD_CHECK(reinterpret_cast<uintptr_t>(gn->stats) % 8 == 0, "conv2d_gn: stats is not 8-byte aligned");
+            a.stats = gn->stats;
+            a.stats_chunks = gn->stats_chunks;
+        }
+        if (gn->query) return;
+    }
+    // the derived weights of this call, then the launch
+    Tmp wp(nw * sizeof(float)), planes(split ? nw * 2 * 3 : 0), ovf(sizeof(int));
+    Tmp wpk(a.w_wino ? wino_packed_bytes(Cout, Cin) + 256 : 0), wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0), scratch(route.scratch_bytes);
+    a.w = wp.as<float>();
+    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
+    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
+    if (split) {
+        split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
+        a.w_split = planes.p;
+        a.ovf = f16 ? ovf.as<int>() : nullptr;
+    }
+    if (a.w_wino) {
+        wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
+        a.w_wino = wpk.p;
+    }
+    if (sub) {
+        subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
+        a.w_subpixel = wsub.p;
+    }
+    if (!ex->no_scratch) {
+        a.scratch = scratch.as<float>();
+        a.scratch_bytes = route.scratch_bytes;
+    }
+    if (launch)
+        launch(a);
+    else
+        conv2d(a, s);
+    int flag = 0;
+    DSD_HIP(hipMemcpyAsync(&flag, ovf.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    DSD_HIP(hipStreamSynchronize(s));
+    DSD_CHECK(!flag, "f16x3: a convolution operand exceeded the fp16 range (|x| > 65504); the result is invalid - use bf16x6 or f32");
+}
+
 int dsd_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
                   int stride, int upsample, const float* emb, const float* res, float* y, void* stream) {
-    DSD_TRY
-    hipStream_t s = (hipStream_t)stream;
-    Tmp wp((size_t)Cout * Cin * ks * ks * sizeof(float));
-    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
-    ConvArgs a;
-    a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = wp.as<float>(); a.bias = bias; a.Cout = Cout; a.ks = ks;
-    a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = Cout; a.res = res; a.y = y;
-    conv2d(a, s);
-    DSD_HIP(hipStreamSynchronize(s));
-    DSD_CATCH
+    return dsd_op_conv2d_prec(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, PREC_F32, y, stream);
 }
 
 int dsd_subpixel_weights_host(const float* w_oihw, int Cout, int Cin, double* out) {
@@ -1085,15 +1192,13 @@ int dsd_conv_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, in
     DSD_CHECK(structure && nt && ksplit && scratch_bytes, "null argument");
     ConvArgs a;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ks = ks; a.stride = stride;
-    a.precision = precision & 3;
-    if (precision & 16) a.variant = 30;
-    if (precision & 32) a.variant = 31;
-    if (precision & 64) a.variant = 32;
-    if (precision & 256) a.lanes = 4;   // as inside a stream-lane region: three launches of the same shape run beside this one
-    static const int dummy = 0;
-    a.w_split = a.precision != PREC_F32 ? &dummy : nullptr;   // only its presence matters to the eligibility test
-    conv2d_plan_query(a, structure, nt, ksplit);
-    *scratch_bytes = conv2d_scratch_bytes(a);
+    conv_option_bits(precision, &a);
+    a.w_split = a.precision != PREC_F32 ? &a : nullptr;   // only its presence matters to the route
+    const ConvRoute r = conv2d_route(a, true);
+    *structure = r.structure;
+    *nt = r.nt;
+    *ksplit = r.ksplit;
+    *scratch_bytes = r.scratch_bytes;
     DSD_CATCH
 }
 
@@ -1101,59 +1206,39 @@ int dsd_bench_conv2d(int N, int H, int W, int Cin, int Cout, int ks, int stride,
                      double* flops) {
     DSD_TRY
     DSD_CHECK(iters >= 1 && avg_ms, "bad argument");
+    // variant numbers (tools/bench_conv.py): 0 / 1 = fp32 with buffer / flat loads; 10 + p = split arithmetic p (0 bf16x3, 1 bf16x6,
+    // 2 f16x3); 20 + p / 30 + p / 40 + p = the same forced onto the staged / 128-row / 256-row A-direct structure; 50 = F(2,3), bf16x6
+    DSD_CHECK(variant == 0 || variant == 1 || variant == 50 || (variant >= 10 && variant < 50 && variant % 10 <= 2), "bad variant %d", variant);
+    static const int structure_bit[5] = {0, 0, 32, 16, 64};
+    const int bits = variant < 10 ? PREC_F32 : variant == 50 ? (PREC_BF16X6 | 128) : ((variant % 10 + 1) | structure_bit[variant / 10]);
     hipStream_t s = nullptr;
     const int pad = ks / 2;
     const int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
     const size_t nx = (size_t)N * H * W * Cin, nw = (size_t)Cout * Cin * ks * ks, ny = (size_t)N * OH * OW * Cout;
     Tmp x(nx * 4), w(nw * 4), b((size_t)Cout * 4), y(ny * 4);
     philox_normal(x.as<float>(), (int64_t)nx, 1, 0, s);
-    philox_normal(w.as<float>(), (int64_t)nw, 2, 0, s);
+    philox_normal(w.as<float>(), (int64_t)nw, 2, 0, s);   // (random weights: their layout does not matter to the timing)
     philox_normal(b.as<float>(), Cout, 3, 0, s);
-    ConvArgs a;
-    a.x = x.as<float>(); a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = w.as<float>(); a.bias = b.as<float>();
-    a.Cout = Cout; a.ks = ks; a.stride = stride; a.y = y.as<float>(); a.variant = variant >= 10 ? -1 : variant;
-    Tmp planes(nw * 2 * 3);
-    const bool wino = variant == 50;   // 50 = bf16x6, F(2,3) along the width (conv_wino.hip)
-    if (wino) variant = 11;
-    if (variant >= 40) {  // 40 = bf16x3, 41 = bf16x6, 42 = f16x3 on the 256-row A-direct tile (forced)
-        a.variant = 32;
-        variant -= 30;
-    } else if (variant >= 30) {  // 30 = bf16x3 A-direct, 31 = bf16x6 A-direct (forced)
-        a.variant = 30;
-        variant -= 20;
-    } else if (variant >= 20) {  // 20 = bf16x3 staged, 21 = bf16x6 staged (forced)
-        a.variant = 31;
-        variant -= 10;
-    }
-    if (variant >= 10) {  // 10 = bf16x3, 11 = bf16x6, 12 = f16x3
-        a.precision = variant == 10 ? PREC_BF16X3 : (variant == 11 ? PREC_BF16X6 : PREC_F16X3);
-        split_weights(w.as<float>(), (int64_t)nw, 3, planes.p, s, a.precision == PREC_F16X3);
-        a.w_split = planes.p;
-    }
-    Tmp wpk(wino ? wino_packed_bytes(Cout, Cin) : 256);
-    if (wino) {
-        DSD_CHECK(conv2d_wino_shape_ok(a), "this shape cannot run on the F(2,3) kernel");
-        // the library keeps weights OHWI: random data is layout-agnostic here (timing only)
-        wino_pack_weights(w.as<float>(), Cout, Cin, wpk.p, s);
-        a.w_wino = wpk.p;
-    }
-    Tmp scratch(conv2d_scratch_bytes(a));
-    a.scratch = scratch.as<float>();
-    a.scratch_bytes = conv2d_scratch_bytes(a);
-    conv2d(a, s);  // warm-up
-    hipEvent_t e0, e1;
-    DSD_HIP(hipEventCreate(&e0));
-    DSD_HIP(hipEventCreate(&e1));
-    DSD_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) conv2d(a, s);
-    DSD_HIP(hipEventRecord(e1, s));
-    DSD_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    DSD_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    if (flops) *flops = conv2d_flops(a);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    dsd_conv_ex ex = conv_ex_defaults();
+    conv2d_op(x.as<float>(), N, H, W, Cin, w.as<float>(), b.as<float>(), Cout, ks, stride, 0, nullptr, nullptr, bits, &ex, nullptr,
+              y.as<float>(), s, [&](ConvArgs& a) {
+        if (variant == 1) a.variant = 1;
+        a.ovf = nullptr;   // (the f16x3 kernels are timed without their range check, as they always were here)
+        conv2d(a, s);  // warm-up
+        hipEvent_t e0, e1;
+        DSD_HIP(hipEventCreate(&e0));
+        DSD_HIP(hipEventCreate(&e1));
+        DSD_HIP(hipEventRecord(e0, s));
+        for (int i = 0; i < iters; ++i) conv2d(a, s);
+        DSD_HIP(hipEventRecord(e1, s));
+        DSD_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        DSD_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = ms / iters;
+        if (flops) *flops = conv2d_flops(a);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    });
     DSD_CATCH
 }
 
@@ -1223,147 +1308,16 @@ int dsd_bench_mfma_peak(int variant, int workgroups_per_cu, float ms_target, int
 int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
                        int stride, int upsample, const float* emb, const float* res, int precision, float* y, void* stream) {
     DSD_TRY
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nw = (size_t)Cout * Cin * ks * ks;
-    Tmp wp(nw * sizeof(float)), planes(nw * 2 * 3);
-    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
-    ConvArgs a;
-    a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = wp.as<float>(); a.bias = bias; a.Cout = Cout; a.ks = ks;
-    a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = Cout; a.res = res; a.y = y;
-    Tmp ovf(sizeof(int));
-    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
-    if ((precision & 3) != PREC_F32) {
-        const bool f16 = (precision & 3) == PREC_F16X3;
-        split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
-        a.w_split = planes.p;
-        a.precision = precision & 3;
-        a.ovf = f16 ? ovf.as<int>() : nullptr;
-        if (precision & 16) a.variant = 30;   // force the A-direct structure
-        if (precision & 32) a.variant = 31;   // force the staged structure
-        if (precision & 64) a.variant = 32;   // force the 256-row A-direct tile
-    }
-    Tmp wpk((precision & 128) ? wino_packed_bytes(Cout, Cin) + 256 : 256);
-    if (precision & 128) {                    // F(2,3)-along-W kernel (conv_wino.hip); fails loudly if the shape cannot take it
-        DSD_CHECK(conv2d_wino_shape_ok(a), "conv2d: this problem cannot run on the F(2,3) kernel (3x3, stride 1, even width, "
-                                           "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
-        wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
-        a.w_wino = wpk.p;
-    }
-    // an upsample layer the planner runs in the sub-pixel form: phase weights built for this call
-    const bool sub = conv2d_subpixel_ok(a);
-    Tmp wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0);
-    if (sub) {
-        subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
-        a.w_subpixel = wsub.p;
-    }
-    Tmp scratch(conv2d_scratch_bytes(a));
-    a.scratch = scratch.as<float>();
-    a.scratch_bytes = conv2d_scratch_bytes(a);
-    conv2d(a, s);
-    int flag = 0;
-    DSD_HIP(hipMemcpyAsync(&flag, ovf.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DSD_HIP(hipStreamSynchronize(s));
-    DSD_CHECK(!flag, "f16x3: a convolution operand exceeded the fp16 range (|x| > 65504); the result is invalid - use bf16x6 or f32");
+    dsd_conv_ex ex = conv_ex_defaults();
+    conv2d_op(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, &ex, nullptr, y, (hipStream_t)stream);
     DSD_CATCH
-}
-
-// dsd_op_conv2d_ex and dsd_op_conv2d_gn: gn == nullptr is the former (no GroupNorm arguments, always launched)
-static void conv2d_ex_run(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
-                          int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex,
-                          dsd_conv_gn* gn, float* y, hipStream_t s) {
-    // every argument is checked before the first launch (the rules of the planner's destination views, net.cpp conv())
-    DSD_CHECK(x && w_oihw && y && ex, "conv2d_ex: null argument");
-    DSD_CHECK(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && (ks == 1 || ks == 3) && (stride == 1 || stride == 2),
-              "conv2d_ex: bad problem size");
-    const int64_t plane = (int64_t)H * W * Cin;
-    DSD_CHECK(ex->x_batch_stride == -1 || ex->x_batch_stride == 0 || ex->x_batch_stride >= plane,
-              "conv2d_ex: x_batch_stride %lld is neither -1, 0 nor at least one plane (%lld)", (long long)ex->x_batch_stride, (long long)plane);
-    DSD_CHECK((ex->pad_lo < 0) == (ex->pad_total < 0) && ex->pad_lo < ks && ex->pad_total < 2 * ks && ex->pad_lo <= std::max(ex->pad_total, 0),
-              "conv2d_ex: pad_lo %d / pad_total %d", ex->pad_lo, ex->pad_total);
-    const int y_ld = ex->y_ld > 0 ? ex->y_ld : Cout, emb_stride = ex->emb_stride > 0 ? ex->emb_stride : Cout;
-    DSD_CHECK(ex->y_ld >= 0 && y_ld >= Cout, "conv2d_ex: y_ld %d is smaller than Cout %d", ex->y_ld, Cout);
-    DSD_CHECK(y_ld == Cout || y_ld % 4 == 0, "conv2d_ex: y_ld %d of a channel slice is not a multiple of 4", y_ld);
-    DSD_CHECK(reinterpret_cast<uintptr_t>(y) % 16 == 0, "conv2d_ex: y is not 16-byte aligned");
-    DSD_CHECK(!ex->out_nchw || y_ld == Cout, "conv2d_ex: an NCHW output has no row stride");
-    DSD_CHECK(ex->emb_stride >= 0 && emb_stride >= Cout, "conv2d_ex: emb_stride %d is smaller than Cout %d", ex->emb_stride, Cout);
-    DSD_CHECK(emb_stride == Cout || emb_stride % 4 == 0, "conv2d_ex: emb_stride %d of a column range is not a multiple of 4", emb_stride);
-    DSD_CHECK(reinterpret_cast<uintptr_t>(emb) % 16 == 0, "conv2d_ex: emb is not 16-byte aligned");
-    // the whole ConvArgs first, on buffers that are allocated but not yet filled: the queries below only look at which pointers
-    // are present, so every refusal comes before the first launch
-    const size_t nw = (size_t)Cout * Cin * ks * ks;
-    Tmp wp(nw * sizeof(float)), planes(nw * 2 * 3);
-    ConvArgs a;
-    a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.w = wp.as<float>(); a.bias = bias; a.Cout = Cout; a.ks = ks;
-    a.stride = stride; a.ups = upsample; a.emb = emb; a.emb_stride = emb_stride; a.res = res; a.y = y;
-    a.x_bs = ex->x_batch_stride; a.pad_lo = ex->pad_lo; a.pad_total = ex->pad_total; a.y_ld = ex->y_ld;
-    Tmp ovf(sizeof(int));
-    const bool split = (precision & 3) != PREC_F32, f16 = (precision & 3) == PREC_F16X3;
-    if (split) {
-        a.w_split = planes.p;
-        a.precision = precision & 3;
-        a.ovf = f16 ? ovf.as<int>() : nullptr;
-        if (precision & 16) a.variant = 30;
-        if (precision & 32) a.variant = 31;
-        if (precision & 64) a.variant = 32;
-    }
-    Tmp wpk((precision & 128) ? wino_packed_bytes(Cout, Cin) + 256 : 256);
-    if (precision & 128) {   // packed as the planner does, before the output layout is known: an NCHW launch then diverts
-        DSD_CHECK(conv2d_wino_shape_ok(a), "conv2d: this problem cannot run on the F(2,3) kernel (3x3, stride 1, even width, "
-                                           "Cin %% 16 == 0, Cout %% 32 == 0, >= 4096 output pixels, bf16x6)");
-        a.w_wino = wpk.p;
-    }
-    a.out_nchw = ex->out_nchw ? 1 : 0;
-    if (gn) {
-        a.gn_scale = gn->gn_scale;
-        a.gn_shift = gn->gn_shift;
-    }
-    const bool sub = conv2d_subpixel_ok(a);
-    Tmp wsub(sub ? subpixel_weight_bytes(Cout, Cin) : 0);
-    if (sub) a.w_subpixel = wsub.p;
-    const size_t sbytes = ex->no_scratch ? 0 : conv2d_scratch_bytes(a);
-    Tmp scratch(sbytes);
-    a.scratch = ex->no_scratch ? nullptr : scratch.as<float>();
-    a.scratch_bytes = sbytes;
-    // what runs: the name of these very arguments, and the split-K factor conv2d() takes with / without scratch
-    snprintf(ex->kernel, sizeof(ex->kernel), "%s", conv2d_variant(a));
-    int st = -1, nt = 0, ksp = 1;
-    if (Cin % 4 == 0 && ks * ks * Cin >= 32 && !a.w_subpixel && !conv2d_wino_eligible(a)) conv2d_plan_query(a, &st, &nt, &ksp, a.scratch != nullptr);
-    ex->ksplit = ksp;
-    if (gn) {
-        gn->stats_chunks = conv2d_stats_chunks(a);
-        DSD_CHECK((gn->gn_scale == nullptr) == (gn->gn_shift == nullptr), "conv2d_gn: gn_scale and gn_shift come together");
-        DSD_CHECK(gn->gn_scale == nullptr || conv2d_fuses_gn(a), "conv2d_gn: GroupNorm coefficients given, but %s does not apply them "
-                                                                  "(conv2d_fuses_gn)", ex->kernel);
-        DSD_CHECK(gn->gn_scale == nullptr || (reinterpret_cast<uintptr_t>(gn->gn_scale) % 16 == 0 && reinterpret_cast<uintptr_t>(gn->gn_shift) % 16 == 0),
-                  "conv2d_gn: gn_scale / gn_shift are not 16-byte aligned");
-        if (gn->stats) {
-            DSD_CHECK(gn->stats_chunks > 0, "conv2d_gn: output statistics requested, but %s cannot emit them for these arguments "
-                                            "(conv2d_stats_chunks = 0)", ex->kernel);
-            DSD_CHECK(gn->stats_doubles >= (int64_t)N * gn->stats_chunks * Cout * 2, "conv2d_gn: the statistics buffer holds %lld doubles, "
-                      "%d chunks need %lld", (long long)gn->stats_doubles, gn->stats_chunks, (long long)N * gn->stats_chunks * Cout * 2);
-            DSD_CHECK(reinterpret_cast<uintptr_t>(gn->stats) % 8 == 0, "conv2d_gn: stats is not 8-byte aligned");
-            a.stats = gn->stats;
-            a.stats_chunks = gn->stats_chunks;
-        }
-        if (gn->query) return;
-    }
-    pack_ohwi(w_oihw, wp.as<float>(), Cout, Cin, ks, s);
-    DSD_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), s));
-    if (split) split_weights(wp.as<float>(), (int64_t)nw, 3, planes.p, s, f16, f16 ? ovf.as<int>() : nullptr);
-    if (a.w_wino) wino_pack_weights(wp.as<float>(), Cout, Cin, wpk.p, s);
-    if (sub) subpixel_weights(wp.as<float>(), Cout, Cin, wsub.p, s);
-    conv2d(a, s);
-    int flag = 0;
-    DSD_HIP(hipMemcpyAsync(&flag, ovf.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    DSD_HIP(hipStreamSynchronize(s));
-    DSD_CHECK(!flag, "f16x3: a convolution operand exceeded the fp16 range (|x| > 65504); the result is invalid - use bf16x6 or f32");
 }
 
 int dsd_op_conv2d_ex(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int ks,
                      int stride, int upsample, const float* emb, const float* res, int precision, dsd_conv_ex* ex, float* y,
                      void* stream) {
     DSD_TRY
-    conv2d_ex_run(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, nullptr, y, (hipStream_t)stream);
+    conv2d_op(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, nullptr, y, (hipStream_t)stream);
     DSD_CATCH
 }
 
@@ -1372,7 +1326,7 @@ int dsd_op_conv2d_gn(const float* x, int N, int H, int W, int Cin, const float* 
                      float* y, void* stream) {
     DSD_TRY
     DSD_CHECK(gn, "conv2d_gn: null argument");
-    conv2d_ex_run(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, gn, y, (hipStream_t)stream);
+    conv2d_op(x, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, emb, res, precision, ex, gn, y, (hipStream_t)stream);
     DSD_CATCH
 }
 

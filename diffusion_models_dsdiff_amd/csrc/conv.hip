@@ -642,29 +642,6 @@ static int pick_nt(int Cout, int tiles_m, int precision, int lanes = 1) {
     return best;
 }
 
-// split-bf16 arithmetic requested and usable for this problem?  (Until the A-direct kernel was software-pipelined, grids
-// of at most one block per CU were faster on the fp32 kernel and stayed there; now the 128-row A-direct kernel ties it in
-// bf16x6 and beats it in the 3-product modes on those layers — tools/bench_conv.py 0 31 30 with DSD_SHAPES=small.)
-static int effective_precision(const ConvArgs& a, int tiles_m) {
-    (void)tiles_m;
-    if (a.precision == PREC_F32 || !conv2d_split_eligible(a)) return PREC_F32;
-    return a.precision;
-}
-
-size_t conv2d_scratch_bytes(const ConvArgs& a) {
-    if (a.w_subpixel) return 0;
-    if (a.precision == PREC_F32 || a.Cin % 32 != 0 || a.Cin % 4 != 0) return 0;
-    if (conv2d_wino_eligible(a)) return 0;
-    int OH, OW;
-    conv_out_hw(a, &OH, &OW);
-    const int64_t M = (int64_t)a.N * OH * OW;
-    const int tm = cdiv(M, BM);
-    if (effective_precision(a, tm) == PREC_F32) return 0;
-    int nt, ks;
-    conv2d_split_plan(a, pick_nt(a.Cout, tm, a.precision, a.lanes), &nt, &ks);
-    return ks > 1 ? (size_t)ks * M * a.Cout * sizeof(float) : 0;
-}
-
 // pixels per workgroup of the first-layer kernel; with_stats: a divisor of OH*OW (one chunk of one sample), 0 = none suitable
 static int direct_cols_ppb(const ConvArgs& a, int64_t M, int ohw, bool with_stats) {
     const int W4 = a.Cout / 4, rpi = 256 / W4;
@@ -673,112 +650,119 @@ static int direct_cols_ppb(const ConvArgs& a, int64_t M, int ohw, bool with_stat
         if (ohw % ppb == 0) return ppb;
     return 0;
 }
-static bool direct_cols_ok(const ConvArgs& a) {
-    return a.Cout % 4 == 0 && a.Cout / 4 <= 256 && a.ks * a.ks * a.Cin <= 9 && !a.out_nchw && (!a.emb || a.emb_stride % 4 == 0);
-}
 
-int conv2d_stats_chunks(const ConvArgs& a) {
-    // the split-precision implicit-GEMM kernels carry the statistics epilogue (not their split-K form, whose output is
-    // written by the reduction kernel), and so does the first-layer kernel
-    if (a.Cin % 4 != 0 || a.ks * a.ks * a.Cin < 32) {
-        if (!direct_cols_ok(a)) return 0;
-        int OH, OW;
-        conv_out_hw(a, &OH, &OW);
-        const int ppb = direct_cols_ppb(a, (int64_t)a.N * OH * OW, OH * OW, true);
-        return ppb ? OH * OW / ppb : 0;
+// The one routing decision: which kernel conv2d() launches for `a`, with what tiling, and what that kernel can do for the
+// caller.  replan = split-K scratch is available, so a grid that leaves CUs idle may be re-planned (conv2d_split_plan).
+//   precision      the arithmetic that runs (PREC_F32 where the split kernels cannot take the problem)
+//   nt, ksplit     column tile in 32-column units (MFMA and split kernels), split-K factor
+//   structure      split kernels: 0 staged, 1 / 2 A-direct with 128 / 256-row tiles; -1 elsewhere
+//   tap_reuse      the tap-reuse instantiation of the 256-row kernel
+//   fuses_gn       the launch can apply GroupNorm + SiLU to its input itself (a.gn_scale / a.gn_shift)
+//   stats_chunks   chunks per sample it can emit output statistics with (0 = it cannot: the caller runs gn_stats on the output)
+//   scratch_bytes  split-K workspace it needs;  launches: kernels per call (2 = with the split-K reduction);  M = N * OH * OW
+ConvRoute conv2d_route(const ConvArgs& a, bool replan) {
+    ConvRoute r;
+    conv_out_hw(a, &r.OH, &r.OW);
+    r.M = (int64_t)a.N * r.OH * r.OW;
+    const int ohw = r.OH * r.OW, Ktot = a.ks * a.ks * a.Cin;
+    // split-bf16 arithmetic requested and usable for this problem?  (Until the A-direct kernel was software-pipelined, grids
+    // of at most one block per CU were faster on the fp32 kernel and stayed there; now the 128-row A-direct kernel ties it in
+    // bf16x6 and beats it in the 3-product modes on those layers — tools/bench_conv.py 0 31 30 with DSD_SHAPES=small.)
+    r.precision = a.precision == PREC_F32 || !conv2d_split_eligible(a) ? PREC_F32 : a.precision;
+    r.nt = pick_nt(a.Cout, cdiv(r.M, BM), r.precision, a.lanes);
+    if (a.w_subpixel) {   // the caller built the phase weights because conv2d_subpixel_ok() chose this form: one kernel, one tile width
+        r.family = CONV_SUBPIXEL;
+        r.precision = PREC_BF16X6;
+        r.nt = 5;
+        r.structure = 2;
+        r.tap_reuse = true;
+        r.stats_chunks = conv2d_subpixel_shape_ok(a) ? 4 * a.H * a.W / (2 * BM) : 0;   // (phase, 256-pixel chunk)
+        return r;
     }
-    if (a.out_nchw) return 0;
-    if (a.w_subpixel) return conv2d_subpixel_shape_ok(a) ? 4 * a.H * a.W / (2 * BM) : 0;   // (phase, 256-pixel chunk)
-    if (conv2d_wino_eligible(a)) return conv2d_wino_stats_chunks(a);
-    int OH, OW;
-    conv_out_hw(a, &OH, &OW);
-    const int64_t M = (int64_t)a.N * OH * OW;
-    const int tm = cdiv(M, BM);
-    const int pr = effective_precision(a, tm);
-    if (pr == PREC_F32) return 0;
-    const int nt0 = pick_nt(a.Cout, tm, pr, a.lanes);
-    int nt = nt0, ks = 1, ad = 0;
-    conv2d_split_plan(a, nt, &nt, &ks, &ad);
-    if (ks > 1 || (ad == 1 && nt >= 4)) return 0;   // (128-row kernels with >= 4 column tiles have no registers for it)
-    // Without split-K no scratch is planned, and conv2d() then launches the layer with allow_split = false, which keeps the
-    // default structure: statistics only when that launch tiles the rows the same way (the f = 8 VAE's 64x64 layers do not)
-    int nt_l = nt0, ks_l = 1, ad_l = 0;
-    conv2d_split_plan(a, nt0, &nt_l, &ks_l, &ad_l, false);
-    if (ad_l != ad || (ad_l == 1 && nt_l >= 4)) return 0;
-    const int rows = ad == 2 ? 2 * BM : BM;
-    const int ohw = OH * OW;
-    return ohw % rows == 0 ? ohw / rows : 0;
-}
-
-bool conv2d_fuses_gn(const ConvArgs& a) {
-    if (a.w_subpixel) return false;
-    if (a.Cin % 4 != 0 || a.ks * a.ks * a.Cin < 32 || a.precision != PREC_BF16X6 || a.w_split == nullptr) return false;
-    static const bool off = getenv("DSD_NO_GN_FUSE") != nullptr;   // A/B
-    if (off || conv2d_wino_eligible(a)) return false;
-    int OH, OW;
-    conv_out_hw(a, &OH, &OW);
-    const int tm = cdiv((int64_t)a.N * OH * OW, BM);
-    if (effective_precision(a, tm) != PREC_BF16X6) return false;
-    int nt = pick_nt(a.Cout, tm, PREC_BF16X6, a.lanes), ks = 1, ad = 0;
-    conv2d_split_plan(a, nt, &nt, &ks, &ad, true);
-    return conv2d_split_tr(a, nt, ks, ad);
-}
-
-void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt_out, int* ks_out, bool allow_split) {
-    int OH, OW;
-    conv_out_hw(a, &OH, &OW);
-    const int tm = cdiv((int64_t)a.N * OH * OW, BM);
-    const int pr = effective_precision(a, tm);
-    int nt = pick_nt(a.Cout, tm, pr, a.lanes), ks = 1, ad = -1;
-    if (pr != PREC_F32) conv2d_split_plan(a, nt, &nt, &ks, &ad, allow_split);
-    *structure = ad;
-    *nt_out = nt;
-    *ks_out = ks;
-}
-
-const char* conv2d_variant(const ConvArgs& a) {
-    const int Ktot = a.ks * a.ks * a.Cin;
-    if (a.Cin % 4 != 0 || Ktot < 32) {
-        if (a.Cout % 4 == 0 && a.Cout / 4 <= 256 && Ktot <= 9 && !a.out_nchw && (!a.emb || a.emb_stride % 4 == 0)) return "conv_direct_cols";
-        return (a.Cout % 4 == 0 && (size_t)Ktot * a.Cout * 4 <= DIRECT_LDS_MAX) ? "conv_direct_lds" : "conv_scalar";
+    if (a.Cin % 4 != 0 || Ktot < 32) {   // small K: the first layers
+        if (a.Cout % 4 == 0 && a.Cout / 4 <= 256 && Ktot <= 9 && !a.out_nchw && (!a.emb || a.emb_stride % 4 == 0)) {
+            r.family = CONV_DIRECT_COLS;
+            const int ppb = direct_cols_ppb(a, r.M, ohw, true);
+            r.stats_chunks = ppb ? ohw / ppb : 0;
+        } else {
+            r.family = a.Cout % 4 == 0 && (size_t)Ktot * a.Cout * sizeof(float) <= DIRECT_LDS_MAX ? CONV_DIRECT_LDS : CONV_SCALAR;
+        }
+        return r;
     }
-    if (a.w_subpixel) return "conv_bf16x6<5>/tr+subpixel";   // (conv2d_subpixel: one kernel, one tile width)
-    int OH, OW;
-    conv_out_hw(a, &OH, &OW);
-    static const char* names[4][6] = {{"", "conv_mfma<1>", "conv_mfma<2>", "conv_mfma<3>", "conv_mfma<4>", "conv_mfma<5>"},
-                                      {"", "conv_bf16x3<1>", "conv_bf16x3<2>", "conv_bf16x3<3>", "conv_bf16x3<4>", "conv_bf16x3<5>"},
-                                      {"", "conv_bf16x6<1>", "conv_bf16x6<2>", "conv_bf16x6<3>", "conv_bf16x6<4>", "conv_bf16x6<5>"},
-                                      {"", "conv_f16x3<1>", "conv_f16x3<2>", "conv_f16x3<3>", "conv_f16x3<4>", "conv_f16x3<5>"}};
-    const int tm = cdiv((int64_t)a.N * OH * OW, BM);
-    const int pr = effective_precision(a, tm);
-    int nt = pick_nt(a.Cout, tm, pr, a.lanes), ks = 1, ad = 2;
-    if (pr == PREC_BF16X6 && conv2d_wino_eligible(a)) return "conv_wino_bf16x6";
-    if (pr == PREC_F32) return names[pr][nt];
-    conv2d_split_plan(a, nt, &nt, &ks, &ad);
-    // the 256-row A-direct kernel keeps the plain name; the other structures and split-K runs are separate kinds, so that a
-    // kind's average launch time is one kernel's (bench.py roofline vs the rocprofv3 kernel trace)
-    static std::string pool[4][6][3][2][2];
-    const bool tr = conv2d_split_tr(a, nt, ks, ad);   // tap reuse through LDS: an instantiation (kernel symbol) of its own
-    std::string& n = pool[pr][nt][ad][ks > 1][tr];
+    if (r.precision == PREC_BF16X6 && conv2d_wino_eligible(a)) {
+        r.family = CONV_WINO;
+        r.stats_chunks = conv2d_wino_stats_chunks(a);
+        return r;
+    }
+    if (r.precision == PREC_F32) {
+        // buffer-load kernel when the operands are addressable with 32-bit byte offsets
+        const int64_t x_bs = a.x_bs >= 0 ? a.x_bs : (int64_t)a.H * a.W * a.Cin;
+        const int64_t xb = ((int64_t)(a.N - 1) * x_bs + (int64_t)a.H * a.W * a.Cin) * 4, wb = (int64_t)a.Cout * Ktot * 4;
+        r.family = a.Cin % BK == 0 && xb < 0xFFFFFF00ll && wb < 0xFFFFFF00ll && conv_variant(a) == 0 ? CONV_MFMA_BUF : CONV_MFMA;
+        return r;
+    }
+    r.family = CONV_SPLIT;
+    // the plan a launch with scratch gets (p) and the one a launch without it gets (d): default structure and tile width, unsplit
+    int nt_p, ks_p, ad_p, nt_d, ks_d, ad_d;
+    conv2d_split_plan(a, r.nt, &nt_p, &ks_p, &ad_p, true);
+    conv2d_split_plan(a, r.nt, &nt_d, &ks_d, &ad_d, false);
+    r.nt = replan ? nt_p : nt_d;
+    r.ksplit = replan ? ks_p : ks_d;
+    r.structure = replan ? ad_p : ad_d;
+    r.launches = r.ksplit > 1 ? 2 : 1;
+    r.scratch_bytes = r.ksplit > 1 ? (size_t)r.ksplit * r.M * a.Cout * sizeof(float) : 0;
+    r.tap_reuse = conv2d_split_tr(a, r.nt, r.ksplit, r.structure);   // tap reuse through LDS: an instantiation (kernel symbol) of its own
+    // What the kernel offers the caller is answered for BOTH plans and granted only where they agree: the planner asks before it
+    // knows whether scratch will be passed (none is when plan p does not split), and the answer decides what the network fuses.
+    static const bool no_gn_fuse = getenv("DSD_NO_GN_FUSE") != nullptr;   // A/B
+    r.fuses_gn = !no_gn_fuse && r.tap_reuse && conv2d_split_tr(a, nt_p, ks_p, ad_p);
+    // statistics epilogue: not in the split-K form (the reduction kernel writes the output), not in the 128-row kernels with
+    // >= 4 column tiles (no registers for it), and only when both plans tile the rows alike (the f = 8 VAE's 64x64 layers do not)
+    const int rows = ad_p == 2 ? 2 * BM : BM;
+    if (!a.out_nchw && ks_p == 1 && ad_d == ad_p && !(ad_p == 1 && (nt_p >= 4 || nt_d >= 4)) && ohw % rows == 0) r.stats_chunks = ohw / rows;
+    return r;
+}
+
+// The 256-row A-direct kernel keeps the plain name; the other structures, split-K runs, tap reuse and the instantiation that
+// also applies GroupNorm + SiLU to its input (gn_applied) are kinds of their own, so that a kind's average launch time is one
+// kernel's (bench.py roofline vs the rocprofv3 kernel trace)
+const char* conv2d_route_name(const ConvRoute& r, bool gn_applied) {
+    switch (r.family) {
+        case CONV_DIRECT_COLS: return "conv_direct_cols";
+        case CONV_DIRECT_LDS: return "conv_direct_lds";
+        case CONV_SCALAR: return "conv_scalar";
+        case CONV_SUBPIXEL: return "conv_bf16x6<5>/tr+subpixel";
+        case CONV_WINO: return "conv_wino_bf16x6";
+        default: break;
+    }
+    static const char* base[4] = {"conv_mfma", "conv_bf16x3", "conv_bf16x6", "conv_f16x3"};
+    static std::string pool[4][6][4][2][2][2];
+    const int ad = r.family == CONV_SPLIT ? r.structure : 3;
+    const bool gn = r.tap_reuse && gn_applied;
+    std::string& n = pool[r.precision][r.nt][ad][r.ksplit > 1][r.tap_reuse][gn];
     if (n.empty())
-        n = std::string(names[pr][nt]) + (ad == 2 ? "" : (ad == 1 ? "/r128" : "/staged")) + (ks > 1 ? "+splitk" : "") + (tr ? "/tr" : "");
-    if (tr && a.gn_scale) {   // the instantiation that also applies GroupNorm + SiLU to its input: a kind (kernel symbol) of its own
-        static std::string gnpool[6];   // per tile width (the 128- and the 160-column tile are different kernels)
-        std::string& gn = gnpool[nt];
-        if (gn.empty()) gn = n + "+gn";
-        return gn.c_str();
-    }
+        n = std::string(base[r.precision]) + "<" + std::to_string(r.nt) + ">" + (ad >= 2 ? "" : (ad == 1 ? "/r128" : "/staged")) +
+            (r.ksplit > 1 ? "+splitk" : "") + (r.tap_reuse ? "/tr" : "") + (gn ? "+gn" : "");
     return n.c_str();
+}
+
+template <int NT> static void launch_mfma(bool buf, dim3 grid, hipStream_t s, const ConvP& p) {
+    if (buf)
+        hipLaunchKernelGGL(conv_mfma_buf_kernel<NT>, grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(conv_mfma_kernel<NT>, grid, dim3(256), 0, s, p);
 }
 
 void conv2d(ConvArgs a, hipStream_t s) {
     DSD_CHECK(a.ks == 1 || a.ks == 3, "conv2d: kernel size %d unsupported", a.ks);
-    DSD_CHECK(a.gn_scale == nullptr || conv2d_fuses_gn(a), "conv2d: GroupNorm coefficients given, but this problem does not run on the kernel that applies them");
     DSD_CHECK(a.stride == 1 || a.stride == 2, "conv2d: stride %d unsupported", a.stride);
-    if (a.w_subpixel) {   // the caller built the phase weights because conv2d_subpixel_ok() chose this form
-        if ((int64_t)a.N * a.H * a.W > 0 && a.Cout > 0) conv2d_subpixel(a, s);
-        return;
-    }
+    const ConvRoute r = conv2d_route(a, a.scratch != nullptr);   // a caller without scratch (never the planned graph) gets the unsplit configuration
+    DSD_CHECK(a.gn_scale == nullptr || r.fuses_gn, "conv2d: GroupNorm coefficients given, but this problem does not run on the kernel that applies them");
+    DSD_CHECK(r.M < (1ll << 31) && r.M * std::max(a.Cout, a.Cin) < (1ll << 40), "conv2d: problem too large");
+    if (r.M == 0 || a.Cout == 0) return;
+    if (r.family == CONV_SUBPIXEL) return conv2d_subpixel(a, s);
+    if (r.family == CONV_WINO) return conv2d_wino(a, s);
+    if (r.family == CONV_SPLIT) return conv2d_split(a, r.nt, r.ksplit, r.structure, s);
     ConvP p{};
     p.x = a.x; p.w = a.w; p.bias = a.bias; p.emb = a.emb; p.res = a.res; p.y = a.y;
     p.N = a.N; p.H = a.H; p.W = a.W; p.Cin = a.Cin; p.Cout = a.Cout; p.ks = a.ks; p.stride = a.stride;
@@ -787,86 +771,50 @@ void conv2d(ConvArgs a, hipStream_t s) {
     p.x_bs = a.x_bs >= 0 ? a.x_bs : (int64_t)a.H * a.W * a.Cin;
     p.IHg = a.ups ? a.H * 2 : a.H;
     p.IWg = a.ups ? a.W * 2 : a.W;
-    conv_out_hw(a, &p.OH, &p.OW);
+    p.OH = r.OH; p.OW = r.OW;
     p.ohw = p.OH * p.OW;
-    const int64_t M64 = (int64_t)a.N * p.ohw;
-    DSD_CHECK(M64 < (1ll << 31) && M64 * std::max(a.Cout, a.Cin) < (1ll << 40), "conv2d: problem too large");
-    p.M = (int)M64;
+    p.M = (int)r.M;
     p.Ktot = a.ks * a.ks * a.Cin;
     p.cchunks = cdiv(a.Cin, BK);
     p.tiles_m = cdiv(p.M, BM);
-    if (p.M == 0 || a.Cout == 0) return;
-
-    if (a.Cin % 4 != 0 || p.Ktot < 32) {
-        const size_t lds = (size_t)p.Ktot * a.Cout * sizeof(float);
-        if (direct_cols_ok(a)) {
-            const int W4 = a.Cout / 4, rpi = 256 / W4;
-            if (a.stats) {
-                const int ppb = direct_cols_ppb(a, p.M, p.ohw, true);
-                DSD_CHECK(ppb > 0 && p.ohw / ppb == a.stats_chunks, "conv2d: statistics chunks %d do not match this launch", a.stats_chunks);
-                hipLaunchKernelGGL((conv_direct_cols_kernel<9, true>), dim3(p.M / ppb), dim3(rpi * W4), 0, s, p, W4, ppb, a.stats, a.stats_chunks);
-            } else {
-                const int ppb = direct_cols_ppb(a, p.M, p.ohw, false);
-                hipLaunchKernelGGL((conv_direct_cols_kernel<9, false>), dim3(cdiv(p.M, ppb)), dim3(rpi * W4), 0, s, p, W4, ppb, nullptr, 0);
-            }
-            check_launch("conv_direct_cols");
-        } else if (a.Cout % 4 == 0 && lds <= DIRECT_LDS_MAX) {
-            // (beyond the 64 KB default the dynamic LDS size has to be allowed once per process; the latent U-Net's first layer,
-            // 6 -> 320 channels, needs 69 KB and used to fall to the scalar kernel: ~1 ms per evaluation)
-            static const hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_lds_kernel),
-                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)DIRECT_LDS_MAX);
-            DSD_CHECK(lds_attr == hipSuccess, "hipFuncSetAttribute(conv_direct_lds_kernel): %s", hipGetErrorString(lds_attr));
-            hipLaunchKernelGGL(conv_direct_lds_kernel, dim3(cdiv(p.M, 64)), dim3(256), lds, s, p);
-            check_launch("conv_direct_lds");
+    if (r.family == CONV_DIRECT_COLS) {
+        const int W4 = a.Cout / 4, rpi = 256 / W4;
+        if (a.stats) {
+            const int ppb = direct_cols_ppb(a, p.M, p.ohw, true);
+            DSD_CHECK(ppb > 0 && r.stats_chunks == a.stats_chunks, "conv2d: statistics chunks %d do not match this launch", a.stats_chunks);
+            hipLaunchKernelGGL((conv_direct_cols_kernel<9, true>), dim3(p.M / ppb), dim3(rpi * W4), 0, s, p, W4, ppb, a.stats, a.stats_chunks);
         } else {
-            const int blocks = (int)std::min<int64_t>(((int64_t)p.M * a.Cout + 255) / 256, 1 << 20);
-            hipLaunchKernelGGL(conv_scalar_kernel, dim3(blocks), dim3(256), 0, s, p);
-            check_launch("conv_scalar");
+            const int ppb = direct_cols_ppb(a, p.M, p.ohw, false);
+            hipLaunchKernelGGL((conv_direct_cols_kernel<9, false>), dim3(cdiv(p.M, ppb)), dim3(rpi * W4), 0, s, p, W4, ppb, nullptr, 0);
         }
-        return;
-    }
-    const int prec = effective_precision(a, p.tiles_m);
-    int nt = pick_nt(a.Cout, p.tiles_m, prec, a.lanes);
-    if (prec == PREC_BF16X6 && conv2d_wino_eligible(a)) {
-        conv2d_wino(a, s);
-        return;
-    }
-    if (prec != PREC_F32) {
-        int ks = 1, ad = 0;
-        // a caller without scratch (never the planned graph) gets the unsplit configuration
-        conv2d_split_plan(a, nt, &nt, &ks, &ad, a.scratch != nullptr);
-        conv2d_split(a, nt, ks, ad, s);
-        return;
-    }
-    p.tiles_n = cdiv(a.Cout, nt * 32);
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-    {
-        // default path: buffer-load kernel when the operands are addressable with 32-bit byte offsets
-        const int64_t xb = ((int64_t)(a.N - 1) * p.x_bs + (int64_t)a.H * a.W * a.Cin) * 4;
-        const int64_t wb = (int64_t)a.Cout * p.Ktot * 4;
-        const bool buf_ok = a.Cin % BK == 0 && xb < 0xFFFFFF00ll && wb < 0xFFFFFF00ll && p.x_bs >= 0;
-        if (buf_ok && (conv_variant(a) == 0)) {
-            p.x_bytes = (unsigned)xb;
-            p.w_bytes = (unsigned)wb;
-            switch (nt) {
-                case 1: hipLaunchKernelGGL(conv_mfma_buf_kernel<1>, grid, dim3(256), 0, s, p); break;
-                case 2: hipLaunchKernelGGL(conv_mfma_buf_kernel<2>, grid, dim3(256), 0, s, p); break;
-                case 3: hipLaunchKernelGGL(conv_mfma_buf_kernel<3>, grid, dim3(256), 0, s, p); break;
-                case 4: hipLaunchKernelGGL(conv_mfma_buf_kernel<4>, grid, dim3(256), 0, s, p); break;
-                default: hipLaunchKernelGGL(conv_mfma_buf_kernel<5>, grid, dim3(256), 0, s, p); break;
-            }
-            check_launch("conv_mfma_buf");
-            return;
+        check_launch("conv_direct_cols");
+    } else if (r.family == CONV_DIRECT_LDS) {
+        // (beyond the 64 KB default the dynamic LDS size has to be allowed once per process; the latent U-Net's first layer,
+        // 6 -> 320 channels, needs 69 KB and used to fall to the scalar kernel: ~1 ms per evaluation)
+        static const hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_lds_kernel),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)DIRECT_LDS_MAX);
+        DSD_CHECK(lds_attr == hipSuccess, "hipFuncSetAttribute(conv_direct_lds_kernel): %s", hipGetErrorString(lds_attr));
+        hipLaunchKernelGGL(conv_direct_lds_kernel, dim3(cdiv(p.M, 64)), dim3(256), (size_t)p.Ktot * a.Cout * sizeof(float), s, p);
+        check_launch("conv_direct_lds");
+    } else if (r.family == CONV_SCALAR) {
+        const int blocks = (int)std::min<int64_t>(((int64_t)p.M * a.Cout + 255) / 256, 1 << 20);
+        hipLaunchKernelGGL(conv_scalar_kernel, dim3(blocks), dim3(256), 0, s, p);
+        check_launch("conv_scalar");
+    } else {   // fp32 MFMA
+        const bool buf = r.family == CONV_MFMA_BUF;
+        p.tiles_n = cdiv(a.Cout, r.nt * 32);
+        p.x_bytes = buf ? (unsigned)((((int64_t)(a.N - 1) * p.x_bs + (int64_t)a.H * a.W * a.Cin)) * 4) : 0;
+        p.w_bytes = buf ? (unsigned)((int64_t)a.Cout * p.Ktot * 4) : 0;
+        const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
+        switch (r.nt) {
+            case 1: launch_mfma<1>(buf, grid, s, p); break;
+            case 2: launch_mfma<2>(buf, grid, s, p); break;
+            case 3: launch_mfma<3>(buf, grid, s, p); break;
+            case 4: launch_mfma<4>(buf, grid, s, p); break;
+            default: launch_mfma<5>(buf, grid, s, p); break;
         }
+        check_launch(buf ? "conv_mfma_buf" : "conv_mfma");
     }
-    switch (nt) {
-        case 1: hipLaunchKernelGGL(conv_mfma_kernel<1>, grid, dim3(256), 0, s, p); break;
-        case 2: hipLaunchKernelGGL(conv_mfma_kernel<2>, grid, dim3(256), 0, s, p); break;
-        case 3: hipLaunchKernelGGL(conv_mfma_kernel<3>, grid, dim3(256), 0, s, p); break;
-        case 4: hipLaunchKernelGGL(conv_mfma_kernel<4>, grid, dim3(256), 0, s, p); break;
-        default: hipLaunchKernelGGL(conv_mfma_kernel<5>, grid, dim3(256), 0, s, p); break;
-    }
-    check_launch("conv_mfma");
 }
 
 }  // namespace dsd

@@ -170,7 +170,6 @@ static bool tr_nt_ok(int nt) {
 static bool conv_tr_ok(const SplitP& p) {
     return tr_enabled() && !p.stamps && tr_shape_ok(p.ks, p.stride, p.pad, p.OW, p.IWg, p.OH, p.IHg, p.ksplit, p.out_nchw, p.ohw, p.M, p.Cin);
 }
-// would conv2d_split(a, nt, ksplit, ad) run the tap-reuse instantiation?  (conv2d_variant: its launches are a kind of their own)
 // the planner's rule for the sub-pixel form (conv2d_subpixel_ok): the tap-reuse kernel on the low-resolution map
 bool conv2d_subpixel_shape_ok(const ConvArgs& a) {
     if (!(tr_enabled() && !a.stamps && a.ks == 3 && a.stride == 1 && a.ups && a.pad_lo < 0 && a.pad_total < 0 && !a.out_nchw &&
@@ -216,6 +215,7 @@ void conv2d_subpixel(const ConvArgs& a, hipStream_t s) {
     check_launch("conv_split_subpixel");
 }
 
+// would conv2d_split(a, nt, ksplit, ad) run the tap-reuse instantiation?  (its launches are a kind of their own: conv2d_route_name)
 bool conv2d_split_tr(const ConvArgs& a, int nt, int ksplit, int ad) {
     if (!(tr_enabled() && !a.stamps && a.precision == PREC_BF16X6 && ad == 2 && tr_nt_ok(nt))) return false;
     int OH, OW;
@@ -254,7 +254,7 @@ static void launch_split(const SplitP& p, int nt, hipStream_t s, int ad) {   // 
         check_launch("conv_split_ad2_tr4");
         return;
     }
-    if (p.gn_scale) fail("conv2d: GroupNorm coefficients given for a problem the tap-reuse kernel does not take (ask conv2d_fuses_gn first)");
+    if (p.gn_scale) fail("conv2d: GroupNorm coefficients given for a problem the tap-reuse kernel does not take (ask ConvRoute::fuses_gn first)");
     if (ad == 2 && conv_dma_enabled() && nt == 5 && NP == 3 && !F16) {
         hipLaunchKernelGGL((conv_split_ad_kernel<5, 3, false, 2, true>), grid, dim3(256), 0, s, p);
         check_launch("conv_split_ad2_dma");
@@ -388,7 +388,7 @@ void conv2d_split(const ConvArgs& a, int nt, int ksplit, int ad, hipStream_t s) 
     p.ksplit = 1;
     if (ad >= 1 && ksplit > 1) {
         DSD_CHECK(a.scratch && (size_t)ksplit * p.M * a.Cout * sizeof(float) <= a.scratch_bytes,
-                  "conv2d: split-K x%d needs %zu bytes of scratch (conv2d_scratch_bytes), got %zu", ksplit,
+                  "conv2d: split-K x%d needs %zu bytes of scratch (ConvRoute::scratch_bytes), got %zu", ksplit,
                   (size_t)ksplit * p.M * a.Cout * sizeof(float), a.scratch_bytes);
         p.ksplit = ksplit;
         p.partial = a.scratch;
@@ -404,7 +404,7 @@ void conv2d_split(const ConvArgs& a, int nt, int ksplit, int ad, hipStream_t s) 
         const int rows = ad == 2 ? 2 * SBM : SBM;
         DSD_CHECK(p.ksplit == 1 && !a.out_nchw && p.ohw % rows == 0 && p.ohw / rows == a.stats_chunks && !(ad == 1 && nt >= 4),
                   "conv2d: output statistics requested with %d chunks but the kernel (tile %d rows, split-K x%d, ohw %d) cannot "
-                  "emit them (conv2d_stats_chunks)", a.stats_chunks, rows, p.ksplit, p.ohw);
+                  "emit them (ConvRoute::stats_chunks)", a.stats_chunks, rows, p.ksplit, p.ohw);
         p.stats = a.stats;
         p.stats_chunks = a.stats_chunks;
     }

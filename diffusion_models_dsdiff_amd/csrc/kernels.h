@@ -22,7 +22,6 @@ struct ConvArgs {
     int y_ld = 0;               // row stride of y in elements (0 -> Cout): lets a conv write a channel slice of a wider
                                 // NHWC tensor, e.g. the decoder's concat buffer (torch.cat([h, skip]) never copied)
     int out_nchw = 0;           // store as [N,Cout,OH,OW] (final layer with out_channels > 1)
-    int OH = 0, OW = 0;         // filled by conv2d()
     int variant = -1;           // kernel variant override (-1 = default / env DSD_CONV_VARIANT)
     int precision = 0;          // PREC_F32 | PREC_BF16X3 | PREC_BF16X6 (conv_split.hip)
     const void* w_split = nullptr;  // [3][Cout][ks*ks*Cin] bf16 pieces of w (needed for the split precisions)
@@ -31,17 +30,17 @@ struct ConvArgs {
     // (subpixel_weights); when present, conv2d() runs the layer as four 2x2 convolutions on the low-resolution map
     const void* w_subpixel = nullptr;
     int* ovf = nullptr;             // device flag set by the f16x3 kernels when an operand exceeds the fp16 range
-    float* scratch = nullptr;       // split-K partial sums (conv2d_scratch_bytes() bytes); without it small grids run unsplit
+    float* scratch = nullptr;       // split-K partial sums (ConvRoute::scratch_bytes); without it small grids run unsplit
     size_t scratch_bytes = 0;
     // GroupNorm statistics of the OUTPUT, accumulated in the epilogue: stats[n][chunk][co][2] doubles (GnSrc layout),
-    // stats_chunks = conv2d_stats_chunks() chunks per sample; nullptr = not wanted
+    // stats_chunks = ConvRoute::stats_chunks chunks per sample; nullptr = not wanted
     double* stats = nullptr;
     int stats_chunks = 0;
     // diagnostic build of the dominant kernel only (tools/conv_stamps.py): 8 int64 per workgroup — (s_memtime,
     // s_memrealtime) at entry, in front of the k-loop, behind it, and after the epilogue
     long long* stamps = nullptr;
     int diag = 0;   // what-if bits (conv_split.hip, DIAG)
-    // GroupNorm + SiLU of the INPUT applied while the filter rows are staged (tap-reuse kernel only: conv2d_fuses_gn()):
+    // GroupNorm + SiLU of the INPUT applied while the filter rows are staged (tap-reuse kernel only: ConvRoute::fuses_gn):
     // x is then the tensor BEFORE the normalisation and gn_scale / gn_shift are gn_finalize's per-(sample, channel)
     // coefficients [N][Cin]; the separate apply pass over HBM disappears
     const float* gn_scale = nullptr;
@@ -60,9 +59,12 @@ inline void conv_out_hw(const ConvArgs& a, int* OH, int* OW) {
     *OH = (IHg + pt - a.ks) / a.stride + 1;
     *OW = (IWg + pt - a.ks) / a.stride + 1;
 }
-// chunks per sample the kernel conv2d() will launch for these arguments can emit output statistics with (0 = it cannot:
-// the caller runs gn_stats on the output instead)
-int conv2d_stats_chunks(const ConvArgs& a);
+// What conv2d() launches for a set of arguments and what that launch offers its caller (the fields: conv.hip, conv2d_route)
+enum ConvFamily { CONV_DIRECT_COLS, CONV_DIRECT_LDS, CONV_SCALAR, CONV_SUBPIXEL, CONV_WINO, CONV_MFMA_BUF, CONV_MFMA, CONV_SPLIT };
+struct ConvRoute { ConvFamily family = CONV_MFMA; int precision = 0, nt = 1, ksplit = 1, structure = -1; bool tap_reuse = false, fuses_gn = false;
+                   int stats_chunks = 0, launches = 1; size_t scratch_bytes = 0; int OH = 0, OW = 0; int64_t M = 0; };
+ConvRoute conv2d_route(const ConvArgs& a, bool replan);   // replan: split-K scratch will be passed; conv2d(a) launches conv2d_route(a, a.scratch != nullptr)
+const char* conv2d_route_name(const ConvRoute& r, bool gn_applied);
 // out = Conv3x3(SiLU(x * scale + shift)) with ONE output channel (conv_out1.hip): x NHWC [N,H,W,C] BEFORE the normalisation,
 // scale / shift = gn_finalize's coefficients [N][C], w = [3][3][C] (the packed OHWI weight of a 1-channel conv), y = [N,H,W]
 struct ConvOut1Args {
@@ -94,16 +96,12 @@ void conv2d_subpixel(const ConvArgs& a, hipStream_t s);
 // process-wide switch of the tap-reuse kernel's MFMA shape (0: 32x32x16, 1: 16x16x32 — conv_tr16.hip); A/B runs in one process
 void conv2d_set_mfma16(int on);
 int conv2d_get_mfma16();
-bool conv2d_fuses_gn(const ConvArgs& a);   // conv2d(a) can apply GroupNorm + SiLU to its input itself (a.gn_scale / a.gn_shift)
 void conv2d_split(const ConvArgs& a, int nt, int ksplit, int structure, hipStream_t s);
 double conv2d_flops(const ConvArgs& a);        // the layer's algorithmic count (3x3 over the upsampled map for an upsample layer)
 double conv2d_exec_flops(const ConvArgs& a);   // what the launched kernel multiplies (4/9 of that in the sub-pixel form)
-size_t conv2d_scratch_bytes(const ConvArgs& a);   // workspace conv2d() can use for these arguments (0 = none)
 // N-tile width (in 32-column units) and split-K factor the split-precision path runs this problem with; nt_default is the
 // width the generic cost model (conv.hip pick_nt) would take
 void conv2d_split_plan(const ConvArgs& a, int nt_default, int* nt, int* ksplit, int* structure = nullptr, bool allow_split = true);
-const char* conv2d_variant(const ConvArgs& a);
-void conv2d_plan_query(const ConvArgs& a, int* structure, int* nt, int* ksplit, bool allow_split = true);   // what conv2d() would launch (allow_split: scratch present)   // name of the kernel conv2d() will launch for these arguments
 void pack_ohwi(const float* w_oihw, float* w_ohwi, int Cout, int Cin, int ks, hipStream_t s);
 // conv_wino.hip: 3x3 stride-1 convolution as F(2,3) along the width (1.5x fewer MFMAs), bf16x6 arithmetic
 bool conv2d_wino_shape_ok(const ConvArgs& a);      // could run there if it had packed weights

@@ -898,21 +898,26 @@ struct Builder {
                 a.w_wino = derived(name + "#wino", wname, WF_BF16_PIECES, wino_packed_bytes(cout, x.c),
                                    [&](void* buf) { wino_pack_weights(a.w, cout, x.c, buf, ps); });
         }
-        if (o.gn) {   // the kernel applies GroupNorm + SiLU to x itself (the caller asked can_fuse_gn first)
-            a.gn_scale = a.gn_shift = reinterpret_cast<const float*>(this);   // non-null placeholders for the plan-time queries
-            DSD_CHECK(o.gn->act == ACT_SILU && conv2d_fuses_gn(a), "conv %s: cannot take the GroupNorm of its input", name.c_str());
+        // everything the route depends on is set before it is asked; pointers the launch fills in are non-null placeholders
+        const bool nchw = to_out && cout > 1;
+        a.y_ld = y_ld;
+        a.out_nchw = nchw ? 1 : 0;
+        if (o.emb && o.emb->valid) {
+            a.emb = reinterpret_cast<const float*>(this);
+            a.emb_stride = o.emb->stride;
         }
+        if (o.gn) a.gn_scale = a.gn_shift = reinterpret_cast<const float*>(this);   // (the caller asked can_fuse_gn first)
+        const ConvRoute route = plan_route(a);
+        if (o.gn) DSD_CHECK(o.gn->act == ACT_SILU && route.fuses_gn, "conv %s: cannot take the GroupNorm of its input", name.c_str());
         const size_t gsc = o.gn ? o.gn->scoff : 0, gsh = o.gn ? o.gn->shoff : 0;
         const bool has_gn = o.gn != nullptr;
-        const size_t skb = conv2d_scratch_bytes(a);            // split-K partial tiles of the small-grid layers
+        const size_t skb = route.scratch_bytes;                // split-K partial tiles of the small-grid layers
         const size_t skoff = skb ? alloc_raw(skb) : 0;
         // GroupNorm statistics of the output from the epilogue, when the kernel this problem gets can emit them
         size_t stoff = 0;
         int stchunks = 0;
         if (o.want_stats && !to_out && hd->fuse_gn_stats) {
-            ConvArgs q = a;
-            q.x_bs = -1;
-            stchunks = conv2d_stats_chunks(q);
+            stchunks = route.stats_chunks;
             if (stchunks > 0) {
                 StatRef sr;
                 sr.chunks = stchunks; sr.c0 = 0; sr.c = cout;
@@ -925,7 +930,6 @@ struct Builder {
         EmbRef e;
         if (o.emb) e = *o.emb;
         dsd_handle* h = hd;
-        const bool nchw = to_out && cout > 1;
         plan.flops += conv2d_flops(a);
         op([=](hipStream_t s) {
             ConvArgs c = a;
@@ -957,7 +961,7 @@ struct Builder {
                 c.gn_shift = h->at<float>(gsh);
             }
             conv2d(c, s);
-        }, skb ? 2 : 1, conv2d_variant(a), conv2d_exec_flops(a),
+        }, route.launches, conv2d_route_name(route, has_gn), conv2d_exec_flops(a),
            4.0 * ((double)x.n * x.h * x.w * x.c + (double)cout * x.c * ks * ks + (double)x.n * OH * OW * cout * (has_res ? 2 : 1)));
         if (skb) release_raw(skoff, skb);
         return y;
@@ -1092,7 +1096,13 @@ struct Builder {
         a.lanes = plan_lanes((int64_t)x.n * x.h * x.w);
         a.w_split = this;   // (non-null: only the shape matters here)
         if (hd->use_winograd && conv2d_wino_worthwhile(a)) return false;
-        return conv2d_fuses_gn(a);
+        return plan_route(a).fuses_gn;
+    }
+
+    // the route a planned launch gets: scratch is passed exactly when the re-planned route needs some
+    static ConvRoute plan_route(const ConvArgs& a) {
+        const ConvRoute r = conv2d_route(a, true);
+        return r.scratch_bytes ? r : conv2d_route(a, false);
     }
 
     Tn resample(const Tn& x, bool up) {

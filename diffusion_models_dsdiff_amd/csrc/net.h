@@ -42,7 +42,7 @@ struct Tn {
 };
 
 // A GroupNorm whose statistics are finalised (per-(sample, channel) scale / shift in the arena) but not yet applied: either
-// the apply pass makes a tensor of it, or the consuming convolution applies it while staging its input (conv2d_fuses_gn).
+// the apply pass makes a tensor of it, or the consuming convolution applies it while staging its input (ConvRoute::fuses_gn).
 struct GnRef {
     Tn x;
     size_t scoff = 0, shoff = 0, sbytes = 0;

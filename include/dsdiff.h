@@ -512,8 +512,8 @@ int dsd_op_conv2d_prec(const float* x, int N, int H, int W, int Cin, const float
  *   out_nchw        y is [N,Cout,OH,OW] (needs y_ld == Cout)
  *   emb_stride      row stride of emb in elements (0 = Cout): emb[n*emb_stride + co], emb pointing at the layer's first column
  *   no_scratch      launch without split-K workspace (what a caller outside the planned graph does)
- * Outputs: kernel = conv2d_variant() of the arguments that were launched, ksplit = the split-K factor that ran (1 without
- * scratch, whatever the name says).  y is caller-allocated; arguments are validated before anything is launched. */
+ * Outputs: kernel = the name of the kernel that was launched (conv2d_route_name), ksplit = the split-K factor that ran (1
+ * without scratch).  y is caller-allocated; arguments are validated before anything is launched. */
 typedef struct dsd_conv_ex {
     int64_t x_batch_stride;
     int32_t pad_lo, pad_total;

@@ -616,6 +616,119 @@ def gen_temb():
     save("temb", **out)
 
 
+# ------------------------------------------------------------------ convolution routes (the library's own host logic, no reference)
+def headline_convs(batch):
+    """(N, H, W, Cin, Cout, ks, stride, ups) of every convolution of the headline U-Net (configs/v2-1-cddpm-ds-disc.yaml at
+    256 x 256), in the order openaimodel.py builds them"""
+    mc, mult, nres, H = 320, [1, 1, 2, 2, 3, 3], 2, 256
+    out = [(batch, H, H, 1, mc, 3, 1, 0)]
+
+    def res(cin, cout):
+        out.extend([(batch, H, H, cin, cout, 3, 1, 0), (batch, H, H, cout, cout, 3, 1, 0)])
+        if cin != cout:
+            out.append((batch, H, H, cin, cout, 1, 1, 0))
+
+    ch, chans = mc, [mc]
+    for lvl, m in enumerate(mult):
+        for _ in range(nres):
+            res(ch, m * mc)
+            ch = m * mc
+            chans.append(ch)
+        if lvl != len(mult) - 1:
+            out.append((batch, H, H, ch, ch, 3, 2, 0))
+            H //= 2
+            chans.append(ch)
+    res(ch, ch)
+    res(ch, ch)
+    for lvl, m in reversed(list(enumerate(mult))):
+        for i in range(nres + 1):
+            res(ch + chans.pop(), m * mc)
+            ch = m * mc
+            if lvl and i == nres:
+                out.append((batch, H, H, ch, ch, 3, 1, 1))
+                H *= 2
+    out.append((batch, H, H, ch, 1, 3, 1, 0))
+    return list(dict.fromkeys(out))
+
+
+def conv_route_rows():
+    """-> (inputs of the dsd_op_conv2d_gn queries, inputs of the dsd_conv_plan queries): tests/test_conv_routes.py OP_IN / PLAN_IN"""
+    # every shape named in test_conv_args_gpu / test_gn_fused_gpu / test_subpixel_gpu / test_host_logic / test_abi, and the
+    # shapes on which the plan that may split and the launch without scratch disagree about the structure
+    k3 = [(2, 32, 32, 1, 32), (2, 16, 16, 6, 320), (1, 4, 4, 6, 5), (2, 4, 4, 6, 5), (2, 5, 5, 6, 5), (2, 5, 4, 6, 5), (2, 4, 5, 6, 5),
+          (3, 12, 20, 64, 160), (3, 12, 20, 64, 100), (3, 5, 7, 36, 20), (2, 5, 7, 36, 20), (3, 16, 16, 320, 2), (3, 16, 16, 320, 3),
+          (3, 16, 16, 320, 4), (3, 16, 16, 320, 8), (2, 16, 16, 64, 64), (3, 16, 16, 64, 64), (2, 15, 17, 64, 64), (2, 64, 64, 64, 96),
+          (2, 64, 64, 64, 100), (3, 40, 24, 64, 320), (2, 125, 96, 64, 300), (2, 128, 96, 64, 300), (2, 16, 16, 64, 4), (2, 16, 16, 64, 8),
+          (2, 16, 16, 64, 100), (2, 64, 64, 64, 4), (2, 64, 64, 64, 8), (3, 40, 24, 64, 4), (3, 40, 24, 64, 8), (3, 40, 24, 64, 100),
+          (2, 8, 8, 320, 100), (1, 8, 8, 960, 960), (9, 64, 64, 32, 160), (8, 64, 64, 32, 160), (2, 128, 128, 64, 320), (2, 128, 128, 64, 300),
+          (2, 128, 128, 64, 224), (2, 128, 256, 64, 128), (1, 256, 256, 64, 128), (2, 64, 64, 32, 320), (2, 16, 64, 64, 160),
+          (1, 64, 64, 64, 128), (3, 44, 32, 64, 192), (2, 32, 64, 32, 320), (1, 8, 8, 32, 32), (1, 128, 128, 320, 320),
+          (1, 64, 64, 640, 640), (2, 32, 32, 640, 640), (2, 16, 16, 640, 1280), (1, 8, 8, 1280, 1280), (16, 256, 256, 320, 320),
+          (16, 256, 256, 640, 320), (16, 128, 128, 320, 320), (16, 64, 64, 640, 640), (16, 32, 32, 640, 640), (16, 8, 8, 960, 960),
+          (16, 8, 8, 1920, 960), (1, 16, 16, 960, 960), (1, 32, 32, 640, 640), (16, 256, 256, 1, 320), (1, 16, 16, 320, 1),
+          (16, 16, 16, 960, 960), (1, 64, 64, 128, 256), (1, 64, 64, 128, 640), (1, 128, 128, 128, 64), (16, 16, 16, 128, 320)]
+    k1 = [(2, 8, 8, 96, 32), (1, 96, 1, 64, 96), (1, 100, 1, 64, 100), (1, 96, 1, 96, 64), (16, 8, 8, 960, 480), (1, 64, 64, 1280, 256)]
+    shapes = [s + (3,) for s in k3] + [s + (1,) for s in k1]
+    modes = [0] + [p | b for p in (1, 2, 3) for b in (0, 16, 32, 64)] + [2 | 128]
+    geometry = [(1, 0, -1, -1), (1, 0, 0, 1), (2, 0, -1, -1), (2, 0, 0, 1), (1, 1, -1, -1)]   # stride, ups, pad_lo, pad_total
+    op = []
+    for (N, H, W, Cin, Cout, ks) in shapes:
+        wide = (Cout + 40 + 3) // 4 * 4
+        for bits in modes:
+            for stride, ups, plo, ptot in geometry:
+                for nchw in (0, 1):
+                    for es in (0, wide):
+                        for ns in (0, 1):
+                            for gn in (0, 1, 2):
+                                op.append((N, H, W, Cin, Cout, ks, stride, ups, bits, plo, ptot, nchw, es, ns, gn))
+    layers = headline_convs(1) + headline_convs(16)
+    for (N, H, W, Cin, Cout, ks, stride, ups) in layers:     # the headline's layers as the network runs them, in every mode
+        for bits in (0, 1, 2, 3):
+            for ns in (0, 1):
+                for gn in (0, 1, 2):
+                    op.append((N, H, W, Cin, Cout, ks, stride, ups, bits, -1, -1, 0, 0, ns, gn))
+    plan = []
+    for (N, H, W, Cin, Cout, ks) in dict.fromkeys(shapes + [l[:6] for l in layers]):
+        for stride in (1, 2):
+            for p in (0, 1, 2, 3):
+                for b in (0, 16, 32, 64):
+                    for lanes in (0, 256):
+                        plan.append((N, H, W, Cin, Cout, ks, stride, p | b | lanes))
+    return np.asarray(op, dtype=np.int32), np.asarray(plan, dtype=np.int32)
+
+
+def gen_conv_routes():
+    """What the library's convolution launcher decides for ~10^5 argument sets, asked through its two device-free entry points
+    (tests/test_conv_routes.py).  Run it on the tree whose decisions are to be kept: the committed table is that of the commit
+    in front of the conv2d_route refactor (its seven routing functions), with query mode already made device-free.  The
+    `unsplit` column — the name under DSD_NO_SPLITK=1, read once per process — comes from a child process."""
+    import subprocess
+    import tempfile
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_conv_routes import query_op, query_plan
+    op_in, plan_in = conv_route_rows()
+    if len(sys.argv) > 2 and sys.argv[1] == "conv_routes" and sys.argv[2].endswith(".json"):   # the child: names only
+        assert os.environ.get("DSD_NO_SPLITK")
+        json.dump([query_op(r)[1] for r in op_in], open(sys.argv[2], "w"))
+        sys.exit(0)
+    assert "DSD_NO_SPLITK" not in os.environ
+    with tempfile.TemporaryDirectory() as d:
+        tmp = os.path.join(d, "unsplit.json")
+        subprocess.run([sys.executable, os.path.abspath(__file__), "conv_routes", tmp], check=True, env=dict(os.environ, DSD_NO_SPLITK="1"))
+        unsplit = json.load(open(tmp))
+    rows = [query_op(r) for r in op_in]
+    names = sorted(set(unsplit) | {r[1] for r in rows})
+    texts = sorted({r[0] for r in rows})
+    ni, ti = {n: i for i, n in enumerate(names)}, {t: i for i, t in enumerate(texts)}
+    op_out = np.asarray([(ti[t], ni[n], ks, sc, ni[u]) for (t, n, ks, sc), u in zip(rows, unsplit)], dtype=np.int32)
+    ns = op_in[:, 13] == 1
+    renamed = int(np.sum(ns & (op_out[:, 1] != op_out[:, 4])))
+    plan_out = np.asarray([query_plan(r) for r in plan_in], dtype=np.int64)
+    save("conv_routes", op_in=op_in, op_out=op_out, plan_in=plan_in, plan_out=plan_out, names=json.dumps(names), texts=json.dumps(texts),
+         renamed=renamed)
+    print(len(op_in), "op rows,", renamed, "renamed by the no_scratch rule;", len(plan_in), "plan rows;", len(names), "names,", len(texts), "texts")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["schedules", "ops", "xattn", "model", "loops", "loops2", "hooks", "dpm", "temb", "vae", "latent_unet"]
     for w in which:

@@ -221,7 +221,7 @@ def test_mfma_masked_n_tile_nchw(ops, cout):
         check(ops, P, r"conv_mfma<1>", **kw)
 
 
-# structure bit -> name suffix (conv2d_variant): the 256-row A-direct kernel keeps the plain name
+# structure bit -> name suffix (conv2d_route_name): the 256-row A-direct kernel keeps the plain name
 SUFFIX = {"staged": "/staged", "adirect": "/r128", "adirect256": ""}
 SPLIT_SHAPES = {"staged": ((2, 16, 16, 64, 64), 2), "adirect": ((2, 64, 64, 64, 96), 1), "adirect256": ((3, 40, 24, 64, 320), 1)}
 
@@ -277,9 +277,9 @@ def test_split_k(ops, key):
     assert ks > 1
     _, ks = check(ops, P, r"conv_f16x3<\d>/r128\+splitk", prec="f16x3", structure="adirect", **FULL)
     assert ks > 1
-    # without scratch the launch is unsplit whatever the name says, and still within the bar
+    # without scratch the launch is unsplit and named so, and still within the bar
     for kw in [dict(), FULL, dict(y="nchw")]:
-        _, ks = check(ops, P, r"conv_bf16x6<\d>/r128\+splitk", prec="bf16x6", no_scratch=True, **kw)
+        _, ks = check(ops, P, r"conv_bf16x6<\d>/r128", prec="bf16x6", no_scratch=True, **kw)
         assert ks == 1, (key, kw, ks)
 
 
