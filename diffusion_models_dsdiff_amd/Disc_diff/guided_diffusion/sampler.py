@@ -1,13 +1,17 @@
-"""DPM-Solver / DPM-Solver++ multistep sampler — native counterpart of the reference's
+"""DPM-Solver / DPM-Solver++ sampler — native counterpart of the reference's
 Disc_diff/guided_diffusion/sampler.py (NoiseScheduleVP :7-149, model_wrapper :151-302, DPM_Solver :305-1222) and of
 its twin ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py.
 
 The noise-schedule scalars are host-side fp32 torch expressions in the reference's operation order; the sampling loop
-(network evaluation, data/noise prediction, dynamic thresholding, first/second-order multistep update) runs on the
-MI355X through ``dsd_sample_dpm`` (include/dsdiff.h).  Built: ``method='multistep'`` with ``order`` 1 or 2, both
-``algorithm_type``s, both ``solver_type``s, all three ``skip_type``s, ``lower_order_final``, ``denoise_to_zero``,
-dynamic thresholding, classifier-free guidance (``dsd_sample_dpm_guided``: both halves in one 2B-row network pass).  Singlestep /
-adaptive solvers, order 3, classifier guidance and python correctors raise ``NotImplementedError`` — there is no CPU fallback.
+(network evaluation, data/noise prediction, dynamic thresholding, update) runs on the MI355X.  Built: ``method='multistep'``
+with ``order`` 1..3, ``method='singlestep'`` ("DPM-Solver-fast", orders and times from
+``get_orders_and_timesteps_for_singlestep_solver``) and ``method='singlestep_fixed'``, both ``algorithm_type``s, both
+``solver_type``s, all three ``skip_type``s, ``lower_order_final``, ``denoise_to_zero``, ``return_intermediate``,
+``DPM_Solver.inverse``, dynamic thresholding, classifier-free guidance (both halves in one 2B-row network pass).  Multistep of
+order 1 or 2 without intermediates runs through ``dsd_sample_dpm`` (include/dsdiff.h); everything else is packed by
+``build_program`` into a ``dsd_dpm_program`` — one row per network evaluation — for ``dsd_sample_dpm_program``.
+``method='adaptive'`` (its step count follows a per-step error norm: a host read-back every step, and no call site uses it),
+``correcting_xt_fn``, classifier guidance and score-type networks raise ``NotImplementedError`` — there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -17,7 +21,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..._lib import DSD_NCOEF, DsdDpmSchedule, check, dptr, lib, stream_ptr
+from ..._lib import (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3, DPM_SS_S1, DPM_SS_S2, DPM_SS_T2, DPM_SS_T3, DPM_SS_T3_TAYLOR, DSD_DPM_NCOEF,
+                      DSD_NCOEF, DsdDpmProgram, DsdDpmSchedule, check, dptr, lib, stream_ptr)
 from ..._sched import Guidance, cat_unconditional, check_latent_io, is_dit, is_latent_denoiser, loop_denoiser
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
@@ -187,6 +192,41 @@ class DpmSchedule:
         return int(self.c.steps)
 
 
+class DpmProgram:
+    """Owns the host arrays a dsd_dpm_program points to: one row per network evaluation.  ``evals`` is a list of dicts with
+    kind, t (continuous time, for the tests), t_input, alpha, sigma, coef (up to DSD_DPM_NCOEF scalars), slot (write, ma, mb,
+    mc) and keep; ``lead_intermediate``: sample() puts x_T in front of the kept states (the multistep loop appends it :1147)."""
+
+    def __init__(self, pred, data_pred, thresholding, ratio, max_val, evals, lead_intermediate=False):
+        n = len(evals)
+        self.evals, self.lead_intermediate = evals, bool(lead_intermediate)
+        self.kind = np.asarray([e["kind"] for e in evals], dtype=np.int32).reshape(n)
+        self.t_input = np.asarray([e["t_input"] for e in evals], dtype=np.float32).reshape(n)
+        self.alpha = np.asarray([e["alpha"] for e in evals], dtype=np.float32).reshape(n)
+        self.sigma = np.asarray([e["sigma"] for e in evals], dtype=np.float32).reshape(n)
+        self.coef = np.zeros((n, DSD_DPM_NCOEF), dtype=np.float32)
+        for k, e in enumerate(evals):
+            self.coef[k, :len(e["coef"])] = np.asarray(e["coef"], dtype=np.float32)
+        self.slot = np.ascontiguousarray([list(e["slot"]) for e in evals], dtype=np.int32).reshape(n, 4)
+        self.keep = np.asarray([1 if e.get("keep") else 0 for e in evals], dtype=np.int32).reshape(n)
+        self.c = DsdDpmProgram()
+        self.c.n_eval, self.c.pred, self.c.data_pred = n, int(pred), int(data_pred)
+        self.c.thresholding, self.c.threshold_ratio, self.c.threshold_max = int(thresholding), float(ratio), float(max_val)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self.c.kind, self.c.t_input = self.kind.ctypes.data_as(i32p), self.t_input.ctypes.data_as(f32p)
+        self.c.alpha, self.c.sigma = self.alpha.ctypes.data_as(f32p), self.sigma.ctypes.data_as(f32p)
+        self.c.coef, self.c.slot = self.coef.ctypes.data_as(f32p), self.slot.ctypes.data_as(i32p)
+        self.c.keep = self.keep.ctypes.data_as(i32p)
+
+    @property
+    def steps(self) -> int:
+        return int(self.c.n_eval)
+
+    @property
+    def n_kept(self) -> int:
+        return int(self.keep.sum())
+
+
 class DPM_Solver:
     def __init__(self, model_fn, noise_schedule, algorithm_type="dpmsolver++", correcting_x0_fn=None,
                  correcting_xt_fn=None, thresholding_max_val=1., dynamic_thresholding_ratio=0.995):
@@ -197,7 +237,8 @@ class DPM_Solver:
         if model_fn.model_type == "score":
             raise NotImplementedError("score-type networks are not part of the conditional-DDPM path")
         if correcting_xt_fn is not None or not (correcting_x0_fn is None or correcting_x0_fn == "dynamic_thresholding"):
-            raise NotImplementedError("python corrector callbacks cannot run inside the device loop")
+            raise NotImplementedError("python corrector callbacks (correcting_xt_fn, a callable correcting_x0_fn) cannot run inside the "
+                                      "device loop")
         self.model_fn_ = model_fn
         self.noise_schedule = noise_schedule
         self.algorithm_type = algorithm_type
@@ -227,7 +268,8 @@ class DPM_Solver:
         if solver_type not in ["dpmsolver", "taylor"]:
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         if order not in (1, 2):
-            raise NotImplementedError("the device loop is built for multistep order 1 and 2 (got {})".format(order))
+            raise NotImplementedError("a dsd_dpm_schedule holds multistep order 1 and 2 (got {}); build_program packs order 3 and "
+                                      "the singlestep solvers".format(order))
         ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
         t_0 = 1. / ns.total_N if t_end is None else t_end
         t_T = ns.T if t_start is None else t_start
@@ -282,20 +324,218 @@ class DPM_Solver:
         return DpmSchedule(_PRED[self.model_fn_.model_type], pp, thr, self.dynamic_thresholding_ratio,
                            self.thresholding_max_val, rows, tin, orders)
 
+    def get_orders_and_timesteps_for_singlestep_solver(self, steps, order, skip_type, t_T, t_0, device=None):
+        """The singlestep schedule of :445-501 ("DPM-Solver-fast"): ``steps`` evaluations spent on as many steps of ``order`` as
+        fit, the rest on lower orders — order 3 ends on [1], [2] or, where ``steps`` divides by 3, on [2, 1] in place of a last
+        third-order step; order 2 ends on [1] for an odd count.  Outer times: with 'logSNR' one spacing of K intervals (K =
+        steps // 3 + 1 for order 3, the number of steps for order 2, and 1 for order 1, where the reference's loop then runs
+        out of times after its first step); otherwise the grid of ``steps`` intervals read at the cumulated orders."""
+        if order not in (1, 2, 3):
+            raise ValueError("'order' must be '1' or '2' or '3'.")
+        if order == 1:
+            orders, K = [1] * steps, 1
+        elif order == 2:
+            orders = [2] * (steps // 2) + [1] * (steps % 2)
+            K = len(orders)
+        else:
+            tail = {0: [2, 1], 1: [1], 2: [2]}[steps % 3]
+            orders = [3] * ((steps - sum(tail)) // 3) + tail
+            K = steps // 3 + 1
+        if skip_type == "logSNR":
+            return self.get_time_steps(skip_type, t_T, t_0, K), orders
+        starts = np.concatenate([[0], np.cumsum(orders)])
+        return self.get_time_steps(skip_type, t_T, t_0, steps)[torch.from_numpy(starts).long()], orders
+
+    def _singlestep_evals(self, s, t, order, r1, r2, solver_type, ev):
+        """The evaluations of one singlestep step from s to t (:509-553, :555-635, :637-758): every scalar the reference forms
+        on its (1,)-tensors, in its expressions; where it writes '+ c * D' the row carries -c (the kernel subtracts)."""
+        ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
+        lam_s, lam_t = ns.marginal_lambda(s), ns.marginal_lambda(t)
+        h = lam_t - lam_s
+        la_s, la_t = ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(t)
+        sig_s, sig_t = ns.marginal_std(s), ns.marginal_std(t)
+        alpha_t = torch.exp(la_t)
+        cx_to = lambda la_u, sig_u: sig_u / sig_s if pp else torch.exp(la_u - la_s)
+        phi_1 = torch.expm1(-h) if pp else torch.expm1(h)
+        lead_t = alpha_t if pp else sig_t
+        if order == 1:
+            ev(s, DPM_MS1, [cx_to(la_t, sig_t), lead_t * phi_1], (0, 0, 0, 0), True)
+            return
+        if r1 is None:
+            r1 = 0.5 if order == 2 else 1. / 3.
+        s1 = ns.inverse_lambda(lam_s + r1 * h)
+        la_s1, sig_s1 = ns.marginal_log_mean_coeff(s1), ns.marginal_std(s1)
+        phi_11 = torch.expm1(-r1 * h) if pp else torch.expm1(r1 * h)
+        lead_s1 = torch.exp(la_s1) if pp else sig_s1
+        ev(s, DPM_SS_S1, [cx_to(la_s1, sig_s1), lead_s1 * phi_11], (0, 0, 0, 0), False)
+        if order == 2:
+            if solver_type == "dpmsolver":
+                cd = (0.5 / r1) * (lead_t * phi_1)
+            elif pp:
+                cd = -((1. / r1) * (alpha_t * (phi_1 / h + 1.)))
+            else:
+                cd = (1. / r1) * (sig_t * (phi_1 / h - 1.))
+            ev(s1, DPM_SS_T2, [cx_to(la_t, sig_t), lead_t * phi_1, cd], (1, 0, 1, 0), True)
+            return
+        if r2 is None:
+            r2 = 2. / 3.
+        s2 = ns.inverse_lambda(lam_s + r2 * h)
+        la_s2, sig_s2 = ns.marginal_log_mean_coeff(s2), ns.marginal_std(s2)
+        lead_s2 = torch.exp(la_s2) if pp else sig_s2
+        if pp:
+            phi_12 = torch.expm1(-r2 * h)
+            phi_22 = torch.expm1(-r2 * h) / (r2 * h) + 1.
+            phi_2 = phi_1 / h + 1.
+        else:
+            phi_12 = torch.expm1(r2 * h)
+            phi_22 = torch.expm1(r2 * h) / (r2 * h) - 1.
+            phi_2 = phi_1 / h - 1.
+        phi_3 = phi_2 / h - 0.5
+        c_s2 = r2 / r1 * (lead_s2 * phi_22)
+        ev(s1, DPM_SS_S2, [cx_to(la_s2, sig_s2), lead_s2 * phi_12, -c_s2 if pp else c_s2], (1, 0, 1, 0), False)
+        if solver_type == "dpmsolver":
+            c_t = (1. / r2) * (lead_t * phi_2)
+            ev(s2, DPM_SS_T3, [cx_to(la_t, sig_t), lead_t * phi_1, -c_t if pp else c_t], (2, 0, 2, 0), True)
+        else:
+            c2 = lead_t * phi_2
+            ev(s2, DPM_SS_T3_TAYLOR, [cx_to(la_t, sig_t), lead_t * phi_1, c2 if pp else -c2, lead_t * phi_3, 1. / r1, 1. / r2, r1, r2,
+                                      r2 - r1], (2, 0, 1, 2), True)
+
+    def build_program(self, steps, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
+                      lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver",
+                      return_intermediate=False) -> DpmProgram:
+        """One row per network evaluation of sample() (:1121-1213) for dsd_sample_dpm_program: the multistep loop of order 1..3
+        (history planes k % 3, (k-1) % 3, (k-2) % 3) or the singlestep / singlestep_fixed loop (model_s, model_s1, model_s2 in
+        planes 0, 1, 2; r1 / r2 from lambda_inner :1192-1200)."""
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        if method == "adaptive":
+            raise NotImplementedError("method='adaptive' is not built: its step count follows a per-step error norm, which needs a "
+                                      "host read-back every step, and no call site uses it")
+        if method not in ("multistep", "singlestep", "singlestep_fixed"):
+            raise ValueError("Got wrong method {}".format(method))
+        if order not in (1, 2, 3):
+            raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+        ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
+        t_0 = 1. / ns.total_N if t_end is None else t_end
+        t_T = ns.T if t_start is None else t_start
+        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        f = lambda v: float(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[0])
+        evals = []
+
+        def ev(t_eval, kind, coef, slot, keep):
+            t_eval = torch.as_tensor(t_eval, dtype=torch.float32).reshape(-1)
+            evals.append(dict(kind=kind, t=f(t_eval), t_input=f(self.model_fn_.input_time(t_eval)), alpha=f(ns.marginal_alpha(t_eval)),
+                              sigma=f(ns.marginal_std(t_eval)), coef=[f(v) for v in coef], slot=slot,
+                              keep=bool(keep and return_intermediate)))
+
+        if method == "multistep":
+            assert steps >= order
+            ts = self.get_time_steps(skip_type, t_T, t_0, steps)
+            assert ts.shape[0] - 1 == steps
+            lam = [ns.marginal_lambda(t) for t in ts]
+            for k in range(steps):
+                s, t, step = ts[k], ts[k + 1], k + 1
+                if step < order:
+                    so = step
+                elif lower_order_final and steps < 10:
+                    so = min(order, steps + 1 - step)
+                else:
+                    so = order
+                h = lam[k + 1] - lam[k]
+                la_s, la_t = ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(t)
+                sig_s, sig_t = ns.marginal_std(s), ns.marginal_std(t)
+                alpha_t = torch.exp(la_t)
+                if pp:
+                    phi_1 = torch.expm1(-h)
+                    cx, lead = sig_t / sig_s, alpha_t
+                else:
+                    phi_1 = torch.expm1(h)
+                    cx, lead = torch.exp(la_t - la_s), sig_t
+                coef = [cx, lead * phi_1]
+                if so == 2:                                                   # :784-815
+                    h_0 = lam[k] - lam[k - 1]
+                    r0 = h_0 / h
+                    if solver_type == "dpmsolver":
+                        cd = 0.5 * (lead * phi_1)
+                    elif pp:
+                        cd = -(lead * (phi_1 / h + 1.))
+                    else:
+                        cd = lead * (phi_1 / h - 1.)
+                    coef += [cd, 1. / r0]
+                elif so == 3:                                                 # :840-867
+                    h_1, h_0 = lam[k - 1] - lam[k - 2], lam[k] - lam[k - 1]
+                    r0, r1 = h_0 / h, h_1 / h
+                    phi_2 = phi_1 / h + 1. if pp else phi_1 / h - 1.
+                    phi_3 = phi_2 / h - 0.5
+                    c2 = lead * phi_2
+                    coef += [c2 if pp else -c2, lead * phi_3, 1. / r0, 1. / r1, r0 / (r0 + r1), 1. / (r0 + r1)]
+                ev(s, (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3)[so], coef, (k % 3, k % 3, (k - 1) % 3, (k - 2) % 3), True)
+        else:
+            if method == "singlestep":
+                outer, orders = self.get_orders_and_timesteps_for_singlestep_solver(steps, order, skip_type, t_T, t_0)
+            else:
+                K = steps // order
+                orders = [order, ] * K
+                outer = self.get_time_steps(skip_type, t_T, t_0, K)
+            for step, so in enumerate(orders):
+                s, t = outer[step], outer[step + 1]
+                lam_in = ns.marginal_lambda(self.get_time_steps(skip_type, s.item(), t.item(), so))
+                h_in = lam_in[-1] - lam_in[0]
+                r1 = None if so <= 1 else (lam_in[1] - lam_in[0]) / h_in
+                r2 = None if so <= 2 else (lam_in[2] - lam_in[0]) / h_in
+                self._singlestep_evals(s, t, so, r1, r2, solver_type, ev)
+        if denoise_to_zero:
+            w = len(evals) % 3
+            ev(torch.ones((1,)) * t_0, DPM_MS0, [], (w, w, w, w), True)
+        thr = self.correcting_x0_fn == "dynamic_thresholding"
+        return DpmProgram(_PRED[self.model_fn_.model_type], pp, thr, self.dynamic_thresholding_ratio, self.thresholding_max_val,
+                          evals, lead_intermediate=return_intermediate and method == "multistep")
+
     # ------------------------------------------------------------------ device loop
     @torch.no_grad()
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
                lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver", atol=0.0078, rtol=0.05,
                return_intermediate=False):
-        """:1017-1222, ``method='multistep'``.  x: [B,1,H,W] x_T on the GPU; returns the sample at t_end."""
-        if method != "multistep":
-            raise NotImplementedError("only the multistep solver (the one the reference's call sites use) is built; got "
-                                      + repr(method))
-        if return_intermediate:
-            raise NotImplementedError("intermediates are not kept by the device loop")
-        sched = self.build_schedule(steps, t_start, t_end, order, skip_type, lower_order_final, denoise_to_zero,
-                                    solver_type)
-        return run_dpm_loop(self.model_fn_, sched, x)
+        """:1017-1217.  x: the state at t_start on the GPU ([B,1,H,W], or [B,Cz,h,w] latents); returns the sample at t_end, with
+        ``return_intermediate`` the pair (sample, list of the states the reference appends)."""
+        if method == "multistep" and order in (1, 2) and not return_intermediate:
+            sched = self.build_schedule(steps, t_start, t_end, order, skip_type, lower_order_final, denoise_to_zero,
+                                        solver_type)
+            return run_dpm_loop(self.model_fn_, sched, x)
+        prog = self.build_program(steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero,
+                                  solver_type, return_intermediate)
+        y, kept = run_dpm_program(self.model_fn_, prog, x)
+        if not return_intermediate:
+            return y
+        lead = [x.detach().float().clone()] if prog.lead_intermediate else []
+        return y, lead + list(kept.unbind(0))
+
+    def inverse(self, x, steps=20, t_start=None, t_end=None, **sample_kwargs):
+        """DPM_Solver.inverse (:1001-1015): sample() run upwards in time, from ``t_start`` (default: the schedule's first time,
+        1/N) to ``t_end`` (default T); every other argument is sample()'s."""
+        ns = self.noise_schedule
+        lo = 1. / ns.total_N if t_start is None else t_start
+        hi = ns.T if t_end is None else t_end
+        assert lo > 0 and hi > 0, f"inverse needs positive times, got t_start {lo} and t_end {hi}"
+        return self.sample(x, steps, lo, hi, **sample_kwargs)
+
+
+def _loop_denoiser_and_guidance(fn: "_ModelFn", steps: int, x_T: torch.Tensor, guidance: Optional[Guidance]):
+    """What both DPM routes settle before they touch the device: the native denoiser behind ``fn`` (None: the per-step path), the
+    'concat' condition, and the guidance — the caller's, or what ``fn`` carries from model_wrapper — checked against them."""
+    unet, cc = loop_denoiser(fn.model, fn.model_kwargs), fn.c_concat()   # None for a DiT that is to receive labels / cond=
+    if guidance is None and fn.unconditional_condition is not None:
+        u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device).detach().float()
+        guidance = Guidance(u, fn.guidance_scale, steps)
+    if guidance is not None:
+        if cc is None:
+            raise ValueError("classifier-free guidance needs the 'concat' condition the unconditional one replaces")
+        guidance.check(torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), steps)
+        if unet is None:
+            raise NotImplementedError("classifier-free guidance runs in the device loop only: it needs a native DSUnetModel / "
+                                      "UNetModel / DiT behind the model")
+    return unet, cc, guidance
 
 
 @torch.no_grad()
@@ -303,18 +543,8 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
     """The multistep loop on the device.  ``guidance`` (default: what ``fn`` carries from model_wrapper): classifier-free
     guidance, dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided; its unconditional conditioning must have the shape, dtype
     and device of the concatenated condition."""
-    unet, cc = loop_denoiser(fn.model, fn.model_kwargs), fn.c_concat()   # None for a DiT that is to receive labels / cond=
-    if guidance is None and fn.unconditional_condition is not None:
-        u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device).detach().float()
-        guidance = Guidance(u, fn.guidance_scale, sched.steps)
+    unet, cc, guidance = _loop_denoiser_and_guidance(fn, sched.steps, x_T, guidance)
     guided = guidance is not None
-    if guided:
-        if cc is None:
-            raise ValueError("classifier-free guidance needs the 'concat' condition the unconditional one replaces")
-        guidance.check(torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), sched.steps)
-        if unet is None:
-            raise NotImplementedError("classifier-free guidance runs in the device loop only: it needs a native DSUnetModel / "
-                                      "UNetModel / DiT behind the model")
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
@@ -355,6 +585,51 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
                                     stream_ptr()))
         m_cur, m_prev = m_prev, m_cur
     return x
+
+
+@torch.no_grad()
+def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance: Optional[Guidance] = None):
+    """A DpmProgram on the device: dsd_sample_dpm_program(_latent) for the native denoisers, guided or not, and for any other
+    callable the python loop over the network with dsd_op_dpm_eval per evaluation.  Returns (sample, kept states
+    [n_kept,B,C,H,W])."""
+    unet, cc, guidance = _loop_denoiser_and_guidance(fn, prog.steps, x_T, guidance)
+    guided = guidance is not None
+    if not x_T.is_cuda:
+        raise NotImplementedError("the singlestep, third-order and intermediate-keeping solvers run on the MI355X only (there is "
+                                  "no CPU implementation and no CPU fallback): x is on the CPU")
+    x = x_T.detach().float().contiguous().clone()
+    B, Cx, H, W = x.shape
+    kept = x.new_empty((prog.n_kept, B, Cx, H, W))
+    g = C.byref(guidance.bind()) if guided else None
+    if unet is not None and cc is None and is_dit(unet):
+        cc = [x.new_zeros((B, 0, H, W))]
+    if unet is not None and cc is not None:
+        unet.sync_params()
+        cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
+        if is_latent_denoiser(unet):
+            check_latent_io(unet, x, cond)
+            check(lib().dsd_sample_dpm_program_latent(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
+                                                      dptr(kept), stream_ptr()))
+            return x, kept
+        assert Cx == 1, "the denoised image has one channel"
+        assert cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
+        check(lib().dsd_sample_dpm_program(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), B, H, W, dptr(kept),
+                                           stream_ptr()))
+        return x, kept
+    # any other callable: python loop over the network, the fused HIP evaluation step after each
+    hist, base = x.new_empty((3, B, Cx, H, W)), torch.empty_like(x)
+    j = 0
+    for k in range(prog.steps):
+        t_in = torch.full((B,), float(prog.t_input[k]), device=x.device, dtype=torch.float32)
+        out = fn.network(x, t_in).float().contiguous()
+        if out.shape[1] not in (Cx, 2 * Cx):
+            raise ValueError(f"the network returned {out.shape[1]} channels for a state of {Cx}")
+        check(lib().dsd_op_dpm_eval(C.byref(prog.c), k, None, dptr(out), out.shape[1] // Cx, 1., dptr(x), 0, dptr(hist), dptr(base),
+                                    B, Cx, H, W, stream_ptr()))
+        if prog.keep[k]:
+            kept[j].copy_(x)
+            j += 1
+    return x, kept
 
 
 @torch.no_grad()

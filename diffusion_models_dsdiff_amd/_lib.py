@@ -15,6 +15,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 DSD_MAX_LEVELS = 8
 DSD_NCOEF = 8
+DSD_DPM_NCOEF = 9
+(DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3, DPM_SS_S1, DPM_SS_S2, DPM_SS_T2, DPM_SS_T3, DPM_SS_T3_TAYLOR) = range(9)
 MODE_A_DDPM, MODE_A_DDIM, MODE_B_DDPM, MODE_B_DDIM, MODE_B_PLMS = 0, 1, 2, 3, 4
 PLMS_PREDICT, PLMS_CORRECT, PLMS_AB2, PLMS_AB3, PLMS_AB4 = 0, 1, 2, 3, 4
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2
@@ -35,6 +37,7 @@ EXPORTS = [
     "dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent",
     "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
     "dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step",
+    "dsd_sample_dpm_program", "dsd_sample_dpm_program_latent", "dsd_op_dpm_eval",
 ]
 
 
@@ -62,6 +65,15 @@ class DsdDpmSchedule(C.Structure):
         ("steps", C.c_int32), ("pred", C.c_int32), ("data_pred", C.c_int32), ("thresholding", C.c_int32),
         ("threshold_ratio", C.c_float), ("threshold_max", C.c_float), ("coef", C.POINTER(C.c_float)),
         ("t_input", C.POINTER(C.c_float)), ("order", C.POINTER(C.c_int32)),
+    ]
+
+
+class DsdDpmProgram(C.Structure):
+    _fields_ = [
+        ("n_eval", C.c_int32), ("pred", C.c_int32), ("data_pred", C.c_int32), ("thresholding", C.c_int32),
+        ("threshold_ratio", C.c_float), ("threshold_max", C.c_float), ("kind", C.POINTER(C.c_int32)),
+        ("t_input", C.POINTER(C.c_float)), ("alpha", C.POINTER(C.c_float)), ("sigma", C.POINTER(C.c_float)),
+        ("coef", C.POINTER(C.c_float)), ("slot", C.POINTER(C.c_int32)), ("keep", C.POINTER(C.c_int32)),
     ]
 
 
@@ -218,6 +230,10 @@ def lib() -> C.CDLL:
                                          i32, i32, vp]
     L.dsd_op_plms_step.argtypes = [i32, C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, f32p, i64,
                                    C.c_float, i32, i32, i32, i32, vp]
+    pp = C.POINTER(DsdDpmProgram)
+    L.dsd_sample_dpm_program.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, f32p, vp]
+    L.dsd_sample_dpm_program_latent.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, i32, f32p, vp]
+    L.dsd_op_dpm_eval.argtypes = [pp, i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

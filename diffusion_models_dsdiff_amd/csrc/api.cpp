@@ -225,7 +225,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -855,6 +855,133 @@ int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sc, int k, const float* out_u
     Tmp sb((size_t)B * sizeof(float));
     dpm_step(dpm_coef(sc, k), out_uncond, out_cond, Cm, scale, x, m_cur, m_prev, sb.as<float>(), sc->threshold_ratio,
              sc->threshold_max, B, Cz * H * W, (hipStream_t)stream, x_row_stride);
+    DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    DSD_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- DPM-Solver programs
+static const int kDpmReads[] = {1, 1, 2, 3, 1, 2, 2, 2, 3};   // history planes a kind reads (ma, mb, mc), by DSD_DPM_*
+
+// Walks the program once: kinds, slots, the history a multistep update reads, the order of singlestep stages.
+static void check_dpm_program(const dsd_dpm_program* p) {
+    DSD_CHECK(p, "null DPM program");
+    DSD_CHECK(p->n_eval >= 1, "a DPM program of %d evaluations", p->n_eval);
+    DSD_CHECK(p->kind && p->t_input && p->alpha && p->sigma && p->coef && p->slot,
+              "DPM program: null array (kind %p t_input %p alpha %p sigma %p coef %p slot %p)", (const void*)p->kind,
+              (const void*)p->t_input, (const void*)p->alpha, (const void*)p->sigma, (const void*)p->coef, (const void*)p->slot);
+    DSD_CHECK(p->pred >= DSD_PRED_EPS && p->pred <= DSD_PRED_V, "DPM program: unknown prediction type %d", p->pred);
+    DSD_CHECK(!p->thresholding || (p->threshold_ratio >= 0.f && p->threshold_ratio <= 1.f),
+              "DPM program: threshold_ratio %g outside [0,1]", (double)p->threshold_ratio);
+    unsigned written = 0;
+    int stage = 0;                                             // 0 between steps, 1 after SS_S1, 2 after SS_S2
+    for (int k = 0; k < p->n_eval; ++k) {
+        const int kind = p->kind[k];
+        const int32_t* sl = p->slot + (size_t)k * 4;
+        DSD_CHECK(kind >= DSD_DPM_MS0 && kind <= DSD_DPM_SS_T3_TAYLOR, "DPM program: evaluation %d has kind %d; the table ends at %d",
+                  k, kind, (int)DSD_DPM_SS_T3_TAYLOR);
+        const int want = kind == DSD_DPM_SS_S2 || kind == DSD_DPM_SS_T2 ? 1 : (kind == DSD_DPM_SS_T3 || kind == DSD_DPM_SS_T3_TAYLOR ? 2 : 0);
+        DSD_CHECK(stage == want,
+                  "DPM program: evaluation %d (kind %d) comes after %d stage(s) of a singlestep step; it needs %d (SS_S2 / SS_T2 follow "
+                  "SS_S1, which saves the base state; SS_T3 / SS_T3_TAYLOR follow SS_S2; every other kind stands between steps)",
+                  k, kind, stage, want);
+        stage = kind == DSD_DPM_SS_S1 ? 1 : (kind == DSD_DPM_SS_S2 ? 2 : 0);
+        for (int j = 0; j < 4; ++j)
+            DSD_CHECK(sl[j] >= 0 && sl[j] <= 2, "DPM program: evaluation %d names history plane %d (slot[%d]); there are planes 0..2", k,
+                      sl[j], j);
+        written |= 1u << sl[0];
+        for (int j = 1; j <= kDpmReads[kind]; ++j)
+            DSD_CHECK(written >> sl[j] & 1u,
+                      "DPM program: evaluation %d (kind %d) reads history plane %d as model value %d, which no evaluation up to it wrote "
+                      "(a higher-order update before its history exists)", k, kind, sl[j], j);
+        DSD_CHECK(sl[1] != sl[2] || kDpmReads[kind] < 2, "DPM program: evaluation %d (kind %d) reads plane %d twice", k, kind, sl[1]);
+        DSD_CHECK(kDpmReads[kind] < 3 || (sl[3] != sl[1] && sl[3] != sl[2]), "DPM program: evaluation %d (kind %d) reads plane %d twice", k,
+                  kind, sl[3]);
+    }
+    DSD_CHECK(stage == 0, "DPM program: it ends after %d stage(s) of a singlestep step, before the step's x_t", stage);
+}
+
+static int dpm_program_kept(const dsd_dpm_program* p) {
+    int n = 0;
+    for (int k = 0; p->keep && k < p->n_eval; ++k) n += p->keep[k] != 0;
+    return n;
+}
+
+static void dpm_program_eval(const dsd_dpm_program* p, int k, const float* out_u, const float* out_c, int Cm, float scale, float* x,
+                             int64_t x_bs, float* hist, float* base, float* s_buf, int B, int64_t n, hipStream_t s) {
+    const int32_t* sl = p->slot + (size_t)k * 4;
+    const size_t plane = (size_t)B * n;
+    DpmCoef c{};
+    c.alpha = p->alpha[k]; c.sigma = p->sigma[k];
+    c.order = 0;
+    c.pred = p->pred;
+    c.data_pred = p->data_pred || p->kind[k] == DSD_DPM_MS0;
+    c.thresh = p->thresholding;
+    DpmEval e;
+    for (int j = 0; j < DSD_DPM_NCOEF; ++j) e.c[j] = p->coef[(size_t)k * DSD_DPM_NCOEF + j];
+    e.kind = p->kind[k];
+    e.mw = hist + sl[0] * plane;
+    e.ma = hist + sl[1] * plane;
+    e.mb = kDpmReads[e.kind] >= 2 ? hist + sl[2] * plane : nullptr;
+    e.mc = kDpmReads[e.kind] >= 3 ? hist + sl[3] * plane : nullptr;
+    e.x = x; e.x_bs = x_bs; e.base = base;
+    dpm_eval(c, e, out_u, out_c, Cm, scale, s_buf, p->threshold_ratio, p->threshold_max, B, (int)n, s);
+}
+
+// One driver for the four-stream model and the state-in-input denoisers, guided or not.  The history planes, the base plane and
+// the thresholds share one handle buffer, sized before the loop and left alone inside it.
+static void sample_dpm_program(bool latent, dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc,
+                               float* x, int Cz, int B, int H, int W, float* inter, void* stream) {
+    check_dpm_program(p);
+    if (g) check_guidance(g, p->n_eval);                          // one scale per evaluation
+    const int kept = dpm_program_kept(p);
+    DSD_CHECK(kept == 0 || inter, "the program keeps %d intermediate states but the output for them is null", kept);
+    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;
+    DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
+    const size_t plane = (size_t)B * b.n();
+    ensure_buf(&h->dpm_prog, &h->dpm_prog_cap, (4 * plane + B) * sizeof(float));
+    float *hist = h->dpm_prog, *base = hist + 3 * plane, *s_buf = hist + 4 * plane;
+    const size_t sample = (size_t)b.n() * sizeof(float);
+    int n_kept = 0;
+    run_loop(h, b, p->t_input, Range{0, p->n_eval}, s, [](int) {}, [&](int k) {
+        dpm_program_eval(p, k, b.out_u, b.out_c, Cm, g ? g->scale[k] : 1.f, b.xs, b.x_bs, hist, base, s_buf, B, b.n(), s);
+        if (p->keep && p->keep[k])
+            DSD_HIP(hipMemcpy2DAsync(inter + (size_t)n_kept++ * plane, sample, b.xs, (size_t)b.x_bs * sizeof(float), sample, B,
+                                     hipMemcpyDeviceToDevice, s));
+    });
+    finish(h, b, s);
+}
+
+int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                           int B, int H, int W, float* intermediates, void* stream) {
+    DSD_TRY
+    sample_dpm_program(false, h, prog, g, cond, Cc, x, 1, B, H, W, intermediates, stream);
+    DSD_CATCH
+}
+
+int dsd_sample_dpm_program_latent(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc,
+                                  float* x, int Cz, int B, int H, int W, float* intermediates, void* stream) {
+    DSD_TRY
+    sample_dpm_program(true, h, prog, g, cond, Cc, x, Cz, B, H, W, intermediates, stream);
+    DSD_CATCH
+}
+
+int dsd_op_dpm_eval(const dsd_dpm_program* prog, int k, const float* out_uncond, const float* out_cond, int Cm, float scale, float* x,
+                    int64_t x_row_stride, float* hist, float* base, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    check_dpm_program(prog);
+    DSD_CHECK(k >= 0 && k < prog->n_eval, "evaluation %d of a program of %d", k, prog->n_eval);
+    DSD_CHECK(out_cond && x && hist, "null argument (out_cond %p x %p hist %p)", (const void*)out_cond, (const void*)x, (const void*)hist);
+    DSD_CHECK(base || prog->kind[k] < DSD_DPM_SS_S1, "evaluation %d (kind %d) is a singlestep stage: it needs the base plane", k,
+              prog->kind[k]);
+    DSD_CHECK(Cm == 1 || Cm == 2, "Cm %d: an output row holds 1 or (with a learned sigma) 2 samples' worth of channels", Cm);
+    check_op_state(B, Cz, H, W, x_row_stride);
+    Tmp sb((size_t)B * sizeof(float));
+    dpm_program_eval(prog, k, out_uncond, out_cond, Cm, scale, x, x_row_stride, hist, base, sb.as<float>(), B, (int64_t)Cz * H * W,
+                     (hipStream_t)stream);
     DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
     DSD_CATCH
 }

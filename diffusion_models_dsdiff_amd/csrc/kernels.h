@@ -265,6 +265,25 @@ struct DpmCoef {
 // m_cur / m_prev and s_buf are per logical sample
 void dpm_step(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
               const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs = 0);
+// One evaluation of a DPM-Solver program (include/dsdiff.h dsd_dpm_program; forms in sampler.hip): after the model value of
+// the evaluation is in plane mw (dpm_model / dpm_quantile with `c`), dpm_eval_kernel thresholds it there and writes the next
+// state from ma / mb / mc (history planes [B,HW]; mb, mc null where the kind reads none) and the base state — the state
+// itself, or for the singlestep kinds from SS_S2 on the plane `base`, which SS_S1 fills.
+struct DpmEval {
+    float c[9] = {};               // DSD_DPM_NCOEF (sampler.hip asserts it)
+    int kind = 0;                  // DSD_DPM_*
+    float* mw = nullptr;
+    const float* ma = nullptr;
+    const float* mb = nullptr;
+    const float* mc = nullptr;
+    const float* s_thr = nullptr;  // set by dpm_eval
+    float* x = nullptr;            // state row b at x + b*x_bs (0 = HW); dup (set by dpm_eval when guided): also row B+b
+    float* base = nullptr;
+    int64_t x_bs = 0;
+    int dup = 0;
+};
+void dpm_eval(const DpmCoef& c, const DpmEval& e, const float* out_u, const float* out_c, int Cm, float scale, float* s_buf,
+              float ratio, float max_val, int B, int HW, hipStream_t s);
 // Image-to-image.  q_sample (+ mask blend): img_orig = a*x0 + s*z with a, s scalars or per row from the device arrays a_row /
 // s_row; mask != nullptr ([B,mask_ch,HW], mask_ch 1 or Cz): x = img_orig*mask + (1 - mask)*x, else x = img_orig.  x0 / noise are
 // [B,Cz,HW]; the state row b is x + b*x_bs (0 = Cz*HW); dup: also written to row B+b (guided 2B-row state).  noise == nullptr:

@@ -653,6 +653,7 @@ void dsd::net_free(dsd_handle* h) {
     if (h->mout) (void)hipFree(h->mout);
     if (h->zplane) (void)hipFree(h->zplane);
     if (h->dpm_m) (void)hipFree(h->dpm_m);
+    if (h->dpm_prog) (void)hipFree(h->dpm_prog);
     if (h->lat_in) (void)hipFree(h->lat_in);
     if (h->cfg_io) (void)hipFree(h->cfg_io);
     if (h->plms_hist) (void)hipFree(h->plms_hist);

@@ -359,22 +359,29 @@ static void dpm_update(bool v4, const DpmCoef& c, float* m0, const float* m1, co
     check_launch("dpm_update");
 }
 
+// The front half of every DPM evaluation: the model value of the network output into m, and with thresholding on a data
+// prediction the per-sample scale into s_buf.  Returns the scales the update kernel applies, or null.
+static const float* dpm_model_value(bool v4, const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale,
+                                    const float* x, float* m, float* s_buf, float ratio, float max_val, int B, int HW, int64_t x_bs,
+                                    hipStream_t s) {
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(dpm_model_kernel<decltype(V)::value>, dim3(ew_blocks((int64_t)B * (HW / decltype(V)::value))), dim3(256),
+                           0, s, c, out_u, out_c, Cm, scale, x, m, B, HW, x_bs);
+    });
+    check_launch("dpm_model");
+    if (!(c.thresh && c.data_pred)) return nullptr;
+    hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m, HW, ratio, max_val, s_buf);   // per logical sample: m is [B,HW]
+    check_launch("dpm_quantile");
+    return s_buf;
+}
+
 void dpm_step(const DpmCoef& c, const float* out_u, const float* out_c, int Cm, float scale, float* x, float* m_cur,
               const float* m_prev, float* s_buf, float ratio, float max_val, int B, int HW, hipStream_t s, int64_t x_bs) {
     if (!B || !HW) return;
     if (x_bs <= 0) x_bs = HW;
     const bool v4 = can_vec4(HW, x_bs, out_u, out_c, x, m_cur, m_prev);
-    launch_vec(v4, [&](auto V) {
-        hipLaunchKernelGGL(dpm_model_kernel<decltype(V)::value>, dim3(ew_blocks((int64_t)B * (HW / decltype(V)::value))), dim3(256),
-                           0, s, c, out_u, out_c, Cm, scale, x, m_cur, B, HW, x_bs);
-    });
-    check_launch("dpm_model");
-    const bool thr = c.thresh && c.data_pred;
-    if (thr) {   // per logical sample: m_cur is [B,HW]
-        hipLaunchKernelGGL(dpm_quantile_kernel, dim3(B), dim3(1024), 0, s, m_cur, HW, ratio, max_val, s_buf);
-        check_launch("dpm_quantile");
-    }
-    dpm_update(v4, c, m_cur, m_prev, thr ? s_buf : nullptr, x, B, HW, x_bs, out_u != nullptr, s);
+    const float* thr = dpm_model_value(v4, c, out_u, out_c, Cm, scale, x, m_cur, s_buf, ratio, max_val, B, HW, x_bs, s);
+    dpm_update(v4, c, m_cur, m_prev, thr, x, B, HW, x_bs, out_u != nullptr, s);
 }
 
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s) {
@@ -386,6 +393,96 @@ void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float m
     c.order = 0;
     dpm_update(can_vec4(n, n, y), c, y, nullptr, s_buf, nullptr, B, n, n, false, s);
     DSD_HIP(hipStreamSynchronize(s));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The DPM-Solver family as a program of evaluations (include/dsdiff.h dsd_dpm_program): multistep up to third order
+// (multistep_dpm_solver_third_update, sampler.py:818-868) and the singlestep solvers of second (:555-635) and third order
+// (:637-758).  Every evaluation forms its model value with dpm_model_kernel / dpm_quantile_kernel above — from the alpha and
+// sigma of ITS time and the state the network just read, stage states included — and dpm_eval_kernel thresholds it in its
+// history plane and writes the next state.  The history is three planes [B,HW] addressed by slot (nothing is copied or rotated:
+// the program names the plane an evaluation writes and the ones it reads).  A singlestep stage reads the BASE state x_s: the
+// first stage (SS_S1) copies it from the state into the base plane before it overwrites the state with x_s1, the later ones read
+// it there.  c[] holds host scalars only (the reference's fp32 torch expressions on its (1,)-tensors); a sign the reference
+// writes as "+ c*D" against "- c*D" between the two algorithm types is folded into c (a - (-c)*D == a + c*D bit for bit).
+//   MS0              x = ma                                                       denoise_to_zero_fn :503-507
+//   MS1, SS_S1       x = c0*xb - c1*ma                                            :509-553 / x_s1
+//   MS2              x = (c0*xb - c1*ma) - c2*(c3*(ma - mb))                      :760-816
+//   MS3              D1_0 = c4*(ma - mb); D1_1 = c5*(mb - mc); D1 = D1_0 + c6*(D1_0 - D1_1); D2 = c7*(D1_0 - D1_1)
+//                    x = ((c0*xb - c1*ma) + c2*D1) - c3*D2                        :840-867
+//   SS_S2/T2/T3      x = (c0*xb - c1*ma) - c2*(mb - ma)                           x_s2, x_t of 'dpmsolver' (:592-631, :692-742)
+//   SS_T3_TAYLOR     D1_0 = c4*(mb - ma); D1_1 = c5*(mc - ma); D1 = (c7*D1_0 - c6*D1_1)/c8; D2 = 2*(D1_1 - D1_0)/c8
+//                    x = ((c0*xb - c1*ma) + c2*D1) - c3*D2                        :705-714, :744-753 (two IEEE divisions)
+static_assert(sizeof(DpmEval::c) == DSD_DPM_NCOEF * sizeof(float), "DpmEval::c is one dsd_dpm_program coefficient row");
+__device__ __forceinline__ float dpm_eval_value(const DpmEval& e, float xb, float ma, float mb, float mc) {
+    const float* c = e.c;
+    if (e.kind == DSD_DPM_MS0) return ma;
+    const float lin = c[0] * xb - c[1] * ma;
+    switch (e.kind) {
+        case DSD_DPM_MS2: return lin - c[2] * (c[3] * (ma - mb));
+        case DSD_DPM_MS3: {
+            const float d10 = c[4] * (ma - mb), d11 = c[5] * (mb - mc);
+            const float dd = d10 - d11;
+            const float d1 = d10 + c[6] * dd, d2 = c[7] * dd;
+            return (lin + c[2] * d1) - c[3] * d2;
+        }
+        case DSD_DPM_SS_S2:
+        case DSD_DPM_SS_T2:
+        case DSD_DPM_SS_T3: return lin - c[2] * (mb - ma);
+        case DSD_DPM_SS_T3_TAYLOR: {
+            const float d10 = c[4] * (mb - ma), d11 = c[5] * (mc - ma);
+            const float d1 = (c[7] * d10 - c[6] * d11) / c[8];
+            const float d2 = 2.f * (d11 - d10) / c[8];
+            return (lin + c[2] * d1) - c[3] * d2;
+        }
+        default: return lin;                                  // MS1, SS_S1
+    }
+}
+
+// mw (the plane this evaluation's model value was written to) may be one of ma / mb / mc: the planes are not __restrict__, and
+// a thread reads its own elements of mw back only through the registers it thresholded.
+template <int V>
+__global__ __launch_bounds__(256) void dpm_eval_kernel(DpmEval e, int B, int HW) {
+    const int64_t nv = HW / V, total = (int64_t)B * nv;
+    const bool from_base = e.kind >= DSD_DPM_SS_S2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t li = b * HW + p, xi = b * e.x_bs + p;
+        Pack<V> mw = ld_pack<V>(e.mw + li);
+        if (e.s_thr) {
+            const float s = e.s_thr[b];
+#pragma unroll
+            for (int j = 0; j < V; ++j) mw.v[j] = fminf(fmaxf(mw.v[j], -s), s) / s;
+            st_pack<V>(e.mw + li, mw);
+        }
+        const Pack<V> ma = e.ma == e.mw ? mw : ld_pack<V>(e.ma + li);
+        Pack<V> mb = ma, mc = ma;
+        if (e.mb) mb = e.mb == e.mw ? mw : ld_pack<V>(e.mb + li);
+        if (e.mc) mc = e.mc == e.mw ? mw : ld_pack<V>(e.mc + li);
+        const Pack<V> xb = from_base ? ld_pack<V>(e.base + li) : ld_pack<V>(e.x + xi);
+        if (e.kind == DSD_DPM_SS_S1) st_pack<V>(e.base + li, xb);
+        Pack<V> res;
+#pragma unroll
+        for (int j = 0; j < V; ++j) res.v[j] = dpm_eval_value(e, xb.v[j], ma.v[j], mb.v[j], mc.v[j]);
+        st_pack<V>(e.x + xi, res);
+        if (e.dup) st_pack<V>(e.x + xi + (int64_t)B * e.x_bs, res);
+    }
+}
+
+void dpm_eval(const DpmCoef& c, const DpmEval& ev, const float* out_u, const float* out_c, int Cm, float scale, float* s_buf,
+              float ratio, float max_val, int B, int HW, hipStream_t s) {
+    if (!B || !HW) return;
+    DpmEval e = ev;
+    if (e.x_bs <= 0) e.x_bs = HW;
+    const bool v4 = can_vec4(HW, e.x_bs, out_u, out_c, e.x, e.mw, e.ma, e.mb, e.mc, e.base);
+    e.s_thr = dpm_model_value(v4, c, out_u, out_c, Cm, scale, e.x, e.mw, s_buf, ratio, max_val, B, HW, e.x_bs, s);
+    e.dup = out_u != nullptr;
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(dpm_eval_kernel<decltype(V)::value>, dim3(ew_blocks((int64_t)B * (HW / decltype(V)::value))), dim3(256), 0,
+                           s, e, B, HW);
+    });
+    check_launch("dpm_eval");
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -30,6 +30,10 @@
  *                                  <- PLMSSampler.sample / p_sample_plms  ldm/models/diffusion/plms.py:59-245
  *                                        with sampling_util.norm_thresholding (dynamic_threshold)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
+ *   dsd_sample_dpm_program / dsd_sample_dpm_program_latent / dsd_op_dpm_eval
+ *                                  <- DPM_Solver.sample / .inverse with method "multistep" order 1..3, "singlestep",
+ *                                        "singlestep_fixed", return_intermediate, guided or not
+ *                                        Disc_diff/guided_diffusion/sampler.py:445-501,555-868,1001-1217
  *   dsd_op_posterior_sample_scaled <- LatentDiffusion.get_first_stage_encoding(encode_first_stage(x))
  *                                        ldm/models/diffusion/ddpm.py:660-667 with distributions.py:24-37
  *   dsd_block_*                    <- ResBlock / AttentionBlock / Upsample / Downsample
@@ -356,6 +360,65 @@ int dsd_op_sampler_update_guided(const dsd_schedule* sched, int k, const float* 
 int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sched, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
                            float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
                            void* stream);
+/* ---- the DPM-Solver family as a program of evaluations -------------------------------------
+ * Replaces DPM_Solver(...).sample / .inverse of Disc_diff/guided_diffusion/sampler.py:1001-1217 (and of the twin
+ * dpm_solver_pytorch.py) for method = "multistep" with order 1..3 (:818-868 adds the third), "singlestep" and "singlestep_fixed"
+ * (:555-758, orders and times from get_orders_and_timesteps_for_singlestep_solver :445-501), with return_intermediate.
+ * dsd_sample_dpm and its schedule stay as they are; this is a second way in, for everything they do not cover.
+ * The program is a host array of network EVALUATIONS.  Evaluation k runs the network at model time t_input[k] on the current
+ * state, forms the model value m from the output as DPM_Solver.model_fn does — noise prediction per `pred` with alpha[k] /
+ * sigma[k] and the state the network read, data prediction with `data_pred` (always for DSD_DPM_MS0), dynamic thresholding per
+ * logical sample — stores it in history plane slot[4k] (three planes, 0..2; nothing is rotated) and writes the next state:
+ *   kind                 ma, mb, mc = planes slot[4k+1..3]          c = coef + k*DSD_DPM_NCOEF
+ *   DSD_DPM_MS0          x = ma                                                          (denoise_to_zero_fn :503-507)
+ *   DSD_DPM_MS1          x = c0*x - c1*ma                                                (:509-553)
+ *   DSD_DPM_MS2          x = (c0*x - c1*ma) - c2*(c3*(ma - mb))                          (:760-816; ma = m_k, mb = m_{k-1})
+ *   DSD_DPM_MS3          D1_0 = c4*(ma - mb), D1_1 = c5*(mb - mc), D1 = D1_0 + c6*(D1_0 - D1_1), D2 = c7*(D1_0 - D1_1)
+ *                        x = ((c0*x - c1*ma) + c2*D1) - c3*D2                            (:818-868; mc = m_{k-2})
+ *   DSD_DPM_SS_S1        base = x;  x = c0*base - c1*ma                                  (x_s1; ma = model_s)
+ *   DSD_DPM_SS_S2        x = (c0*base - c1*ma) - c2*(mb - ma)                            (x_s2 of the third order; mb = model_s1)
+ *   DSD_DPM_SS_T2 / _T3  x = (c0*base - c1*ma) - c2*(mb - ma)                            (x_t, 'dpmsolver'; mb = model_s1 / model_s2)
+ *   DSD_DPM_SS_T3_TAYLOR D1_0 = c4*(mb - ma), D1_1 = c5*(mc - ma), D1 = (c7*D1_0 - c6*D1_1)/c8, D2 = 2*(D1_1 - D1_0)/c8
+ *                        x = ((c0*base - c1*ma) + c2*D1) - c3*D2                         (x_t, 'taylor' :705-714; c6 r1, c7 r2, c8 r2-r1)
+ * A singlestep step of order 1 is DSD_DPM_MS1.  The base state x_s of a singlestep step lives in a library plane from SS_S1
+ * until the step's x_t is written.  Every coefficient is a host scalar: the value of the reference's fp32 torch expression on
+ * its (1,)-tensors, with the sign the reference writes in front of a term folded in where the two algorithm types differ.
+ * keep[k] != 0: the state after evaluation k is an intermediate (sample(return_intermediate=True) appends it, :1147-1213).
+ * Rejected before any device work, each with its numbers: a kind outside the table, a slot outside 0..2, a multistep update
+ * that reads a plane no earlier evaluation wrote, stage kinds out of sequence (SS_S2 / SS_T2 not after SS_S1, SS_T3* not after
+ * SS_S2, anything but the next stage inside a step, a program that ends inside a step), null arrays, threshold_ratio outside
+ * [0,1], a guidance whose n_scale differs from n_eval. */
+enum { DSD_DPM_MS0 = 0, DSD_DPM_MS1 = 1, DSD_DPM_MS2 = 2, DSD_DPM_MS3 = 3, DSD_DPM_SS_S1 = 4, DSD_DPM_SS_S2 = 5, DSD_DPM_SS_T2 = 6,
+       DSD_DPM_SS_T3 = 7, DSD_DPM_SS_T3_TAYLOR = 8 };
+#define DSD_DPM_NCOEF 9   /* the widest row: DSD_DPM_SS_T3_TAYLOR, c0..c8 */
+typedef struct dsd_dpm_program {
+    int32_t n_eval;           /* network evaluations */
+    int32_t pred;             /* DSD_PRED_* */
+    int32_t data_pred;        /* 1 = dpmsolver++, 0 = dpmsolver */
+    int32_t thresholding;
+    float threshold_ratio;
+    float threshold_max;
+    const int32_t* kind;      /* host, n_eval: DSD_DPM_* */
+    const float* t_input;     /* host, n_eval: fp32 model time of the evaluation */
+    const float* alpha;       /* host, n_eval: marginal alpha / sigma at the evaluation's time */
+    const float* sigma;
+    const float* coef;        /* host, n_eval*DSD_DPM_NCOEF */
+    const int32_t* slot;      /* host, n_eval*4: plane written, planes read as ma, mb, mc (unread ones: any value in 0..2) */
+    const int32_t* keep;      /* host, n_eval, or NULL = none kept */
+} dsd_dpm_program;
+/* x [B,1,H,W] in place with the four-stream model, cond as in dsd_sample.  g: NULL, or classifier-free guidance with one scale
+ * per evaluation.  intermediates: NULL, or device [n_kept,B,1,H,W] (n_kept = the nonzero keep entries), filled in order.
+ * dsd_set_graph, the stream lanes and dsd_set_slice_ids work as in the other loops. */
+int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                           int B, int H, int W, float* intermediates, void* stream);
+/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, as dsd_sample_dpm_latent. */
+int dsd_sample_dpm_program_latent(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc,
+                                  float* x, int Cz, int B, int H, int W, float* intermediates, void* stream);
+/* Evaluation k's post-network part alone (host loops, kernel-level tests).  out_cond [B,Cm*Cz,H,W] is the network output
+ * (Cm = 1, or 2 with a learned sigma in the second half of the channels, which is left unread; any Cz); out_uncond NULL, or the unconditional half: then x holds 2B rows as in dsd_op_dpm_step_guided and both rows of a sample are
+ * written.  hist: the three history planes [3,B,Cz,H,W]; base [B,Cz,H,W] (may be NULL for the multistep kinds). */
+int dsd_op_dpm_eval(const dsd_dpm_program* prog, int k, const float* out_uncond, const float* out_cond, int Cm, float scale, float* x,
+                    int64_t x_row_stride, float* hist, float* base, int B, int Cz, int H, int W, void* stream);
 /* ---- image-to-image: masked sampling and DDIM inversion -----------------------------------
  * Masked sampling (DDIMSampler.sample(mask=, x0=), ddim.py:160-163; LatentDiffusion.p_sample_loop(mask=, x0=), ddpm.py:1085-1087):
  *   img_orig = sqrt_acp[t]*x0 + sqrt_1m_acp[t]*z        (q_sample, ddpm.py:356-359; coef[k][0], coef[k][1] of the iteration)

@@ -18,12 +18,18 @@ With --plms the PLMS device loop (dsd_sample_plms_latent: one network evaluation
 steps + 1 in all) is timed against the DDIM loop of the same steps: plms_over_ddim is expected near (steps + 1) / steps and is
 measured here, not assumed.  The network of this bench is a v-model, which PLMS does not take; the PLMS schedule is packed as for
 a noise-predicting one — the same kernels and the same work.
+With --dpm-family LIST (of ss3, ms3, ms2) the DPM-Solver++ loops of 21 network evaluations are timed in the same alternation:
+singlestep order 3 and multistep order 3 (dsd_sample_dpm_program_latent) and multistep order 2 (dsd_sample_dpm_latent, the loop
+that existed before them).  The host tables are built once outside the timed region, every timed run follows an untimed run of
+the same loop, and the result holds the ms per network evaluation of each and the ratios to ms2.  For a build from before the
+program entry, copy this script into a checkout of that commit (this tree's binding does not load such a library) and run
+`--dpm-family ms2` there; --baseline with those lines then also records this build's ms2 loop over that build's.
 With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
 run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this
 build's plain loop (the median of its device, unmasked and sample loops, which are the same call) to their mean.
 
     python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--mask] [--encode]
-                                 [--plms] [--baseline other.json ...] [--json out.json]
+                                 [--plms] [--dpm-family ss3,ms3,ms2] [--baseline other.json ...] [--json out.json]
 """
 import argparse
 import json
@@ -120,6 +126,27 @@ def run_k(K, args):
             return run_plms_loop(unet, plms_sched, xT, c, n_steps=n_steps)
         return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps)       # "unmasked" / "sample" / "ddim": the plain loop
 
+    DPM_EVALS = 21
+    dpm_kinds = tuple(k for k in args.dpm_family.split(",") if k)
+    assert set(dpm_kinds) <= {"ss3", "ms3", "ms2"}, dpm_kinds
+    dpm_runs = {}
+
+    def dpm_prepare():
+        from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
+        ns = dsa.NoiseScheduleVP("discrete", alphas_cumprod=ld.alphas_cumprod.detach().float().cpu())
+        fn = dsa.model_wrapper(unet, ns, model_type="v", model_kwargs=dict(c_concat=[c]))
+        sol = dsa.DPM_Solver(fn, ns, algorithm_type="dpmsolver++")
+        for kind in dpm_kinds:
+            if kind == "ms2":
+                sched = sol.build_schedule(DPM_EVALS, order=2, skip_type="time_uniform")
+                assert sched.steps == DPM_EVALS
+                dpm_runs[kind] = lambda sched=sched: dsa.run_dpm_loop(fn, sched, xT)
+            else:
+                prog = sol.build_program(DPM_EVALS, order=3, skip_type="time_uniform",
+                                         method="singlestep" if kind == "ss3" else "multistep")
+                assert prog.steps == DPM_EVALS
+                dpm_runs[kind] = lambda prog=prog: dsa.run_dpm_program(fn, prog, xT)[0]
+
     i2i_kinds = ((("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ()) +
                  (("plms", "ddim") if args.plms else ()))
     cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
@@ -128,6 +155,10 @@ def run_k(K, args):
         cfg_loop(kind)
     for kind in i2i_kinds:
         i2i_loop(kind)
+    if dpm_kinds:
+        dpm_prepare()
+    for kind in dpm_kinds:
+        dpm_runs[kind]()
     y = device(False)
     device(True)
     device(True)
@@ -135,7 +166,7 @@ def run_k(K, args):
     ld.decode_first_stage(y)
     torch.cuda.synchronize()
     t = {"encode_ms": [], "device_loop_ms": [], "device_loop_graph_ms": [], "python_loop_ms": [], "decode_ms": []}
-    t.update({kind + "_loop_ms": [] for kind in cfg_kinds + i2i_kinds})
+    t.update({kind + "_loop_ms": [] for kind in cfg_kinds + i2i_kinds + dpm_kinds})
     outs = {}
     for _ in range(args.repeats):
         c, ms = timed(lambda: ld.encode_conditions(cond, seed=3)["c_concat"][0])
@@ -158,6 +189,11 @@ def run_k(K, args):
             torch.cuda.synchronize()
             _, ms = timed(lambda: i2i_loop(kind))
             t[kind + "_loop_ms"].append(ms)
+        for kind in dpm_kinds:
+            dpm_runs[kind]()                                       # untimed run of the same loop
+            torch.cuda.synchronize()
+            _, ms = timed(dpm_runs[kind])
+            t[kind + "_loop_ms"].append(ms)
     res = {k: stats(v) for k, v in t.items()}
     for k in ("device_loop", "device_loop_graph", "python_loop") + tuple(kind + "_loop" for kind in cfg_kinds + i2i_kinds):
         res[k + "_ms_per_step"] = res[k + "_ms"]["median"] / sched.steps
@@ -172,6 +208,12 @@ def run_k(K, args):
     if args.plms:
         res["plms_over_ddim"] = res["plms_loop_ms"]["median"] / res["ddim_loop_ms"]["median"]
         res["plms_network_evaluations"] = sched.steps + 1
+    if dpm_kinds:
+        res["dpm_network_evaluations"] = DPM_EVALS
+        for kind in dpm_kinds:
+            res[kind + "_ms_per_evaluation"] = res[kind + "_loop_ms"]["median"] / DPM_EVALS
+            if "ms2" in dpm_kinds and kind != "ms2":
+                res[kind + "_over_ms2"] = res[kind + "_loop_ms"]["median"] / res["ms2_loop_ms"]["median"]
     e2e = res["encode_ms"]["median"] + res["device_loop_ms"]["median"] + res["decode_ms"]["median"]
     res["end_to_end_ms"] = e2e
     res["slices_per_s"] = B / (e2e / 1000.)
@@ -193,6 +235,7 @@ def main():
     ap.add_argument("--mask", action="store_true", help="also time the masked loop against the unmasked loop")
     ap.add_argument("--encode", action="store_true", help="also time the DDIM inversion loop against plain sampling")
     ap.add_argument("--plms", action="store_true", help="also time the PLMS loop against the DDIM loop of the same steps")
+    ap.add_argument("--dpm-family", default="", help="comma list of ss3, ms3, ms2: also time those DPM-Solver++ loops of 21 evaluations")
     ap.add_argument("--baseline", action="append", default=[],
                     help="bench line of another build on the same machine (repeatable): record its plain loop beside this one's")
     ap.add_argument("--json", default=None)
@@ -217,6 +260,10 @@ def main():
             res["baseline_device_loop_ms"] = theirs
             res["plain_loop_ms"] = statistics.median(plain)
             res["plain_over_baseline"] = res["plain_loop_ms"] / statistics.mean(theirs)
+            ms2 = [b["keys"][K]["ms2_loop_ms"]["median"] for b in base if "ms2_loop_ms" in b["keys"].get(K, {})]
+            if ms2 and "ms2_loop_ms" in res:
+                res["baseline_ms2_loop_ms"] = ms2
+                res["ms2_over_baseline"] = res["ms2_loop_ms"]["median"] / statistics.mean(ms2)
     line = json.dumps(out)
     print(line)
     if args.json:
