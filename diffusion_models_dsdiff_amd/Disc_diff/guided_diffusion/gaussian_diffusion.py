@@ -1,9 +1,11 @@
-"""GaussianDiffusion — drop-in for Disc_diff/guided_diffusion/gaussian_diffusion.py (sampling side).
+"""GaussianDiffusion — drop-in for Disc_diff/guided_diffusion/gaussian_diffusion.py (sampling and evaluation side).
 
 Same constructor, enums and sampling entry points as the reference (``p_sample_loop`` :524-567,
 ``ddim_sample_loop`` :705-737, ``p_sample`` :422-465, ``ddim_sample`` :618-665 and their
 ``*_progressive`` generators).  The float64 schedule tables are built on the host exactly as
-:141-178 does; the loop itself (network + fused update) runs on the MI355X through dsd_sample.
+:141-178 does; the loop itself (network + fused update) runs on the MI355X through dsd_sample.  The evaluation half — ``calc_bpd_loop``
+:938-991 with ``_vb_terms_bpd`` / ``_prior_bpd``, ``p_mean_variance`` as a method, ``ddim_reverse_sample`` and the q_* helpers —
+runs through dsd_calc_bpd and the dsd_op_vlb_terms / dsd_op_prior_bpd / dsd_op_ddim_reverse_step kernels.
 Training losses are out of scope.
 """
 from __future__ import annotations
@@ -15,7 +17,8 @@ import numpy as np
 import torch as th
 
 from ... import _lib
-from ..._sched import Schedule, is_dit, loop_denoiser, run_device_loop, sampler_update, _seed_from_torch
+from ..._sched import (Schedule, ddim_reverse_step, is_dit, loop_denoiser, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
+                       run_device_loop, sampler_update, vlb_terms, _seed_from_torch)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
@@ -203,21 +206,7 @@ class GaussianDiffusion:
         grad = None
         if cond_fn is not None:
             grad = cond_fn(x, t, **model_kwargs).float()              # x is still x_t here; t as the network received it
-        run = sched
-        if denoised_fn is not None:
-            c = th.from_numpy(sched.coef[k]).to(x.device)
-            xs = x.shape
-            C = xs[1]
-            eps_or_v, rest = (out[:, :C], out[:, C:]) if sched.c.learned_range else (out, None)
-            if sched.c.pred == _lib.PRED_V:                            # predict_start_from_z_and_v :236-242
-                x0 = c[0] * x - c[1] * eps_or_v
-            elif sched.c.pred == _lib.PRED_EPS:                        # _predict_xstart_from_eps :352-357
-                x0 = c[2] * x - c[3] * eps_or_v
-            else:
-                x0 = eps_or_v
-            x0 = denoised_fn(x0).float()
-            out = x0 if rest is None else th.cat([x0, rest], 1)
-            run = sched.with_pred(_lib.PRED_X0)
+        out, run = self._apply_denoised_fn(sched, k, out, x, denoised_fn)
         x0_out = sampler_update(run, k, out, x, noise, seed, want_x0=want_x0)
         if grad is not None:
             # p_mean_var["variance"] of this step (:296-309): the variance TABLE (FIXED_SMALL pairs the raw posterior variance,
@@ -227,6 +216,24 @@ class GaussianDiffusion:
                    else self.posterior_variance)
             x.add_(float(np.float32(var[i])) * grad)
         return x0_out
+
+    @staticmethod
+    def _apply_denoised_fn(sched, k, out, x, denoised_fn):
+        """process_xstart's hook (:311-313): (network output, schedule) for the kernels.  With a denoised_fn the x_start is
+        formed here with the reference's fp32 expressions, post-processed, and handed on as an x_start prediction."""
+        if denoised_fn is None:
+            return out, sched
+        c = th.from_numpy(sched.coef[k]).to(x.device)
+        C = x.shape[1]
+        eps_or_v, rest = (out[:, :C], out[:, C:]) if sched.c.learned_range else (out, None)
+        if sched.c.pred == _lib.PRED_V:                            # predict_start_from_z_and_v :236-242
+            x0 = c[0] * x - c[1] * eps_or_v
+        elif sched.c.pred == _lib.PRED_EPS:                        # _predict_xstart_from_eps :352-357
+            x0 = c[2] * x - c[3] * eps_or_v
+        else:
+            x0 = eps_or_v
+        x0 = denoised_fn(x0).float()
+        return (x0 if rest is None else th.cat([x0, rest], 1)), sched.with_pred(_lib.PRED_X0)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, step_noise=None, seed=None):
@@ -325,6 +332,143 @@ class GaussianDiffusion:
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
         """:618-665."""
         return self._single(True, model, x, t, clip_denoised, model_kwargs, eta, denoised_fn, cond_fn)
+
+    # ------------------------------------------------------------------ the forward process and its posterior
+    def q_mean_variance(self, x_start, t):
+        """:180-194."""
+        mean = _extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = _extract_into_tensor(1.0 - self.alphas_cumprod, t, x_start.shape)
+        log_variance = _extract_into_tensor(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    def q_sample(self, x_start, t, noise=None):
+        """:196-212, on the q_sample kernel (dsd_op_q_sample, per-row coefficients)."""
+        if noise is None:
+            noise = th.randn_like(x_start)
+        assert noise.shape == x_start.shape
+        t = t.to(x_start.device)
+        a = _extract_into_tensor(self.sqrt_alphas_cumprod, t, t.shape)
+        s = _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, t.shape)
+        return q_sample_rows(a, s, x_start, noise)
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """:214-234."""
+        assert x_start.shape == x_t.shape
+        posterior_mean = (_extract_into_tensor(self.posterior_mean_coef1, t, x_t.shape) * x_start
+                          + _extract_into_tensor(self.posterior_mean_coef2, t, x_t.shape) * x_t)
+        posterior_variance = _extract_into_tensor(self.posterior_variance, t, x_t.shape)
+        posterior_log_variance_clipped = _extract_into_tensor(self.posterior_log_variance_clipped, t, x_t.shape)
+        return posterior_mean, posterior_variance, posterior_log_variance_clipped
+
+    def _predict_xstart_from_eps(self, x_t, t, eps):
+        """:352-357."""
+        assert x_t.shape == eps.shape
+        return (_extract_into_tensor(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t
+                - _extract_into_tensor(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * eps)
+
+    def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
+        """:369-373."""
+        return ((_extract_into_tensor(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - pred_xstart)
+                / _extract_into_tensor(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape))
+
+    # ------------------------------------------------------------------ variational bound
+    def _post_log_var(self) -> np.ndarray:
+        """posterior_log_variance_clipped in loop order, fp32 of the float64 table (:225-227, :1003)."""
+        return self.posterior_log_variance_clipped[::-1].astype(np.float32)
+
+    def _step_of(self, t) -> int:
+        i = int(t[0])
+        assert bool((t == i).all()), "all samples of a batch share the timestep in every reference loop"
+        return i
+
+    def _evaluate(self, model, x, t, clip_denoised, denoised_fn, model_kwargs):
+        """The network evaluation in front of p_mean_variance's arithmetic: (loop index i, iteration k, output, schedule)."""
+        i = self._step_of(t)
+        sched = self._schedule(False, 0.0, clip_denoised)
+        out = self._call_model(model, x, t.to(x.device), model_kwargs or {})
+        out, run = self._apply_denoised_fn(sched, self.num_timesteps - 1 - i, out.float(), x.float(), denoised_fn)
+        return i, self.num_timesteps - 1 - i, out, run
+
+    def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
+        """:244-350 as a method: {"mean", "variance", "log_variance", "pred_xstart"}, the planes of the terms kernel
+        (dsd_op_vlb_terms).  ``denoised_fn`` goes through the x_start-mode hook path of the sampling loops: x_start is formed
+        from the network output, post-processed, and the kernel runs as for an x_start prediction."""
+        i, k, out, run = self._evaluate(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+        xc = x.float().contiguous()
+        mean, log_variance, pred_xstart = vlb_terms(run, k, float(self._post_log_var()[k]), out, xc, xc, xc, want_planes=True)
+        if self.model_var_type == ModelVarType.LEARNED_RANGE:
+            variance = th.exp(log_variance)                                        # :294
+        else:
+            table = (np.append(self.posterior_variance[1], self.betas[1:]) if self.model_var_type == ModelVarType.FIXED_LARGE
+                     else self.posterior_variance)                                 # :296-308
+            variance = _extract_into_tensor(table, t.to(x.device), x.shape)
+        return {"mean": mean, "variance": variance, "log_variance": log_variance, "pred_xstart": pred_xstart}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """:667-703 on dsd_op_ddim_reverse_step."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        i, k, out, run = self._evaluate(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+        xn = x.float().contiguous().clone()
+        x0 = ddim_reverse_step(run, k, float(np.float32(self.alphas_cumprod_next[i])), out, xn, want_x0=True)
+        return {"sample": xn, "pred_xstart": x0}
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """:788-819: {"output": [N] bits per dimension (the decoder NLL at t == 0, else the KL), "pred_xstart"}."""
+        i, k, out, run = self._evaluate(model, x_t, t, clip_denoised, None, model_kwargs)
+        output = th.empty((x_start.shape[0],), device=x_t.device, dtype=th.float32)
+        xt = x_t.float().contiguous()
+        _, _, pred_xstart = vlb_terms(run, k, float(self._post_log_var()[k]), out, xt, x_start.to(x_t.device), xt, vb=output,
+                                      want_planes=True)
+        return {"output": output, "pred_xstart": pred_xstart}
+
+    def _prior_bpd(self, x_start):
+        """:922-936 on dsd_op_prior_bpd."""
+        T = self.num_timesteps
+        return prior_bpd(np.float32(self.sqrt_alphas_cumprod[T - 1]), np.float32(self.log_one_minus_alphas_cumprod[T - 1]), x_start)
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, step_noise=None, seed=None):
+        """:938-991: {"total_bpd", "prior_bpd" [N]; "vb", "xstart_mse", "mse" [N,T], column k at t = T-1-k}.  ``step_noise``
+        ([T,N,C,H,W]) / ``seed`` are extensions as on the sampling loops: the normals q_sample draws at every timestep, fed for
+        parity runs, else on-device Philox seeded from torch's generator.  A native denoiser with at most ``c_concat`` runs the
+        device loop (dsd_calc_bpd / dsd_calc_bpd_latent); a generic callable, or a DiT that is to receive labels, is evaluated
+        step by step around the same kernels."""
+        model_kwargs = model_kwargs or {}
+        sched = self._schedule(False, 0.0, clip_denoised)
+        T = self.num_timesteps
+        plv = self._post_log_var()
+        prior_lv = float(np.float32(self.log_one_minus_alphas_cumprod[T - 1]))
+        if not x_start.is_cuda:
+            x_start = x_start.to(th.device("cuda"))
+        device = x_start.device
+        xs = x_start.float().contiguous()
+        unet = loop_denoiser(model, model_kwargs)
+        c_concat = model_kwargs.get("c_concat")
+        if unet is not None and c_concat is None and is_dit(unet):
+            c_concat = [xs.new_zeros((xs.shape[0], 0) + tuple(xs.shape[2:]))]
+        if unet is not None and c_concat is not None:
+            cond = th.cat([c.to(device) for c in c_concat], 1)
+            res = run_bpd_loop(unet, sched, plv, prior_lv, xs, cond, step_noise=step_noise, seed=seed)
+        else:
+            seed = philox_seed(seed)
+            B = xs.shape[0]
+            res = {key: th.zeros((B, T), device=device, dtype=th.float32) for key in ("vb", "xstart_mse", "mse")}
+            res["prior_bpd"] = self._prior_bpd(xs)
+            tvals = th.from_numpy(sched.t_model)
+            for k in range(T):
+                a = th.full((B,), float(sched.coef[k, 0]), device=device)
+                s = th.full((B,), float(sched.coef[k, 1]), device=device)
+                z = None if step_noise is None else step_noise[k].to(device)
+                x_t = q_sample_rows(a, s, xs, z, seed, k)              # the loop's Philox stream (seed, k + 2^32) when not fed
+                tv = tvals[k]
+                is_int = (not self.rescale_timesteps) and float(tv) == int(tv)
+                t = th.full((B,), int(tv) if is_int else float(tv), device=device, dtype=th.long if is_int else th.float32)
+                out = model(x_t, t, **model_kwargs)
+                if isinstance(out, tuple):
+                    out = out[0]
+                vlb_terms(sched, k, float(plv[k]), out, x_t, xs, z, seed, vb=res["vb"][:, k], xstart_mse=res["xstart_mse"][:, k],
+                          mse=res["mse"][:, k])
+        res["total_bpd"] = res["vb"].sum(dim=1) + res["prior_bpd"]             # :984
+        return res
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

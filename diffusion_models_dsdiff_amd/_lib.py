@@ -38,6 +38,7 @@ EXPORTS = [
     "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
     "dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step",
     "dsd_sample_dpm_program", "dsd_sample_dpm_program_latent", "dsd_op_dpm_eval",
+    "dsd_calc_bpd", "dsd_calc_bpd_latent", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
 ]
 
 
@@ -87,6 +88,11 @@ class DsdInpaint(C.Structure):
 
 class DsdInvertSchedule(C.Structure):
     _fields_ = [("steps", C.c_int32), ("coef", C.POINTER(C.c_float)), ("t_model", C.POINTER(C.c_float))]
+
+
+class DsdBpd(C.Structure):
+    _fields_ = [("post_log_var", C.POINTER(C.c_float)), ("vb", C.c_void_p), ("xstart_mse", C.c_void_p), ("mse", C.c_void_p),
+                ("prior", C.c_void_p), ("prior_log_var", C.c_float)]
 
 
 class DsdConvEx(C.Structure):
@@ -234,6 +240,13 @@ def lib() -> C.CDLL:
     L.dsd_sample_dpm_program.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, f32p, vp]
     L.dsd_sample_dpm_program_latent.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, i32, f32p, vp]
     L.dsd_op_dpm_eval.argtypes = [pp, i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p, i32, i32, i32, i32, vp]
+    bp, sp = C.POINTER(DsdBpd), C.POINTER(DsdSchedule)
+    L.dsd_calc_bpd.argtypes = [vp, sp, bp, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_calc_bpd_latent.argtypes = [vp, sp, bp, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_op_vlb_terms.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, f32p, C.c_uint64, f32p, f32p, f32p, i64, f32p, f32p,
+                                   f32p, i32, i32, i32, i32, vp]
+    L.dsd_op_prior_bpd.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, i32, i32, i32, vp]
+    L.dsd_op_ddim_reverse_step.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

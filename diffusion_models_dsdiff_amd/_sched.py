@@ -7,7 +7,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import DSD_NCOEF, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
+from ._lib import DSD_NCOEF, DsdBpd, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
 
 
 class Schedule:
@@ -431,6 +431,103 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     check(lib().dsd_invert(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), B, H, W, first_step, n_steps,
                            stream_ptr()))
     return x
+
+
+@torch.no_grad()
+def run_bpd_loop(unet, sched: Schedule, post_log_var: np.ndarray, prior_log_var: float, x_start: torch.Tensor, cond: torch.Tensor,
+                 step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, first_step: int = 0, n_steps: int = 0,
+                 out: Optional[dict] = None) -> dict:
+    """The variational-bound device loop (dsd_calc_bpd / dsd_calc_bpd_latent) on a DSD_MODE_A_DDPM schedule: x_start [B,1,H,W]
+    with the four-stream model, [B,Cz,H,W] with the UNetModel or the DiT; read only.  ``post_log_var`` [steps]: the fp32
+    posterior_log_variance_clipped in iteration order; ``prior_log_var``: log(1 - alphas_cumprod[T-1]).  ``step_noise``
+    [steps,B,Cz,H,W] feeds q_sample's normals, else Philox stream (seed, k + 2^32).  Returns {"vb", "xstart_mse", "mse"} [B,steps]
+    (column k = iteration k) and {"prior_bpd"} [B]; ``out`` (a dict this function returned) is written in place, so a split run
+    fills its columns call by call."""
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNetModel / DiT) behind the model handed to the bound")
+    if not x_start.is_cuda:
+        raise RuntimeError("the variational bound runs on the MI355X only (no CPU fallback): x_start is on the CPU")
+    unet.sync_params()
+    xs = x_start.detach().float().contiguous()
+    cond = cond.detach().float().contiguous()
+    post_log_var = np.ascontiguousarray(post_log_var, dtype=np.float32)
+    assert post_log_var.shape == (sched.steps,)
+    B, Cz, H, W = xs.shape
+    if step_noise is not None:
+        step_noise = step_noise.detach().float().contiguous()
+        if tuple(step_noise.shape) != (sched.steps, B, Cz, H, W):
+            raise ValueError(f"step_noise must be [steps,B,C,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
+    seed = philox_seed(seed)
+    if out is None:
+        out = {k: torch.zeros((B, sched.steps), device=xs.device, dtype=torch.float32) for k in ("vb", "xstart_mse", "mse")}
+        out["prior_bpd"] = torch.zeros((B,), device=xs.device, dtype=torch.float32)
+    bpd = DsdBpd()
+    bpd.post_log_var = post_log_var.ctypes.data_as(C.POINTER(C.c_float))
+    bpd.vb, bpd.xstart_mse, bpd.mse = out["vb"].data_ptr(), out["xstart_mse"].data_ptr(), out["mse"].data_ptr()
+    bpd.prior, bpd.prior_log_var = out["prior_bpd"].data_ptr(), float(prior_log_var)
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, xs, cond)
+        check(lib().dsd_calc_bpd_latent(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), Cz,
+                                        dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+        return out
+    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == xs.shape[2:]
+    check(lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), dptr(step_noise),
+                             C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def vlb_terms(sched: Schedule, k: int, post_log_var: float, model_out: torch.Tensor, x_t: torch.Tensor, x_start: torch.Tensor,
+              noise: Optional[torch.Tensor], seed: int = 0, vb: Optional[torch.Tensor] = None,
+              xstart_mse: Optional[torch.Tensor] = None, mse: Optional[torch.Tensor] = None, want_planes: bool = False,
+              state_channels: Optional[int] = None):
+    """The bound's terms of iteration k (dsd_op_vlb_terms).  ``vb`` / ``xstart_mse`` / ``mse``: fp32 views of B elements with one
+    stride — a column of the [B,steps] results — written in place (None: not wanted).  ``x_t`` is [B,Cz,H,W], or a [B,Cz+Cc,H,W]
+    denoiser input with ``state_channels`` = Cz; ``model_out`` [B,Cz,H,W], or [B,2Cz,H,W] where it carries a variance half.
+    ``want_planes``: returns p_mean_variance's (mean, log_variance, pred_xstart)."""
+    B, Cz, H, W = x_start.shape
+    cz, x_stride = _rows(x_t, state_channels)
+    assert cz == Cz and x_t.shape[0] == B and tuple(x_t.shape[2:]) == (H, W)
+    mo, xs, z = _f32c(model_out), _f32c(x_start), _f32c(noise)
+    assert mo.shape[0] == B and mo.shape[1] in (Cz, 2 * Cz) and tuple(mo.shape[2:]) == (H, W)
+    if sched.c.learned_range and mo.shape[1] != 2 * Cz:
+        raise ValueError(f"a learned-range variance needs {2 * Cz} output channels; the model output has {mo.shape[1]}")
+    terms = [t for t in (vb, xstart_mse, mse) if t is not None]
+    stride = 0
+    for t in terms:
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.shape[0] == B
+        assert stride in (0, t.stride(0) or 1) or B == 1, "vb / xstart_mse / mse must share their stride"
+        stride = t.stride(0) or 1
+    planes = [torch.empty((B, Cz, H, W), device=xs.device, dtype=torch.float32) for _ in range(3)] if want_planes else [None] * 3
+    tp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    check(lib().dsd_op_vlb_terms(C.byref(sched.c), int(k), float(post_log_var), dptr(mo), mo.shape[1] * H * W, dptr(x_t), x_stride,
+                                 dptr(xs), dptr(z), C.c_uint64(seed), tp(vb), tp(xstart_mse), tp(mse), stride, dptr(planes[0]),
+                                 dptr(planes[1]), dptr(planes[2]), B, Cz, H, W, stream_ptr()))
+    return tuple(planes) if want_planes else None
+
+
+@torch.no_grad()
+def prior_bpd(sqrt_acp: float, log_1m_acp: float, x_start: torch.Tensor) -> torch.Tensor:
+    """_prior_bpd (dsd_op_prior_bpd): [B] bits per dimension."""
+    B, Cz, H, W = x_start.shape
+    xs = _f32c(x_start)
+    out = torch.empty((B,), device=xs.device, dtype=torch.float32)
+    check(lib().dsd_op_prior_bpd(float(sqrt_acp), float(log_1m_acp), dptr(xs), dptr(out), B, Cz, H, W, stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def ddim_reverse_step(sched: Schedule, k: int, alpha_bar_next: float, model_out: torch.Tensor, x: torch.Tensor,
+                      want_x0: bool = False, state_channels: Optional[int] = None):
+    """One step of the DDIM reverse ODE (dsd_op_ddim_reverse_step), x updated in place to x_{t+1}."""
+    B, _, H, W = x.shape
+    Cz, stride = _rows(x, state_channels)
+    mo = _f32c(model_out)
+    assert mo.shape[0] == B and mo.shape[1] >= Cz and tuple(mo.shape[2:]) == (H, W)
+    x0 = torch.empty((B, Cz, H, W), device=x.device, dtype=torch.float32) if want_x0 else None
+    check(lib().dsd_op_ddim_reverse_step(C.byref(sched.c), int(k), float(alpha_bar_next), dptr(mo), mo.shape[1] * H * W, dptr(x),
+                                         stride, dptr(x0), B, Cz, H, W, stream_ptr()))
+    return x0
 
 
 def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:

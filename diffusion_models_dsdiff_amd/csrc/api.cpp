@@ -225,7 +225,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->bpd_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -1159,6 +1159,135 @@ int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const f
     DSD_CHECK(out_cond && x, "null argument");
     check_op_state(B, Cz, H, W, x_row_stride);
     ddim_invert_step(cx, ce, out_uncond, out_cond, scale, x, B, Cz, H * W, (hipStream_t)stream, x_row_stride);
+    DSD_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- variational bound
+// calc_bpd_loop (gaussian_diffusion.py:938-991): the sampling loops' bindings with a state of the loop's own — pre(k) is the
+// q_sample of x_start into it, step(k) the read-only terms pass — so the caller's x_start is never written and finish() never runs.
+static void check_bpd_schedule(const dsd_schedule* sc) {
+    check_schedule(sc);
+    DSD_CHECK(sc->mode == DSD_MODE_A_DDPM,
+              "the variational bound is defined on the guided-diffusion posterior (DSD_MODE_A_DDPM: coef 4-7 hold its mean "
+              "coefficients and log-variances); the schedule has mode %d", sc->mode);
+}
+
+static VlbStep vlb_step(const dsd_schedule* sc, int k, float post_log_var) {
+    VlbStep a;
+    a.sc = step_coef(sc, k);
+    a.post_log_var = post_log_var;
+    a.step = (uint64_t)k;
+    return a;
+}
+
+static void calc_bpd(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc,
+                     const float* x_start, int Cz, const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
+                     void* stream) {
+    check_bpd_schedule(sc);
+    DSD_CHECK(bpd, "null dsd_bpd");
+    DSD_CHECK(bpd->post_log_var, "the bound needs the true posterior's log-variances (post_log_var is null; %d steps)", sc->steps);
+    DSD_CHECK(bpd->vb && bpd->xstart_mse && bpd->mse, "null output: vb %p xstart_mse %p mse %p", (void*)bpd->vb, (void*)bpd->xstart_mse,
+              (void*)bpd->mse);
+    DSD_CHECK(!(sc->learned_range && Cz > 1) || is_dit(h),
+              "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
+    const int want_ch = (sc->learned_range ? 2 : 1) * Cz;
+    const int out_ch = check_denoiser(latent, h, nullptr, cond, Cc, x_start, Cz, B, H, W, want_ch);
+    DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d%s", h->cfg.out_channels,
+              out_ch, sc->learned_range ? " (learned_range needs a variance half)" : "");
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W, n = Cz * hw;
+    const size_t part_bytes = (vlb_part_doubles(B, n) * sizeof(double) + 15) / 16 * 16;
+    ensure_buf(&h->bpd_buf, &h->bpd_cap, part_bytes + (latent ? 0 : (size_t)B * n * sizeof(float)));
+    double* part = reinterpret_cast<double*>(h->bpd_buf);
+    // the four-stream model reads its state plane in place: it gets the loop's own; the latent binding copies into lat_in and
+    // only finish() would write back
+    float* state = latent ? const_cast<float*>(x_start) : h->bpd_buf + part_bytes / sizeof(float);
+    const LoopBinding b = bind_denoiser(latent, h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s);
+    const float* c_first = sc->coef;
+    if (bpd->prior) prior_bpd(c_first[0], bpd->prior_log_var, x_start, part, bpd->prior, B, n, s);
+    run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s,
+             [&](int k) {
+                 const float* c = sc->coef + (size_t)k * DSD_NCOEF;
+                 q_sample_blend(c[0], c[1], nullptr, nullptr, x_start, nullptr, 0, b.xs, noise ? noise + (size_t)k * B * n : nullptr,
+                                seed, (uint64_t)k, B, Cz, (int)hw, s, b.x_bs, false, b.ids);
+             },
+             [&](int k) {
+                 VlbStep a = vlb_step(sc, k, bpd->post_log_var[k]);
+                 a.x_start = x_start;
+                 a.xt = b.xs; a.x_bs = b.x_bs;
+                 a.out = b.out_c; a.o_bs = out_ch * hw;
+                 a.noise = noise ? noise + (size_t)k * B * n : nullptr;
+                 a.seed = seed;
+                 a.slice_ids = b.ids;
+                 a.part = part;
+                 vlb_terms(a, k == sc->steps - 1, bpd->vb + k, bpd->xstart_mse + k, bpd->mse + k, sc->steps, B, Cz, (int)hw, s);
+             });
+    net_check_overflow(h, s);
+}
+
+int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
+                 const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    calc_bpd(false, h, sc, bpd, cond, Cc, x_start, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_calc_bpd_latent(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
+                        int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+                        void* stream) {
+    DSD_TRY
+    calc_bpd(true, h, sc, bpd, cond, Cc, x_start, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
+    DSD_CATCH
+}
+
+int dsd_op_vlb_terms(const dsd_schedule* sc, int k, float post_log_var, const float* model_out, int64_t out_row_stride,
+                     const float* x_t, int64_t x_row_stride, const float* x_start, const float* noise, uint64_t philox_seed,
+                     float* vb, float* xstart_mse, float* mse, int64_t term_stride, float* mean, float* log_variance,
+                     float* pred_xstart, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    check_bpd_schedule(sc);
+    DSD_CHECK(k >= 0 && k < sc->steps && model_out && x_t && x_start, "bad argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    const int64_t need = (int64_t)(sc->learned_range ? 2 : 1) * Cz * H * W;
+    DSD_CHECK(out_row_stride == 0 || out_row_stride >= need, "out_row_stride %lld is smaller than one output row (%lld)",
+              (long long)out_row_stride, (long long)need);
+    DSD_CHECK(term_stride >= 0, "term_stride %lld", (long long)term_stride);
+    Tmp part(vlb_part_doubles(B, (int64_t)Cz * H * W) * sizeof(double));
+    VlbStep a = vlb_step(sc, k, post_log_var);
+    a.x_start = x_start;
+    a.xt = x_t; a.x_bs = x_row_stride;
+    a.out = model_out; a.o_bs = out_row_stride;
+    a.noise = noise;
+    a.seed = philox_seed;
+    a.part = part.as<double>();
+    a.mean = mean; a.log_variance = log_variance; a.pred_xstart = pred_xstart;
+    vlb_terms(a, k == sc->steps - 1, vb, xstart_mse, mse, term_stride, B, Cz, H * W, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_prior_bpd(float sqrt_acp, float log_1m_acp, const float* x_start, float* prior, int B, int Cz, int H, int W,
+                     void* stream) {
+    DSD_TRY
+    DSD_CHECK(x_start && prior, "null argument");
+    check_op_state(B, Cz, H, W, 0);
+    Tmp part(vlb_part_doubles(B, (int64_t)Cz * H * W) * sizeof(double));
+    prior_bpd(sqrt_acp, log_1m_acp, x_start, part.as<double>(), prior, B, (int64_t)Cz * H * W, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_ddim_reverse_step(const dsd_schedule* sc, int k, float alpha_bar_next, const float* model_out, int64_t out_row_stride,
+                             float* x, int64_t x_row_stride, float* pred_xstart, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    check_schedule(sc);
+    DSD_CHECK(sc->mode == DSD_MODE_A_DDPM || sc->mode == DSD_MODE_A_DDIM,
+              "ddim_reverse_sample belongs to the guided-diffusion family (DSD_MODE_A_*: coef 0-3); the schedule has mode %d", sc->mode);
+    DSD_CHECK(k >= 0 && k < sc->steps && model_out && x, "bad argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    DSD_CHECK(out_row_stride == 0 || out_row_stride >= (int64_t)Cz * H * W, "out_row_stride %lld is smaller than one sample (%lld)",
+              (long long)out_row_stride, (long long)Cz * H * W);
+    ddim_reverse_step(step_coef(sc, k), alpha_bar_next, model_out, x, pred_xstart, B, Cz, H * W, (hipStream_t)stream, x_row_stride,
+                      out_row_stride);
     DSD_CATCH
 }
 

@@ -319,6 +319,37 @@ struct PlmsStep {
 };
 size_t plms_norm_doubles(int B, int64_t n);
 void plms_step(const PlmsStep& a, int B, int Cz, int HW, hipStream_t s);
+// Variational bound (sampler.hip; gaussian_diffusion.py:788-819, 938-991): the terms of one timestep on B samples of n = Cz*HW
+// elements from the network output of x_t = q_sample(x_start, t, noise).  sc: the DSD_MODE_A_DDPM coefficients of the step;
+// post_log_var: posterior_log_variance_clipped[t] (c[6] except under FIXED_LARGE).  x_start / noise and the optional planes
+// mean / log_variance / pred_xstart are [B,n]; x_t row b at xt + b*x_bs (0 = n); output row b at out + b*o_bs (0 = n, 2n with
+// learned_range: the variance half follows the prediction).  noise == nullptr: the normals of Philox stream (seed, step + 2^32),
+// counter keyed by slice_ids — the ones q_sample_blend drew x_t from.  part: vlb_part_doubles(B, n) doubles of scratch.
+struct VlbStep {
+    StepCoef sc;
+    float post_log_var = 0.f;
+    const float* x_start = nullptr;
+    const float* xt = nullptr;
+    const float* out = nullptr;
+    const float* noise = nullptr;
+    int64_t x_bs = 0, o_bs = 0;
+    uint64_t seed = 0, step = 0;
+    const int64_t* slice_ids = nullptr;
+    double* part = nullptr;
+    float* mean = nullptr;
+    float* log_variance = nullptr;
+    float* pred_xstart = nullptr;
+};
+size_t vlb_part_doubles(int B, int64_t n);
+// decoder: t == 0, the term is the discretised decoder NLL instead of the KL.  Sample b's vb (bits), mean (pred_xstart - x_start)^2
+// and mean (eps - noise)^2 go to vb / xstart_mse / mse [b*term_stride] (each optional; all null: the planes only).
+void vlb_terms(const VlbStep& a, bool decoder, float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int HW,
+               hipStream_t s);
+// _prior_bpd (:922-936): mean normal_kl(c0*x_start, logvar, 0, 0) / ln 2 per sample; part: vlb_part_doubles(B, n) doubles
+void prior_bpd(float c0, float logvar, const float* x_start, double* part, float* prior, int B, int64_t n, hipStream_t s);
+// ddim_reverse_sample (:691-701) in place on the state rows; x0_out (optional, [B,Cz*HW]) receives the clipped pred_xstart
+void ddim_reverse_step(const StepCoef& sc, float abar_next, const float* out, float* x, float* x0_out, int B, int Cz, int HW,
+                       hipStream_t st, int64_t x_bs = 0, int64_t o_bs = 0);
 void dpm_threshold(const float* x0, float* y, float* s_buf, float ratio, float max_val, int B, int n, hipStream_t s);
 void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_t s);
 // DiagonalGaussianDistribution.sample (ldm/modules/distributions/distributions.py:24-37): moments [B,2E,HW] (NCHW) ->

@@ -657,6 +657,7 @@ void dsd::net_free(dsd_handle* h) {
     if (h->lat_in) (void)hipFree(h->lat_in);
     if (h->cfg_io) (void)hipFree(h->cfg_io);
     if (h->plms_hist) (void)hipFree(h->plms_hist);
+    if (h->bpd_buf) (void)hipFree(h->bpd_buf);
     if (h->freqs) (void)hipFree(h->freqs);
     if (h->ovf) (void)hipFree(h->ovf);
     if (h->slice_ids) (void)hipFree(h->slice_ids);

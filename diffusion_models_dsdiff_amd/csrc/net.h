@@ -156,6 +156,7 @@ struct dsd_handle {
     // with first_step > 0 continues it: plms_next is the iteration it is valid for (-1: none), for plms_B samples of plms_n
     // elements under a schedule of plms_steps iterations.
     float* plms_hist = nullptr;
+    float* bpd_buf = nullptr;  // variational-bound loops: the per-block partial sums (doubles), then the four-stream loop's x_t state [B,H*W]
     int plms_next = -1, plms_B = 0, plms_steps = 0;
     int64_t plms_n = 0;
     float* freqs = nullptr;    // [model_channels/2] optional timestep-embedding frequency table (host-supplied)
@@ -203,7 +204,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, bpd_cap = 0;
 
     float* P(const std::string& name) const;
     float* slab_at(size_t off) const { return reinterpret_cast<float*>(slab + off); }

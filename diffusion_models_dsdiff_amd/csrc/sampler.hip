@@ -118,10 +118,11 @@ __device__ __forceinline__ float ddim_update(const StepCoef& sc, float out, floa
     return sqrtf(c[5]) * x0 + dir + c[6] * z;
 }
 
-// x_{t-1} of one element in any of the four modes; var = the learned-range variance channel (read only with learned_range)
-__device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float out, float xt, float z, float var, float& x0) {
-    if (sc.mode == DSD_MODE_B_DDIM) return ddim_update(sc, out, xt, z, x0);
+// pred_xstart of the guided-diffusion family and of ldm's DDPM (gaussian_diffusion.py:311-341): the network output as v, eps or
+// x_start, then process_xstart's clip
+__device__ __forceinline__ float pred_xstart_value(const StepCoef& sc, float out, float xt) {
     const float* c = sc.c;
+    float x0;
     if (sc.pred == DSD_PRED_V)
         x0 = c[0] * xt - c[1] * out;
     else if (sc.pred == DSD_PRED_EPS)
@@ -129,6 +130,20 @@ __device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float 
     else
         x0 = out;
     if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    return x0;
+}
+// the learned-range log-variance (gaussian_diffusion.py:287-293) from the variance channel, or the step's fixed one
+__device__ __forceinline__ float model_log_variance(const StepCoef& sc, float var) {
+    if (!sc.learned_range) return sc.c[6];
+    const float frac = (var + 1.f) / 2.f;
+    return frac * sc.c[7] + (1.f - frac) * sc.c[6];
+}
+
+// x_{t-1} of one element in any of the four modes; var = the learned-range variance channel (read only with learned_range)
+__device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float out, float xt, float z, float var, float& x0) {
+    if (sc.mode == DSD_MODE_B_DDIM) return ddim_update(sc, out, xt, z, x0);
+    const float* c = sc.c;
+    x0 = pred_xstart_value(sc, out, xt);
     const float nz = sc.nonzero ? 1.f : 0.f;
     if (sc.mode == DSD_MODE_A_DDIM) {
         // gaussian_diffusion.py:646-664
@@ -140,11 +155,7 @@ __device__ __forceinline__ float sampler_update_value(const StepCoef& sc, float 
     }
     // DDPM: q_posterior mean + exp(0.5 logvar) z   (gaussian_diffusion.py:220-223,464; trainer_ddpm.py:467)
     const float mean = c[4] * x0 + c[5] * xt;
-    float logvar = c[6];
-    if (sc.learned_range) {  // gaussian_diffusion.py:287-293
-        const float frac = (var + 1.f) / 2.f;
-        logvar = frac * c[7] + (1.f - frac) * c[6];
-    }
+    const float logvar = model_log_variance(sc, var);
     return mean + nz * expf(0.5f * logvar) * z;
 }
 
@@ -497,8 +508,8 @@ void dpm_eval(const DpmCoef& c, const DpmEval& ev, const float* out_u, const flo
 static constexpr uint64_t kBlendStream = 1ull << 32;
 
 // Grid: x over the packs of one sample (capped, strided), y = the sample — the row's coefficients and its slice id are
-// block-uniform and no 64-bit division is left.  BLEND selects the mask blend (scalar a, s) or the plain q_sample (a_row, s_row):
-// one kernel with every argument live spilled scalar registers.
+// block-uniform and no 64-bit division is left.  BLEND selects the mask blend (scalar a, s) or the plain q_sample (a_row, s_row,
+// or without them the scalars: one timestep for the whole batch): one kernel with every argument live spilled scalar registers.
 template <int V, bool BLEND>
 __global__ __launch_bounds__(256) void q_sample_blend_kernel(float a, float s, const float* __restrict__ a_row,
                                                              const float* __restrict__ s_row, const float* __restrict__ x0,
@@ -507,7 +518,7 @@ __global__ __launch_bounds__(256) void q_sample_blend_kernel(float a, float s, c
                                                              int n, int hw, int64_t x_bs, int dup,
                                                              const int64_t* __restrict__ slice_ids) {
     const int b = blockIdx.y;
-    const float ca = BLEND ? a : a_row[b], cs = BLEND ? s : s_row[b];
+    const float ca = (BLEND || !a_row) ? a : a_row[b], cs = (BLEND || !s_row) ? s : s_row[b];
     const int64_t row = (int64_t)b * n;                                       // in the [B,n] tensors
     const int64_t ctr = slice_ids ? slice_ids[b] * n : row;                   // Philox counter of the row's first element
     float* xr = x + (int64_t)b * x_bs;
@@ -707,6 +718,257 @@ void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
     const dim3 grid((unsigned)std::min<int64_t>(blocks, 2048), (unsigned)B);
     launch_vec(v4, [&](auto V) { hipLaunchKernelGGL(plms_update_kernel<decltype(V)::value>, grid, dim3(256), 0, s, a, B, (int)n, nblk); });
     check_launch("plms_update");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Variational bound (gaussian_diffusion.py:788-819, 922-991; losses.py).  One read-only pass after the network evaluation of
+// iteration k forms, per element and in the reference's fp32 operation order, the KL of the true posterior against the model's
+// (DECODER, t == 0: the negated discretised log-likelihood), (pred_xstart - x_start)^2 and (eps - noise)^2, and sums the three
+// per sample as plms_x0_norm_kernel sums its norm: every thread in fp64, the block in a fixed LDS tree, block j of sample b into
+// part[(b*gridDim.x + j)*3 + q]; vlb_finalize_kernel adds the partials in a fixed order.  No atomics: two runs are bit-identical.
+// Grid: x over the 1024-element pieces of one sample, y = the sample.  A thread owns four consecutive elements and there is NO
+// grid-stride loop: out of a loop the compiler hoists the constants of the inlined logf / sinf / cosf / expf / tanhf into scalar
+// registers and spilled them (12-38 per instantiation), as it did in sampler_update_kernel.  V only selects how the four are
+// loaded and stored (one 16-byte access, or guarded scalar ones), so both forms add the same values in the same order.
+static constexpr int kVlbPiece = 1024;
+
+template <int V> __device__ __forceinline__ Pack<4> ld_quad(const float* p, int valid) {
+    if constexpr (V == 4) return ld_pack<4>(p);
+    Pack<4> r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[j] = j < valid ? p[j] : 0.f;
+    return r;
+}
+template <int V> __device__ __forceinline__ void st_quad(float* p, const Pack<4>& a, int valid) {
+    if constexpr (V == 4) {
+        st_pack<4>(p, a);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < valid) p[j] = a.v[j];
+    }
+}
+
+// the NQ sums of a block: the 256 threads' sums folded in the fixed tree, thread 0 writes them
+template <int NQ>
+__device__ __forceinline__ void vlb_block_fold(const double (&acc)[NQ], double* red, double* dst) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) red[q * 256 + threadIdx.x] = acc[q];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) red[q * 256 + threadIdx.x] += red[q * 256 + threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) dst[q] = red[q * 256];
+    }
+}
+
+// normal_kl (losses.py:32-38), left to right
+__device__ __forceinline__ float normal_kl_value(float mean1, float logvar1, float mean2, float logvar2) {
+    const float d = mean1 - mean2;
+    return 0.5f * (-1.0f + logvar2 - logvar1 + expf(logvar1 - logvar2) + (d * d) * expf(-logvar2));
+}
+// approx_standard_normal_cdf (losses.py:41-46); pow(x, 3) is x*x*x in torch
+__device__ __forceinline__ float approx_normal_cdf(float x) {
+    return 0.5f * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * (x * x * x))));
+}
+// discretized_gaussian_log_likelihood (losses.py:49-77)
+__device__ __forceinline__ float discretized_log_likelihood(float x, float mean, float log_scale) {
+    const float centered = x - mean;
+    const float inv_stdv = expf(-log_scale);
+    const float cdf_plus = approx_normal_cdf(inv_stdv * (centered + (float)(1.0 / 255.0)));
+    const float cdf_min = approx_normal_cdf(inv_stdv * (centered - (float)(1.0 / 255.0)));
+    float arg = fmaxf(cdf_plus - cdf_min, 1e-12f);
+    if (x > 0.999f) arg = fmaxf(1.0f - cdf_min, 1e-12f);
+    if (x < -0.999f) arg = fmaxf(cdf_plus, 1e-12f);
+    return logf(arg);                                          // one logf: the selects choose its argument
+}
+
+template <int V, bool DECODER>
+__global__ __launch_bounds__(256) void vlb_terms_kernel(VlbStep a, int n) {
+    __shared__ double red[3 * 256];
+    const int b = blockIdx.y;
+    const StepCoef& sc = a.sc;
+    const int64_t row = (int64_t)b * n;
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int valid = n - p;                                   // <= 0: nothing of this thread's lies inside the sample
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (valid > 0) {
+        const float* orow = a.out + (int64_t)b * a.o_bs + p;
+        const Pack<4> xs = ld_quad<V>(a.x_start + row + p, valid), xt = ld_quad<V>(a.xt + (int64_t)b * a.x_bs + p, valid);
+        const Pack<4> out = ld_quad<V>(orow, valid);
+        Pack<4> z, var = {};
+        if (a.noise) {
+            z = ld_quad<V>(a.noise + row + p, valid);
+        } else {
+            const int64_t ctr = (a.slice_ids ? a.slice_ids[b] * n : row) + p;
+            if constexpr (V == 4) {
+                z = philox_normal_pack<4>(ctr, a.seed, a.step + kBlendStream);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z.v[j] = j < valid ? philox_normal_at(ctr + j, a.seed, a.step + kBlendStream) : 0.f;
+            }
+        }
+        if (sc.learned_range) var = ld_quad<V>(orow + n, valid);
+        Pack<4> mean, lv, x0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            x0.v[j] = pred_xstart_value(sc, out.v[j], xt.v[j]);
+            mean.v[j] = sc.c[4] * x0.v[j] + sc.c[5] * xt.v[j];                 // q_posterior_mean_variance :220-223
+            lv.v[j] = model_log_variance(sc, var.v[j]);
+            float term;
+            if constexpr (DECODER) {
+                term = -discretized_log_likelihood(xs.v[j], mean.v[j], 0.5f * lv.v[j]);
+            } else {
+                const float true_mean = sc.c[4] * xs.v[j] + sc.c[5] * xt.v[j];
+                term = normal_kl_value(true_mean, a.post_log_var, mean.v[j], lv.v[j]);
+            }
+            const float dx = x0.v[j] - xs.v[j];
+            const float eps = (sc.c[2] * xt.v[j] - x0.v[j]) / sc.c[3];         // _predict_eps_from_xstart :369-373
+            const float de = eps - z.v[j];
+            if (j < valid) {
+                acc[0] += (double)term;
+                acc[1] += (double)(dx * dx);
+                acc[2] += (double)(de * de);
+            }
+        }
+        if (a.mean) st_quad<V>(a.mean + row + p, mean, valid);
+        if (a.log_variance) st_quad<V>(a.log_variance + row + p, lv, valid);
+        if (a.pred_xstart) st_quad<V>(a.pred_xstart + row + p, x0, valid);
+    }
+    vlb_block_fold<3>(acc, red, a.part + ((int64_t)b * gridDim.x + blockIdx.x) * 3);
+}
+
+// _prior_bpd's kl_prior (:932-935): normal_kl(c0*x_start, log(1 - acp[T-1]), 0.0, 0.0) per element
+template <int V>
+__global__ __launch_bounds__(256) void prior_kl_kernel(float c0, float logvar, const float* __restrict__ x_start, int n,
+                                                       double* __restrict__ part) {
+    __shared__ double red[256];
+    const int b = blockIdx.y;
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int valid = n - p;
+    double acc[1] = {0.0};
+    if (valid > 0) {
+        const Pack<4> xs = ld_quad<V>(x_start + (int64_t)b * n + p, valid);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float kl = normal_kl_value(c0 * xs.v[j], logvar, 0.0f, 0.0f);
+            if (j < valid) acc[0] += (double)kl;
+        }
+    }
+    vlb_block_fold<1>(acc, red, part + (int64_t)b * gridDim.x + blockIdx.x);
+}
+
+// One wave per sample: lane l adds the partials l, l+64, ... in index order, the 64 lane sums fold in a fixed tree; mean_flat
+// in fp64 rounded to fp32 once, then (quantity 0) the reference's fp32 division by np.log(2.0).  Quantity q of sample b goes to
+// out[q][b*stride].
+__global__ __launch_bounds__(64) void vlb_finalize_kernel(const double* __restrict__ part, int nblk, int nq, int n, float* o0,
+                                                          float* o1, float* o2, int64_t stride) {
+    __shared__ double red[3 * 64];
+    const int b = blockIdx.x;
+    for (int q = 0; q < nq; ++q) {
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < nblk; j += 64) sum += part[((int64_t)b * nblk + j) * nq + q];
+        red[q * 64 + threadIdx.x] = sum;
+    }
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int q = 0; q < nq; ++q) red[q * 64 + threadIdx.x] += red[q * 64 + threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        float* outs[3] = {o0, o1, o2};
+        for (int q = 0; q < nq; ++q) {
+            if (!outs[q]) continue;
+            float v = (float)(red[q * 64] / (double)n);
+            if (q == 0) v = v / 0.6931471805599453f;
+            outs[q][(int64_t)b * stride] = v;
+        }
+    }
+}
+
+static int vlb_blocks(int64_t n) { return (int)((n + kVlbPiece - 1) / kVlbPiece); }
+size_t vlb_part_doubles(int B, int64_t n) { return (size_t)B * vlb_blocks(n) * 3; }
+
+void vlb_terms(const VlbStep& step, bool decoder, float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int HW,
+               hipStream_t s) {
+    VlbStep a = step;
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    DSD_CHECK(n <= (int64_t)1 << 30, "variational bound: one sample has %lld elements; up to 2^30 are taken", (long long)n);
+    DSD_CHECK(B <= 65535, "variational bound: %d samples; up to 65535 are taken", B);
+    DSD_CHECK(a.part, "variational bound: the reduction needs its scratch");
+    const int64_t need = (a.sc.learned_range ? 2 : 1) * n;
+    if (a.x_bs <= 0) a.x_bs = n;
+    if (a.o_bs <= 0) a.o_bs = need;
+    DSD_CHECK(a.o_bs >= need, "variational bound: output rows of %lld elements, the terms read %lld", (long long)a.o_bs, (long long)need);
+    const bool v4 = can_vec4(n, a.x_bs, a.x_start, a.xt, a.out, a.noise, a.mean, a.log_variance, a.pred_xstart) && a.o_bs % 4 == 0;
+    const int nblk = vlb_blocks(n);
+    launch_vec(v4, [&](auto V) {
+        auto kern = decoder ? vlb_terms_kernel<decltype(V)::value, true> : vlb_terms_kernel<decltype(V)::value, false>;
+        hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, s, a, (int)n);
+    });
+    check_launch("vlb_terms");
+    if (!vb && !xstart_mse && !mse) return;
+    hipLaunchKernelGGL(vlb_finalize_kernel, dim3(B), dim3(64), 0, s, a.part, nblk, 3, (int)n, vb, xstart_mse, mse,
+                       term_stride > 0 ? term_stride : (int64_t)1);
+    check_launch("vlb_finalize");
+}
+
+void prior_bpd(float c0, float logvar, const float* x_start, double* part, float* prior, int B, int64_t n, hipStream_t s) {
+    if (!B || !n) return;
+    DSD_CHECK(n <= (int64_t)1 << 30, "prior bpd: one sample has %lld elements; up to 2^30 are taken", (long long)n);
+    DSD_CHECK(B <= 65535, "prior bpd: %d samples; up to 65535 are taken", B);
+    const int nblk = vlb_blocks(n);
+    launch_vec(can_vec4(n, n, x_start), [&](auto V) {
+        hipLaunchKernelGGL(prior_kl_kernel<decltype(V)::value>, dim3(nblk, B), dim3(256), 0, s, c0, logvar, x_start, (int)n, part);
+    });
+    check_launch("prior_kl");
+    hipLaunchKernelGGL(vlb_finalize_kernel, dim3(B), dim3(64), 0, s, part, nblk, 1, (int)n, prior, nullptr, nullptr, (int64_t)1);
+    check_launch("vlb_finalize");
+}
+
+// ddim_reverse_sample (gaussian_diffusion.py:691-701): eps re-derived from the clipped pred_xstart, x_{t+1} written in place
+template <int V>
+__global__ __launch_bounds__(256) void ddim_reverse_kernel(StepCoef sc, float abar_next, const float* __restrict__ mo,
+                                                           float* __restrict__ x, float* __restrict__ x0_out, int B, int64_t n,
+                                                           int64_t x_bs, int64_t o_bs) {
+    const int64_t nv = n / V, total = (int64_t)B * nv;
+    const float sa = sqrtf(abar_next), sb = sqrtf(1.f - abar_next);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / nv;
+        const int64_t p = (i - b * nv) * V;
+        const int64_t oi = b * o_bs + p, xi = b * x_bs + p;
+        const Pack<V> out = ld_pack<V>(mo + oi), xt = ld_pack<V>(x + xi);
+        Pack<V> res, x0;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            x0.v[j] = pred_xstart_value(sc, out.v[j], xt.v[j]);
+            const float eps = (sc.c[2] * xt.v[j] - x0.v[j]) / sc.c[3];
+            res.v[j] = x0.v[j] * sa + sb * eps;
+        }
+        st_pack<V>(x + xi, res);
+        if (x0_out) st_pack<V>(x0_out + b * n + p, x0);
+    }
+}
+
+void ddim_reverse_step(const StepCoef& sc, float abar_next, const float* out, float* x, float* x0_out, int B, int Cz, int HW,
+                       hipStream_t st, int64_t x_bs, int64_t o_bs) {
+    const int64_t n = (int64_t)Cz * HW;
+    if (!B || !n) return;
+    if (x_bs <= 0) x_bs = n;
+    if (o_bs <= 0) o_bs = n;
+    launch_vec(can_vec4(n, x_bs, out, x, x0_out) && o_bs % 4 == 0, [&](auto V) {
+        hipLaunchKernelGGL(ddim_reverse_kernel<decltype(V)::value>, dim3(ew_blocks(B * (n / decltype(V)::value))), dim3(256), 0, st, sc,
+                           abar_next, out, x, x0_out, B, n, x_bs, o_bs);
+    });
+    check_launch("ddim_reverse");
 }
 
 // scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed

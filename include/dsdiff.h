@@ -469,6 +469,55 @@ int dsd_op_q_sample(const float* a, const float* s, const float* x0, const float
 /* One inversion step.  out_uncond == NULL: x (B rows) <- cx*x + ce*out_cond; else the guided step on the 2B-row state. */
 int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const float* out_cond, float scale, float* x,
                             int64_t x_row_stride, int B, int Cz, int H, int W, void* stream);
+/* ---- variational bound in bits per dimension ------------------------------------------------
+ * Replaces GaussianDiffusion.calc_bpd_loop / _vb_terms_bpd / _prior_bpd (Disc_diff/guided_diffusion/gaussian_diffusion.py:
+ * 788-819, 922-991; losses.py) on a DSD_MODE_A_DDPM schedule.  Iteration k (t = steps-1-k) forms x_t = c0*x_start + c1*z in a
+ * state of the loop's own (x_start is read only and comes out untouched), evaluates the network once at t_model[k] and reduces,
+ * per sample, over the Cz*H*W elements:
+ *   vb          mean normal_kl(true posterior mean / post_log_var[k], model mean / model log-variance) / ln 2, or at t = 0
+ *               mean -discretized_gaussian_log_likelihood(x_start, model mean, 0.5 * model log-variance) / ln 2
+ *   xstart_mse  mean (pred_xstart - x_start)^2
+ *   mse         mean (eps - z)^2,  eps = (c2*x_t - pred_xstart) / c3
+ * pred_xstart (clipped with clip_denoised), the model mean and the fixed or learned-range log-variance are the values of
+ * dsd_sample's update; every product and sum is one rounded fp32 operation in the reference's order.  The sums are formed in
+ * fp64 from fixed per-block partials added in index order (no atomics): two runs are bit-identical.
+ * z: noise[k] of the fed [steps,B,Cz,H,W], or the Philox normals of stream (philox_seed, k + 2^32), keyed by logical sample and
+ * dsd_set_slice_ids.  Column k of the [B,steps] outputs is iteration k: the reference's stack order.  first_step / n_steps
+ * and dsd_set_graph work as in dsd_sample; columns outside the range are left as they are.
+ * Rejected before any device work: a mode other than DSD_MODE_A_DDPM, null outputs or a null post_log_var, learned_range on a
+ * model without a variance half, and the channel / shape / slice-id misfits of the sampling loops.  The entry points take no
+ * dsd_guidance: the reference evaluates the bound unguided. */
+typedef struct dsd_bpd {
+    const float* post_log_var; /* host, steps: posterior_log_variance_clipped[t] in iteration order (fp32 of the float64 table) */
+    float* vb;                 /* device, [B,steps] */
+    float* xstart_mse;         /* device, [B,steps] */
+    float* mse;                /* device, [B,steps] */
+    float* prior;              /* device, [B], or NULL: _prior_bpd from coef[0] (sqrt_acp at T-1) and prior_log_var */
+    float prior_log_var;       /* log(1 - alphas_cumprod[T-1]) */
+} dsd_bpd;
+int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sched, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
+                 const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
+/* The same on x_start [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, set up as in dsd_sample_latent. */
+int dsd_calc_bpd_latent(dsd_handle* h, const dsd_schedule* sched, const dsd_bpd* bpd, const float* cond, int Cc,
+                        const float* x_start, int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step,
+                        int n_steps, void* stream);
+/* The terms of iteration k alone, on caller buffers: model_out rows at model_out + b*out_row_stride (0: Cz*H*W, or 2*Cz*H*W
+ * with learned_range), x_t rows at x_t + b*x_row_stride (0: Cz*H*W), x_start and noise [B,Cz,H,W] (noise NULL: Philox stream
+ * (philox_seed, k + 2^32)).  Sample b's scalars go to vb / xstart_mse / mse [b*term_stride] (0: 1; each may be NULL); mean /
+ * log_variance / pred_xstart ([B,Cz,H,W], each may be NULL) receive p_mean_variance's planes. */
+int dsd_op_vlb_terms(const dsd_schedule* sched, int k, float post_log_var, const float* model_out, int64_t out_row_stride,
+                     const float* x_t, int64_t x_row_stride, const float* x_start, const float* noise, uint64_t philox_seed,
+                     float* vb, float* xstart_mse, float* mse, int64_t term_stride, float* mean, float* log_variance,
+                     float* pred_xstart, int B, int Cz, int H, int W, void* stream);
+/* _prior_bpd: prior[b] = mean normal_kl(sqrt_acp*x_start_b, log_1m_acp, 0, 0) / ln 2. */
+int dsd_op_prior_bpd(float sqrt_acp, float log_1m_acp, const float* x_start, float* prior, int B, int Cz, int H, int W,
+                     void* stream);
+/* ddim_reverse_sample (:667-703) after the network evaluation of iteration k of a family-A schedule: x (rows at x +
+ * b*x_row_stride, 0: Cz*H*W) <- pred_xstart*sqrt(alpha_bar_next) + sqrt(1 - alpha_bar_next)*eps, eps = (c2*x - pred_xstart)/c3,
+ * in place; pred_xstart (optional, [B,Cz,H,W]) receives the clipped prediction. */
+int dsd_op_ddim_reverse_step(const dsd_schedule* sched, int k, float alpha_bar_next, const float* model_out,
+                             int64_t out_row_stride, float* x, int64_t x_row_stride, float* pred_xstart, int B, int Cz, int H,
+                             int W, void* stream);
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in

@@ -24,12 +24,15 @@ that existed before them).  The host tables are built once outside the timed reg
 the same loop, and the result holds the ms per network evaluation of each and the ratios to ms2.  For a build from before the
 program entry, copy this script into a checkout of that commit (this tree's binding does not load such a library) and run
 `--dpm-family ms2` there; --baseline with those lines then also records this build's ms2 loop over that build's.
+With --bpd the variational-bound loop (dsd_calc_bpd_latent: q_sample, one network evaluation and the terms / finalize launches per
+step, Philox noise) is timed against the mode-A DDPM sampling loop of the same handle, schedule and step count (dsd_sample_latent):
+bpd_over_ddpm is what the three small launches cost beside a network evaluation.  Same alternation and untimed first step.
 With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
 run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this
 build's plain loop (the median of its device, unmasked and sample loops, which are the same call) to their mean.
 
     python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--mask] [--encode]
-                                 [--plms] [--dpm-family ss3,ms3,ms2] [--baseline other.json ...] [--json out.json]
+                                 [--plms] [--bpd] [--dpm-family ss3,ms3,ms2] [--baseline other.json ...] [--json out.json]
 """
 import argparse
 import json
@@ -63,8 +66,8 @@ def stats(v):
 
 def run_k(K, args):
     from diffusion_models_dsdiff_amd import _lib
-    from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, invert_coefficients, run_device_loop, run_invert_loop,
-                                                    run_plms_loop, sampler_update)
+    from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, invert_coefficients, run_device_loop, run_bpd_loop,
+                                                    run_invert_loop, run_plms_loop, sampler_update)
     from diffusion_models_dsdiff_amd.ldm.models.autoencoder import AutoencoderKL
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
     from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddpm import LatentDiffusion
@@ -117,7 +120,19 @@ def run_k(K, args):
     mask[:, :, h // 4:h - h // 4, h // 4:h - h // 4] = 0.
     inv_coef = invert_coefficients(torch.from_numpy(smp.ddim_alphas.astype("float32")), torch.tensor(smp.ddim_alphas_prev))
 
+    if args.bpd:
+        import numpy as np
+        from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion.script_util import create_gaussian_diffusion
+        gd_a = create_gaussian_diffusion(steps=1000, timestep_respacing=str(args.steps), parameterization="v")
+        sched_a, plv = gd_a._schedule(False, 0.0, True), gd_a._post_log_var()
+        prior_lv = float(np.float32(gd_a.log_one_minus_alphas_cumprod[-1]))
+        x_start = x0.clamp(-1, 1)
+
     def i2i_loop(kind, n_steps=0):
+        if kind == "bpd":
+            return run_bpd_loop(unet, sched_a, plv, prior_lv, x_start, c, seed=1, n_steps=n_steps)["vb"]
+        if kind == "ddpm_a":
+            return run_device_loop(unet, sched_a, xT, c, seed=1, n_steps=n_steps)
         if kind == "masked":
             return run_device_loop(unet, sched, xT, c, seed=1, n_steps=n_steps, inpaint=Inpaint(x0, mask))
         if kind == "invert":
@@ -148,7 +163,7 @@ def run_k(K, args):
                 dpm_runs[kind] = lambda prog=prog: dsa.run_dpm_program(fn, prog, xT)[0]
 
     i2i_kinds = ((("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ()) +
-                 (("plms", "ddim") if args.plms else ()))
+                 (("plms", "ddim") if args.plms else ()) + (("bpd", "ddpm_a") if args.bpd else ()))
     cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
     c = ld.encode_conditions(cond, seed=3)["c_concat"][0]          # warm-up: plans, code objects
     for kind in cfg_kinds:
@@ -208,6 +223,8 @@ def run_k(K, args):
     if args.plms:
         res["plms_over_ddim"] = res["plms_loop_ms"]["median"] / res["ddim_loop_ms"]["median"]
         res["plms_network_evaluations"] = sched.steps + 1
+    if args.bpd:
+        res["bpd_over_ddpm"] = res["bpd_loop_ms"]["median"] / res["ddpm_a_loop_ms"]["median"]
     if dpm_kinds:
         res["dpm_network_evaluations"] = DPM_EVALS
         for kind in dpm_kinds:
@@ -235,6 +252,7 @@ def main():
     ap.add_argument("--mask", action="store_true", help="also time the masked loop against the unmasked loop")
     ap.add_argument("--encode", action="store_true", help="also time the DDIM inversion loop against plain sampling")
     ap.add_argument("--plms", action="store_true", help="also time the PLMS loop against the DDIM loop of the same steps")
+    ap.add_argument("--bpd", action="store_true", help="also time the variational-bound loop against the mode-A DDPM sampling loop")
     ap.add_argument("--dpm-family", default="", help="comma list of ss3, ms3, ms2: also time those DPM-Solver++ loops of 21 evaluations")
     ap.add_argument("--baseline", action="append", default=[],
                     help="bench line of another build on the same machine (repeatable): record its plain loop beside this one's")
