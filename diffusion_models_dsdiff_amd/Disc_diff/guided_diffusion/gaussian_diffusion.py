@@ -17,7 +17,7 @@ import numpy as np
 import torch as th
 
 from ... import _lib
-from ..._sched import (Schedule, ddim_reverse_step, is_dit, loop_denoiser, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
+from ..._sched import (Schedule, ddim_reverse_step, is_dit, kwargs_conditioning, loop_denoiser, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
                        run_device_loop, sampler_update, vlb_terms, _seed_from_torch)
 
 
@@ -149,7 +149,8 @@ class GaussianDiffusion:
             # a Python hook sits between network and update: per-step host loop; a bare native U-Net does not concatenate
             # c_concat itself (DiffusionWrapper.forward does, ddpm.py:1328-1333)
             if unet is model:
-                model = lambda x, t, _u=unet, **kw: _u(th.cat([x] + [c.to(x.device) for c in kw.get("c_concat", [])], 1), t)
+                model = lambda x, t, _u=unet, **kw: _u(th.cat([x] + [c.to(x.device) for c in kw.get("c_concat", [])], 1), t,
+                                                       context=kw.get("context"), y=kw.get("y"))
             unet = None
         if device is None:
             device = next(model.parameters()).device if hasattr(model, "parameters") else th.device("cuda")
@@ -157,6 +158,9 @@ class GaussianDiffusion:
                 device = th.device("cuda")
         img = noise if noise is not None else th.randn(*shape, device=device)      # :591-594
         img = img.to(device)
+        bundle = kwargs_conditioning(unet, model, model_kwargs, device) if unet is not None and not is_dit(unet) else None
+        if bundle is not None:                                # context= / y= (or c_crossattn / c_adm) for a UNetModel
+            return run_device_loop(unet, sched, img, bundle, step_noise=step_noise, seed=seed)
         c_concat = model_kwargs.get("c_concat")
         if unet is not None and c_concat is None and is_dit(unet):
             c_concat = [img.new_zeros((img.shape[0], 0) + tuple(img.shape[2:]))]      # an unconditional DiT: all input is state
@@ -442,11 +446,12 @@ class GaussianDiffusion:
         device = x_start.device
         xs = x_start.float().contiguous()
         unet = loop_denoiser(model, model_kwargs)
+        bundle = kwargs_conditioning(unet, model, model_kwargs, device) if unet is not None and not is_dit(unet) else None
         c_concat = model_kwargs.get("c_concat")
         if unet is not None and c_concat is None and is_dit(unet):
             c_concat = [xs.new_zeros((xs.shape[0], 0) + tuple(xs.shape[2:]))]
-        if unet is not None and c_concat is not None:
-            cond = th.cat([c.to(device) for c in c_concat], 1)
+        if unet is not None and (c_concat is not None or bundle is not None):
+            cond = bundle if bundle is not None else th.cat([c.to(device) for c in c_concat], 1)
             res = run_bpd_loop(unet, sched, plv, prior_lv, xs, cond, step_noise=step_noise, seed=seed)
         else:
             seed = philox_seed(seed)

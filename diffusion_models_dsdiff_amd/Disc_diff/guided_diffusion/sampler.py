@@ -23,7 +23,8 @@ import torch
 
 from ..._lib import (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3, DPM_SS_S1, DPM_SS_S2, DPM_SS_T2, DPM_SS_T3, DPM_SS_T3_TAYLOR, DSD_DPM_NCOEF,
                       DSD_NCOEF, DsdDpmProgram, DsdDpmSchedule, check, dptr, lib, stream_ptr)
-from ..._sched import Guidance, cat_unconditional, check_latent_io, is_dit, is_latent_denoiser, loop_denoiser
+from ..._sched import (Conditioning, Guidance, cat_conditioning, cat_unconditional, check_latent_io, concat_of, conditioning_set,
+                       is_dit, is_latent_denoiser, kwargs_conditioning, loop_denoiser, wrapper_key)
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
 
@@ -122,6 +123,19 @@ class _ModelFn:
         if isinstance(out, tuple):
             out = out[0]
         return out
+
+    def bundle(self, unet, device):
+        """The Conditioning of a UNetModel denoiser where the condition (or model_kwargs) carries more than ``c_concat``: the
+        wrapper's c_crossattn / c_adm under its key, or the bare network's context= / y=.  None: the 'concat' path."""
+        if unet is None or is_dit(unet) or not is_latent_denoiser(unet):
+            return None
+        if self.condition is None:
+            return kwargs_conditioning(unet, self.model, self.model_kwargs, device)
+        key = wrapper_key(self.model)
+        if key in (None, "concat") and not (isinstance(self.condition, dict) and
+                                            ("c_crossattn" in self.condition or "c_adm" in self.condition)):
+            return None
+        return cat_conditioning(self.condition, device, key)
 
     def c_concat(self) -> Optional[list]:
         src = self.condition if self.condition is not None else self.model_kwargs
@@ -525,17 +539,20 @@ def _loop_denoiser_and_guidance(fn: "_ModelFn", steps: int, x_T: torch.Tensor, g
     """What both DPM routes settle before they touch the device: the native denoiser behind ``fn`` (None: the per-step path), the
     'concat' condition, and the guidance — the caller's, or what ``fn`` carries from model_wrapper — checked against them."""
     unet, cc = loop_denoiser(fn.model, fn.model_kwargs), fn.c_concat()   # None for a DiT that is to receive labels / cond=
+    bundle = fn.bundle(unet, x_T.device)
+    if bundle is not None:
+        cc = [concat_of(bundle, x_T)]
     if guidance is None and fn.unconditional_condition is not None:
-        u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device).detach().float()
-        guidance = Guidance(u, fn.guidance_scale, steps)
+        u = cat_unconditional(fn.condition, fn.unconditional_condition, x_T.device, wrapper_key(fn.model) if bundle is not None else None)
+        guidance = Guidance(u if isinstance(u, Conditioning) else u.detach().float(), fn.guidance_scale, steps)
     if guidance is not None:
         if cc is None:
             raise ValueError("classifier-free guidance needs the 'concat' condition the unconditional one replaces")
-        guidance.check(torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), steps)
+        guidance.check(bundle if bundle is not None else torch.cat([c.to(x_T.device) for c in cc], 1).detach().float(), steps)
         if unet is None:
             raise NotImplementedError("classifier-free guidance runs in the device loop only: it needs a native DSUnetModel / "
                                       "UNetModel / DiT behind the model")
-    return unet, cc, guidance
+    return unet, cc, guidance, bundle
 
 
 @torch.no_grad()
@@ -543,7 +560,7 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
     """The multistep loop on the device.  ``guidance`` (default: what ``fn`` carries from model_wrapper): classifier-free
     guidance, dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided; its unconditional conditioning must have the shape, dtype
     and device of the concatenated condition."""
-    unet, cc, guidance = _loop_denoiser_and_guidance(fn, sched.steps, x_T, guidance)
+    unet, cc, guidance, bundle = _loop_denoiser_and_guidance(fn, sched.steps, x_T, guidance)
     guided = guidance is not None
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
@@ -557,13 +574,14 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
         # latent state [B,Cz,h,w] under the plain UNetModel or the DiT: dsd_sample_dpm_latent
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
-        check_latent_io(unet, x, cond)
-        if guided:
-            check(lib().dsd_sample_dpm_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cx,
-                                                     B, H, W, stream_ptr()))
-            return x
-        check(lib().dsd_sample_dpm_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
-                                          stream_ptr()))
+        check_latent_io(unet, x, bundle if bundle is not None else cond)
+        with conditioning_set(unet, bundle, guidance.uncond if guided else None):
+            if guided:
+                check(lib().dsd_sample_dpm_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x),
+                                                         Cx, B, H, W, stream_ptr()))
+            else:
+                check(lib().dsd_sample_dpm_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
+                                                  stream_ptr()))
         return x
     assert Cx == 1, "the denoised image has one channel"
     if unet is not None and cc is not None:
@@ -592,7 +610,7 @@ def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance:
     """A DpmProgram on the device: dsd_sample_dpm_program(_latent) for the native denoisers, guided or not, and for any other
     callable the python loop over the network with dsd_op_dpm_eval per evaluation.  Returns (sample, kept states
     [n_kept,B,C,H,W])."""
-    unet, cc, guidance = _loop_denoiser_and_guidance(fn, prog.steps, x_T, guidance)
+    unet, cc, guidance, bundle = _loop_denoiser_and_guidance(fn, prog.steps, x_T, guidance)
     guided = guidance is not None
     if not x_T.is_cuda:
         raise NotImplementedError("the singlestep, third-order and intermediate-keeping solvers run on the MI355X only (there is "
@@ -607,9 +625,10 @@ def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance:
         unet.sync_params()
         cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
         if is_latent_denoiser(unet):
-            check_latent_io(unet, x, cond)
-            check(lib().dsd_sample_dpm_program_latent(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
-                                                      dptr(kept), stream_ptr()))
+            check_latent_io(unet, x, bundle if bundle is not None else cond)
+            with conditioning_set(unet, bundle, guidance.uncond if guided else None):
+                check(lib().dsd_sample_dpm_program_latent(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H,
+                                                          W, dptr(kept), stream_ptr()))
             return x, kept
         assert Cx == 1, "the denoised image has one channel"
         assert cond.shape[0] == B and cond.shape[2:] == x.shape[2:]

@@ -38,6 +38,7 @@ EXPORTS = [
     "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
     "dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step",
     "dsd_sample_dpm_program", "dsd_sample_dpm_program_latent", "dsd_op_dpm_eval",
+    "dsd_set_conditioning",
     "dsd_calc_bpd", "dsd_calc_bpd_latent", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
 ]
 
@@ -80,6 +81,11 @@ class DsdDpmProgram(C.Structure):
 
 class DsdGuidance(C.Structure):
     _fields_ = [("uncond", C.c_void_p), ("scale", C.POINTER(C.c_float)), ("n_scale", C.c_int32)]
+
+
+class DsdConditioning(C.Structure):
+    _fields_ = [("context", C.c_void_p), ("context_uncond", C.c_void_p), ("tokens", C.c_int32), ("y", C.c_void_p),
+                ("y_uncond", C.c_void_p), ("y_width", C.c_int32), ("B", C.c_int32)]
 
 
 class DsdInpaint(C.Structure):
@@ -247,6 +253,8 @@ def lib() -> C.CDLL:
                                    f32p, i32, i32, i32, i32, vp]
     L.dsd_op_prior_bpd.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_ddim_reverse_step.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, i32, i32, i32, i32, vp]
+    if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
+        L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     _lib = L
     return L
 

@@ -1,13 +1,14 @@
 """Host side of dsd_sample: packs per-iteration fp32 coefficient rows and drives the device loop."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from ._lib import DSD_NCOEF, DsdBpd, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
+from ._lib import DSD_NCOEF, DsdBpd, DsdConditioning, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
 
 
 class Schedule:
@@ -54,10 +55,23 @@ class Guidance:
                              "(ucg_schedule needs one scale per step)")
         self.uncond = uncond
 
-    def check(self, cond: torch.Tensor, steps: int) -> None:
+    def check(self, cond, steps: int) -> None:
         u = self.uncond
         if self.scale.shape[0] != int(steps):
             raise ValueError(f"guidance carries {self.scale.shape[0]} scales but the schedule executes {int(steps)} steps")
+        if isinstance(cond, Conditioning) or isinstance(u, Conditioning):
+            # part by part, as p_sample_ddim pairs the two dicts key by key (ddim.py:199-217)
+            if not (isinstance(cond, Conditioning) and isinstance(u, Conditioning)):
+                raise ValueError("the unconditional conditioning must come in the form of the conditioning (a dict with its keys)")
+            for name, key in (("concat", "c_concat"), ("context", "c_crossattn"), ("y", "c_adm")):
+                a, b = getattr(cond, name), getattr(u, name)
+                if (a is None) != (b is None):
+                    raise ValueError(f"unconditional_conditioning and conditioning differ in {key!r}: guidance needs the "
+                                     f"unconditional twin of every part ({name})")
+                if a is not None and (tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype or a.device != b.device):
+                    raise ValueError(f"the unconditional {key!r} must have the shape, dtype and device of the conditional one: "
+                                     f"{tuple(b.shape)} {b.dtype} {b.device} against {tuple(a.shape)} {a.dtype} {a.device}")
+            return
         if not torch.is_tensor(u) or tuple(u.shape) != tuple(cond.shape) or u.dtype != cond.dtype or u.device != cond.device:
             raise ValueError("the unconditional conditioning must have the shape, dtype and device of the conditioning: "
                              f"{tuple(getattr(u, 'shape', ()))} {getattr(u, 'dtype', None)} {getattr(u, 'device', None)} against "
@@ -65,9 +79,10 @@ class Guidance:
 
     def bind(self) -> DsdGuidance:
         """The C struct (the arrays it points to stay alive on self)."""
-        self._u = self.uncond.detach().float().contiguous()
+        u = self.uncond.concat if isinstance(self.uncond, Conditioning) else self.uncond
+        self._u = u.detach().float().contiguous() if u is not None and u.shape[1] else None
         g = DsdGuidance()
-        g.uncond = self._u.data_ptr()
+        g.uncond = self._u.data_ptr() if self._u is not None else None
         g.scale = self.scale.ctypes.data_as(C.POINTER(C.c_float))
         g.n_scale = int(self.scale.shape[0])
         return g
@@ -116,16 +131,90 @@ def guidance_active(scale, uncond, ucg_schedule=None) -> bool:
     return ucg_schedule is not None or scale != 1.
 
 
-def cat_conditioning(c, device):
-    """The 'concat' conditioning in the three forms the reference takes (dict with c_concat lists, list, tensor) -> one
-    [B,Cc,H,W] tensor on ``device``."""
-    if isinstance(c, dict):
-        c = c["c_concat"]
-    parts = list(c) if isinstance(c, (list, tuple)) else [c]
-    return torch.cat([t.to(device) for t in parts], 1)
+CONCAT_KEYS = ("concat", "hybrid", "hybrid-adm")
+CONTEXT_KEYS = ("crossattn", "hybrid", "hybrid-adm", "crossattn-adm")
+ADM_KEYS = ("hybrid-adm", "crossattn-adm")
 
 
-def cat_unconditional(c, u, device):
+class Conditioning:
+    """The conditioning bundle of a latent device loop beside plain 'concat': ``concat`` [B,Cc,H,W] (appended to the state),
+    ``context`` [B,tokens,context_dim] (cross-attention) and ``y`` (the label_emb input: int labels [B] or vectors [B,width]),
+    each a tensor or None — what DiffusionWrapper.forward (ddpm.py:1328-1365) makes of the reference's conditioning dict."""
+
+    def __init__(self, concat=None, context=None, y=None):
+        self.concat, self.context, self.y = concat, context, y
+
+    def __eq__(self, other):
+        if not isinstance(other, Conditioning):
+            return NotImplemented
+        same = lambda a, b: (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and torch.equal(a, b))
+        return same(self.concat, other.concat) and same(self.context, other.context) and same(self.y, other.y)
+
+    __hash__ = None
+
+    def __repr__(self):
+        d = lambda t: None if t is None else tuple(t.shape)
+        return f"Conditioning(concat={d(self.concat)}, context={d(self.context)}, y={d(self.y)})"
+
+
+def conditioning_key_of(c) -> Optional[str]:
+    """The conditioning key a dict spells out by the entries it carries (None where it cannot: 'adm' reads its vector from
+    ``c_crossattn[0]`` and is told apart by the wrapper's key only)."""
+    if not isinstance(c, dict):
+        return "concat"
+    has = tuple(k in c and c[k] is not None for k in ("c_concat", "c_crossattn", "c_adm"))
+    return {(True, False, False): "concat", (False, True, False): "crossattn", (True, True, False): "hybrid",
+            (True, True, True): "hybrid-adm", (False, True, True): "crossattn-adm"}.get(has)
+
+
+def _parts(c, name, key, device):
+    if not isinstance(c, dict) or name not in c or c[name] is None:
+        raise ValueError(f"the conditioning lacks {name!r}, which conditioning_key={key!r} reads")
+    v = c[name]
+    parts = list(v) if isinstance(v, (list, tuple)) else [v]
+    if not parts or not all(torch.is_tensor(t) for t in parts):
+        raise ValueError(f"conditioning[{name!r}] must be a tensor or a non-empty list of tensors")
+    return [t.to(device) for t in parts]
+
+
+def cat_conditioning(c, device, key: Optional[str] = None):
+    """What the denoiser receives of a conditioning in the forms the reference takes, on ``device``.  ``key``: the wrapper's
+    conditioning_key (default: read off the dict's entries).  Under 'concat' — a dict with c_concat lists, a list, a tensor — one
+    [B,Cc,H,W] tensor; under every other key a Conditioning: c_concat joined along the channels where the key has it,
+    c_crossattn along the tokens, ``y`` = c_adm, or c_crossattn[0] under 'adm' (ddpm.py:1328-1365).  A list or tensor under a
+    key other than 'concat' is c_crossattn, as apply_model files it (:862-866)."""
+    if key is None:
+        key = conditioning_key_of(c)
+        if key is None:
+            raise ValueError(f"cannot tell the conditioning key from the entries {sorted(c)}: c_concat, c_crossattn (+ c_adm) "
+                             "combine to 'concat', 'crossattn', 'hybrid', 'hybrid-adm', 'crossattn-adm'")
+    if key == "concat":
+        if isinstance(c, dict):
+            c = c["c_concat"]
+        parts = list(c) if isinstance(c, (list, tuple)) else [c]
+        return torch.cat([t.to(device) for t in parts], 1)
+    if not isinstance(c, dict):
+        c = {"c_crossattn": list(c) if isinstance(c, (list, tuple)) else [c]}
+    out = Conditioning()
+    if key in CONCAT_KEYS:
+        out.concat = torch.cat(_parts(c, "c_concat", key, device), 1)
+    if key in CONTEXT_KEYS:
+        out.context = torch.cat(_parts(c, "c_crossattn", key, device), 1)
+        if out.context.dim() != 3:
+            raise ValueError(f"conditioning['c_crossattn'] must hold [B, tokens, context_dim] tensors, got {tuple(out.context.shape)}")
+    if key in ADM_KEYS:
+        adm = _parts(c, "c_adm", key, device)
+        if len(adm) != 1:
+            raise ValueError("conditioning['c_adm'] must be one tensor")
+        out.y = adm[0]
+    elif key == "adm":
+        out.y = _parts(c, "c_crossattn", key, device)[0]
+    elif key not in CONTEXT_KEYS:
+        raise ValueError(f"conditioning_key={key!r} is not one the reference's DiffusionWrapper dispatches")
+    return out
+
+
+def cat_unconditional(c, u, device, key: Optional[str] = None):
     """The unconditional conditioning must come in the form of the conditioning, as p_sample_ddim asserts (ddim.py:199-217)."""
     if isinstance(c, dict):
         assert isinstance(u, dict), "unconditional_conditioning must be a dict like the conditioning"
@@ -138,7 +227,87 @@ def cat_unconditional(c, u, device):
         assert isinstance(u, list) and len(u) == len(c), "unconditional_conditioning must be a list like the conditioning"
     else:
         assert torch.is_tensor(u), "unconditional_conditioning must be a tensor like the conditioning"
-    return cat_conditioning(u, device)
+    if key is None and isinstance(c, dict):
+        key = conditioning_key_of(c)
+    return cat_conditioning(u, device, key)
+
+
+def wrapper_key(model) -> Optional[str]:
+    """The conditioning_key of the DiffusionWrapper behind what a sampler was handed (None: no wrapper, or an unconditional
+    one — the conditioning's own entries then say what it is)."""
+    for m in (model, getattr(model, "model", None)):
+        k = getattr(m, "conditioning_key", None)
+        if isinstance(k, str):
+            return k
+    return None
+
+
+def kwargs_conditioning(unet, model, model_kwargs, device):
+    """The Conditioning a ``model_kwargs`` dict spells for a UNetModel denoiser, or None where it holds at most ``c_concat`` (the
+    callers' own path).  Two spellings: UNetModel.forward's keywords ``context=`` / ``y=`` (beside ``c_concat``), for the bare
+    network, and the wrapper's ``c_crossattn`` / ``c_adm`` under its conditioning_key."""
+    kw = dict(model_kwargs or {})
+    if "context" in kw or "y" in kw:
+        extra = set(kw) - {"c_concat", "context", "y"}
+        if extra:
+            raise ValueError(f"model_kwargs {sorted(extra)} beside context= / y= cannot reach the UNetModel")
+        cc = kw.get("c_concat")
+        cc = [cc] if torch.is_tensor(cc) else cc
+        mv = lambda t: None if t is None else t.to(device)
+        return Conditioning(torch.cat([t.to(device) for t in cc], 1) if cc else None, mv(kw.get("context")), mv(kw.get("y")))
+    if "c_crossattn" in kw or "c_adm" in kw:
+        return cat_conditioning(kw, device, wrapper_key(model))
+    return None
+
+
+def concat_of(cond, x: torch.Tensor) -> torch.Tensor:
+    """The 'concat' tensor of a loop's conditioning (a tensor, or a Conditioning whose concat part may be absent: [B,0,H,W])."""
+    if isinstance(cond, Conditioning):
+        return cond.concat if cond.concat is not None else x.new_zeros((x.shape[0], 0) + tuple(x.shape[2:]))
+    return cond
+
+
+@contextlib.contextmanager
+def conditioning_set(unet, cond, uncond=None):
+    """dsd_set_conditioning around a latent device loop: installs the context / y of ``cond`` (and their unconditional twins of
+    ``uncond``) on the denoiser's handle and clears them afterwards, whatever the loop did.  A tensor ``cond`` installs nothing."""
+    if not isinstance(cond, Conditioning) or (cond.context is None and cond.y is None):
+        yield
+        return
+    from .ldm.modules.diffusionmodules.openaimodel import UNetModel
+    if not isinstance(unet, UNetModel):
+        raise ValueError("'c_crossattn' / 'c_adm' conditioning needs a UNetModel denoiser: the DiT and the four-stream model take "
+                         "'concat' conditioning only")
+    u = uncond if isinstance(uncond, Conditioning) else Conditioning()
+    keep = []
+
+    def ctx(t):
+        if t is None:
+            return None
+        t = t.detach().float().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    def lab(t):
+        if t is None:
+            return None
+        t = unet.label_input(t.detach(), cond.y.device)
+        keep.append(t)
+        return t.data_ptr()
+
+    c = DsdConditioning()
+    if cond.context is not None:
+        c.context, c.context_uncond, c.tokens = ctx(cond.context), ctx(u.context), int(cond.context.shape[1])
+        c.B = int(cond.context.shape[0])
+    if cond.y is not None:
+        c.y, c.y_uncond = lab(cond.y), lab(u.y)
+        c.y_width = 0 if unet.label_kind == 1 else int(unet.label_width)
+        c.B = int(cond.y.shape[0])
+    check(lib().dsd_set_conditioning(unet._h, C.byref(c)))
+    try:
+        yield
+    finally:
+        check(lib().dsd_set_conditioning(unet._h, None))
 
 
 def find_unet(model):
@@ -201,9 +370,14 @@ def dit_state_channels(in_channels: int, learn_sigma: bool, cond_channels: int):
     return cz, out_ch
 
 
-def check_latent_io(unet, x: torch.Tensor, cond: torch.Tensor) -> None:
-    """Shape checks of the latent loops that the C entry points cannot see (they take one H, W)."""
+def check_latent_io(unet, x: torch.Tensor, cond) -> None:
+    """Shape checks of the latent loops that the C entry points cannot see (they take one H, W), and the parts of a Conditioning
+    against what the network can take, each named by its key, before any device work."""
+    bundle = cond if isinstance(cond, Conditioning) else Conditioning()
+    cond = concat_of(cond, x)
     if is_dit(unet):
+        if bundle.context is not None or bundle.y is not None:
+            raise ValueError("the DiT takes 'concat' conditioning only in the device loops: 'c_crossattn' / 'c_adm' cannot reach it")
         if cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:]):
             raise ValueError(f"conditioning {tuple(cond.shape)} does not match the state {tuple(x.shape)} "
                              "(same batch and spatial size needed for the 'concat' conditioning)")
@@ -215,8 +389,24 @@ def check_latent_io(unet, x: torch.Tensor, cond: torch.Tensor) -> None:
             raise ValueError(f"the DiT takes {unet.in_channels} input channels but state + conditioning have {x.shape[1]} + "
                              f"{cond.shape[1]}")
         return
+    B = x.shape[0]
     if unet.use_spatial_transformer:
-        raise ValueError("the latent loops take 'concat' conditioning only; this UNetModel has a spatial transformer")
+        ctx = bundle.context
+        if ctx is None:
+            raise ValueError("this UNetModel has a spatial transformer: the conditioning needs 'c_crossattn' (a context)")
+        if ctx.dim() != 3 or ctx.shape[0] != B or ctx.shape[2] != unet.context_dim:
+            raise ValueError(f"'c_crossattn' must be [B, tokens, context_dim] = [{B}, tokens, {unet.context_dim}], got {tuple(ctx.shape)}")
+    elif bundle.context is not None:
+        raise ValueError("'c_crossattn' given but this UNetModel has no spatial transformer (use_spatial_transformer=False)")
+    if unet.num_classes is not None:
+        if bundle.y is None:
+            raise ValueError(f"this UNetModel has a label_emb (num_classes={unet.num_classes!r}): the conditioning needs 'c_adm' "
+                             "('c_crossattn' under the key 'adm')")
+        if bundle.y.shape[0] != B:
+            raise ValueError(f"'c_adm' has {bundle.y.shape[0]} rows but the state has {B}")
+        unet.label_input(bundle.y, bundle.y.device)
+    elif bundle.y is not None:
+        raise ValueError("'c_adm' given but this UNetModel has no label_emb (num_classes is None)")
     if cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:]):
         raise ValueError(f"conditioning {tuple(cond.shape)} does not match the latent state {tuple(x.shape)} "
                          "(same batch and spatial size needed for the 'concat' conditioning)")
@@ -235,7 +425,8 @@ def philox_seed(seed: Optional[int] = None) -> int:
 def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidance: Optional[Guidance],
                  inpaint: Optional[Inpaint], cpu_message: str):
     """The prologue every device loop shares: the guidance / inpaint checks, the denoiser and device tests, parameters synced,
-    the state cloned.  Returns (x, cond, bound guidance or None, bound inpaint or None)."""
+    the state cloned.  ``cond``: the 'concat' tensor or a Conditioning.  Returns (x, the 'concat' tensor, bound guidance or None,
+    bound inpaint or None, the context manager that holds the rest of the conditioning on the handle)."""
     if guidance is not None:
         guidance.check(cond, steps)
     if inpaint is not None:
@@ -246,10 +437,15 @@ def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidan
         raise RuntimeError(cpu_message)
     unet.sync_params()
     x = x_T.detach().float().contiguous().clone()
-    cond = cond.detach().float().contiguous()
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, x, cond)
+    elif isinstance(cond, Conditioning):
+        raise ValueError("the four-stream model takes 'concat' conditioning only: 'c_crossattn' / 'c_adm' cannot reach it")
+    held = conditioning_set(unet, cond, guidance.uncond if guidance is not None else None)
+    cond = concat_of(cond, x).detach().float().contiguous()
     g = guidance.bind() if guidance is not None else None
     inp = inpaint.bind() if inpaint is not None else None
-    return x, cond, g, inp
+    return x, cond, g, inp, held
 
 
 @torch.no_grad()
@@ -262,10 +458,9 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
     ``guidance``: classifier-free guidance (dsd_sample_guided / dsd_sample_latent_guided, mode B_DDIM); its unconditional
     conditioning must have the shape, dtype and device of ``cond``.
     ``inpaint``: masked sampling (dsd_sample_masked / dsd_sample_latent_masked, modes B_DDIM and B_DDPM), guided or not."""
-    x, cond, g, inp = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
-                                   "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
+    x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
+                                         "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     if is_latent_denoiser(unet):
-        check_latent_io(unet, x, cond)
         B, Cz, H, W = x.shape
         if step_noise is not None:
             step_noise = step_noise.detach().float().contiguous()
@@ -273,17 +468,17 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
                 raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
         if seed is None:
             seed = _seed_from_torch()
-        if inp is not None:
-            check(lib().dsd_sample_latent_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp),
-                                                 dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise), C.c_uint64(seed), B, H,
-                                                 W, first_step, n_steps, stream_ptr()))
-            return x
-        if g is not None:
-            check(lib().dsd_sample_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cz,
-                                                 dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
-            return x
-        check(lib().dsd_sample_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise),
-                                      C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+        with held:
+            if inp is not None:
+                check(lib().dsd_sample_latent_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp),
+                                                     dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise), C.c_uint64(seed), B,
+                                                     H, W, first_step, n_steps, stream_ptr()))
+            elif g is not None:
+                check(lib().dsd_sample_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cz,
+                                                     dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+            else:
+                check(lib().dsd_sample_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise),
+                                              C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
         return x
     B, Cx, H, W = x.shape
     assert Cx == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
@@ -315,16 +510,16 @@ def run_plms_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor, 
     off).  The history of noise predictions stays on the denoiser's handle: ``first_step`` = k > 0 continues the run whose
     iterations 0 .. k-1 ran last on it (x_T = the state they returned) and fails otherwise.  ``seed`` keys the blend noise of
     ``inpaint`` when it carries none; PLMS itself draws no noise."""
-    x, cond, g, inp = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
-                                   "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
+    x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
+                                         "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     gp, ip = C.byref(g) if g is not None else None, C.byref(inp) if inp is not None else None
     thr = C.c_float(float(threshold) if threshold is not None else 0.0)
     seed = C.c_uint64(philox_seed(seed) if inp is not None and inp.noise is None else 0)
     B, Cz, H, W = x.shape
     if is_latent_denoiser(unet):
-        check_latent_io(unet, x, cond)
-        check(lib().dsd_sample_plms_latent(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed, B, H,
-                                           W, first_step, n_steps, stream_ptr()))
+        with held:
+            check(lib().dsd_sample_plms_latent(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed, B,
+                                               H, W, first_step, n_steps, stream_ptr()))
         return x
     assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
     check(lib().dsd_sample_plms(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), seed, B, H, W,
@@ -413,8 +608,8 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     coef = np.ascontiguousarray(coef, dtype=np.float32)
     steps = int(coef.shape[0])
     assert coef.shape == (steps, 2)
-    x, cond, g, _ = _loop_inputs(unet, x0, cond, steps, guidance, None,
-                                 "DDIM inversion runs on the MI355X only (no CPU fallback): x0 is on the CPU")
+    x, cond, g, _, held = _loop_inputs(unet, x0, cond, steps, guidance, None,
+                                       "DDIM inversion runs on the MI355X only (no CPU fallback): x0 is on the CPU")
     t_model = np.arange(steps, dtype=np.float32)
     sc = DsdInvertSchedule()
     sc.steps = steps
@@ -423,9 +618,9 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     gp = C.byref(g) if g is not None else None
     B, Cz, H, W = x.shape
     if is_latent_denoiser(unet):
-        check_latent_io(unet, x, cond)
-        check(lib().dsd_invert_latent(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), Cz, B, H, W, first_step,
-                                      n_steps, stream_ptr()))
+        with held:
+            check(lib().dsd_invert_latent(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), Cz, B, H, W, first_step,
+                                          n_steps, stream_ptr()))
         return x
     assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
     check(lib().dsd_invert(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), B, H, W, first_step, n_steps,
@@ -449,7 +644,12 @@ def run_bpd_loop(unet, sched: Schedule, post_log_var: np.ndarray, prior_log_var:
         raise RuntimeError("the variational bound runs on the MI355X only (no CPU fallback): x_start is on the CPU")
     unet.sync_params()
     xs = x_start.detach().float().contiguous()
-    cond = cond.detach().float().contiguous()
+    bundle = cond
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, xs, bundle)
+    elif isinstance(bundle, Conditioning):
+        raise ValueError("the four-stream model takes 'concat' conditioning only: 'c_crossattn' / 'c_adm' cannot reach it")
+    cond = concat_of(bundle, xs).detach().float().contiguous()
     post_log_var = np.ascontiguousarray(post_log_var, dtype=np.float32)
     assert post_log_var.shape == (sched.steps,)
     B, Cz, H, W = xs.shape
@@ -466,9 +666,9 @@ def run_bpd_loop(unet, sched: Schedule, post_log_var: np.ndarray, prior_log_var:
     bpd.vb, bpd.xstart_mse, bpd.mse = out["vb"].data_ptr(), out["xstart_mse"].data_ptr(), out["mse"].data_ptr()
     bpd.prior, bpd.prior_log_var = out["prior_bpd"].data_ptr(), float(prior_log_var)
     if is_latent_denoiser(unet):
-        check_latent_io(unet, xs, cond)
-        check(lib().dsd_calc_bpd_latent(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), Cz,
-                                        dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+        with conditioning_set(unet, bundle):
+            check(lib().dsd_calc_bpd_latent(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), Cz,
+                                            dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
         return out
     assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == xs.shape[2:]
     check(lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), dptr(step_noise),

@@ -53,6 +53,24 @@ void set_device(int device) {
     if (device >= 0) DSD_HIP(hipSetDevice(device));
 }
 
+// y of a dsd_conditioning against the handle's label_emb (kind lk, width lw) and the call's batch; int labels are read back
+// and checked against the table, whose rows the lookup kernel indexes unchecked
+void check_y(dsd_handle* h, const dsd_conditioning& c, int lk, int lw, int B) {
+    const int want = lk == 1 ? 0 : lw;
+    DSD_CHECK(c.y_width == want, "y_width %d does not match the handle's label_emb (kind %d wants %d: 0 = int64 labels)", c.y_width, lk, want);
+    DSD_CHECK(c.B == B, "the conditioning was set for a batch of %d but the call has %d", c.B, B);
+    if (lk == 1) {
+        std::vector<long long> lab((size_t)B);
+        for (const void* p : {c.y, c.y_uncond}) {
+            if (!p) continue;
+            DSD_HIP(hipDeviceSynchronize());
+            DSD_HIP(hipMemcpy(lab.data(), p, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost));
+            for (int i = 0; i < B; ++i)
+                DSD_CHECK(lab[i] >= 0 && lab[i] < lw, "label %d is %lld but the model has %d classes", i, lab[i], lw);
+        }
+    }
+}
+
 void bind_planes(dsd_handle* h, const float* x, int C, int H, int W, hipStream_t s) {
     const int64_t hw = (int64_t)H * W;
     DSD_CHECK(C == 2 || C == 4, "x must have 2 or 4 channels (noise + 1 or 3 conditions), got %d", C);
@@ -225,7 +243,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->bpd_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->ctx_cap + h->y_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->bpd_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -376,15 +394,49 @@ int dsd_profile_op_name(dsd_handle* h, int idx, const char** name) {
     DSD_CATCH
 }
 
+int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c) {
+    DSD_TRY
+    DSD_CHECK(h, "null handle");
+    if (!c) {
+        h->cond = dsd_conditioning{};
+        h->has_cond = false;
+    } else {
+        DSD_CHECK(h->is_block, "the four-stream model takes 'concat' conditioning only: no context or y reaches DSUnetModel.forward");
+        DSD_CHECK(h->block_kind != DSD_BLOCK_DIT,
+                  "the DiT takes 'concat' conditioning only in the device loops: no context or y reaches it through DiffusionWrapper");
+        DSD_CHECK(h->block_kind == DSD_BLOCK_UNET, "dsd_set_conditioning takes a DSD_BLOCK_UNET handle, got block kind %d", h->block_kind);
+        DSD_CHECK(c->B >= 1 && c->tokens >= 0 && c->y_width >= 0, "bad conditioning: B %d tokens %d y_width %d", c->B, c->tokens, c->y_width);
+        DSD_CHECK(!c->context || c->tokens >= 1, "a context needs tokens >= 1, got %d", c->tokens);
+        DSD_CHECK(c->context || !c->context_uncond, "context_uncond without a context");
+        DSD_CHECK(c->y || !c->y_uncond, "y_uncond without y");
+        h->cond = *c;
+        h->has_cond = true;
+    }
+    DSD_CATCH
+}
+
 int dsd_block_forward(dsd_handle* h, const float* x, int B, int C, int H, int W, const float* aux, int aux_len,
                       const float* aux2, int aux_len2, float* out, void* stream) {
     DSD_TRY
     DSD_CHECK(h && h->is_block && x && out, "null argument / not a block handle");
     set_device(h->device);
+    const void* y = nullptr;
+    if (h->block_kind == DSD_BLOCK_UNET) {   // label_emb: y comes through dsd_set_conditioning
+        int lk = 0, lw = 0;
+        net_unet_label_emb(h, &lk, &lw);
+        const bool has_y = h->has_cond && h->cond.y;
+        DSD_CHECK(has_y == (lk != 0), lk ? "UNetModel with label_emb: y is missing (dsd_set_conditioning)"
+                                         : "UNetModel without label_emb takes no y");
+        if (lk) {
+            check_y(h, h->cond, lk, lw, B);
+            y = h->cond.y;
+        }
+    }
     net_plan(h, B, C, H, W, 0, 0, aux ? aux_len : 0, aux2 ? aux_len2 : 0, 0, (hipStream_t)stream);
     h->io.x_nchw = x;
     h->io.aux = aux;
     h->io.aux2 = aux2;
+    h->io.aux3 = y;
     h->io.out = out;
     net_run(h, (hipStream_t)stream);
     net_check_overflow(h, (hipStream_t)stream);
@@ -455,12 +507,31 @@ int check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc
         check_slice_ids(h, B);
         return out_ch;
     }
-    DSD_CHECK(h && cond && x, "null argument");
+    DSD_CHECK(h && x, "null argument");
     DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
-    DSD_CHECK(!net_unet_has_spatial_transformer(h), "the latent loops take a UNetModel without spatial transformer ('concat' conditioning only)");
     const std::vector<int32_t>& a = h->iargs;
     DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
-    DSD_CHECK(!g || Cc >= 1, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+    // the bundle of dsd_set_conditioning against the handle (context <-> spatial transformer, y <-> label_emb)
+    const dsd_conditioning none{};
+    const dsd_conditioning& c = h->has_cond ? h->cond : none;
+    const int ctx_dim = net_unet_context_dim(h);
+    int lk = 0, lw = 0;
+    net_unet_label_emb(h, &lk, &lw);
+    DSD_CHECK(!ctx_dim || c.context, "the UNetModel has a spatial transformer (context_dim %d) but no context is set (dsd_set_conditioning)",
+              ctx_dim);
+    DSD_CHECK(ctx_dim || !c.context, "a context of %d tokens is set but the UNetModel has no spatial transformer", c.tokens);
+    DSD_CHECK(!lk || c.y, "the UNetModel has a label_emb (kind %d, width %d) but no y is set (dsd_set_conditioning)", lk, lw);
+    DSD_CHECK(lk || !c.y, "a y of width %d is set but the UNetModel has no label_emb", c.y_width);
+    DSD_CHECK(!h->has_cond || c.B == B, "the conditioning was set for a batch of %d but the call has %d", c.B, B);
+    if (lk) check_y(h, c, lk, lw, B);
+    DSD_CHECK(cond || Cc == 0, "null argument: cond with Cc = %d", Cc);
+    if (g) {
+        DSD_CHECK(Cc >= 1 || c.context || c.y, "guidance needs a 'concat' conditioning to replace (Cc = %d)", Cc);
+        DSD_CHECK(Cc == 0 || g->uncond, "guidance needs the unconditional conditioning (uncond is null)");
+        DSD_CHECK(!c.context || c.context_uncond, "guidance needs the unconditional twin of the context (context_uncond is null, %d tokens)",
+                  c.tokens);
+        DSD_CHECK(!c.y || c.y_uncond, "guidance needs the unconditional twin of y (y_uncond is null, y_width %d)", c.y_width);
+    }
     DSD_CHECK(a[0] == Cz + Cc, "the UNetModel takes %d input channels but state + conditioning have %d + %d", a[0], Cz, Cc);
     DSD_CHECK(a[2] == want_ch, "the UNetModel has %d output channels but the sampler expects %d", a[2], want_ch);
     check_slice_ids(h, B);
@@ -528,7 +599,10 @@ LoopBinding bind_latent(dsd_handle* h, const dsd_guidance* g, const float* cond,
                         int out_ch, hipStream_t s) {
     const int64_t hw = (int64_t)H * W, Cin = Cz + Cc;
     const int rows = g ? 2 * B : B;
-    net_plan(h, rows, (int)Cin, H, W, 0, 0, 1, 0, 0, s);
+    const dsd_conditioning none{};
+    const dsd_conditioning& c = h->has_cond ? h->cond : none;
+    const int tokens = c.context ? c.tokens : 0;
+    net_plan(h, rows, (int)Cin, H, W, 0, 0, 1, tokens, 0, s);
     ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
     ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
     ensure_buf(&h->lat_in, &h->lat_in_cap, (size_t)rows * Cin * hw * sizeof(float));
@@ -545,6 +619,23 @@ LoopBinding bind_latent(dsd_handle* h, const dsd_guidance* g, const float* cond,
     h->io.x_nchw = h->lat_in;
     h->io.aux = h->tbuf;
     h->io.out = h->mout;
+    // context and y: copied once into `rows` rows of the handle's own (c_in = cat([uncond, cond]) part by part, ddim.py:199-217)
+    if (c.context) {
+        const size_t half_bytes = (size_t)B * tokens * net_unet_context_dim(h) * sizeof(float);
+        ensure_buf(&h->ctx_buf, &h->ctx_cap, rows / B * half_bytes);
+        for (int half = 0; half * B < rows; ++half)
+            DSD_HIP(hipMemcpyAsync(reinterpret_cast<char*>(h->ctx_buf) + half * half_bytes, (g && half == 0) ? c.context_uncond : c.context,
+                                   half_bytes, hipMemcpyDeviceToDevice, s));
+        h->io.aux2 = h->ctx_buf;
+    }
+    if (c.y) {
+        const size_t half_bytes = (size_t)B * (c.y_width ? c.y_width * sizeof(float) : sizeof(long long));
+        ensure_buf(&h->y_buf, &h->y_cap, rows / B * half_bytes);
+        for (int half = 0; half * B < rows; ++half)
+            DSD_HIP(hipMemcpyAsync(reinterpret_cast<char*>(h->y_buf) + half * half_bytes, (g && half == 0) ? c.y_uncond : c.y, half_bytes,
+                                   hipMemcpyDeviceToDevice, s));
+        h->io.aux3 = h->y_buf;
+    }
     LoopBinding b = make_binding(h, g, h->lat_in, Cin * hw, x, Cz, B, hw, out_ch);
     b.latent = true;
     return b;
@@ -606,8 +697,9 @@ void check_schedule(const dsd_schedule* sc) {
 // Classifier-free guidance (ddim.py:194-219 / dpm_solver_pytorch.py:324-332): both halves in ONE network pass over 2B rows (uncond
 // half first), combined by the update kernels (sampler.hip), which write x_{t-1} to both state rows.  Noise and slice ids stay per
 // logical sample.
-void check_guidance(const dsd_guidance* g, int steps) {
-    DSD_CHECK(g->uncond, "guidance needs the unconditional conditioning (uncond is null)");
+// need_uncond: false where a latent call has no 'concat' part (Cc = 0) and a dsd_set_conditioning bundle carries what is replaced
+void check_guidance(const dsd_guidance* g, int steps, bool need_uncond = true) {
+    DSD_CHECK(g->uncond || !need_uncond, "guidance needs the unconditional conditioning (uncond is null)");
     DSD_CHECK(g->scale && g->n_scale == steps, "guidance carries %d scales but the schedule executes %d steps (one scale per step)",
               g->scale ? g->n_scale : 0, steps);
 }
@@ -652,7 +744,7 @@ static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd
     }
     if (g) {
         check_guided_schedule(sc);
-        check_guidance(g, sc->steps);
+        check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
     }
     DSD_CHECK(!(sc->learned_range && Cz > 1) || is_dit(h),
               "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
@@ -783,7 +875,7 @@ static DpmCoef dpm_coef(const dsd_dpm_schedule* sc, int k) {
 static void sample_dpm(bool latent, dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
                        float* x, int Cz, int B, int H, int W, void* stream) {
     check_dpm_schedule(sc);
-    if (g) check_guidance(g, sc->steps);
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
     const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
     const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;   // an output row is Cm samples long; the solver reads the first
     DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
@@ -932,7 +1024,7 @@ static void dpm_program_eval(const dsd_dpm_program* p, int k, const float* out_u
 static void sample_dpm_program(bool latent, dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc,
                                float* x, int Cz, int B, int H, int W, float* inter, void* stream) {
     check_dpm_program(p);
-    if (g) check_guidance(g, p->n_eval);                          // one scale per evaluation
+    if (g) check_guidance(g, p->n_eval, !(latent && Cc == 0 && h && h->has_cond));                          // one scale per evaluation
     const int kept = dpm_program_kept(p);
     DSD_CHECK(kept == 0 || inter, "the program keeps %d intermediate states but the output for them is null", kept);
     const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
@@ -1006,7 +1098,7 @@ static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, cons
                         const float* cond, int Cc, float* x, int Cz, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
                         void* stream) {
     check_plms_schedule(sc);
-    if (g) check_guidance(g, sc->steps);
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
     if (inp) check_mask(inp, Cz);
     const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
@@ -1105,7 +1197,7 @@ int dsd_op_plms_step(int order, float a_t, float a_prev, float sqrt_1m_at, const
 static void invert(bool latent, dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
                    int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
-    if (g) check_guidance(g, sc->steps);
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
     const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
     set_device(h->device);

@@ -81,6 +81,22 @@ StOpt st_opt_from_iargs(const std::vector<int32_t>& a) {
     }
     return o;
 }
+// label_emb of a UNetModel handle (openaimodel.py:696-712): two more trailing integers behind the SpatialTransformer options.
+// kind 0 none, 1 nn.Embedding(width, ted) for an int num_classes, 2 Linear(1, ted) ("continuous"), 3 Linear(width, ted) -> SiLU
+// -> Linear(ted, ted) ("sequential" on adm_in_channels)
+struct LabelOpt {
+    int kind = 0, width = 0;
+};
+LabelOpt label_opt_from_iargs(const std::vector<int32_t>& a) {
+    LabelOpt o;
+    if (a.size() < 12) return o;
+    const int nl = a[10];
+    const size_t base = 12 + 2 * (size_t)nl + (size_t)a[11 + 2 * nl] + 4;
+    if (a.size() >= base + 2) {
+        o.kind = a[base]; o.width = a[base + 1];
+    }
+    return o;
+}
 struct Spec {
     std::vector<std::vector<Layer>> input_blocks, output_blocks;
     std::vector<Layer> middle;
@@ -369,6 +385,16 @@ void p_plain_unet(dsd_handle* h) {
     const bool film = h->cfg.use_scale_shift_norm;
     p_lin(h, "time_embed.0", h->cfg.model_channels, s.ted);
     p_lin(h, "time_embed.2", s.ted, s.ted);
+    const LabelOpt lo = label_opt_from_iargs(h->iargs);
+    DSD_CHECK(lo.kind >= 0 && lo.kind <= 3, "UNetModel: label_emb kind %d (0 none, 1 classes, 2 continuous, 3 sequential)", lo.kind);
+    DSD_CHECK(lo.kind == 0 || lo.kind == 2 || lo.width >= 1, "UNetModel: label_emb kind %d needs a width (num_classes / adm_in_channels), got %d",
+              lo.kind, lo.width);
+    if (lo.kind == 1) add_param(h, "label_emb.weight", {lo.width, s.ted});
+    if (lo.kind == 2) p_lin(h, "label_emb", 1, s.ted);
+    if (lo.kind == 3) {
+        p_lin(h, "label_emb.0.0", lo.width, s.ted);
+        p_lin(h, "label_emb.0.2", s.ted, s.ted);
+    }
     for (size_t bi = 0; bi < s.input_blocks.size(); ++bi)
         for (size_t li = 0; li < s.input_blocks[bi].size(); ++li)
             p_layer(h, "input_blocks." + std::to_string(bi) + "." + std::to_string(li), s.input_blocks[bi][li], s.ted, film);
@@ -606,6 +632,17 @@ bool dsd::net_unet_has_spatial_transformer(const dsd_handle* h) {
     return h->is_block && h->block_kind == DSD_BLOCK_UNET && st_opt_from_iargs(h->iargs).on != 0;
 }
 
+int dsd::net_unet_context_dim(const dsd_handle* h) {
+    return net_unet_has_spatial_transformer(h) ? st_opt_from_iargs(h->iargs).ctx_dim : 0;
+}
+
+void dsd::net_unet_label_emb(const dsd_handle* h, int* kind, int* width) {
+    LabelOpt o;
+    if (h->is_block && h->block_kind == DSD_BLOCK_UNET) o = label_opt_from_iargs(h->iargs);
+    *kind = o.kind;
+    *width = o.kind == 2 ? 1 : o.width;
+}
+
 void dsd::net_drop_graph(dsd_handle* h) {
     if (h->gexec) {
         (void)hipDeviceSynchronize();
@@ -655,6 +692,8 @@ void dsd::net_free(dsd_handle* h) {
     if (h->dpm_m) (void)hipFree(h->dpm_m);
     if (h->dpm_prog) (void)hipFree(h->dpm_prog);
     if (h->lat_in) (void)hipFree(h->lat_in);
+    if (h->ctx_buf) (void)hipFree(h->ctx_buf);
+    if (h->y_buf) (void)hipFree(h->y_buf);
     if (h->cfg_io) (void)hipFree(h->cfg_io);
     if (h->plms_hist) (void)hipFree(h->plms_hist);
     if (h->bpd_buf) (void)hipFree(h->bpd_buf);
@@ -1526,18 +1565,32 @@ struct TimeEmb {
 
 // ---- timestep embedding MLP + all emb_layers (68 of them in the headline network) as ONE GEMM (model.py:645-646,
 // openaimodel.py:939-940; :222-228,273).  t_from_aux: the timesteps are the fp32 vector io.aux (block handles), else io.t
-TimeEmb time_embed(Builder& b, const Spec& sp, bool t_from_aux) {
+// label: the UNetModel's label_emb (openaimodel.py:696-712, 941-943): emb = time_embed(t_emb) + label_emb(y), formed once in
+// front of the GEMM over all emb_layers; y is io.aux3 (int64 [B] for the class table, fp32 [B, width] for the two Linear forms)
+TimeEmb time_embed(Builder& b, const Spec& sp, bool t_from_aux, LabelOpt label = LabelOpt()) {
     dsd_handle* hd = b.hd;
     const int B = b.B, mc = hd->cfg.model_channels, ted = sp.ted, etot = (int)hd->emb_total;
     Tn temb = b.alloc(B, 1, 1, mc), e1 = b.alloc(B, 1, 1, ted), emb = b.alloc(B, 1, 1, ted);
+    Tn l1, lemb;
+    if (label.kind >= 2) lemb = b.alloc(B, 1, 1, ted);
+    if (label.kind == 3) l1 = b.alloc(B, 1, 1, ted);
     TimeEmb te;
     te.all = b.alloc(B, 1, 1, etot);
     {
-        const size_t to = temb.off, e1o = e1.off, eo = emb.off, ao = te.all.off;
+        const size_t to = temb.off, e1o = e1.off, eo = emb.off, ao = te.all.off, l1o = l1.off, lo = lemb.off;
         const float *w0 = b.W("time_embed.0.weight"), *b0 = b.W("time_embed.0.bias");
         const float *w2 = b.W("time_embed.2.weight"), *b2 = b.W("time_embed.2.bias");
+        const int lk = label.kind, lw = label.kind == 2 ? 1 : label.width;
+        const float *la = nullptr, *lab = nullptr, *lb = nullptr, *lbb = nullptr;
+        if (lk == 1) la = b.W("label_emb.weight");
+        if (lk == 2) { la = b.W("label_emb.weight"); lab = b.W("label_emb.bias"); }
+        if (lk == 3) {
+            la = b.W("label_emb.0.0.weight"); lab = b.W("label_emb.0.0.bias");
+            lb = b.W("label_emb.0.2.weight"); lbb = b.W("label_emb.0.2.bias");
+        }
         const float *wall = hd->slab_at(hd->emb_w_off), *ball = hd->slab_at(hd->emb_b_off);
-        const double fl = 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot);
+        double fl = 2.0 * B * ((double)mc * ted + (double)ted * ted + (double)ted * etot);
+        if (lk >= 2) fl += 2.0 * B * ((double)lw * ted + (lk == 3 ? (double)ted * ted : 0.0));
         b.plan.flops += fl;
         b.op([=](hipStream_t s) {
             float *tp = hd->at<float>(to), *e1p = hd->at<float>(e1o), *ep = hd->at<float>(eo), *ap = hd->at<float>(ao);
@@ -1547,10 +1600,26 @@ TimeEmb time_embed(Builder& b, const Spec& sp, bool t_from_aux) {
                 timestep_embedding(hd->io.t, hd->io.t_is_float, B, mc, tp, s, hd->freqs);
             linear(tp, B, mc, mc, w0, b0, ted, ACT_NONE, e1p, ted, s);
             linear(e1p, B, ted, ted, w2, b2, ted, ACT_SILU, ep, ted, s);
+            if (lk == 1) {
+                embed_add(ep, la, reinterpret_cast<const long long*>(hd->io.aux3), B, ted, ep, s);
+            } else if (lk >= 2) {
+                const float* y = reinterpret_cast<const float*>(hd->io.aux3);
+                float* lp = hd->at<float>(lo);
+                if (lk == 2) {
+                    linear(y, B, 1, 1, la, lab, ted, ACT_NONE, lp, ted, s);
+                } else {
+                    float* l1p = hd->at<float>(l1o);
+                    linear(y, B, lw, lw, la, lab, ted, ACT_NONE, l1p, ted, s);
+                    linear(l1p, B, ted, ted, lb, lbb, ted, ACT_SILU, lp, ted, s);
+                }
+                add2(ep, lp, (int64_t)B * ted, ep, s);
+            }
             linear(ep, B, ted, ted, wall, ball, etot, ACT_SILU, ap, etot, s);
-        }, 4, "time_embed_mlp", fl);
+        }, 4 + lk, "time_embed_mlp", fl);   // label_emb: 1, 2 or 3 launches more
     }
     b.release(temb); b.release(e1); b.release(emb);
+    if (lemb.valid()) b.release(lemb);
+    if (l1.valid()) b.release(l1);
     // column of each ResBlock inside emb_all = position of its bias in the contiguous bias region (declaration order)
     int64_t col = 0;
     for (const auto& p : hd->params)
@@ -1725,7 +1794,8 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
 }
 
 // --------------------------------------------------------------------------------- UNetModel.forward (openaimodel.py:926-958)
-// x: NCHW [B, in_channels, H, W] (latents, with the `concat` conditioning already appended), aux = timesteps [B] fp32.
+// x: NCHW [B, in_channels, H, W] (latents, with the `concat` conditioning already appended), aux = timesteps [B] fp32,
+// aux2 = context [B, tokens, context_dim] (spatial transformer), aux3 = y (label_emb; the callers check that it is bound).
 void build_plain_unet(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
     dsd_handle* hd = b.hd;
     const dsd_config& cfg = hd->cfg;
@@ -1738,7 +1808,7 @@ void build_plain_unet(Builder& b, int C, int H, int W, int aux_len, int aux_len2
     DSD_CHECK(C == cfg.in_channels, "UNetModel: input has %d channels, expected %d", C, cfg.in_channels);
     DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
     DSD_CHECK(aux_len == 1, "UNetModel: timesteps missing");
-    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/true);
+    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/true, label_opt_from_iargs(hd->iargs));
     // ---- encoder: h = module(h, emb, context); hs.append(h)   (:946-948)
     Tn x = b.import_ext(0, B, H, W, C, /*from_nchw=*/true);
     if (so.on) b.st_ctx = b.import_ext(2, B, aux_len2, 1, so.ctx_dim, false);
@@ -2274,7 +2344,7 @@ static GraphKey graph_key(const dsd_handle* h) {
         k.bs[i] = h->io.plane_bs[i];
     }
     k.ptr[4] = h->io.t; k.ptr[5] = h->io.out; k.ptr[6] = h->io.feats; k.ptr[7] = h->io.x_nchw; k.ptr[8] = h->io.aux;
-    k.ptr[9] = h->io.aux2; k.ptr[10] = h->arena; k.ptr[11] = h->freqs;
+    k.ptr[9] = h->io.aux2; k.ptr[10] = h->arena; k.ptr[11] = h->freqs; k.ptr[12] = h->io.aux3;
     k.t_is_float = h->io.t_is_float;
     return k;
 }

@@ -68,6 +68,7 @@ struct IO {
     const float* x_nchw = nullptr;  // block handles
     const float* aux = nullptr;
     const float* aux2 = nullptr;
+    const void* aux3 = nullptr;     // DSD_BLOCK_UNET with label_emb: y, int64 [B] (class table) or fp32 [B, width]
 };
 
 struct Plan {
@@ -92,12 +93,12 @@ struct Plan {
 // What a captured forward bakes in besides the plan: every pointer the closures read from dsd_handle::io.
 struct GraphKey {
     int plan_gen = -1;
-    const void* ptr[12] = {};
+    const void* ptr[13] = {};
     int64_t bs[4] = {};
     int t_is_float = 0;
     bool operator==(const GraphKey& o) const {
         if (plan_gen != o.plan_gen || t_is_float != o.t_is_float) return false;
-        for (int i = 0; i < 12; ++i) if (ptr[i] != o.ptr[i]) return false;
+        for (int i = 0; i < 13; ++i) if (ptr[i] != o.ptr[i]) return false;
         for (int i = 0; i < 4; ++i) if (bs[i] != o.bs[i]) return false;
         return true;
     }
@@ -149,6 +150,12 @@ struct dsd_handle {
     float* zplane = nullptr;   // [H*W] zeros
     float* dpm_m = nullptr;    // DPM-Solver step body: m_k, m_{k-1} [B,Cz*H*W] each + thresholds [B]
     float* lat_in = nullptr;   // latent binding (UNET block): the denoiser's NCHW input [rows,Cz+Cc,h,w]; channels [0,Cz) are the state
+    // dsd_set_conditioning: the caller's bundle (device pointers, read when a latent loop binds) and the loop's persistent
+    // copies of `rows` rows each (uncond half first under guidance), which io.aux2 / io.aux3 point at
+    dsd_conditioning cond{};
+    bool has_cond = false;
+    float* ctx_buf = nullptr;  // [rows, tokens, context_dim]
+    float* y_buf = nullptr;    // [rows] int64 or [rows, y_width] fp32
     float* cfg_io = nullptr;   // guided four-stream binding: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
     float* dpm_prog = nullptr; // DPM-Solver program: three history planes + the base-state plane [B,Cz*H*W] each + thresholds [B]
     // PLMS loops: three history planes [B,Cz,h,w] (a ring: iteration k >= 1 reads its newest prediction from plane (k-1) % 3 and
@@ -204,7 +211,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, bpd_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, bpd_cap = 0, ctx_cap = 0, y_cap = 0;
 
     float* P(const std::string& name) const;
     float* slab_at(size_t off) const { return reinterpret_cast<float*>(slab + off); }
@@ -230,6 +237,10 @@ void net_run_cached(dsd_handle* h, hipStream_t s);
 void net_drop_graph(dsd_handle* h);
 // DSD_BLOCK_UNET handles: built with use_spatial_transformer (a SpatialTransformer on `context` in every attention slot)
 bool net_unet_has_spatial_transformer(const dsd_handle* h);
+int net_unet_context_dim(const dsd_handle* h);   // 0 without spatial transformer
+// label_emb of a DSD_BLOCK_UNET handle: kind 0 none, 1 int classes (width = num_classes), 2 continuous (width 1), 3 sequential
+// (width = adm_in_channels)
+void net_unet_label_emb(const dsd_handle* h, int* kind, int* width);
 // frees the derived weights whose family (WeightFamily) `precision` does not read
 void net_drop_other_pieces(dsd_handle* h, int precision);
 size_t net_piece_bytes(const dsd_handle* h);

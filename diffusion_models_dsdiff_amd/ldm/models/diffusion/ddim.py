@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .... import _lib
-from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active,
+from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active, wrapper_key,
                          invert_coefficients, philox_seed, q_sample_rows, run_device_loop, run_invert_loop)
 
 
@@ -120,13 +120,13 @@ class DDIMSampler(object):
         if ucg_schedule is not None:
             assert len(ucg_schedule) == sched.steps                                   # :166
         if guidance_active(unconditional_guidance_scale, unconditional_conditioning, ucg_schedule):
-            u = cat_unconditional(conditioning, unconditional_conditioning, device)
+            u = cat_unconditional(conditioning, unconditional_conditioning, device, wrapper_key(self.model))
             guidance = Guidance(u, ucg_schedule if ucg_schedule is not None else unconditional_guidance_scale, sched.steps)
         img = x_T if x_T is not None else torch.randn(size, device=device)
         inpaint = None
         if mask is not None:                                                          # x0 alone changes nothing (:160)
             inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
-        out = run_device_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device), step_noise=step_noise,
+        out = run_device_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device, wrapper_key(self.model)), step_noise=step_noise,
                               seed=seed, guidance=guidance, inpaint=inpaint)
         return out, {"x_inter": [img, out], "pred_x0": [img, out]}
 
@@ -136,7 +136,7 @@ class DDIMSampler(object):
     def _guidance(self, cond, scale, uncond, steps, device):
         if not guidance_active(scale, uncond):
             return None
-        return Guidance(cat_unconditional(cond, uncond, device), scale, steps)
+        return Guidance(cat_unconditional(cond, uncond, device, wrapper_key(self.model)), scale, steps)
 
     @torch.no_grad()
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
@@ -162,7 +162,7 @@ class DDIMSampler(object):
         device = self.model.betas.device
         if unconditional_guidance_scale != 1.:
             assert unconditional_conditioning is not None                             # :286
-        cond = cat_conditioning(c, device)
+        cond = cat_conditioning(c, device, wrapper_key(self.model))
         guidance = self._guidance(c, unconditional_guidance_scale, unconditional_conditioning, n, device)
         marks = []                                                                    # :296-302
         for i in range(n):
@@ -215,6 +215,6 @@ class DDIMSampler(object):
             full = torch.zeros((sched.steps,) + tuple(step_noise.shape[1:]), device=device, dtype=torch.float32)
             full[first:] = step_noise.to(device)
             step_noise = full
-        return run_device_loop(self._unet(), sched, x_latent.to(device), cat_conditioning(cond, device), step_noise=step_noise,
+        return run_device_loop(self._unet(), sched, x_latent.to(device), cat_conditioning(cond, device, wrapper_key(self.model)), step_noise=step_noise,
                                seed=seed, first_step=first, guidance=guidance)
 

@@ -34,25 +34,46 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise ValueError(f"schedule '{schedule}' unknown.")
 
 
+CONDITIONING_KEYS = (None, "concat", "crossattn", "hybrid", "adm", "hybrid-adm", "crossattn-adm")
+
+
 class DiffusionWrapper(nn.Module):
-    """ddpm.py:1319-1365 — 'concat' (and unconditional) conditioning of the native U-Net."""
+    """ddpm.py:1319-1365 — every conditioning key of the reference in front of the native denoiser: 'concat' appends channels,
+    'crossattn' hands the token-concatenated context on, 'adm' the vector / label ``y``, the hybrids combine them."""
 
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
         diff_model_config = dict(diff_model_config)
         self.sequential_cross_attn = diff_model_config.pop("sequential_crossattn", False)
+        if self.sequential_cross_attn:
+            raise NotImplementedError("sequential_crossattn=True hands the context on as a list, one entry per transformer block: "
+                                      "that needs transformer_depth > 1, which is not built")
         self.diffusion_model = instantiate_from_config(diff_model_config)
         self.conditioning_key = conditioning_key
-        assert self.conditioning_key in [None, "concat", "crossattn", "hybrid", "adm", "hybrid-adm", "crossattn-adm"]
+        assert self.conditioning_key in CONDITIONING_KEYS
 
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, c_adm=None):
-        if self.conditioning_key is None:
+        key = self.conditioning_key
+        if key is None:
             return self.diffusion_model(x, t)
-        if self.conditioning_key == "concat":
+        if key == "concat":
             xc = torch.cat([x] + c_concat, dim=1)
             return self.diffusion_model(xc, t)
-        raise NotImplementedError(f"conditioning_key={self.conditioning_key!r}: only 'concat' is on the hot path "
-                                  "(every shipped medical yaml, SURVEY.md 8a-15)")
+        if key == "crossattn":
+            return self.diffusion_model(x, t, context=torch.cat(c_crossattn, 1))
+        if key == "hybrid":
+            xc = torch.cat([x] + c_concat, dim=1)
+            return self.diffusion_model(xc, t, context=torch.cat(c_crossattn, 1))
+        if key == "hybrid-adm":
+            assert c_adm is not None
+            xc = torch.cat([x] + c_concat, dim=1)
+            return self.diffusion_model(xc, t, context=torch.cat(c_crossattn, 1), y=c_adm)
+        if key == "crossattn-adm":
+            assert c_adm is not None
+            return self.diffusion_model(x, t, context=torch.cat(c_crossattn, 1), y=c_adm)
+        if key == "adm":
+            return self.diffusion_model(x, t, y=c_crossattn[0])
+        raise NotImplementedError(f"conditioning_key={key!r}")
 
 
 class DDPM(nn.Module):
@@ -163,7 +184,7 @@ def select_checkpoint(sd, own_keys, ignore_keys=()):
 
 class LatentDiffusion(DDPM):
     """The sampling surface of ldm/models/diffusion/ddpm.py:526-1115 (LatentDiffusion) as trainers/trainer_latent_diffusion.py
-    uses it: a KL first stage (AutoencoderKL) around a native UNetModel with 'concat' conditioning.  ``sample`` (DDPM,
+    uses it: a KL first stage (AutoencoderKL) around a native UNetModel under any of the reference's conditioning keys.  ``sample`` (DDPM,
     :1048-1115) and the DDIMSampler / DPMSolverSampler handed this object run in the library's device-resident latent loops
     (dsd_sample_latent / dsd_sample_dpm_latent).  Training (losses, scale_by_std estimation, EMA, Lightning) is out of scope."""
 
@@ -178,8 +199,8 @@ class LatentDiffusion(DDPM):
             conditioning_key = "concat" if concat_mode else "crossattn"
         if cond_stage_config == "__is_unconditional__" and not self.force_null_conditioning:
             conditioning_key = None
-        if conditioning_key not in ("concat", None):
-            raise NotImplementedError(f"conditioning_key={conditioning_key!r}: the latent path runs 'concat' conditioning only")
+        if conditioning_key not in CONDITIONING_KEYS:
+            raise NotImplementedError(f"conditioning_key={conditioning_key!r}: not one of {CONDITIONING_KEYS}")
         ckpt_path = kwargs.pop("ckpt_path", None)
         ignore_keys = kwargs.pop("ignore_keys", [])
         kwargs.pop("reset_ema", None), kwargs.pop("reset_num_ema_updates", None)
@@ -282,9 +303,11 @@ class LatentDiffusion(DDPM):
 
     # ------------------------------------------------------------------ denoiser
     def apply_model(self, x_noisy, t, cond, return_ids=False):
-        """:857-878, 'concat' conditioning."""
+        """:857-878: a dict goes to the wrapper as it is; anything else under the key the wrapper concatenates by."""
         if not isinstance(cond, dict):
-            cond = {"c_concat": cond if isinstance(cond, list) else [cond]}
+            if not isinstance(cond, list):
+                cond = [cond]
+            cond = {"c_concat" if self.model.conditioning_key == "concat" else "c_crossattn": cond}
         out = self.model(x_noisy, t, **cond)
         return out[0] if isinstance(out, tuple) and not return_ids else out
 
@@ -327,7 +350,7 @@ class LatentDiffusion(DDPM):
         """:1048-1093 on the device.  ``step_noise`` ([steps,B,C,h,w]) / ``seed`` are extensions for reproducible runs.
         ``mask`` / ``x0`` (:1071-1073,1085-1087): after every update, the last included, the state becomes
         q_sample(x0, t)*mask + (1 - mask)*state; ``mask_noise`` ([steps,B,C,h,w]) feeds q_sample's draws, else Philox of ``seed``."""
-        from ...._sched import Inpaint, find_unet, run_device_loop
+        from ...._sched import Inpaint, cat_conditioning, find_unet, run_device_loop
         if quantize_denoised or callback is not None or img_callback is not None:
             raise NotImplementedError("quantize / per-step callbacks are not on the device loop")
         if mask is not None:
@@ -337,12 +360,12 @@ class LatentDiffusion(DDPM):
         img = x_T if x_T is not None else torch.randn(shape, device=device)
         if start_T is not None:
             timesteps = min(timesteps or self.num_timesteps, start_T)
-        c = cond["c_concat"] if isinstance(cond, dict) else (cond if isinstance(cond, list) else [cond])
         inpaint = None
         if mask is not None:
             inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
         out = run_device_loop(find_unet(self.model), self._schedule(timesteps), img.to(device),
-                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed, inpaint=inpaint)
+                              cat_conditioning(cond, device, self.model.conditioning_key), step_noise=step_noise, seed=seed,
+                              inpaint=inpaint)
         if return_intermediates:
             return out, [img, out]
         return out
@@ -371,9 +394,10 @@ class LatentDiffusion(DDPM):
         from .ddim import DDIMSampler
         from .dpm_solver_new.sampler import DPMSolverSampler
         shape = (self.channels, self.image_size, self.image_size)
-        actual = tuple(cond["c_concat"][0].shape[2:])
-        if actual != shape[1:]:
-            shape = (self.channels, *actual)
+        if isinstance(cond, dict) and cond.get("c_concat"):
+            actual = tuple(cond["c_concat"][0].shape[2:])
+            if actual != shape[1:]:
+                shape = (self.channels, *actual)
         if sampler == "dpm":
             return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, **kwargs)
         if sampler == "ddim":

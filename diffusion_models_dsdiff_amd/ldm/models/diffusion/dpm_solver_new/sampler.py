@@ -16,6 +16,7 @@ class _ApplyModel:
     def __init__(self, ldm_model):
         self.ldm_model = ldm_model
         self.diffusion_model = getattr(getattr(ldm_model, "model", None), "diffusion_model", None)
+        self.conditioning_key = getattr(getattr(ldm_model, "model", None), "conditioning_key", None)
 
     def __call__(self, x, t, c):
         return self.ldm_model.apply_model(x, t, c)
@@ -44,14 +45,16 @@ class DPMSolverSampler(object):
         device = self.model.betas.device
         img = torch.randn(size, device=device) if x_T is None else x_T
         ns = NoiseScheduleVP("discrete", betas=self.betas)
+        slot = "c_concat" if getattr(getattr(self.model, "model", None), "conditioning_key", None) in (None, "concat") \
+            else "c_crossattn"                                # apply_model's filing of a tensor or list (ddpm.py:862-866)
         if not isinstance(conditioning, dict):
             if unconditional_conditioning is not None:        # the same wrapping keeps the two in one form
                 assert not isinstance(unconditional_conditioning, dict) and \
                     isinstance(unconditional_conditioning, list) == isinstance(conditioning, list), \
                     "unconditional_conditioning must come in the form of the conditioning"
-                unconditional_conditioning = dict(c_concat=unconditional_conditioning if isinstance(
-                    unconditional_conditioning, list) else [unconditional_conditioning])
-            conditioning = dict(c_concat=conditioning if isinstance(conditioning, list) else [conditioning])
+                unconditional_conditioning = {slot: unconditional_conditioning if isinstance(
+                    unconditional_conditioning, list) else [unconditional_conditioning]}
+            conditioning = {slot: conditioning if isinstance(conditioning, list) else [conditioning]}
         model_fn = model_wrapper(_ApplyModel(self.model), ns, model_type=MODEL_TYPES[self.model.parameterization],
                                  guidance_type="classifier-free", condition=conditioning,
                                  unconditional_condition=unconditional_conditioning,

@@ -7,7 +7,7 @@ from __future__ import annotations
 import torch
 
 from .... import _lib
-from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active,
+from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active, wrapper_key,
                          run_plms_loop)
 from .ddim import DDIMSampler, MaskWithoutX0, pack_schedule
 
@@ -63,12 +63,12 @@ class PLMSSampler(object):
         device = self.model.betas.device
         guidance = None
         if guidance_active(unconditional_guidance_scale, unconditional_conditioning):
-            u = cat_unconditional(conditioning, unconditional_conditioning, device)
+            u = cat_unconditional(conditioning, unconditional_conditioning, device, wrapper_key(self.model))
             guidance = Guidance(u, unconditional_guidance_scale, sched.steps)
         img = x_T if x_T is not None else torch.randn(size, device=device)
         inpaint = None
         if mask is not None:
             inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
-        out = run_plms_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device),
+        out = run_plms_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device, wrapper_key(self.model)),
                             threshold=dynamic_threshold, guidance=guidance, inpaint=inpaint, seed=seed)
         return out, {"x_inter": [img, out], "pred_x0": [img, out]}

@@ -257,7 +257,8 @@ int dsd_op_sampler_update(const dsd_schedule* sched, int k, const float* model_o
 
 /* ---- latent sampling loops (DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser) --------------------
  * The loops of dsd_sample / dsd_sample_dpm on a multi-channel state: x [B,Cz,H,W] (VAE latents, in = x_T, out = sample, in
- * place) denoised by a DSD_BLOCK_UNET handle (the plain UNetModel, no spatial transformer) with in_channels = Cz + Cc and
+ * place) denoised by a DSD_BLOCK_UNET handle (the plain UNetModel; with a spatial transformer or a label_emb its context / y come through
+ * dsd_set_conditioning, below, and Cc may be 0) with in_channels = Cz + Cc and
  * out_channels = Cz (2 with a learned-range variance, which needs Cz = 1).  cond [B,Cc,H,W] is concatenated after the state
  * (DiffusionWrapper 'concat', ldm/models/diffusion/ddpm.py:1331-1333): both are copied ONCE into the denoiser's persistent
  * NCHW input, and every update writes x_{t-1} straight into its state channels.  Schedules, first_step / n_steps,
@@ -360,6 +361,37 @@ int dsd_op_sampler_update_guided(const dsd_schedule* sched, int k, const float* 
 int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sched, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
                            float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
                            void* stream);
+/* ---- cross-attention and vector conditioning of the latent loops ----------------------------
+ * The conditioning keys beside 'concat' that the reference's latent inference runs on: trainers/trainer_latent_diffusion.py:153-189
+ * builds {"c_crossattn": [c], "c_adm": c_adm, "c_concat": [...]}, :492-524 samples with an unconditional_conditioning dict that
+ * replaces c_crossattn and keeps c_adm / c_concat, DiffusionWrapper.forward (ldm/models/diffusion/ddpm.py:1328-1365) dispatches
+ * 'crossattn', 'hybrid', 'adm', 'hybrid-adm', 'crossattn-adm', and UNetModel.forward
+ * (ldm/modules/diffusionmodules/openaimodel.py:926-958) adds label_emb(y) (:696-712) to the time embedding.
+ * dsd_set_conditioning installs one bundle on a DSD_BLOCK_UNET handle; NULL clears it.  The struct holds DEVICE pointers that
+ * must stay valid until the bundle is cleared or replaced; the library reads them when a call binds:
+ *   - every latent entry (dsd_sample_latent*, dsd_sample_dpm*_latent*, dsd_sample_plms_latent, dsd_invert_latent,
+ *     dsd_calc_bpd_latent, masked and guided variants) copies the parts once per call into buffers of its own of `rows` rows
+ *     (rows = B, or 2B under a dsd_guidance: the unconditional twins first, as for the denoiser's input), which the network
+ *     reads every step; a cached plan or a replayed graph sees stable addresses, a different `tokens` re-plans.  The context
+ *     projections run every step, as in the reference.
+ *   - dsd_block_forward on a DSD_BLOCK_UNET handle with label_emb reads y (B rows) from the bundle; its context stays aux2.
+ * Checked before any device work, each misfit with its numbers: a spatial-transformer handle without a context and a context
+ * for a handle without one; y if and only if the handle has label_emb; y_width against the handle's kind (0 for int classes,
+ * 1 for "continuous", adm_in_channels for "sequential"); B against the call's; int labels outside [0, num_classes).  Under a
+ * dsd_guidance every part that is set needs its unconditional twin (a twin equal to the conditional part is legal: the
+ * reference's c_adm), and Cc = 0 is allowed when a context or y is there to be replaced (g->uncond may then be NULL).  DSD_BLOCK_DIT
+ * and four-stream handles refuse any bundle. */
+typedef struct dsd_conditioning {
+    const float* context;        /* [B,tokens,context_dim], or NULL */
+    const float* context_uncond; /* [B,tokens,context_dim], or NULL */
+    int32_t tokens;              /* context length */
+    const void* y;               /* int64 [B] (y_width 0) or fp32 [B,y_width], or NULL */
+    const void* y_uncond;        /* like y, or NULL */
+    int32_t y_width;             /* 0 = int64 labels, else fp32 floats per row */
+    int32_t B;                   /* batch size */
+} dsd_conditioning;
+int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c);
+
 /* ---- the DPM-Solver family as a program of evaluations -------------------------------------
  * Replaces DPM_Solver(...).sample / .inverse of Disc_diff/guided_diffusion/sampler.py:1001-1217 (and of the twin
  * dpm_solver_pytorch.py) for method = "multistep" with order 1..3 (:818-868 adds the third), "singlestep" and "singlestep_fixed"
@@ -570,9 +602,9 @@ enum { DSD_BLOCK_RES = 0, DSD_BLOCK_ATTN = 1, DSD_BLOCK_UPSAMPLE = 2, DSD_BLOCK_
        /* transformer backbone (SURVEY f-4): DiT of UNet_DS_Diff/DiT_models.py:145-262 (adaLN-Zero blocks, timm-style
         * PatchEmbed / Attention / Mlp); parameter names are the DiT state_dict's */
        DSD_BLOCK_DIT = 12,
-       /* the plain single-stream UNetModel of ldm/modules/diffusionmodules/openaimodel.py:571-958 (no class embedding): the
+       /* the plain single-stream UNetModel of ldm/modules/diffusionmodules/openaimodel.py:571-958: the
         * denoiser that consumes the VAE latents in the latent path; optionally with a SpatialTransformer on `context` in
-        * every attention slot (use_spatial_transformer=True, :761-765,818-822,872-876) */
+        * every attention slot (use_spatial_transformer=True, :761-765,818-822,872-876) and with label_emb on y (:696-712) */
        DSD_BLOCK_UNET = 13 };
 /* iargs by kind:
  *   RES: cin, cout, emb_ch, use_scale_shift_norm, up, down      ATTN: ch, heads, new_order
@@ -591,9 +623,13 @@ enum { DSD_BLOCK_RES = 0, DSD_BLOCK_ATTN = 1, DSD_BLOCK_UPSAMPLE = 2, DSD_BLOCK_
  *   UNET: in_channels, model_channels, out_channels, num_heads, num_head_channels, num_heads_upsample, use_scale_shift_norm,
  *        resblock_updown, use_new_attention_order, legacy, len(channel_mult), channel_mult..., num_res_blocks per level...,
  *        len(attention_resolutions), attention_resolutions...  (the ctor kwargs of openaimodel.py:601-633), optionally followed by
- *        use_spatial_transformer, transformer_depth (1), context_dim, use_linear_in_transformer.
+ *        use_spatial_transformer, transformer_depth (1), context_dim, use_linear_in_transformer, and behind those by the
+ *        label_emb kind (0 none, 1 int num_classes, 2 "continuous", 3 "sequential") and its width (num_classes /
+ *        adm_in_channels; openaimodel.py:696-712).  Parameters: label_emb.weight (kind 1, [num_classes, 4*model_channels]),
+ *        label_emb.weight / .bias (kind 2), label_emb.0.0.* and label_emb.0.2.* (kind 3).
  *        x [B,in_channels,H,W], aux = timesteps [B] fp32 (aux_len 1), aux2 = context [B,tokens,context_dim] with
- *        aux_len2 = tokens (spatial-transformer variant only, else NULL / 0); out [B,out_channels,H,W]. */
+ *        aux_len2 = tokens (spatial-transformer variant only, else NULL / 0); y of a label_emb handle comes through
+ *        dsd_set_conditioning; out [B,out_channels,H,W]. */
 int dsd_block_create(int kind, const int32_t* iargs, int n_iargs, int device, dsd_handle** out);
 /* x: NCHW [B,C,H,W] (token blocks: [B,N,C] passed as H=N, W=1 "NHWC"), aux: emb [B,emb_ch] for RES,
  * context [B,Nc,Cc] for cross-attention kinds (aux2/aux_len2 = second context for depth-2 spatial
