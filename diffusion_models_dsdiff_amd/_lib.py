@@ -23,12 +23,12 @@ PRED_EPS, PRED_X0, PRED_V = 0, 1, 2
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 5}
 (BLOCK_RES, BLOCK_ATTN, BLOCK_UPSAMPLE, BLOCK_DOWNSAMPLE, BLOCK_DISENTANGLE, BLOCK_SE, BLOCK_CROSSATTN,
  BLOCK_FF_GEGLU, BLOCK_BASIC_TRANSFORMER, BLOCK_SPATIAL_TRANSFORMER, BLOCK_VAE_ENCODER, BLOCK_VAE_DECODER,
- BLOCK_DIT, BLOCK_UNET) = range(14)
+ BLOCK_DIT, BLOCK_UNET, BLOCK_VAE_ATTN) = range(15)
 
 # every symbol include/dsdiff.h declares (tests/test_abi.py checks the header against this list)
 EXPORTS = [
     "dsd_last_error", "dsd_device_info", "dsd_create", "dsd_destroy", "dsd_param_count", "dsd_param_info",
-    "dsd_set_param", "dsd_set_timestep_freqs", "dsd_set_precision", "dsd_get_precision", "dsd_set_share_zero_streams", "dsd_params_ready", "dsd_plan", "dsd_workspace_bytes", "dsd_device_bytes", "dsd_set_graph", "dsd_graph_stats", "dsd_set_fuse_gn_stats", "dsd_set_fuse_gn_apply", "dsd_set_stream_lanes", "dsd_set_winograd", "dsd_set_slice_ids", "dsd_plan_launches", "dsd_plan_flops",
+    "dsd_set_param", "dsd_set_timestep_freqs", "dsd_set_precision", "dsd_get_precision", "dsd_set_share_zero_streams", "dsd_params_ready", "dsd_plan", "dsd_workspace_bytes", "dsd_device_bytes", "dsd_set_graph", "dsd_graph_stats", "dsd_set_fuse_gn_stats", "dsd_set_fuse_gn_apply", "dsd_set_stream_lanes", "dsd_set_winograd", "dsd_set_vae_fused_attention", "dsd_set_slice_ids", "dsd_plan_launches", "dsd_plan_flops",
     "dsd_profile_enable", "dsd_profile_count", "dsd_profile_get", "dsd_profile_op_count", "dsd_profile_op_get", "dsd_profile_op_name", "dsd_forward", "dsd_sample", "dsd_op_sampler_update", "dsd_sample_dpm", "dsd_op_dpm_step", "dsd_op_dpm_threshold", "dsd_block_create", "dsd_block_forward", "dsd_bench_conv2d", "dsd_bench_conv2d_stamps", "dsd_bench_mfma_peak", "dsd_conv_plan", "dsd_subpixel_weights_host", "dsd_set_conv_mfma16", "dsd_op_conv2d", "dsd_op_conv2d_prec", "dsd_op_conv2d_ex", "dsd_op_conv2d_gn", "dsd_op_gn_finalize", "dsd_op_avg_into_stats", "dsd_op_gn_small", "dsd_op_gn_silu_conv_out1",
     "dsd_op_gaussian_sample", "dsd_op_group_norm", "dsd_op_qkv_attention", "dsd_op_attention", "dsd_op_gemm_half", "dsd_bench_gemm_half", "dsd_bench_attention_half", "dsd_op_attention_half", "dsd_op_timestep_embedding", "dsd_op_linear", "dsd_op_philox_normal",
     "dsd_sample_latent", "dsd_sample_dpm_latent", "dsd_op_posterior_sample_scaled",
@@ -164,6 +164,7 @@ def lib() -> C.CDLL:
     L.dsd_set_fuse_gn_apply.argtypes = [vp, i32]
     L.dsd_set_stream_lanes.argtypes = [vp, i32, i32]
     L.dsd_set_winograd.argtypes = [vp, i32]
+    L.dsd_set_vae_fused_attention.argtypes = [vp, i32]
     L.dsd_graph_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dsd_set_slice_ids.argtypes = [vp, C.POINTER(C.c_int64), i32]
     L.dsd_plan_launches.argtypes = [vp]

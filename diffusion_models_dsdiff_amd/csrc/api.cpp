@@ -301,6 +301,16 @@ int dsd_set_winograd(dsd_handle* h, int on) {
     DSD_CATCH
 }
 
+int dsd_set_vae_fused_attention(dsd_handle* h, int on) {
+    DSD_TRY
+    DSD_CHECK(h, "null handle");
+    if (h->vae_fused_attention != (on != 0)) {
+        h->vae_fused_attention = on != 0;
+        h->plan.valid = false;
+    }
+    DSD_CATCH
+}
+
 int dsd_graph_stats(dsd_handle* h, int* captures, int* launches) {
     DSD_TRY
     DSD_CHECK(h, "null handle");
@@ -1807,7 +1817,7 @@ int dsd_op_attention(const float* q, const float* k, const float* v, int N, int 
     a.q_hs = q_hs; a.k_hs = k_hs; a.v_hs = v_hs;
     a.scale_q = scale_q; a.scale_k = scale_k; a.scale_s = scale_s;
     a.split = split != 0;
-    attention(a, (hipStream_t)stream);
+    attention_any(a, (hipStream_t)stream);
     DSD_CATCH
 }
 

@@ -154,7 +154,9 @@ struct AttnArgs {
     float* out = nullptr;  // [N][Tq][ldo], head h at +h*d
     int split = 0;         // 1: both products on the bf16 matrix cores with operands split into 3 bf16 pieces (bf16x6), 0: fp32 MFMA
 };
-void attention(const AttnArgs& a, hipStream_t s);
+void attention(const AttnArgs& a, hipStream_t s);        // d % 4 == 0, d <= 128
+void attention_wide(const AttnArgs& a, hipStream_t s);   // attention_wide.hip: 128 < d <= 512, d % 4 == 0
+void attention_any(const AttnArgs& a, hipStream_t s);    // attention_wide.hip: dispatches on d between the two (d <= 512)
 
 // ---------------------------------------------------------------- gemm16.hip / attention16.hip
 // Single-product half-precision arithmetic of the transformer backbone (PREC_F16 / PREC_BF16: 16-bit operands, one MFMA per

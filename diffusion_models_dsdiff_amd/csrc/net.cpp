@@ -536,6 +536,7 @@ void dsd::net_declare_params(dsd_handle* h) {
                 break;
             case DSD_BLOCK_VAE_ENCODER: p_vae_encoder(h, vae_cfg(a)); break;
             case DSD_BLOCK_VAE_DECODER: p_vae_decoder(h, vae_cfg(a)); break;
+            case DSD_BLOCK_VAE_ATTN: need(1); p_vae_attn(h, "", a[0]); break;
             default: fail("unknown block kind %d", h->block_kind);
         }
         // block parameter names carry no leading '.'
@@ -1457,15 +1458,39 @@ struct Builder {
         if (proj) release(skip);
         return out;
     }
-    // AttnBlock.forward (:185-209): ONE head over all C channels, softmax(q k^T C^-1/2) v.  C is 512 at the yaml's size, far
-    // beyond the flash kernel's head dims, so the score matrix is materialised per sample and both products run as GEMMs
-    // on the convolution kernels (a 1x1 convolution whose "weights" are the other operand: y[m][n] = sum_k A[m][k] B[n][k]).
+    // AttnBlock.forward (:185-209): ONE head over all C channels, softmax(q k^T C^-1/2) v.  C is 512 at the yaml's size.  By
+    // default the score matrix is materialised per sample and both products run as GEMMs on the convolution kernels (a 1x1
+    // convolution whose "weights" are the other operand: y[m][n] = sum_k A[m][k] B[n][k]); dsd_set_vae_fused_attention
+    // switches to one fused attention() launch with a single C-wide head.
     Tn vae_attn(const std::string& p, const Tn& x) {
         const int C = x.c, T = x.hw(), Bn = x.n;
-        Tn n = gn_act(p + ".norm", x, ACT_NONE, 1e-6f);
-        Tn q = conv(p + ".q", n, C, 1), k = conv(p + ".k", n, C, 1), v = conv(p + ".v", n, C, 1);
+        Tn n = gn_act(pre(p, "norm"), x, ACT_NONE, 1e-6f);
+        Tn q = conv(pre(p, "q"), n, C, 1), k = conv(pre(p, "k"), n, C, 1), v = conv(pre(p, "v"), n, C, 1);
         release(n);
         Tn a = alloc(Bn, x.h, x.w, C);
+        if (hd->vae_fused_attention && C % 4 == 0 && C <= 512) {
+            // dsd_set_vae_fused_attention: one head of width C through the flash kernels (attention_wide.hip above 128) — no
+            // score buffer, no V transpose, no split planes
+            AttnArgs aa;
+            aa.ldq = aa.ldk = aa.ldv = aa.ldo = C;
+            aa.q_hs = aa.k_hs = aa.v_hs = C;
+            aa.N = Bn; aa.Tq = T; aa.Tk = T; aa.heads = 1; aa.d = C;
+            aa.scale_s = 1.f / std::sqrt((float)C);   // int(c)**(-0.5), :196
+            aa.split = hd->precision != PREC_F32;
+            const size_t qo = q.off, ko = k.off, vo = v.off, ao = a.off;
+            dsd_handle* h = hd;
+            const double fl = 4.0 * Bn * (double)T * T * C;
+            plan.flops += fl;
+            op([=](hipStream_t s) {
+                AttnArgs r = aa;
+                r.q = h->at<float>(qo); r.k = h->at<float>(ko); r.v = h->at<float>(vo); r.out = h->at<float>(ao);
+                attention_any(r, s);
+            }, 1, "vae_attention", fl);
+            release(q); release(k); release(v);
+            Tn out = conv(pre(p, "proj_out"), a, C, 1, {.res = &x, .want_stats = true});
+            release(a);
+            return out;
+        }
         const bool split = hd->precision != PREC_F32 && C % 32 == 0 && T % 32 == 0;
         const bool f16 = hd->precision == PREC_F16X3;
         const size_t sb = (size_t)T * T * sizeof(float), vb = (size_t)C * T * sizeof(float), pb = split ? (size_t)T * C * 6 : 0;
@@ -1507,7 +1532,7 @@ struct Builder {
         release_raw(vtoff, vb);
         if (pb) release_raw(poff, pb);
         release(q); release(k); release(v);
-        Tn out = conv(p + ".proj_out", a, C, 1, {.res = &x, .want_stats = true});
+        Tn out = conv(pre(p, "proj_out"), a, C, 1, {.res = &x, .want_stats = true});
         release(a);
         return out;
     }
@@ -2171,6 +2196,10 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
             b.release(n);
             break;
         }
+        case DSD_BLOCK_VAE_ATTN:
+            DSD_CHECK(C == a[0], "VAE AttnBlock: input has %d channels, expected %d", C, a[0]);
+            y = b.vae_attn("", x);
+            break;
         default: fail("unknown block kind");
     }
     b.export_out(y, !token);

@@ -178,6 +178,7 @@ struct dsd_handle {
     hipStream_t last_param_stream = nullptr;
     bool any_param_upload = false;
     int use_graph = 0;
+    int vae_fused_attention = 0;   // opt-in: the KL-VAE's AttnBlock as one fused attention() launch (no T x T score buffer)
     int use_winograd = 0;    // bf16x6 only, opt-in: 3x3 stride-1 convolutions as F(2,3) along the width (conv_wino.hip)
     int fuse_gn_stats = 1;   // GroupNorm statistics from the producing kernel's epilogue (0: always the standalone pass)
     int fuse_gn_apply = 1;   // GroupNorm + SiLU applied by the consuming 3x3 convolution while it stages its input (0: apply pass)

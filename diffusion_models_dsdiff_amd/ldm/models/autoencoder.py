@@ -71,6 +71,12 @@ class AutoencoderKL(nn.Module):
         self._dec.set_precision(precision)
         return self
 
+    def set_fused_attention(self, on: bool = True):
+        """Both halves' AttnBlocks as fused attention launches (off by default; see Encoder.set_fused_attention)."""
+        self._enc.set_fused_attention(on)
+        self._dec.set_fused_attention(on)
+        return self
+
     def encode(self, x):
         """:138-142"""
         return DiagonalGaussianDistribution(self._enc(x))

@@ -27,9 +27,31 @@ def _check(dropout, resamp_with_conv, use_linear_attn, attn_type):
                                   "(every shipped autoencoder yaml)")
 
 
+def _set_fused_attention(self, on: bool = True):
+    """AttnBlock as one fused attention launch instead of the materialised T x T score matrix (off by default; include/dsdiff.h:
+    dsd_set_vae_fused_attention)."""
+    _lib.check(_lib.lib().dsd_set_vae_fused_attention(self._h, int(bool(on))))
+    return self
+
+
+class AttnBlock(_Block):
+    """AttnBlock (:178-209) alone: GroupNorm, 1x1 q / k / v, one head over all channels, 1x1 proj_out, residual."""
+    _zero_sites = False
+    set_fused_attention = _set_fused_attention
+
+    def __init__(self, in_channels, device_index=0):
+        super().__init__()
+        self.in_channels = in_channels
+        self._create(_lib.BLOCK_VAE_ATTN, [in_channels], device_index)
+
+    def forward(self, x):
+        return self._call(x)
+
+
 class Encoder(_Block):
     _zero_sites = False
     _strip = "encoder."
+    set_fused_attention = _set_fused_attention
 
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, double_z=True, use_linear_attn=False,
@@ -54,6 +76,7 @@ class Encoder(_Block):
 class Decoder(_Block):
     _zero_sites = False
     _strip = "decoder."
+    set_fused_attention = _set_fused_attention
 
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False,

@@ -159,6 +159,13 @@ int dsd_set_stream_lanes(dsd_handle* h, int on, int max_pixels);
  * the layers it takes (its operand feeding costs what the saved MFMAs gain: conv_wino.hip header) — 2 % on a whole
  * denoising step — and stays below the 300 TF/s go / no-go set for it. */
 int dsd_set_winograd(dsd_handle* h, int on);
+/* KL-VAE handles, OFF by default: AttnBlock (one head over all C <= 512 channels) as ONE fused attention launch — online
+ * softmax, the T x T score matrix never leaves the chip (csrc/attention_wide.hip for C > 128) — instead of the materialised
+ * route (two GEMMs around a row softmax, per sample).  With it on the plan holds neither the 4 T^2-byte score buffer nor the
+ * V transpose nor the split planes, so dsd_workspace_bytes shrinks.  Both routes are fp32-grade (exact fp32 MFMA in
+ * DSD_PREC_F32, bf16x6 otherwise) and agree to fp32 rounding, not bit for bit.  A block with C > 512 or C % 4 != 0 keeps
+ * the materialised route. */
+int dsd_set_vae_fused_attention(dsd_handle* h, int on);
 /* 0 if every parameter has been set, else -1 with the first missing name in dsd_last_error(). */
 int dsd_params_ready(dsd_handle* h);
 
@@ -605,7 +612,10 @@ enum { DSD_BLOCK_RES = 0, DSD_BLOCK_ATTN = 1, DSD_BLOCK_UPSAMPLE = 2, DSD_BLOCK_
        /* the plain single-stream UNetModel of ldm/modules/diffusionmodules/openaimodel.py:571-958: the
         * denoiser that consumes the VAE latents in the latent path; optionally with a SpatialTransformer on `context` in
         * every attention slot (use_spatial_transformer=True, :761-765,818-822,872-876) and with label_emb on y (:696-712) */
-       DSD_BLOCK_UNET = 13 };
+       DSD_BLOCK_UNET = 13,
+       /* the KL-VAE's AttnBlock alone (ldm/modules/diffusionmodules/model.py:185-209): one head over all channels; parameter
+        * names norm / q / k / v / proj_out.  Takes dsd_set_vae_fused_attention like the encoder and the decoder. */
+       DSD_BLOCK_VAE_ATTN = 14 };
 /* iargs by kind:
  *   RES: cin, cout, emb_ch, use_scale_shift_norm, up, down      ATTN: ch, heads, new_order
  *   UPSAMPLE/DOWNSAMPLE: ch     DISENTANGLE: ch, half_ch       SE: ch, reduction
@@ -616,6 +626,7 @@ enum { DSD_BLOCK_RES = 0, DSD_BLOCK_ATTN = 1, DSD_BLOCK_UPSAMPLE = 2, DSD_BLOCK_
  *        with_quant (1: AutoencoderKL.encode / decode incl. quant_conv / post_quant_conv, 0: bare Encoder / Decoder),
  *        len(ch_mult), ch_mult..., len(attn_resolutions), attn_resolutions...    (configs/autoencoder_kl_64x64x3.yaml:14-24)
  *        encoder: x [B,in_channels,H,W] -> moments [B,2*embed_dim,H/f,W/f];  decoder: z [B,embed_dim,h,w] -> [B,out_ch,h*f,w*f]
+ *   VAE_ATTN: in_channels
  *   DIT: input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_hidden, num_classes, learn_sigma,
  *        use_cfg_embedding.  x [B,in_channels,S,S] (x and cond already concatenated), aux = timesteps [B] fp32 (aux_len 1),
  *        aux2 = class labels [B] int64 or NULL (aux_len2 1 / 0); out [B, out_channels, S, S].  dsd_set_timestep_freqs
@@ -773,7 +784,10 @@ int dsd_op_qkv_attention(const float* qkv, int N, int T, int C, int heads, int n
 /* The fp32-grade attention kernels with every launch argument of AttnArgs (csrc/kernels.h): out[n,t,h*d + :] =
  * softmax((q scale_q)(k scale_k)^T scale_s) v per head.  q rows [N*Tq] of ldq floats with head h at +h*q_hs (k, v alike over
  * N*Tk rows), out rows of ldo floats with head h at +h*d.  Strides and pointers must keep rows 16-byte aligned.  split as in
- * dsd_op_qkv_attention. */
+ * dsd_op_qkv_attention.  d % 4 == 0 and d <= 512: up to 128 one wave owns a query's whole head (csrc/attention.hip, the kernels
+ * every network uses), above it the head dim is sliced across the four waves of a workgroup (csrc/attention_wide.hip: this entry
+ * and the KL-VAE's fused AttnBlock, dsd_set_vae_fused_attention); anything else is an error.  The networks' own attention slots
+ * (U-Net, SpatialTransformer, DiT) still stop at d = 128. */
 int dsd_op_attention(const float* q, const float* k, const float* v, int N, int Tq, int Tk, int heads, int d, int ldq, int ldk,
                      int ldv, int ldo, int q_hs, int k_hs, int v_hs, float scale_q, float scale_k, float scale_s, int split,
                      float* out, void* stream);
