@@ -1,8 +1,13 @@
 """CPU oracle of the DiT backbone — TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED: the reference's UNet_DS_Diff/DiT_models.py imports timm (PatchEmbed, Attention, Mlp), which is absent
-from the build image, so the reference itself could not be run to produce fixtures and holds no tests or golden vectors
-for this path.  This file restates DiT.forward (DiT_models.py:224-243) in torch-CPU fp32, with the three timm modules
+PINNED BY THE REFERENCE at whole-network level: tests/golden/dit.npz holds forwards, forward_with_cfg and a DDIM chain of the
+reference's own UNet_DS_Diff/DiT_models.py, run unchanged (tests/golden/gen_dit.py), and this file reproduces every one of
+them to the last bit (tests/test_pinned_cpu.py).  The reference imports timm (PatchEmbed, Attention, Mlp), absent from the
+build image; the generator serves that import from tests/golden/ref_standins.py, so the fixtures rest on the reference's code
+plus those three small modules, which are witnessed against nn.MultiheadAttention and F.unfold.  Still UNPINNED: the rounding
+places of the half-precision modes (``half=`` below; the reference would run torch.autocast on a GPU, and CPU autocast follows
+another op policy) and host_io.py's metrics.
+This file restates DiT.forward (DiT_models.py:224-243) in torch-CPU fp32, with the three timm modules
 written out from their published definition (timm 0.9, models/vision_transformer.py / layers/{patch_embed,mlp}.py):
   PatchEmbed   Conv2d(in, D, kernel = stride = p, bias) -> flatten(2).transpose(1, 2)            (norm_layer=None)
   Attention    qkv = Linear(D, 3D, bias); reshape(B, N, 3, heads, hd).permute(2, 0, 3, 1, 4); q * hd^-0.5;
@@ -69,7 +74,7 @@ def attention(sd, p, x, heads):                               # timm Attention.f
 def dit_forward(sd, x, t, y=None, *, patch_size, num_heads, out_channels, half=None):
     """half: None (fp32, the oracle proper) | torch.float16 | torch.bfloat16 — the latter two restate the NATIVE
     half-precision mode rounding for rounding (operands of the four Linears of a block and of the two attention products
-    rounded once, everything else fp32); parity of that mode with the reference's autocast is unpinned like the rest."""
+    rounded once, everything else fp32); parity of that mode with the reference's autocast is unpinned (the fp32 path is pinned)."""
     D = sd["pos_embed"].shape[-1]
     depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
     x = F.conv2d(x, sd["x_embedder.proj.weight"], sd["x_embedder.proj.bias"], stride=patch_size)   # PatchEmbed

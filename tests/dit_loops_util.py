@@ -1,9 +1,12 @@
 """Shared by tests/test_dit_loops_cpu.py and tests/test_dit_loops_gpu.py: the small DiT models, their inputs and the oracle
 chains of the DiT-under-the-device-loops tests.
 
-PARITY UNPINNED BY THE REFERENCE: DiT_models.py needs timm, absent from the image, so no reference-generated fixture exists;
-the network of every oracle chain here is oracle/dit.py (see tests/test_dit_gpu.py).  The samplers around it are the oracle's
-restatements of the reference loops (oracle/samplers.py, oracle/dpm.py)."""
+PINNED BY THE REFERENCE: the network of every oracle chain here is oracle/dit.py, which reproduces the reference's own DiT to
+the last bit on the fixtures of tests/golden/dit.npz (tests/test_pinned_cpu.py; M3 is the layout of that file's DDIM chain).
+Those fixtures are the reference's code plus tests/golden/ref_standins.py, three timm modules (timm is absent from the image)
+witnessed against nn.MultiheadAttention and F.unfold.  The samplers around the network are the oracle's restatements of the
+reference loops (oracle/samplers.py, oracle/dpm.py).  Still unpinned: the half-precision modes' rounding places and
+host_io.py's metrics."""
 import functools
 
 import numpy as np

@@ -17,9 +17,11 @@ the DDPM buffers, as gen_latent_ldm.py does for 'concat' (ddpm.py itself does no
 the network's input is the state alone, so the chain's network is the class-table one with in_channels = out_channels = 4; the
 three forward cases keep in_channels = 6.
 
-MODEL-LEVEL PARITY OF 'crossattn' / 'hybrid' IS UNPINNED: the reference's constructor imports omegaconf for
-use_spatial_transformer=True (openaimodel.py:640), which is absent here, so no fixture of that branch can be generated; its
-blocks are pinned by xattn.npz and the composition is checked against the oracle (tests/test_cond_keys_gpu.py).
+MODEL-LEVEL PARITY OF 'crossattn' / 'hybrid' IS PINNED ELSEWHERE: the reference's constructor imports omegaconf for
+use_spatial_transformer=True (openaimodel.py:640), which is absent here, so this generator holds no fixture of that branch;
+gen_unet_xattn.py runs it through an empty ListConfig stand-in (ref_standins.py, witnessed in tests/test_pinned_cpu.py) and
+stores forwards and DDIM chains of those networks in unet_xattn.npz.  Still unpinned in the project: the half-precision modes'
+rounding places and host_io.py's metrics.
 Weights are not stored: (names, shapes, seed) only; inputs come from seeds.
 """
 import json

@@ -220,7 +220,7 @@ KEYS = ("total_bpd", "prior_bpd", "vb", "xstart_mse", "mse")
 def test_device_loop_against_the_reference_and_the_per_step_path(fx, name):
     """The device loop returns the reference's keys and shapes, equals the per-step path bit for bit with fed and with Philox
     noise, leaves x_start untouched, and lies within 5x max(op bar, recorded 3e-6-noise movement) of every scalar the reference
-    recorded (the DiT's network is the restated one: its parity stays unpinned, as everywhere)."""
+    recorded (the DiT's network is the restated one, oracle/dit.py, pinned on the reference's own DiT by tests/golden/dit.npz)."""
     g, tab, bars = fx
     _, _, x_start, _, z = loop_env(name)
     keep = x_start.clone()

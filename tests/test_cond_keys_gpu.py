@@ -3,9 +3,12 @@ fixture (tests/golden/cond_keys.npz), context and y together against the oracle,
 bit for bit against a per-step loop over DiffusionWrapper.forward and the dsd_op_* updates, guidance with an unconditional
 context, chains against the reference and the oracle, the rejections, and the clearing of the bundle.
 
-MODEL-LEVEL PARITY OF 'crossattn' / 'hybrid' IS UNPINNED BY THE REFERENCE: its constructor imports omegaconf for
-use_spatial_transformer=True, absent here (see tests/golden/gen_cond_keys.py); those networks are compared with the oracle, whose
-blocks are pinned by tests/golden/xattn.npz and whose label_emb lines are pinned by tests/test_cond_keys_cpu.py."""
+MODEL-LEVEL PARITY OF 'crossattn' / 'hybrid' / 'crossattn-adm' / 'hybrid-adm' IS PINNED BY THE REFERENCE: forwards of the six
+models below and DDIM chains of 'crossattn' and 'hybrid', unguided and guided, come from the reference's own UNetModel and
+DDIMSampler (tests/golden/unet_xattn.npz: gen_unet_xattn.py).  The reference's constructor imports omegaconf for
+use_spatial_transformer=True, absent here; tests/golden/ref_standins.py serves that import with an empty ListConfig class
+(witnessed, with the three timm modules of the DiT fixtures, in tests/test_pinned_cpu.py), nothing else stands in.  Still
+unpinned in the project: the rounding places of the DiT's half-precision modes and host_io.py's metrics."""
 import ctypes as C
 import json
 
@@ -14,6 +17,7 @@ import pytest
 import torch
 
 import cond_keys_util as U
+import pinned_util as P
 from oracle import samplers as OS
 from oracle.synth import synth_params
 from util import fixture_params, golden, randn, rel_l2
@@ -382,6 +386,50 @@ def test_adm_ddim_chain_against_the_reference():
     other, _ = DDIMSampler(m).sample(int(g["adm_steps"]), 2, tuple(xT.shape[1:]), dict(c_crossattn=[(labels + 1) % 7]), eta=0.0,
                                      verbose=False, x_T=xT)
     assert rel_l2(other, g["adm_ddim_y"]) > 1e-3
+
+
+def _fixture_weights_are_the_env(e):
+    """unet_xattn.npz regenerates its weights from the reference's (names, shapes) and cond_keys_util.WEIGHT_SEED: the tensors
+    env() drew from the native parameter table in its order, or the fixture would describe another network."""
+    sd = fixture_params(P.fixture("unet_xattn"), e["name"])
+    assert sorted(sd) == sorted(e["sd"]) and all(torch.equal(sd[k], e["sd"][k]) for k in sd), e["name"]
+
+
+@pytest.mark.parametrize("name", sorted(U.MODELS))
+def test_forward_of_every_model_against_the_reference(name):
+    """DiffusionWrapper.forward over the six networks against the reference's own UNetModel under the same dispatch, at integer
+    and at fractional timesteps; crossattn5 on its 5x5 state, the three label_emb forms beside a context."""
+    e = env(name)
+    _fixture_weights_are_the_env(e)
+    params, _, x, c, runs = P.cond_case(name)
+    assert params == e["params"]
+    for tag, t, want in runs:
+        got = e["wrap"](x.cuda(), t.cuda(), **U.to_cuda(c))
+        err = rel_l2(got, want)
+        print(f"{name} t {tag}: rel-L2 vs the reference UNetModel {err:.3e} (bar 5e-6)")
+        assert got.shape == want.shape and err < 5e-6, (name, tag, err)
+
+
+@pytest.mark.parametrize("name", ["crossattn", "hybrid"])
+def test_ddim_chains_against_the_reference(name):
+    """The reference's own DDIMSampler over its UNetModel, 4 steps, eta 0.5, fed noise: the device loop unguided, and guided at
+    3.0 through the dsd_guidance bundle against another conditioning (context and, for 'hybrid', c_concat), at the bar
+    tests/test_latent_ldm_gpu.py holds its 'concat' chains to against latent_ldm.npz."""
+    g = P.fixture("unet_xattn")
+    e = env(name)
+    _fixture_weights_are_the_env(e)
+    x_T, c, u, z, steps, eta, scale = P.chain_inputs(name)
+    x_T, c, u, z = x_T.cuda(), U.to_cuda(c), U.to_cuda(u), z.cuda()
+    shape = tuple(x_T.shape[1:])
+    out = {}
+    for tag, kw in (("plain", {}), ("guided", dict(unconditional_guidance_scale=scale, unconditional_conditioning=u))):
+        y, _ = ddim_sampler(e, steps, eta).sample(steps, 2, shape, c, eta=eta, verbose=False, x_T=x_T, step_noise=z, **kw)
+        want = g[f"{name}_chain_{tag}_y"]
+        err = rel_l2(y, want)
+        print(f"'{name}' {steps}-step DDIM chain, {tag}: rel-L2 vs reference {err:.3e} (bar {TOL:g})")
+        assert y.shape == want.shape and err < TOL, (name, tag, err)
+        out[tag] = y
+    assert rel_l2(out["guided"], out["plain"]) > 1e-2
 
 
 def test_hybrid_ddim_chain_against_the_oracle():

@@ -2,8 +2,11 @@
 fp32 operation order of the multi-channel learned-range update, the stubs' refusals, and the conditioning of the oracle chains
 tests/test_dit_loops_gpu.py holds the device loops to.
 
-PARITY UNPINNED BY THE REFERENCE: DiT_models.py needs timm, absent from the image, so the network of every chain is
-oracle/dit.py (see tests/test_dit_gpu.py); the sampler arithmetic is pinned by oracle/samplers.py as everywhere else."""
+PINNED BY THE REFERENCE: the network of every chain is oracle/dit.py, equal to the last bit to the reference's own DiT on the
+fixtures of tests/golden/dit.npz (tests/test_pinned_cpu.py), which rest on the reference's code and on the three timm modules
+of tests/golden/ref_standins.py (timm is absent from the image; witnessed against nn.MultiheadAttention and F.unfold); the
+sampler arithmetic is pinned by oracle/samplers.py as everywhere else.  Still unpinned: the half-precision modes' rounding
+places and host_io.py's metrics."""
 import numpy as np
 import pytest
 import torch

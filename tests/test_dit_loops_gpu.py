@@ -3,10 +3,13 @@ bit for bit what a per-step loop over dsd_block_forward and the per-step ops com
 replay, first_step / n_steps segments, slice-keyed Philox noise; guidance, masks, PLMS and DDIM encode / decode through the
 reference's sampler classes; the rejections.
 
-PARITY UNPINNED BY THE REFERENCE: DiT_models.py needs timm, absent from the image, so no reference-generated fixture exists
-and the network of every oracle chain is oracle/dit.py (see tests/test_dit_gpu.py).  The sampler arithmetic around it is the
-oracle's restatement of the reference loops (oracle/samplers.py, oracle/dpm.py), held to the project's 1e-4 chain bar; the
-chains' conditioning is guarded in tests/test_dit_loops_cpu.py."""
+PINNED BY THE REFERENCE: the network of every oracle chain is oracle/dit.py, which equals the reference's own DiT to the last
+bit on the fixtures of tests/golden/dit.npz (tests/test_pinned_cpu.py), and one chain of that file — the reference's DDIMSampler
+over the reference DiT of M3 — is run here on the device loop.  The fixtures rest on the reference's code and on
+tests/golden/ref_standins.py: three timm modules (PatchEmbed, Attention, Mlp; timm is absent from the image), witnessed against
+nn.MultiheadAttention and F.unfold.  The sampler arithmetic is the oracle's restatement of the reference loops
+(oracle/samplers.py, oracle/dpm.py), held to the project's 1e-4 chain bar; the chains' conditioning is guarded in
+tests/test_dit_loops_cpu.py.  Still unpinned: the rounding places of the half-precision modes and host_io.py's metrics."""
 import ctypes as C
 import json
 
@@ -295,6 +298,36 @@ def test_chains_against_the_oracle(name, kind):
     err = rel_l2(got, U.oracle_chain_cached(name, kind))
     print(f"{name} {kind}: {U.CHAIN_STEPS}-step chain rel-L2 vs oracle {err:.3e}")
     assert err <= TOL
+
+
+def test_ddim_chain_against_the_reference():
+    """tests/golden/dit.npz: the reference's own DDIMSampler (ldm/models/diffusion/ddim.py) over the reference's own DiT in the
+    layout of M3, 4 steps, eta 0 and eta 0.5 with fed noise, at the bar tests/test_latent_ldm_gpu.py holds its chains to.  The
+    weights are the fixture's; M3's own come back afterwards."""
+    import pinned_util as P
+    from util import fixture_params
+    g = P.fixture("dit")
+    kw = P.cfg_of(g, "chain")
+    assert kw == U.MODELS["M3"][0]
+    e = env("M3")
+    steps = int(g["chain_steps"])
+    xT = randn((2, 3, 16, 16), int(g["chain_xT_seed"])).cuda()
+    none = torch.zeros((2, 0, 16, 16), device="cuda")                  # M3 takes no conditioning
+    e["unet"].load_state_dict(fixture_params(g, "chain"), strict=True)
+    try:
+        out = {}
+        for key in ("chain_eta0", "chain_eta05"):
+            eta = float(g[key + "_eta"])
+            z = randn((steps,) + tuple(xT.shape), int(g[key + "_noise_seed"])).cuda()
+            y, _ = ddim_sampler(e, steps, eta).sample(steps, 2, tuple(xT.shape[1:]), [none], eta=eta, verbose=False, x_T=xT,
+                                                      step_noise=z)
+            err = rel_l2(y, g[key + "_y"])
+            print(f"M3 {key}: {steps}-step DDIM chain rel-L2 vs reference {err:.3e}")
+            assert y.shape == g[key + "_y"].shape and err <= TOL, (key, err)
+            out[key] = y
+        assert rel_l2(out["chain_eta05"], out["chain_eta0"]) > 1e-2
+    finally:
+        e["unet"].load_state_dict(U.weights("M3"), strict=True)
 
 
 # ---------------------------------------------------------------------------------------- 4. loop properties

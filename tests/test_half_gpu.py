@@ -5,13 +5,20 @@ in those modes.
 The kernel checks compare with float64 arithmetic on THE SAME 16-bit-rounded operands, so the bars are those of the kernel
 (fp32 accumulation order, one rounding of the result): 1.5 ulp of the 16-bit type per element, and a few 1e-4 rel-L2.
 The network checks compare with oracle/dit.py twice: with its restatement of the mode's roundings (tight) and with the fp32
-oracle (the mode's own accuracy, an autocast-grade bar written in the test).  PARITY UNPINNED BY THE REFERENCE for all of
-this: DiT_models.py needs timm (absent), and torch.autocast on a GPU is what the reference would run."""
+oracle (the mode's own accuracy, an autocast-grade bar written in the test), and at that second bar with the reference's own
+fp32 DiT as well (tests/golden/dit.npz: gen_dit.py).
+
+The fp32 network these modes approximate is PINNED BY THE REFERENCE: dit.npz is the reference's own DiT_models.py, run unchanged
+except for three timm modules (PatchEmbed, Attention, Mlp; timm is absent from the image) that tests/golden/ref_standins.py
+writes out and tests/test_pinned_cpu.py witnesses against nn.MultiheadAttention and F.unfold.  THE ROUNDING PLACES OF THE HALF
+MODES STAY UNPINNED: torch.autocast on a GPU is what the reference would run and it cannot run here; CPU autocast follows another
+op policy (it does not promote softmax), so a fixture from it would pin the wrong thing.  host_io.py's metrics are unpinned too."""
 import math
 
 import pytest
 import torch
 
+import pinned_util as P
 from oracle import dit as OD
 from oracle.synth import synth_params
 from util import rel_l2, randn
@@ -157,6 +164,26 @@ def test_dit_half_modes_vs_oracle(kw, labels):
         assert torch.equal(got, m(x.cuda(), t.cuda(), None if y is None else y.cuda(), cond=cond.cuda()))   # deterministic
     m.set_precision("bf16x6")
     assert rel_l2(m(x.cuda(), t.cuda(), None if y is None else y.cuda(), cond=cond.cuda()), full) < 1e-5   # and back
+
+
+@pytest.mark.parametrize("key", ["d64", "d96", "d768", "d144"])
+def test_dit_half_modes_vs_reference(key):
+    """The same modes against the reference's own fp32 DiT (tests/golden/dit.npz) at the bar32 of
+    test_dit_half_modes_vs_oracle, 2e-4 (fp16) / 1.5e-3 (bf16): the oracle equals the reference to the last bit on these
+    networks (tests/test_pinned_cpu.py), so the bar's derivation carries over.  d64, d96, d144: the configurations above with the
+    fixture's weights and inputs; d768: the same DiT-B blocks on 16 tokens."""
+    from diffusion_models_dsdiff_amd.UNet_DS_Diff.DiT_models import DiT
+    kw, sd, x, cond, y, runs = P.dit_case(key)
+    m = DiT(**kw)
+    m.load_state_dict(sd, strict=True)
+    dev = lambda v: None if v is None else v.cuda()
+    for prec, bar32 in (("f16", 2e-4), ("bf16", 1.5e-3)):
+        m.set_precision(prec)
+        for tag, t, want in runs:
+            got = m(dev(x), dev(t), dev(y), cond=dev(cond))
+            err = rel_l2(got, want)
+            print(f"{key} t {tag} {prec}: vs the reference's fp32 DiT {err:.3e} (bar {bar32:g})")
+            assert got.shape == want.shape and bool(torch.isfinite(got).all()) and err < bar32, (key, tag, prec, err)
 
 
 def test_dit_b8_at_512_half():
