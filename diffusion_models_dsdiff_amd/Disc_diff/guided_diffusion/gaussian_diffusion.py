@@ -17,7 +17,7 @@ import numpy as np
 import torch as th
 
 from ... import _lib
-from ..._sched import (Schedule, ddim_reverse_step, is_dit, kwargs_conditioning, loop_denoiser, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
+from ..._sched import (Schedule, ddim_reverse_step, disc_planes, is_disc, is_dit, kwargs_conditioning, loop_denoiser, model_output_of, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
                        run_device_loop, sampler_update, vlb_terms, _seed_from_torch)
 
 
@@ -148,7 +148,10 @@ class GaussianDiffusion:
         if hooks and unet is not None:
             # a Python hook sits between network and update: per-step host loop; a bare native U-Net does not concatenate
             # c_concat itself (DiffusionWrapper.forward does, ddpm.py:1328-1333)
-            if unet is model:
+            if unet is model and is_disc(unet):
+                if "c_concat" in model_kwargs:               # (t1 / t2 / dwi are concatenated by the loop below, as :271-275)
+                    model = lambda x, t, _u=unet, **kw: _u(th.cat([x] + [c.to(x.device) for c in kw["c_concat"]], 1), t)
+            elif unet is model:
                 model = lambda x, t, _u=unet, **kw: _u(th.cat([x] + [c.to(x.device) for c in kw.get("c_concat", [])], 1), t,
                                                        context=kw.get("context"), y=kw.get("y"))
             unet = None
@@ -158,6 +161,9 @@ class GaussianDiffusion:
                 device = th.device("cuda")
         img = noise if noise is not None else th.randn(*shape, device=device)      # :591-594
         img = img.to(device)
+        planes = disc_planes(model_kwargs, device)               # t1 / t2 / dwi: concatenated behind x (:271-275)
+        if unet is not None and is_disc(unet) and planes is not None:
+            return run_device_loop(unet, sched, img, th.cat(planes, 1), step_noise=step_noise, seed=seed)
         bundle = kwargs_conditioning(unet, model, model_kwargs, device) if unet is not None and not is_dit(unet) else None
         if bundle is not None:                                # context= / y= (or c_crossattn / c_adm) for a UNetModel
             return run_device_loop(unet, sched, img, bundle, step_noise=step_noise, seed=seed)
@@ -177,9 +183,7 @@ class GaussianDiffusion:
             is_int = (not self.rescale_timesteps) and float(tv) == int(tv)
             t = th.full((B,), int(tv) if is_int else float(tv), device=device,
                         dtype=th.long if is_int else th.float32)
-            out = model(x, t, **model_kwargs)
-            if isinstance(out, tuple):
-                out = out[0]
+            out = model_output_of(model(x if planes is None else th.cat([x] + planes, 1), t, **model_kwargs))
             self._hooked_update(sched, k, out, x, t, None if step_noise is None else step_noise[k].to(device), seed,
                                 denoised_fn, cond_fn, model_kwargs)
         return x
@@ -314,8 +318,8 @@ class GaussianDiffusion:
         tv = th.from_numpy(self._model_timestep_values()).to(x.device)[t]
         if not self.rescale_timesteps:
             tv = tv.long()
-        out = model(x, tv, **model_kwargs)
-        return out[0] if isinstance(out, tuple) else out
+        planes = disc_planes(model_kwargs, x.device)             # :271-275
+        return model_output_of(model(x if planes is None else th.cat([x] + planes, 1), tv, **model_kwargs))
 
     def _single(self, ddim, model, x, t, clip_denoised, model_kwargs, eta, denoised_fn=None, cond_fn=None):
         model_kwargs = model_kwargs or {}
@@ -448,6 +452,9 @@ class GaussianDiffusion:
         unet = loop_denoiser(model, model_kwargs)
         bundle = kwargs_conditioning(unet, model, model_kwargs, device) if unet is not None and not is_dit(unet) else None
         c_concat = model_kwargs.get("c_concat")
+        planes = disc_planes(model_kwargs, device)               # t1 / t2 / dwi: the three condition planes of UNet_disc_Model
+        if unet is not None and is_disc(unet) and planes is not None:
+            c_concat = planes
         if unet is not None and c_concat is None and is_dit(unet):
             c_concat = [xs.new_zeros((xs.shape[0], 0) + tuple(xs.shape[2:]))]
         if unet is not None and (c_concat is not None or bundle is not None):
@@ -467,9 +474,7 @@ class GaussianDiffusion:
                 tv = tvals[k]
                 is_int = (not self.rescale_timesteps) and float(tv) == int(tv)
                 t = th.full((B,), int(tv) if is_int else float(tv), device=device, dtype=th.long if is_int else th.float32)
-                out = model(x_t, t, **model_kwargs)
-                if isinstance(out, tuple):
-                    out = out[0]
+                out = model_output_of(model(x_t if planes is None else th.cat([x_t] + planes, 1), t, **model_kwargs))
                 vlb_terms(sched, k, float(plv[k]), out, x_t, xs, z, seed, vb=res["vb"][:, k], xstart_mse=res["xstart_mse"][:, k],
                           mse=res["mse"][:, k])
         res["total_bpd"] = res["vb"].sum(dim=1) + res["prior_bpd"]             # :984

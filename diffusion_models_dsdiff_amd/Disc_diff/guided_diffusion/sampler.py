@@ -24,7 +24,7 @@ import torch
 from ..._lib import (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3, DPM_SS_S1, DPM_SS_S2, DPM_SS_T2, DPM_SS_T3, DPM_SS_T3_TAYLOR, DSD_DPM_NCOEF,
                       DSD_NCOEF, DsdDpmProgram, DsdDpmSchedule, check, dptr, lib, stream_ptr)
 from ..._sched import (Conditioning, Guidance, cat_conditioning, cat_unconditional, check_latent_io, concat_of, conditioning_set,
-                       is_dit, is_latent_denoiser, kwargs_conditioning, loop_denoiser, wrapper_key)
+                       is_dit, is_latent_denoiser, kwargs_conditioning, loop_denoiser, model_output_of, wrapper_key)
 
 _PRED = {"noise": 0, "x_start": 1, "v": 2}
 
@@ -120,9 +120,7 @@ class _ModelFn:
             out = self.model(x, t_input, **self.model_kwargs)
         else:
             out = self.model(x, t_input, self.condition, **self.model_kwargs)
-        if isinstance(out, tuple):
-            out = out[0]
-        return out
+        return model_output_of(out)
 
     def bundle(self, unet, device):
         """The Conditioning of a UNetModel denoiser where the condition (or model_kwargs) carries more than ``c_concat``: the

@@ -40,6 +40,7 @@ EXPORTS = [
     "dsd_sample_dpm_program", "dsd_sample_dpm_program_latent", "dsd_op_dpm_eval",
     "dsd_set_conditioning",
     "dsd_calc_bpd", "dsd_calc_bpd_latent", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
+    "dsd_create_disc", "dsd_op_disc_bottleneck",
 ]
 
 
@@ -254,6 +255,10 @@ def lib() -> C.CDLL:
                                    f32p, i32, i32, i32, i32, vp]
     L.dsd_op_prior_bpd.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_ddim_reverse_step.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, i32, i32, i32, i32, vp]
+    if hasattr(L, "dsd_create_disc"):          # (likewise absent from an older build under DSD_LIBRARY)
+        L.dsd_create_disc.argtypes = [C.POINTER(DsdConfig), i32, C.POINTER(vp)]
+        L.dsd_op_disc_bottleneck.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, f32p,
+                                             C.POINTER(vp), i32, vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     _lib = L

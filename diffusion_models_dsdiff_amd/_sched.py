@@ -318,7 +318,8 @@ def find_unet(model):
     from .UNet_DS_Diff.DiT_models import DiT
     from .UNet_DS_Diff.model import DSUnetModel
     from .ldm.modules.diffusionmodules.openaimodel import UNetModel
-    kinds = (DSUnetModel, UNetModel, DiT)
+    from .Disc_diff.guided_diffusion.unet import UNet_disc_Model
+    kinds = (DSUnetModel, UNetModel, DiT, UNet_disc_Model)
     if isinstance(model, kinds):
         return model
     inner = getattr(model, "diffusion_model", None)
@@ -338,7 +339,39 @@ def loop_denoiser(model, model_kwargs=None):
     unet = find_unet(model)
     if unet is not None and is_dit(unet) and set(model_kwargs or {}) - {"c_concat"}:
         return None
+    if unet is not None and is_disc(unet) and disc_planes(model_kwargs) is not None:
+        from .Disc_diff.guided_diffusion.unet import SuperResModelNew
+        if unet is model and not isinstance(unet, SuperResModelNew):
+            # the reference calls model(x_input, t, **model_kwargs): UNet_disc_Model.forward takes no keywords (unet.py:985)
+            raise TypeError("UNet_disc_Model.forward() got an unexpected keyword argument 't1' (only SuperResModelNew takes and "
+                            "ignores the t1 / t2 / dwi of model_kwargs)")
     return unet
+
+
+def is_disc(unet) -> bool:
+    """The four-stream DisC-Diff denoiser (UNet_disc_Model / SuperResModelNew): a one-channel state beside t1, t2, dwi."""
+    from .Disc_diff.guided_diffusion.unet import UNet_disc_Model
+    return isinstance(unet, UNet_disc_Model)
+
+
+DISC_KEYS = ("t1", "t2", "dwi")
+
+
+def disc_planes(model_kwargs, device=None):
+    """[t1, t2, dwi] of a ``model_kwargs`` dict in the order p_mean_variance concatenates them behind x
+    (Disc_diff/guided_diffusion/gaussian_diffusion.py:271-275), or None where ``t1`` is absent."""
+    kw = model_kwargs or {}
+    if kw.get("t1") is None:
+        return None
+    return [kw[k] if device is None else kw[k].to(device) for k in DISC_KEYS]
+
+
+def model_output_of(out):
+    """The tensor a sampler reads of what a network returned: the ninth element of UNet_disc_Model's 9-tuple
+    (gaussian_diffusion.py:277-278), the first of any other tuple (DSUnetModel's (out, dict))."""
+    if isinstance(out, tuple):
+        return out[8] if len(out) == 9 else out[0]
+    return out
 
 
 def is_dit(unet) -> bool:

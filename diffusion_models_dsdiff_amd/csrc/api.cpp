@@ -131,6 +131,28 @@ int dsd_create(const dsd_config* cfg, int device, dsd_handle** out) {
     DSD_CATCH
 }
 
+int dsd_create_disc(const dsd_config* cfg, int device, dsd_handle** out) {
+    DSD_TRY
+    DSD_CHECK(cfg && out, "null argument");
+    set_device(device);
+    auto* h = new dsd_handle();
+    h->device = device;
+    h->is_disc = true;
+    h->cfg = *cfg;
+    // UNet_disc_Model has only the openai-style AttentionBlock(num_heads, num_head_channels): the head rule the spec builder
+    // applies under `legacy` (heads = the argument, or channels / num_head_channels), decoder heads from num_heads_upsample
+    h->cfg.legacy = 1;
+    try {
+        net_declare_params(h);
+    } catch (...) {
+        net_free(h);
+        delete h;
+        throw;
+    }
+    *out = h;
+    DSD_CATCH
+}
+
 int dsd_block_create(int kind, const int32_t* iargs, int n_iargs, int device, dsd_handle** out) {
     DSD_TRY
     DSD_CHECK(out && (iargs || n_iargs == 0), "null argument");
@@ -218,6 +240,7 @@ int dsd_get_precision(dsd_handle* h) { return h ? h->precision : -1; }
 int dsd_set_share_zero_streams(dsd_handle* h, int on) {
     DSD_TRY
     DSD_CHECK(h && !h->is_block, "needs a model handle");
+    DSD_CHECK(!(h->is_disc && on), "UNet_disc_Model has no zero streams to share: all four encoder streams (x, T1, T2, DWI) are live");
     h->share_zero_streams = on != 0;
     DSD_CATCH
 }
@@ -234,6 +257,7 @@ int dsd_plan(dsd_handle* h, int B, int C, int H, int W) {
     DSD_CHECK(h && !h->is_block, "dsd_plan needs a model handle");
     set_device(h->device);
     DSD_CHECK(C == 2 || C == 4, "x must have 2 or 4 channels, got %d", C);
+    DSD_CHECK(!h->is_disc || C == 4, "UNet_disc_Model takes 4 channels (x, T1, T2, DWI), got %d", C);
     net_plan(h, B, C, H, W, C == 2, 0, 0, 0);
     DSD_CATCH
 }
@@ -345,6 +369,7 @@ int dsd_forward(dsd_handle* h, const float* x, const void* t, int t_is_float, in
                 float* const* feats, void* stream) {
     DSD_TRY
     DSD_CHECK(h && !h->is_block && x && t && out, "null argument");
+    DSD_CHECK(!h->is_disc || C == 4, "UNet_disc_Model takes 4 channels (x, T1, T2, DWI), got %d", C);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
     net_plan(h, B, C, H, W, C == 2, feats != nullptr, 0, 0, 0, s);
@@ -486,6 +511,8 @@ void check_slice_ids(const dsd_handle* h, int B) {
 // the four-stream denoiser (DSUnetModel): a one-channel state beside 1 or 3 condition planes
 void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x, int B, int H, int W) {
     DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+    DSD_CHECK(!h->is_disc || Cc == 3, "UNet_disc_Model takes 3 condition planes (t1, t2, dwi) behind the state, got Cc = %d (%d input channels, 4 needed)",
+              Cc, Cc + 1);
     DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
     DSD_CHECK(B >= 1 && H >= 1 && W >= 1, "bad shape: B %d H %d W %d", B, H, W);
     check_slice_ids(h, B);
@@ -1725,6 +1752,33 @@ int dsd_op_avg_into_stats(const float* a, const float* b, const float* c, const 
     DSD_CHECK(partial_doubles >= (int64_t)N * *nchunk * C * 2, "avg_into_stats: the statistics buffer holds %lld doubles, %d chunks need %lld",
               (long long)partial_doubles, *nchunk, (long long)N * *nchunk * C * 2);
     avg_into_stats(a, b, c, d, div, N, HW, C, dst, dstC, coff, act, bmask, partial, *nchunk, s);
+    DSD_HIP(hipStreamSynchronize(s));
+    DSD_CATCH
+}
+
+int dsd_op_disc_bottleneck(const float* const* com, const float* const* dist, const float* const* w1, const float* const* w2,
+                           int B, int HW, int half, int Cr, float* cat, float* const* feats, int unfused, void* stream) {
+    DSD_TRY
+    hipStream_t s = (hipStream_t)stream;
+    DSD_CHECK(com && dist && w1 && w2 && cat, "disc_bottleneck: null argument");
+    DSD_CHECK(B >= 1 && HW >= 1 && half >= 4 && Cr >= 1, "disc_bottleneck: bad shape (B %d, HW %d, half %d, Cr %d)", B, HW, half, Cr);
+    DSD_CHECK(half % 4 == 0, "disc_bottleneck: half = %d is not a multiple of 4 (the kernels move 16 bytes per access)", half);
+    DiscArgs a;
+    a.B = B; a.HW = HW; a.half = half; a.Cr = Cr; a.cat = cat;
+    for (int i = 0; i < 4; ++i) { a.com[i] = com[i]; a.dist[i] = dist[i]; }
+    for (int i = 0; i < 5; ++i) { a.w1[i] = w1[i]; a.w2[i] = w2[i]; }
+    if (feats)
+        for (int i = 0; i < 8; ++i) a.feat[i] = feats[i];
+    for (int i = 0; i < 4; ++i)
+        DSD_CHECK(a.com[i] && a.dist[i] && reinterpret_cast<uintptr_t>(a.com[i]) % 16 == 0 && reinterpret_cast<uintptr_t>(a.dist[i]) % 16 == 0,
+                  "disc_bottleneck: inputs must be non-null and 16-byte aligned");
+    DSD_CHECK(reinterpret_cast<uintptr_t>(cat) % 16 == 0, "disc_bottleneck: cat must be 16-byte aligned");
+    for (int i = 0; i < 8; ++i)
+        DSD_CHECK(!feats || (a.feat[i] && reinterpret_cast<uintptr_t>(a.feat[i]) % 16 == 0), "disc_bottleneck: feature outputs must be non-null and 16-byte aligned");
+    const bool uf = unfused < 0 ? disc_unfused_env() : unfused != 0;
+    Tmp scratch(disc_scratch_bytes(B, HW, half, uf));
+    a.scratch = scratch.p;
+    if (uf) disc_bottleneck_unfused(a, s); else disc_bottleneck(a, s);
     DSD_HIP(hipStreamSynchronize(s));
     DSD_CATCH
 }

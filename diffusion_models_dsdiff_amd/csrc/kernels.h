@@ -237,6 +237,27 @@ void embed_add(const float* a, const float* table, const long long* idx, int N, 
 void softmax_rows(float* s, int64_t rows, int cols, float scale, hipStream_t st);
 void add2(const float* a, const float* b, int64_t n, float* y, hipStream_t s);
 
+// ---------------------------------------------------------------- disc.hip
+// Bottleneck head of UNet_disc_Model (Disc_diff/guided_diffusion/unet.py:1015-1033).  com / dist: the PRE-activation outputs of
+// conv_common / conv_distinct on the four streams, NHWC [B][HW][half]; w1[k] [Cr][half] / w2[k] [half][Cr]: the SE linears of
+// SE_Attention_com (k = 0) and SE_Attention_dist_1..4; cat [B][HW][5*half] = [SE_com(mean_i SiLU(com_i)), SE_dist_i(SiLU(dist_i))];
+// feat (all eight or none), NHWC [B][HW][half]: SiLU(com_i) and the four scaled dist_i — the first eight values the forward returns.
+struct DiscArgs {
+    const float* com[4] = {};
+    const float* dist[4] = {};
+    const float* w1[5] = {};
+    const float* w2[5] = {};
+    int B = 0, HW = 0, half = 0, Cr = 0;
+    float* cat = nullptr;
+    float* feat[8] = {};
+    void* scratch = nullptr;   // disc_scratch_bytes(B, HW, half, unfused) bytes
+};
+int disc_nchunks(int HW);
+size_t disc_scratch_bytes(int B, int HW, int half, bool unfused);
+bool disc_unfused_env();                                       // DSD_DISC_UNFUSED set (and not "0"), read at every call
+void disc_bottleneck(const DiscArgs& a, hipStream_t s);          // three launches: pool, gate, scale
+void disc_bottleneck_unfused(const DiscArgs& a, hipStream_t s);  // avg_into / se_scale / concat copies (A/B, cross-check)
+
 // ---------------------------------------------------------------- sampler.hip
 struct StepCoef {
     float c[8];

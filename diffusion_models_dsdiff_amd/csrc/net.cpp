@@ -487,8 +487,45 @@ int* dsd_handle::ensure_ovf() {
     return ovf;
 }
 
+// UNet_disc_Model (Disc_diff/guided_diffusion/unet.py:754-967): names, shapes and order of its state_dict
+static void p_disc(dsd_handle* h) {
+    const dsd_config& c = h->cfg;
+    DSD_CHECK(c.n_levels >= 1 && c.n_levels <= DSD_MAX_LEVELS, "channel_mult must have 1..%d entries", DSD_MAX_LEVELS);
+    DSD_CHECK(c.channel_mult[0] == 1, "UNet_disc_Model: channel_mult[0] = %d; the decoder ends at int(model_channels * channel_mult[0]) "
+              "channels but out.2 reads model_channels (unet.py:802,966), so only 1 builds a network", c.channel_mult[0]);
+    const Spec s = build_spec(c);
+    DSD_CHECK(s.conv_ch % 2 == 0 && s.half % 4 == 0 && s.half >= 8,
+              "UNet_disc_Model: the bottleneck halves have %d channels; the head kernels move 16 bytes per access (multiples of 4) "
+              "and SE_Attention(reduction=8) needs at least 8", s.half);
+    const bool film = c.use_scale_shift_norm;
+    p_lin(h, "time_embed.0", c.model_channels, s.ted);
+    p_lin(h, "time_embed.2", s.ted, s.ted);
+    auto encoder = [&](const char* sfx) {
+        for (size_t bi = 0; bi < s.input_blocks.size(); ++bi)
+            for (size_t li = 0; li < s.input_blocks[bi].size(); ++li)
+                p_layer(h, "input_blocks" + std::string(sfx) + "." + std::to_string(bi) + "." + std::to_string(li), s.input_blocks[bi][li], s.ted, film);
+    };
+    encoder("");
+    for (size_t li = 0; li < s.middle.size(); ++li) p_layer(h, "middle_block." + std::to_string(li), s.middle[li], s.ted, film);
+    for (size_t bi = 0; bi < s.output_blocks.size(); ++bi)
+        for (size_t li = 0; li < s.output_blocks[bi].size(); ++li)
+            p_layer(h, "output_blocks." + std::to_string(bi) + "." + std::to_string(li), s.output_blocks[bi][li], s.ted, film);
+    for (const char* sfx : {"_T1", "_T2", "_DWI"}) encoder(sfx);
+    for (const char* nm : {"SE_Attention_com", "SE_Attention_dist_1", "SE_Attention_dist_2", "SE_Attention_dist_3", "SE_Attention_dist_4"}) {
+        p_lin(h, std::string(nm) + ".se.0", s.half, s.half / 8, false);
+        p_lin(h, std::string(nm) + ".se.2", s.half / 8, s.half, false);
+    }
+    p_conv(h, "dim_reduction_non_zeros.0", (int)(2.5 * s.conv_ch), s.conv_ch, 1);
+    p_conv(h, "conv_common.0", s.conv_ch, s.half, 3);
+    p_conv(h, "conv_distinct.0", s.conv_ch, s.half, 3);
+    p_norm(h, "out.0", s.final_ch);
+    p_conv(h, "out.2", c.model_channels, c.out_channels, 3);
+}
+
 void dsd::net_declare_params(dsd_handle* h) {
-    if (!h->is_block) {
+    if (h->is_disc) {
+        p_disc(h);
+    } else if (!h->is_block) {
         const Spec s = build_spec(h->cfg);
         const bool film = h->cfg.use_scale_shift_norm;
         p_lin(h, "time_embed.0", h->cfg.model_channels, s.ted);
@@ -1705,24 +1742,15 @@ Tn decode(Builder& b, const Spec& sp, const TimeEmb& te, Tn h, std::vector<Tn>* 
     return h;
 }
 
-// --------------------------------------------------------------------------------- DSUnetModel.forward
-void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool share) {
+// The four encoders of a four-stream model over the caller's planes io.plane[0..3] (stream s carries the parameter prefix
+// input_blocks<sfx[s]>); hs[s] receives what stream s pushed.  share: streams 2 and 3 run on a batch of one.
+void encode_streams(Builder& b, const Spec& sp, const TimeEmb& te, int H, int W, const char* const sfx[4], bool share,
+                    std::vector<Tn>* hs) {
     dsd_handle* hd = b.hd;
-    const dsd_config& cfg = hd->cfg;
-    const Spec sp = build_spec(cfg);
     const int B = b.B;
-    const int nds = cfg.n_levels - 1;
-    DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
-    // share: the al / l streams see the same (all-zero) plane and the same timestep for every slice -> batch of ONE
-    DSD_CHECK(!share || (zero_al_l && !want_feats), "zero-stream sharing needs the 2-channel branch and no feature outputs");
-    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/false);
-
-    // ---- four encoder streams (model.py:674-686): stream order n, a, al, l ; planes io.plane[0..3]
-    const char* sfx[4] = {"", "_a", "_al", "_l"};
     // Emission order: first the blocks whose layers fill the chip, stream after stream; then — from the first block whose
     // input has few enough pixels (dsd_handle::lane_pixels) — the rest of the four encoders as four LANES that the executor
     // runs concurrently (net_launch_ops): small grids of independent chains share the 256 CUs instead of queueing.
-    std::vector<Tn> hs[4];
     Tn cur4[4];
     size_t split = sp.input_blocks.size();
     {
@@ -1755,6 +1783,24 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
         }
         b.end_parallel();
     }
+}
+
+// --------------------------------------------------------------------------------- DSUnetModel.forward
+void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool share) {
+    dsd_handle* hd = b.hd;
+    const dsd_config& cfg = hd->cfg;
+    const Spec sp = build_spec(cfg);
+    const int B = b.B;
+    const int nds = cfg.n_levels - 1;
+    DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
+    // share: the al / l streams see the same (all-zero) plane and the same timestep for every slice -> batch of ONE
+    DSD_CHECK(!share || (zero_al_l && !want_feats), "zero-stream sharing needs the 2-channel branch and no feature outputs");
+    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/false);
+
+    // ---- four encoder streams (model.py:674-686): stream order n, a, al, l ; planes io.plane[0..3]
+    const char* sfx[4] = {"", "_a", "_al", "_l"};
+    std::vector<Tn> hs[4];
+    encode_streams(b, sp, te, H, W, sfx, share, hs);
     // ---- middle block on the noise stream only (model.py:688)
     size_t mei = 0;
     Tn h_n = b.block("middle_block", sp.middle, hs[0].back(), /*keep_input=*/true, te.of("middle_block", sp.middle), mei);
@@ -1813,6 +1859,101 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
     b.release(cat);
     h = decode(b, sp, te, h, hs, 4);
     // ---- out = Conv3x3(SiLU(GN(h)))  (model.py:511-515,751)
+    b.out_conv1("out.0", "out.2", h, cfg.out_channels);
+    b.release(h);
+    b.release(te.all);
+}
+
+// --------------------------------------------------------------------------------- UNet_disc_Model.forward
+// Disc_diff/guided_diffusion/unet.py:985-1044.  Four encoders with their own weights over the planes x, T1, T2, DWI; every
+// skip is the four-stream mean (fused into the decoder's concat, as for DSUnetModel); conv_common / conv_distinct (one weight
+// set each, applied to all four streams) feed the bottleneck head of disc.hip; Conv1x1 + SiLU; middle block, decoder, out.
+// want_feats: io.feats[0..7] receive com_h1..4 (after the SiLU) and dist_h1..4 (after their SE), NCHW.
+void build_disc(Builder& b, int H, int W, bool want_feats) {
+    dsd_handle* hd = b.hd;
+    const dsd_config& cfg = hd->cfg;
+    const Spec sp = build_spec(cfg);
+    const int B = b.B, half = sp.half, Cr = half / 8;
+    const int nds = cfg.n_levels - 1;
+    DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
+    TimeEmb te = time_embed(b, sp, /*t_from_aux=*/false);
+    const char* sfx[4] = {"", "_T1", "_T2", "_DWI"};
+    std::vector<Tn> hs[4];
+    encode_streams(b, sp, te, H, W, sfx, /*share=*/false, hs);
+    // ---- conv_common / conv_distinct: pre-activation here, the SiLU of both nn.Sequential lives in the head
+    Tn com[4], dist[4];
+    for (int s = 0; s < 4; ++s) com[s] = b.conv("conv_common.0", hs[s].back(), half, 3);
+    for (int s = 0; s < 4; ++s) dist[s] = b.conv("conv_distinct.0", hs[s].back(), half, 3);
+    const int hh = com[0].h, ww = com[0].w, HW = hh * ww;
+    Tn cat = b.alloc(B, hh, ww, 5 * half);
+    Tn feat[8];
+    if (want_feats)
+        for (auto& f : feat) f = b.alloc(B, hh, ww, half);
+    const char* se_name[5] = {"SE_Attention_com", "SE_Attention_dist_1", "SE_Attention_dist_2", "SE_Attention_dist_3", "SE_Attention_dist_4"};
+    if (!b.plan.disc_unfused) {
+        DiscArgs a;
+        a.B = B; a.HW = HW; a.half = half; a.Cr = Cr;
+        for (int k = 0; k < 5; ++k) {
+            DSD_CHECK(hd->PP(std::string(se_name[k]) + ".se.0.weight").numel == (int64_t)Cr * half, "%s: SE weight does not fit %d x %d", se_name[k], Cr, half);
+            a.w1[k] = b.W(std::string(se_name[k]) + ".se.0.weight");
+            a.w2[k] = b.W(std::string(se_name[k]) + ".se.2.weight");
+        }
+        const size_t sb = disc_scratch_bytes(B, HW, half, false), so = b.alloc_raw(sb);
+        size_t co[4], dof[4], fo[8] = {};
+        for (int s = 0; s < 4; ++s) { co[s] = com[s].off; dof[s] = dist[s].off; }
+        for (int i = 0; i < 8; ++i) fo[i] = feat[i].off;
+        const size_t cato = cat.off;
+        const double px = (double)B * HW * half * 4.0;
+        b.op([=](hipStream_t s) {
+            DiscArgs r = a;
+            for (int i = 0; i < 4; ++i) { r.com[i] = hd->at<float>(co[i]); r.dist[i] = hd->at<float>(dof[i]); }
+            if (want_feats)
+                for (int i = 0; i < 8; ++i) r.feat[i] = hd->at<float>(fo[i]);
+            r.cat = hd->at<float>(cato);
+            r.scratch = hd->arena + so;
+            disc_bottleneck(r, s);
+        }, 3, "disc_bottleneck", 0.0, px * (16 + 5 + (want_feats ? 8 : 0)));   // eight inputs read twice, five slices written
+        b.release_raw(so, sb);
+    } else {   // DSD_DISC_UNFUSED: the same head from Builder::avg (SiLU), Builder::se and concat copies
+        Tn ca[4];
+        for (int s = 0; s < 4; ++s) {
+            ca[s] = want_feats ? feat[s] : b.alloc(B, hh, ww, half);
+            b.avg(&com[s], 1, 1.f, ca[s], 0, ACT_SILU);
+        }
+        Tn m = b.alloc(B, hh, ww, half);
+        b.avg(ca, 4, 4.f, m, 0, ACT_NONE);
+        if (!want_feats)
+            for (auto& t : ca) b.release(t);
+        Tn cs = b.se("SE_Attention_com", m);
+        b.release(m);
+        b.avg(&cs, 1, 1.f, cat, 0, ACT_NONE);
+        b.release(cs);
+        for (int s = 0; s < 4; ++s) {
+            Tn da = b.alloc(B, hh, ww, half);
+            b.avg(&dist[s], 1, 1.f, da, 0, ACT_SILU);
+            Tn ds = b.se(se_name[1 + s], da);
+            b.release(da);
+            b.avg(&ds, 1, 1.f, cat, (1 + s) * half, ACT_NONE);
+            if (want_feats) b.avg(&ds, 1, 1.f, feat[4 + s], 0, ACT_NONE);
+            b.release(ds);
+        }
+    }
+    for (int s = 0; s < 4; ++s) { b.release(com[s]); b.release(dist[s]); }
+    if (want_feats)
+        for (int i = 0; i < 8; ++i) {
+            b.export_out(feat[i], true, i);
+            b.release(feat[i]);
+        }
+    // ---- dim_reduction_non_zeros: Conv1x1 then SiLU (the activation comes after the convolution); the SiLU pass also emits
+    // the GroupNorm statistics middle_block.0.in_layers.0 reads
+    Tn r = b.conv("dim_reduction_non_zeros.0", cat, sp.conv_ch, 1);
+    b.release(cat);
+    Tn h = b.alloc(B, hh, ww, sp.conv_ch);
+    b.avg(&r, 1, 1.f, h, 0, ACT_SILU, /*want_stats=*/true);
+    b.release(r);
+    size_t mei = 0;
+    h = b.block("middle_block", sp.middle, h, /*keep_input=*/false, te.of("middle_block", sp.middle), mei);
+    h = decode(b, sp, te, h, hs, 4);
     b.out_conv1("out.0", "out.2", h, cfg.out_channels);
     b.release(h);
     b.release(te.all);
@@ -2212,8 +2353,9 @@ void build_block(Builder& b, int C, int H, int W, int aux_len, int aux_len2) {
 void dsd::net_plan(dsd_handle* h, int B, int C, int H, int W, int zero_al_l, int want_feats, int aux_len, int aux_len2,
                    int share, hipStream_t s) {
     Plan& p = h->plan;
+    const int disc_unfused = h->is_disc && disc_unfused_env() ? 1 : 0;   // (read at every call: the two routes are A/B'd in one process)
     if (p.valid && p.B == B && p.C == C && p.H == H && p.W == W && p.zero_al_l == zero_al_l && p.want_feats == want_feats &&
-        p.aux_len == aux_len && p.aux_len2 == aux_len2 && p.share == share)
+        p.aux_len == aux_len && p.aux_len2 == aux_len2 && p.share == share && p.disc_unfused == disc_unfused)
         return;
     DSD_CHECK(h->device >= 0, "this handle was created without a device (table only)");
     for (const auto& prm : h->params) DSD_CHECK(prm.set, "parameter '%s' has not been set", prm.name.c_str());
@@ -2223,12 +2365,14 @@ void dsd::net_plan(dsd_handle* h, int B, int C, int H, int W, int zero_al_l, int
     p = Plan{};
     p.gen = gen;
     p.B = B; p.C = C; p.H = H; p.W = W; p.zero_al_l = zero_al_l; p.want_feats = want_feats;
-    p.aux_len = aux_len; p.aux_len2 = aux_len2; p.share = share;
+    p.aux_len = aux_len; p.aux_len2 = aux_len2; p.share = share; p.disc_unfused = disc_unfused;
     for (auto& kv : h->param_evs) DSD_HIP(hipStreamWaitEvent(s, kv.second, 0));   // uploads enqueued on ANY stream have landed first
     Builder b(h, p, B, s);
     try {
         if (h->is_block)
             build_block(b, C, H, W, aux_len, aux_len2);
+        else if (h->is_disc)
+            build_disc(b, H, W, want_feats != 0);
         else
             build_unet(b, H, W, zero_al_l != 0, want_feats != 0, share != 0);
     } catch (...) {

@@ -74,6 +74,7 @@ struct IO {
 struct Plan {
     int B = 0, H = 0, W = 0, C = 0;
     int zero_al_l = 0, want_feats = 0, share = 0;
+    int disc_unfused = 0;   // UNet_disc_Model: the bottleneck head composed from the older ops (DSD_DISC_UNFUSED) instead of disc.hip
     int aux_len = 0, aux_len2 = 0;
     bool valid = false;
     std::vector<std::function<void(hipStream_t)>> ops;
@@ -127,6 +128,7 @@ using Net = dsd_net;
 struct dsd_handle {
     int device = 0;
     bool is_block = false;
+    bool is_disc = false;   // dsd_create_disc: UNet_disc_Model (four live streams, shared bottleneck head) instead of DSUnetModel
     int block_kind = -1;
     std::vector<int32_t> iargs;
     dsd_config cfg{};

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from ...util import instantiate_from_config
+from ...._sched import model_output_of
 
 
 def _linspace_f64_like_torch(start: float, end: float, steps: int) -> np.ndarray:
@@ -309,7 +310,7 @@ class LatentDiffusion(DDPM):
                 cond = [cond]
             cond = {"c_concat" if self.model.conditioning_key == "concat" else "c_crossattn": cond}
         out = self.model(x_noisy, t, **cond)
-        return out[0] if isinstance(out, tuple) and not return_ids else out
+        return model_output_of(out) if isinstance(out, tuple) and not return_ids else out   # (UNet_disc_Model's 9-tuple: its last)
 
     @torch.no_grad()
     def q_sample(self, x_start, t, noise=None, seed=None):

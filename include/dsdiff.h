@@ -13,6 +13,12 @@
  *   dsd_create / dsd_set_param     <- DSUnetModel.__init__           UNet_DS_Diff/model.py:172-611
  *                                     + nn.Module.load_state_dict (names = reference state_dict keys)
  *   dsd_forward                    <- DSUnetModel.forward            UNet_DS_Diff/model.py:629-756
+ *   dsd_create_disc                <- UNet_disc_Model.__init__ / SuperResModelNew   Disc_diff/guided_diffusion/unet.py:726-967,1063-1076
+ *                                     (the four-stream DisC-Diff denoiser of configs/disc-diff.yaml and disc-diff-origin.yaml);
+ *                                     dsd_forward on such a handle <- UNet_disc_Model.forward :985-1044, and every four-stream
+ *                                     loop (dsd_sample ... dsd_calc_bpd) takes it with Cc = 3 (t1, t2, dwi behind the state,
+ *                                     Disc_diff/guided_diffusion/gaussian_diffusion.py:271-278)
+ *   dsd_op_disc_bottleneck         <- the bottleneck head of that forward, :1015-1033 (csrc/disc.hip)
  *   dsd_sample                     <- GaussianDiffusion.p_sample_loop / ddim_sample_loop
  *                                        Disc_diff/guided_diffusion/gaussian_diffusion.py:524-616,705-786
  *                                     DDPMModel.p_sample_loop        trainers/trainer_ddpm.py:447-482
@@ -84,6 +90,20 @@ int dsd_device_info(int device, char* name, int name_len, int* n_cu, int64_t* hb
 /* ---- model handle ------------------------------------------------------------------------ */
 /* device < 0 creates a table-only handle (parameter names/shapes, no GPU needed; compute calls fail). */
 int dsd_create(const dsd_config* cfg, int device, dsd_handle** out);
+/* UNet_disc_Model (Disc_diff/guided_diffusion/unet.py:726-1044): four single-channel encoder streams with their own weights
+ * (input_blocks, input_blocks_T1, _T2, _DWI), every skip the four-stream mean, a bottleneck head — conv_common / conv_distinct
+ * (one weight set each, applied to all four streams), SE gates, Conv1x1 + SiLU — then middle block, decoder and out.  The
+ * parameter table carries the reference state_dict's names, shapes and order.  Of dsd_config, `legacy` is ignored (this network
+ * has only the openai-style AttentionBlock); num_heads_upsample and use_new_attention_order are honoured; in_channels and
+ * channel_mult[0] must be 1.  The handle is a model handle: dsd_plan / dsd_forward take C = 4 (x, T1, T2, DWI), the sampling
+ * loops take it wherever they take dsd_create's with Cc = 3 (any other count fails before device work), graph replay,
+ * first_step / n_steps and dsd_set_slice_ids included; dsd_set_share_zero_streams(on) fails (all four streams are live).
+ * dsd_forward's feats: NULL or 8 device pointers to [B,half,H/2^(L-1),W/2^(L-1)] NCHW buffers, com_h1..4 (after the SiLU,
+ * before any SE) then dist_h1..4 (after their SE): with `out` the 9-tuple the reference returns.
+ * The head runs as three launches of csrc/disc.hip; with the environment variable DSD_DISC_UNFUSED set (read when a plan is
+ * built) it is composed from the older ops instead (SiLU copies, four-way mean, the one-workgroup-per-sample SE, concat
+ * copies): A/B timing and cross-check. */
+int dsd_create_disc(const dsd_config* cfg, int device, dsd_handle** out);
 void dsd_destroy(dsd_handle* h);
 
 /* Parameter table (names/shapes identical to the reference state_dict, OIHW conv weights). */
@@ -724,6 +744,16 @@ int dsd_op_gn_finalize(const double* p0, int chunks0, int c0, const double* p1, 
 int dsd_op_avg_into_stats(const float* a, const float* b, const float* c, const float* d, float div, int N, int HW, int C,
                           float* dst, int dstC, int coff, int act, int bmask, double* partial, int64_t partial_doubles,
                           int* nchunk, void* stream);
+/* The bottleneck head of UNet_disc_Model without a network (Disc_diff/guided_diffusion/unet.py:1015-1033).  com[4] / dist[4]:
+ * the PRE-activation outputs of conv_common / conv_distinct on the four streams, NHWC [B][HW][half] each; w1[5] / w2[5]: the
+ * bias-free SE linears [Cr][half] / [half][Cr] of SE_Attention_com and SE_Attention_dist_1..4, in that order (all device
+ * pointers, the pointer arrays themselves on the host).  cat [B][HW][5*half] receives
+ * [SE_com(mean_i SiLU(com_i)), SE_dist_1(SiLU(dist_1)), ..., SE_dist_4(SiLU(dist_4))]; feats: NULL, or 8 device pointers to
+ * NHWC [B][HW][half] buffers for SiLU(com_1..4) and the four scaled dist_i.  half % 4 == 0 and 16-byte aligned pointers, else
+ * the call fails.  unfused: 0 the three launches of csrc/disc.hip (fp64 pooling partials added in index order, no atomics: two
+ * runs are bit-identical), 1 the composition of older ops, -1 as the environment variable DSD_DISC_UNFUSED says. */
+int dsd_op_disc_bottleneck(const float* const* com, const float* const* dist, const float* const* w1, const float* const* w2,
+                           int B, int HW, int half, int Cr, float* cat, float* const* feats, int unfused, void* stream);
 /* The one-launch GroupNorm32 (+ FiLM, + activation) of small maps, called directly (the DSD_GN_SMALL switch of the networks is
  * not consulted): x, y [N][HW][C], C % 32 == 0, HW * C / 32 <= 32768; film as in dsd_op_gn_finalize; act: 0 none, 1 SiLU. */
 int dsd_op_gn_small(const float* x, int N, int HW, int C, const float* gamma, const float* beta, float eps, const float* film,
