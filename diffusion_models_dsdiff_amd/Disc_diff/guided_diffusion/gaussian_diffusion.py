@@ -438,7 +438,7 @@ class GaussianDiffusion:
         """:938-991: {"total_bpd", "prior_bpd" [N]; "vb", "xstart_mse", "mse" [N,T], column k at t = T-1-k}.  ``step_noise``
         ([T,N,C,H,W]) / ``seed`` are extensions as on the sampling loops: the normals q_sample draws at every timestep, fed for
         parity runs, else on-device Philox seeded from torch's generator.  A native denoiser with at most ``c_concat`` runs the
-        device loop (dsd_calc_bpd / dsd_calc_bpd_latent); a generic callable, or a DiT that is to receive labels, is evaluated
+        device loop (dsd_calc_bpd); a generic callable, or a DiT that is to receive labels, is evaluated
         step by step around the same kernels."""
         model_kwargs = model_kwargs or {}
         sched = self._schedule(False, 0.0, clip_denoised)

@@ -553,45 +553,40 @@ def _loop_denoiser_and_guidance(fn: "_ModelFn", steps: int, x_T: torch.Tensor, g
     return unet, cc, guidance, bundle
 
 
+def _native_loop_inputs(unet, cc, bundle, guidance: Optional[Guidance], x: torch.Tensor):
+    """What a device DPM loop hands the library for a native denoiser: (the 'concat' tensor, the bound guidance or None, the context
+    manager that holds the rest of the conditioning on the handle); None for the per-step path."""
+    if unet is not None and cc is None and is_dit(unet):
+        cc = [x.new_zeros((x.shape[0], 0) + tuple(x.shape[2:]))]    # an unconditional DiT: all input is state
+    if unet is None or cc is None:
+        return None
+    unet.sync_params()
+    cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, x, bundle if bundle is not None else cond)
+    else:
+        assert x.shape[1] == 1, "the denoised image has one channel"
+        assert cond.shape[0] == x.shape[0] and cond.shape[2:] == x.shape[2:]
+    g = C.byref(guidance.bind()) if guidance is not None else None
+    return cond, g, conditioning_set(unet, bundle, guidance.uncond if guidance is not None else None)
+
+
 @torch.no_grad()
 def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: Optional[Guidance] = None) -> torch.Tensor:
-    """The multistep loop on the device.  ``guidance`` (default: what ``fn`` carries from model_wrapper): classifier-free
-    guidance, dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided; its unconditional conditioning must have the shape, dtype
-    and device of the concatenated condition."""
+    """The multistep loop on the device (dsd_sample_dpm).  ``guidance`` (default: what ``fn`` carries from model_wrapper):
+    classifier-free guidance; its unconditional conditioning must have the shape, dtype and device of the concatenated condition."""
     unet, cc, guidance, bundle = _loop_denoiser_and_guidance(fn, sched.steps, x_T, guidance)
-    guided = guidance is not None
     if not x_T.is_cuda:
         raise RuntimeError("sampling runs on the MI355X only (no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
     B, Cx, H, W = x.shape
-    if guided:
-        g = guidance.bind()
-    if unet is not None and cc is None and is_dit(unet):
-        cc = [x.new_zeros((B, 0, H, W))]                           # an unconditional DiT: all input is state
-    if unet is not None and cc is not None and is_latent_denoiser(unet):
-        # latent state [B,Cz,h,w] under the plain UNetModel or the DiT: dsd_sample_dpm_latent
-        unet.sync_params()
-        cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
-        check_latent_io(unet, x, bundle if bundle is not None else cond)
-        with conditioning_set(unet, bundle, guidance.uncond if guided else None):
-            if guided:
-                check(lib().dsd_sample_dpm_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x),
-                                                         Cx, B, H, W, stream_ptr()))
-            else:
-                check(lib().dsd_sample_dpm_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
-                                                  stream_ptr()))
+    ready = _native_loop_inputs(unet, cc, bundle, guidance, x)
+    if ready is not None:
+        cond, g, held = ready
+        with held:
+            check(lib().dsd_sample_dpm(unet._h, C.byref(sched.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W, stream_ptr()))
         return x
     assert Cx == 1, "the denoised image has one channel"
-    if unet is not None and cc is not None:
-        unet.sync_params()
-        cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
-        assert cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
-        if guided:
-            check(lib().dsd_sample_dpm_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), B, H, W,
-                                              stream_ptr()))
-            return x
-        check(lib().dsd_sample_dpm(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), B, H, W, stream_ptr()))
-        return x
     # any other callable: python loop over the network, fused HIP post-network step per evaluation
     m_cur, m_prev = torch.empty_like(x), torch.empty_like(x)
     for k in range(sched.steps):
@@ -605,33 +600,22 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
 
 @torch.no_grad()
 def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance: Optional[Guidance] = None):
-    """A DpmProgram on the device: dsd_sample_dpm_program(_latent) for the native denoisers, guided or not, and for any other
+    """A DpmProgram on the device: dsd_sample_dpm_program for the native denoisers, guided or not, and for any other
     callable the python loop over the network with dsd_op_dpm_eval per evaluation.  Returns (sample, kept states
     [n_kept,B,C,H,W])."""
     unet, cc, guidance, bundle = _loop_denoiser_and_guidance(fn, prog.steps, x_T, guidance)
-    guided = guidance is not None
     if not x_T.is_cuda:
         raise NotImplementedError("the singlestep, third-order and intermediate-keeping solvers run on the MI355X only (there is "
                                   "no CPU implementation and no CPU fallback): x is on the CPU")
     x = x_T.detach().float().contiguous().clone()
     B, Cx, H, W = x.shape
     kept = x.new_empty((prog.n_kept, B, Cx, H, W))
-    g = C.byref(guidance.bind()) if guided else None
-    if unet is not None and cc is None and is_dit(unet):
-        cc = [x.new_zeros((B, 0, H, W))]
-    if unet is not None and cc is not None:
-        unet.sync_params()
-        cond = torch.cat([c.to(x.device) for c in cc], 1).detach().float().contiguous()
-        if is_latent_denoiser(unet):
-            check_latent_io(unet, x, bundle if bundle is not None else cond)
-            with conditioning_set(unet, bundle, guidance.uncond if guided else None):
-                check(lib().dsd_sample_dpm_program_latent(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H,
-                                                          W, dptr(kept), stream_ptr()))
-            return x, kept
-        assert Cx == 1, "the denoised image has one channel"
-        assert cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
-        check(lib().dsd_sample_dpm_program(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), B, H, W, dptr(kept),
-                                           stream_ptr()))
+    ready = _native_loop_inputs(unet, cc, bundle, guidance, x)
+    if ready is not None:
+        cond, g, held = ready
+        with held:
+            check(lib().dsd_sample_dpm_program(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
+                                               dptr(kept), stream_ptr()))
         return x, kept
     # any other callable: python loop over the network, the fused HIP evaluation step after each
     hist, base = x.new_empty((3, B, Cx, H, W)), torch.empty_like(x)

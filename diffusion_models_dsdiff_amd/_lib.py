@@ -31,15 +31,11 @@ EXPORTS = [
     "dsd_set_param", "dsd_set_timestep_freqs", "dsd_set_precision", "dsd_get_precision", "dsd_set_share_zero_streams", "dsd_params_ready", "dsd_plan", "dsd_workspace_bytes", "dsd_device_bytes", "dsd_set_graph", "dsd_graph_stats", "dsd_set_fuse_gn_stats", "dsd_set_fuse_gn_apply", "dsd_set_stream_lanes", "dsd_set_winograd", "dsd_set_vae_fused_attention", "dsd_set_slice_ids", "dsd_plan_launches", "dsd_plan_flops",
     "dsd_profile_enable", "dsd_profile_count", "dsd_profile_get", "dsd_profile_op_count", "dsd_profile_op_get", "dsd_profile_op_name", "dsd_forward", "dsd_sample", "dsd_op_sampler_update", "dsd_sample_dpm", "dsd_op_dpm_step", "dsd_op_dpm_threshold", "dsd_block_create", "dsd_block_forward", "dsd_bench_conv2d", "dsd_bench_conv2d_stamps", "dsd_bench_mfma_peak", "dsd_conv_plan", "dsd_subpixel_weights_host", "dsd_set_conv_mfma16", "dsd_op_conv2d", "dsd_op_conv2d_prec", "dsd_op_conv2d_ex", "dsd_op_conv2d_gn", "dsd_op_gn_finalize", "dsd_op_avg_into_stats", "dsd_op_gn_small", "dsd_op_gn_silu_conv_out1",
     "dsd_op_gaussian_sample", "dsd_op_group_norm", "dsd_op_qkv_attention", "dsd_op_attention", "dsd_op_gemm_half", "dsd_bench_gemm_half", "dsd_bench_attention_half", "dsd_op_attention_half", "dsd_op_timestep_embedding", "dsd_op_linear", "dsd_op_philox_normal",
-    "dsd_sample_latent", "dsd_sample_dpm_latent", "dsd_op_posterior_sample_scaled",
-    "dsd_sample_guided", "dsd_sample_latent_guided", "dsd_sample_dpm_guided", "dsd_sample_dpm_latent_guided",
-    "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
-    "dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent",
-    "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
-    "dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step",
-    "dsd_sample_dpm_program", "dsd_sample_dpm_program_latent", "dsd_op_dpm_eval",
+    "dsd_op_posterior_sample_scaled", "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
+    "dsd_invert", "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
+    "dsd_sample_plms", "dsd_op_plms_step", "dsd_sample_dpm_program", "dsd_op_dpm_eval",
     "dsd_set_conditioning",
-    "dsd_calc_bpd", "dsd_calc_bpd_latent", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
+    "dsd_calc_bpd", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
     "dsd_create_disc", "dsd_op_disc_bottleneck",
 ]
 
@@ -180,9 +176,17 @@ def lib() -> C.CDLL:
     L.dsd_profile_get.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.dsd_forward.argtypes = [vp, f32p, vp, i32, i32, i32, i32, i32, f32p, C.POINTER(vp), vp]
-    L.dsd_sample.argtypes = [vp, C.POINTER(DsdSchedule), f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    # The six device loops: one entry point each, the handle picks the denoiser, g / inp are NULL for unguided / unmasked.  A
+    # library from before this layout, loaded through DSD_LIBRARY, still exports dsd_sample & co. but with the older, shorter
+    # signatures: it no longer matches these and must not be used for A/B runs of the loops.
+    sp, gp, ip = C.POINTER(DsdSchedule), C.POINTER(DsdGuidance), C.POINTER(DsdInpaint)
+    L.dsd_sample.argtypes = [vp, sp, gp, ip, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_sample_dpm.argtypes = [vp, C.POINTER(DsdDpmSchedule), gp, f32p, i32, f32p, i32, i32, i32, i32, vp]
+    L.dsd_sample_dpm_program.argtypes = [vp, C.POINTER(DsdDpmProgram), gp, f32p, i32, f32p, i32, i32, i32, i32, f32p, vp]
+    L.dsd_sample_plms.argtypes = [vp, sp, gp, ip, C.c_float, f32p, i32, f32p, i32, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_invert.argtypes = [vp, C.POINTER(DsdInvertSchedule), gp, f32p, i32, f32p, i32, i32, i32, i32, i32, i32, vp]
+    L.dsd_calc_bpd.argtypes = [vp, sp, C.POINTER(DsdBpd), f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
     L.dsd_op_sampler_update.argtypes = [C.POINTER(DsdSchedule), i32, f32p, f32p, f32p, C.c_uint64, i32, i32, i32, f32p, vp]
-    L.dsd_sample_dpm.argtypes = [vp, C.POINTER(DsdDpmSchedule), f32p, i32, f32p, i32, i32, i32, vp]
     L.dsd_op_dpm_step.argtypes = [C.POINTER(DsdDpmSchedule), i32, f32p, i32, f32p, f32p, f32p, i32, i32, i32, vp]
     L.dsd_op_dpm_threshold.argtypes = [f32p, i32, i32, C.c_float, C.c_float, f32p, f32p, vp]
     L.dsd_block_create.argtypes = [i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(vp)]
@@ -216,41 +220,18 @@ def lib() -> C.CDLL:
     L.dsd_op_linear.argtypes = [f32p, i32, i32, f32p, f32p, i32, i32, f32p, vp]
     L.dsd_op_gaussian_sample.argtypes = [f32p, f32p, C.c_uint64, i32, i32, i32, i32, f32p, vp]
     L.dsd_op_philox_normal.argtypes = [f32p, i64, C.c_uint64, C.c_uint64, vp]
-    L.dsd_sample_latent.argtypes = [vp, C.POINTER(DsdSchedule), f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
-    L.dsd_sample_dpm_latent.argtypes = [vp, C.POINTER(DsdDpmSchedule), f32p, i32, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_posterior_sample_scaled.argtypes = [f32p, f32p, C.c_uint64, i32, i32, i32, i32, C.c_float, f32p, vp]
-    gp = C.POINTER(DsdGuidance)
-    L.dsd_sample_guided.argtypes = [vp, C.POINTER(DsdSchedule), gp, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
-    L.dsd_sample_latent_guided.argtypes = [vp, C.POINTER(DsdSchedule), gp, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32,
-                                           i32, i32, vp]
-    L.dsd_sample_dpm_guided.argtypes = [vp, C.POINTER(DsdDpmSchedule), gp, f32p, i32, f32p, i32, i32, i32, vp]
-    L.dsd_sample_dpm_latent_guided.argtypes = [vp, C.POINTER(DsdDpmSchedule), gp, f32p, i32, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_sampler_update_guided.argtypes = [C.POINTER(DsdSchedule), i32, f32p, f32p, C.c_float, f32p, i64, f32p, C.c_uint64,
                                                i32, i32, i32, i32, f32p, vp]
     L.dsd_op_dpm_step_guided.argtypes = [C.POINTER(DsdDpmSchedule), i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p,
                                          i32, i32, i32, i32, vp]
-    ip, vs = C.POINTER(DsdInpaint), C.POINTER(DsdInvertSchedule)
-    L.dsd_sample_masked.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
-    L.dsd_sample_latent_masked.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32,
-                                           i32, i32, i32, vp]
-    L.dsd_invert.argtypes = [vp, vs, gp, f32p, i32, f32p, i32, i32, i32, i32, i32, vp]
-    L.dsd_invert_latent.argtypes = [vp, vs, gp, f32p, i32, f32p, i32, i32, i32, i32, i32, i32, vp]
     L.dsd_op_mask_blend.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, f32p, i64, i32, f32p, C.c_uint64, C.c_uint64, i32, i32,
                                     i32, i32, vp]
     L.dsd_op_q_sample.argtypes = [f32p, f32p, f32p, f32p, C.c_uint64, C.c_uint64, f32p, i64, i32, i32, i32, i32, vp]
     L.dsd_op_ddim_invert_step.argtypes = [C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, i64, i32, i32, i32, i32, vp]
-    L.dsd_sample_plms.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, C.c_float, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
-    L.dsd_sample_plms_latent.argtypes = [vp, C.POINTER(DsdSchedule), gp, ip, C.c_float, f32p, i32, f32p, i32, C.c_uint64, i32, i32, i32,
-                                         i32, i32, vp]
     L.dsd_op_plms_step.argtypes = [i32, C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, f32p, i64,
                                    C.c_float, i32, i32, i32, i32, vp]
-    pp = C.POINTER(DsdDpmProgram)
-    L.dsd_sample_dpm_program.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, f32p, vp]
-    L.dsd_sample_dpm_program_latent.argtypes = [vp, pp, gp, f32p, i32, f32p, i32, i32, i32, i32, f32p, vp]
-    L.dsd_op_dpm_eval.argtypes = [pp, i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p, i32, i32, i32, i32, vp]
-    bp, sp = C.POINTER(DsdBpd), C.POINTER(DsdSchedule)
-    L.dsd_calc_bpd.argtypes = [vp, sp, bp, f32p, i32, f32p, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
-    L.dsd_calc_bpd_latent.argtypes = [vp, sp, bp, f32p, i32, f32p, i32, f32p, C.c_uint64, i32, i32, i32, i32, i32, vp]
+    L.dsd_op_dpm_eval.argtypes = [C.POINTER(DsdDpmProgram), i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_vlb_terms.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, f32p, C.c_uint64, f32p, f32p, f32p, i64, f32p, f32p,
                                    f32p, i32, i32, i32, i32, vp]
     L.dsd_op_prior_bpd.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, i32, i32, i32, vp]

@@ -314,7 +314,7 @@ def find_unet(model):
     """Locate the native denoiser behind the object the reference passes as ``model``
     (DiffusionWrapper.diffusion_model, ddpm.py:1323; or the network itself): the four-stream DSUnetModel, or one of the two
     that read the state from their own input — the plain UNetModel that denoises VAE latents and the DiT the reference's
-    trainer swaps in for the U-Net (both run by the latent loops, dsd_sample_latent / dsd_sample_dpm_latent)."""
+    trainer swaps in for the U-Net (the device loops read the kind off the handle)."""
     from .UNet_DS_Diff.DiT_models import DiT
     from .UNet_DS_Diff.model import DSUnetModel
     from .ldm.modules.diffusionmodules.openaimodel import UNetModel
@@ -455,6 +455,18 @@ def philox_seed(seed: Optional[int] = None) -> int:
     return int(seed) if seed is not None else _seed_from_torch()
 
 
+def _ref(struct):
+    """byref of a bound guidance / inpaint struct, or None (NULL: unguided / unmasked)."""
+    return C.byref(struct) if struct is not None else None
+
+
+def _check_four_stream_io(unet, x: torch.Tensor, cond: torch.Tensor) -> None:
+    """The four-stream model denoises a one-channel image beside 'concat' planes of its size (the library checks the latent
+    denoisers' shapes against their handles)."""
+    if not is_latent_denoiser(unet):
+        assert x.shape[1] == 1 and cond.shape[0] == x.shape[0] and cond.shape[2:] == x.shape[2:]
+
+
 def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidance: Optional[Guidance],
                  inpaint: Optional[Inpaint], cpu_message: str):
     """The prologue every device loop shares: the guidance / inpaint checks, the denoiser and device tests, parameters synced,
@@ -486,51 +498,21 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
                     step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                     first_step: int = 0, n_steps: int = 0, guidance: Optional[Guidance] = None,
                     inpaint: Optional[Inpaint] = None) -> torch.Tensor:
-    """x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations.
-    With the plain UNetModel the state is a latent x_T [B,Cz,H,W] (dsd_sample_latent; step_noise [steps,B,Cz,H,W]).
-    ``guidance``: classifier-free guidance (dsd_sample_guided / dsd_sample_latent_guided, mode B_DDIM); its unconditional
-    conditioning must have the shape, dtype and device of ``cond``.
-    ``inpaint``: masked sampling (dsd_sample_masked / dsd_sample_latent_masked, modes B_DDIM and B_DDPM), guided or not."""
+    """dsd_sample.  x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations.
+    With the plain UNetModel or the DiT the state is a latent x_T [B,Cz,H,W]; step_noise is [steps,B,Cz,H,W].
+    ``guidance``: classifier-free guidance (mode B_DDIM); its unconditional conditioning must have the shape, dtype and device
+    of ``cond``.  ``inpaint``: masked sampling (modes B_DDIM and B_DDPM), guided or not."""
     x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
                                          "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
-    if is_latent_denoiser(unet):
-        B, Cz, H, W = x.shape
-        if step_noise is not None:
-            step_noise = step_noise.detach().float().contiguous()
-            if tuple(step_noise.shape) != (sched.steps, B, Cz, H, W):
-                raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
-        if seed is None:
-            seed = _seed_from_torch()
-        with held:
-            if inp is not None:
-                check(lib().dsd_sample_latent_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp),
-                                                     dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise), C.c_uint64(seed), B,
-                                                     H, W, first_step, n_steps, stream_ptr()))
-            elif g is not None:
-                check(lib().dsd_sample_latent_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), Cz,
-                                                     dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
-            else:
-                check(lib().dsd_sample_latent(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), Cz, dptr(step_noise),
-                                              C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
-        return x
-    B, Cx, H, W = x.shape
-    assert Cx == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
+    B, Cz, H, W = x.shape
+    _check_four_stream_io(unet, x, cond)
     if step_noise is not None:
         step_noise = step_noise.detach().float().contiguous()
-        assert step_noise.shape == (sched.steps, B, 1, H, W), "step_noise must be [steps,B,1,H,W]"
-    if seed is None:
-        seed = _seed_from_torch()
-    if inp is not None:
-        check(lib().dsd_sample_masked(unet._h, C.byref(sched.c), C.byref(g) if g is not None else None, C.byref(inp), dptr(cond),
-                                      cond.shape[1], dptr(x), dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps,
-                                      stream_ptr()))
-        return x
-    if g is not None:
-        check(lib().dsd_sample_guided(unet._h, C.byref(sched.c), C.byref(g), dptr(cond), cond.shape[1], dptr(x), dptr(step_noise),
-                                      C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
-        return x
-    check(lib().dsd_sample(unet._h, C.byref(sched.c), dptr(cond), cond.shape[1], dptr(x), dptr(step_noise),
-                           C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+        if tuple(step_noise.shape) != (sched.steps, B, Cz, H, W):
+            raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
+    with held:
+        check(lib().dsd_sample(unet._h, C.byref(sched.c), _ref(g), _ref(inp), dptr(cond), cond.shape[1], dptr(x), Cz,
+                               dptr(step_noise), C.c_uint64(philox_seed(seed)), B, H, W, first_step, n_steps, stream_ptr()))
     return x
 
 
@@ -538,25 +520,20 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
 def run_plms_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor, threshold: Optional[float] = None,
                   guidance: Optional[Guidance] = None, inpaint: Optional[Inpaint] = None, seed: Optional[int] = None,
                   first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
-    """The PLMS device loop (dsd_sample_plms / dsd_sample_plms_latent) on a DSD_MODE_B_PLMS schedule: x_T [B,1,H,W] with the
-    four-stream model, [B,Cz,H,W] with the plain UNetModel.  ``threshold``: dynamic_threshold of norm_thresholding (None / <= 0:
+    """The PLMS device loop (dsd_sample_plms) on a DSD_MODE_B_PLMS schedule: x_T [B,1,H,W] with the four-stream model,
+    [B,Cz,H,W] with the plain UNetModel.  ``threshold``: dynamic_threshold of norm_thresholding (None / <= 0:
     off).  The history of noise predictions stays on the denoiser's handle: ``first_step`` = k > 0 continues the run whose
     iterations 0 .. k-1 ran last on it (x_T = the state they returned) and fails otherwise.  ``seed`` keys the blend noise of
     ``inpaint`` when it carries none; PLMS itself draws no noise."""
     x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
                                          "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
-    gp, ip = C.byref(g) if g is not None else None, C.byref(inp) if inp is not None else None
     thr = C.c_float(float(threshold) if threshold is not None else 0.0)
     seed = C.c_uint64(philox_seed(seed) if inp is not None and inp.noise is None else 0)
     B, Cz, H, W = x.shape
-    if is_latent_denoiser(unet):
-        with held:
-            check(lib().dsd_sample_plms_latent(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed, B,
-                                               H, W, first_step, n_steps, stream_ptr()))
-        return x
-    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
-    check(lib().dsd_sample_plms(unet._h, C.byref(sched.c), gp, ip, thr, dptr(cond), cond.shape[1], dptr(x), seed, B, H, W,
-                                first_step, n_steps, stream_ptr()))
+    _check_four_stream_io(unet, x, cond)
+    with held:
+        check(lib().dsd_sample_plms(unet._h, C.byref(sched.c), _ref(g), _ref(inp), thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed,
+                                    B, H, W, first_step, n_steps, stream_ptr()))
     return x
 
 
@@ -635,8 +612,8 @@ def invert_coefficients(alphas_next: torch.Tensor, alphas: torch.Tensor) -> np.n
 @torch.no_grad()
 def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor, guidance: Optional[Guidance] = None,
                     first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
-    """DDIM inversion on the device (dsd_invert / dsd_invert_latent): ``coef`` [steps,2] from invert_coefficients.  The model
-    time of iteration i is the loop index i itself — DDIMSampler.encode passes ``i``, not a timestep of the schedule
+    """DDIM inversion on the device (dsd_invert): ``coef`` [steps,2] from invert_coefficients.  The model time of iteration i
+    is the loop index i itself — DDIMSampler.encode passes ``i``, not a timestep of the schedule
     (ddim.py:282); a quirk of the reference, kept for parity."""
     coef = np.ascontiguousarray(coef, dtype=np.float32)
     steps = int(coef.shape[0])
@@ -648,16 +625,11 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
     sc.steps = steps
     sc.coef = coef.ctypes.data_as(C.POINTER(C.c_float))
     sc.t_model = t_model.ctypes.data_as(C.POINTER(C.c_float))
-    gp = C.byref(g) if g is not None else None
     B, Cz, H, W = x.shape
-    if is_latent_denoiser(unet):
-        with held:
-            check(lib().dsd_invert_latent(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), Cz, B, H, W, first_step,
-                                          n_steps, stream_ptr()))
-        return x
-    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == x.shape[2:]
-    check(lib().dsd_invert(unet._h, C.byref(sc), gp, dptr(cond), cond.shape[1], dptr(x), B, H, W, first_step, n_steps,
-                           stream_ptr()))
+    _check_four_stream_io(unet, x, cond)
+    with held:
+        check(lib().dsd_invert(unet._h, C.byref(sc), _ref(g), dptr(cond), cond.shape[1], dptr(x), Cz, B, H, W, first_step, n_steps,
+                               stream_ptr()))
     return x
 
 
@@ -665,8 +637,8 @@ def run_invert_loop(unet, coef: np.ndarray, x0: torch.Tensor, cond: torch.Tensor
 def run_bpd_loop(unet, sched: Schedule, post_log_var: np.ndarray, prior_log_var: float, x_start: torch.Tensor, cond: torch.Tensor,
                  step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, first_step: int = 0, n_steps: int = 0,
                  out: Optional[dict] = None) -> dict:
-    """The variational-bound device loop (dsd_calc_bpd / dsd_calc_bpd_latent) on a DSD_MODE_A_DDPM schedule: x_start [B,1,H,W]
-    with the four-stream model, [B,Cz,H,W] with the UNetModel or the DiT; read only.  ``post_log_var`` [steps]: the fp32
+    """The variational-bound device loop (dsd_calc_bpd) on a DSD_MODE_A_DDPM schedule: x_start [B,1,H,W] with the
+    four-stream model, [B,Cz,H,W] with the UNetModel or the DiT; read only.  ``post_log_var`` [steps]: the fp32
     posterior_log_variance_clipped in iteration order; ``prior_log_var``: log(1 - alphas_cumprod[T-1]).  ``step_noise``
     [steps,B,Cz,H,W] feeds q_sample's normals, else Philox stream (seed, k + 2^32).  Returns {"vb", "xstart_mse", "mse"} [B,steps]
     (column k = iteration k) and {"prior_bpd"} [B]; ``out`` (a dict this function returned) is written in place, so a split run
@@ -698,14 +670,10 @@ def run_bpd_loop(unet, sched: Schedule, post_log_var: np.ndarray, prior_log_var:
     bpd.post_log_var = post_log_var.ctypes.data_as(C.POINTER(C.c_float))
     bpd.vb, bpd.xstart_mse, bpd.mse = out["vb"].data_ptr(), out["xstart_mse"].data_ptr(), out["mse"].data_ptr()
     bpd.prior, bpd.prior_log_var = out["prior_bpd"].data_ptr(), float(prior_log_var)
-    if is_latent_denoiser(unet):
-        with conditioning_set(unet, bundle):
-            check(lib().dsd_calc_bpd_latent(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), Cz,
-                                            dptr(step_noise), C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
-        return out
-    assert Cz == 1 and cond.shape[0] == B and cond.shape[2:] == xs.shape[2:]
-    check(lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), dptr(step_noise),
-                             C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
+    _check_four_stream_io(unet, xs, cond)
+    with conditioning_set(unet, bundle):
+        check(lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), dptr(cond), cond.shape[1], dptr(xs), Cz, dptr(step_noise),
+                                 C.c_uint64(seed), B, H, W, first_step, n_steps, stream_ptr()))
     return out
 
 

@@ -509,8 +509,9 @@ void check_slice_ids(const dsd_handle* h, int B) {
 }
 
 // the four-stream denoiser (DSUnetModel): a one-channel state beside 1 or 3 condition planes
-void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x, int B, int H, int W) {
-    DSD_CHECK(h && !h->is_block && cond && x, "null argument");
+void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W) {
+    DSD_CHECK(cond && x, "null argument");
+    DSD_CHECK(Cz == 1, "the four-stream model denoises a state of %d channel (the denoised image has one channel), got Cz = %d", 1, Cz);
     DSD_CHECK(!h->is_disc || Cc == 3, "UNet_disc_Model takes 3 condition planes (t1, t2, dwi) behind the state, got Cc = %d (%d input channels, 4 needed)",
               Cc, Cc + 1);
     DSD_CHECK(Cc == 1 || Cc == 3, "cond must have 1 or 3 channels, got %d", Cc);
@@ -524,7 +525,7 @@ void check_four_stream(dsd_handle* h, const float* cond, int Cc, const float* x,
 // range) 2*Cz.  Returns the handle's output channel count, the row stride of mout in planes: the UNetModel's equals want_ch; the
 // DiT's (in_channels // 3 * 2 with learn_sigma, sic) is Cz or 2*Cz, and a sampler without learned variance ignores the second
 // half (gaussian_diffusion.py:484-485).
-bool is_dit(const dsd_handle* h) { return h && h->is_block && h->block_kind == DSD_BLOCK_DIT; }
+bool is_dit(const dsd_handle* h) { return h->is_block && h->block_kind == DSD_BLOCK_DIT; }
 
 int check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W,
                  int want_ch) {
@@ -544,8 +545,8 @@ int check_latent(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc
         check_slice_ids(h, B);
         return out_ch;
     }
-    DSD_CHECK(h && x, "null argument");
-    DSD_CHECK(h->is_block && h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
+    DSD_CHECK(x, "null argument");
+    DSD_CHECK(h->block_kind == DSD_BLOCK_UNET, "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)");
     const std::vector<int32_t>& a = h->iargs;
     DSD_CHECK(Cz >= 1 && Cc >= 0 && B >= 1 && H >= 1 && W >= 1, "bad shape: Cz %d Cc %d B %d H %d W %d", Cz, Cc, B, H, W);
     // the bundle of dsd_set_conditioning against the handle (context <-> spatial transformer, y <-> label_emb)
@@ -678,18 +679,25 @@ LoopBinding bind_latent(dsd_handle* h, const dsd_guidance* g, const float* cond,
     return b;
 }
 
-// `latent` selects the denoiser: a state-in-input one (UNetModel / DiT) on a Cz-channel state, or the four-stream model (Cz = 1).
+// The handle picks the denoiser: a block handle reads the state from its own input (UNetModel / DiT, a Cz-channel state), a model
+// handle is the four-stream model (Cz = 1).  Every loop rejects a null handle with this before anything else.
+bool state_in_input(const dsd_handle* h) {
+    DSD_CHECK(h, "null argument");
+    return h->is_block;
+}
+
 // want_ch: the output channels the sampler reads; returns the channels one output row holds (the four-stream callers check theirs).
-int check_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B,
-                   int H, int W, int want_ch) {
-    if (latent) return check_latent(h, g, cond, Cc, x, Cz, B, H, W, want_ch);
-    check_four_stream(h, cond, Cc, x, B, H, W);
+int check_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, const float* x, int Cz, int B, int H, int W,
+                   int want_ch) {
+    if (state_in_input(h)) return check_latent(h, g, cond, Cc, x, Cz, B, H, W, want_ch);
+    check_four_stream(h, cond, Cc, x, Cz, B, H, W);
     return want_ch;
 }
 
-LoopBinding bind_denoiser(bool latent, dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B,
-                          int H, int W, int out_ch, hipStream_t s) {
-    return latent ? bind_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s) : bind_four_stream(h, g, cond, Cc, x, B, H, W, out_ch, s);
+LoopBinding bind_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B, int H, int W,
+                          int out_ch, hipStream_t s) {
+    return state_in_input(h) ? bind_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s)
+                             : bind_four_stream(h, g, cond, Cc, x, B, H, W, out_ch, s);
 }
 
 // iterations [r.k0, r.k1): pre(k) in front of the network evaluation at time t[k] (through the cached graph), step(k) after it
@@ -724,8 +732,7 @@ StepCoef step_coef(const dsd_schedule* sc, int k) {
 void check_schedule(const dsd_schedule* sc) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
     DSD_CHECK(sc->mode != DSD_MODE_B_PLMS,
-              "DSD_MODE_B_PLMS carries a history of noise predictions across iterations: it runs in dsd_sample_plms / "
-              "dsd_sample_plms_latent only");
+              "DSD_MODE_B_PLMS carries a history of noise predictions across iterations: it runs in dsd_sample_plms only");
     DSD_CHECK(sc->mode >= DSD_MODE_A_DDPM && sc->mode <= DSD_MODE_B_DDIM, "unknown sampler mode %d", sc->mode);
     DSD_CHECK(sc->pred >= DSD_PRED_EPS && sc->pred <= DSD_PRED_V, "unknown prediction type %d", sc->pred);
     DSD_CHECK(!(sc->learned_range && sc->mode >= DSD_MODE_B_DDPM), "learned-range variance exists only in the guided-diffusion family");
@@ -767,11 +774,13 @@ void blend_step(const dsd_schedule* sc, int k, const dsd_inpaint* inp, const Loo
 extern "C" {
 
 // ------------------------------------------------------------------------------------------- DDPM / DDIM
-// dsd_sample and its kin: the fused update after every evaluation; guided (g) in DSD_MODE_B_DDIM; masked (inp): ddim.py:160-163
-// blends in front of every network evaluation, ddpm.py:1085-1087 after every update (the masked entry points check inp itself).
-static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
-                   int Cc, float* x, int Cz, const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
-                   void* stream) {
+// dsd_sample: the fused update after every evaluation; guided (g) in DSD_MODE_B_DDIM; masked (inp): ddim.py:160-163 blends in front
+// of every network evaluation, ddpm.py:1085-1087 after every update.
+int dsd_sample(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond, int Cc,
+               float* x, int Cz, const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
+    if (inp) check_mask(inp, Cz);
     check_schedule(sc);
     if (inp) {
         DSD_CHECK(sc->mode == DSD_MODE_B_DDPM || sc->mode == DSD_MODE_B_DDIM,
@@ -781,17 +790,17 @@ static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd
     }
     if (g) {
         check_guided_schedule(sc);
-        check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
+        check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
     }
     DSD_CHECK(!(sc->learned_range && Cz > 1) || is_dit(h),
               "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
     const int want_ch = (sc->learned_range ? 2 : 1) * Cz;
-    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, want_ch);
+    const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, want_ch);
     DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d", h->cfg.out_channels,
               out_ch);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
+    const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     const bool blend_first = inp && sc->mode == DSD_MODE_B_DDIM, blend_last = inp && !blend_first;
     run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s,
              [&](int k) {
@@ -804,54 +813,6 @@ static void sample(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd
                  if (blend_last) blend_step(sc, k, inp, b, seed, s);
              });
     finish(h, b, s);
-}
-
-int dsd_sample(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, const float* noise,
-               uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    sample(false, h, sc, nullptr, nullptr, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sc, const float* cond, int Cc, float* x, int Cz, const float* noise,
-                      uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    sample(true, h, sc, nullptr, nullptr, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    DSD_CHECK(g, "null guidance");
-    sample(false, h, sc, g, nullptr, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                             void* stream) {
-    DSD_TRY
-    DSD_CHECK(g, "null guidance");
-    sample(true, h, sc, g, nullptr, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
-                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                      void* stream) {
-    DSD_TRY
-    check_mask(inp, 1);
-    sample(false, h, sc, g, inp, cond, Cc, x, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
-                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
-                             int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    check_mask(inp, Cz);
-    sample(true, h, sc, g, inp, cond, Cc, x, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
@@ -909,16 +870,18 @@ static DpmCoef dpm_coef(const dsd_dpm_schedule* sc, int k) {
 
 // One sample = all Cz*h*w elements: the dynamic-thresholding quantile is per sample over C*h*w (sampler.py:379-388).  The
 // four-stream model and the DiT may carry a learned sigma in a second half of the output channels, which the solver ignores.
-static void sample_dpm(bool latent, dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
-                       float* x, int Cz, int B, int H, int W, void* stream) {
+int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
+                   int B, int H, int W, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
     check_dpm_schedule(sc);
-    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
-    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
+    const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;   // an output row is Cm samples long; the solver reads the first
     DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
+    const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
     const size_t plane = (size_t)B * b.n();
     ensure_buf(&h->dpm_m, &h->dpm_m_cap, (2 * plane + B) * sizeof(float));
     float *m_cur = h->dpm_m, *m_prev = h->dpm_m + plane, *s_buf = h->dpm_m + 2 * plane;
@@ -928,35 +891,6 @@ static void sample_dpm(bool latent, dsd_handle* h, const dsd_dpm_schedule* sc, c
         std::swap(m_cur, m_prev);
     });
     finish(h, b, s);
-}
-
-int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond, int Cc, float* x, int B, int H, int W,
-                   void* stream) {
-    DSD_TRY
-    sample_dpm(false, h, sc, nullptr, cond, Cc, x, 1, B, H, W, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sc, const float* cond, int Cc, float* x, int Cz, int B, int H,
-                          int W, void* stream) {
-    DSD_TRY
-    sample_dpm(true, h, sc, nullptr, cond, Cc, x, Cz, B, H, W, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                          int B, int H, int W, void* stream) {
-    DSD_TRY
-    DSD_CHECK(g, "null guidance");
-    sample_dpm(false, h, sc, g, cond, Cc, x, 1, B, H, W, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance* g, const float* cond, int Cc,
-                                 float* x, int Cz, int B, int H, int W, void* stream) {
-    DSD_TRY
-    DSD_CHECK(g, "null guidance");
-    sample_dpm(true, h, sc, g, cond, Cc, x, Cz, B, H, W, stream);
     DSD_CATCH
 }
 
@@ -1058,18 +992,20 @@ static void dpm_program_eval(const dsd_dpm_program* p, int k, const float* out_u
 
 // One driver for the four-stream model and the state-in-input denoisers, guided or not.  The history planes, the base plane and
 // the thresholds share one handle buffer, sized before the loop and left alone inside it.
-static void sample_dpm_program(bool latent, dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc,
-                               float* x, int Cz, int B, int H, int W, float* inter, void* stream) {
+int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
+                           int B, int H, int W, float* inter, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
     check_dpm_program(p);
-    if (g) check_guidance(g, p->n_eval, !(latent && Cc == 0 && h && h->has_cond));                          // one scale per evaluation
+    if (g) check_guidance(g, p->n_eval, !(latent && Cc == 0 && h->has_cond));                          // one scale per evaluation
     const int kept = dpm_program_kept(p);
     DSD_CHECK(kept == 0 || inter, "the program keeps %d intermediate states but the output for them is null", kept);
-    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;
     DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
+    const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
     const size_t plane = (size_t)B * b.n();
     ensure_buf(&h->dpm_prog, &h->dpm_prog_cap, (4 * plane + B) * sizeof(float));
     float *hist = h->dpm_prog, *base = hist + 3 * plane, *s_buf = hist + 4 * plane;
@@ -1082,19 +1018,6 @@ static void sample_dpm_program(bool latent, dsd_handle* h, const dsd_dpm_program
                                      hipMemcpyDeviceToDevice, s));
     });
     finish(h, b, s);
-}
-
-int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                           int B, int H, int W, float* intermediates, void* stream) {
-    DSD_TRY
-    sample_dpm_program(false, h, prog, g, cond, Cc, x, 1, B, H, W, intermediates, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_dpm_program_latent(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc,
-                                  float* x, int Cz, int B, int H, int W, float* intermediates, void* stream) {
-    DSD_TRY
-    sample_dpm_program(true, h, prog, g, cond, Cc, x, Cz, B, H, W, intermediates, stream);
     DSD_CATCH
 }
 
@@ -1120,7 +1043,7 @@ int dsd_op_dpm_eval(const dsd_dpm_program* prog, int k, const float* out_uncond,
 // of noise predictions stays on the handle: iterations from first_step > 0 need it resident, first_step = 0 starts it.
 static void check_plms_schedule(const dsd_schedule* sc) {
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad schedule");
-    DSD_CHECK(sc->mode == DSD_MODE_B_PLMS, "the PLMS loops take a DSD_MODE_B_PLMS schedule; mode %d belongs to dsd_sample and its kin",
+    DSD_CHECK(sc->mode == DSD_MODE_B_PLMS, "the PLMS loops take a DSD_MODE_B_PLMS schedule; mode %d belongs to dsd_sample",
               sc->mode);
     DSD_CHECK(!sc->learned_range, "PLMS does not take a learned-range variance (learned_range is set)");
     DSD_CHECK(sc->pred == DSD_PRED_EPS,
@@ -1131,13 +1054,14 @@ static void check_plms_schedule(const dsd_schedule* sc) {
                   (double)sc->coef[(size_t)k * DSD_NCOEF + 6]);
 }
 
-static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float thr,
-                        const float* cond, int Cc, float* x, int Cz, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
-                        void* stream) {
+int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float thr, const float* cond,
+                    int Cc, float* x, int Cz, uint64_t seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
     check_plms_schedule(sc);
-    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
     if (inp) check_mask(inp, Cz);
-    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
     const int64_t n = (int64_t)Cz * H * W, plane = (int64_t)B * n;
     const Range r = step_range(first_step, n_steps, sc->steps);
@@ -1151,7 +1075,7 @@ static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, cons
     hipStream_t s = (hipStream_t)stream;
     const size_t planes = ((size_t)3 * plane * sizeof(float) + 15) / 16 * 16;   // nothing is allocated once the planes have their size
     ensure_buf(&h->plms_hist, &h->plms_hist_cap, planes + plms_norm_doubles(B, n) * sizeof(double));
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
+    const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     PlmsStep a;
     a.thr = thr > 0.f ? thr : 0.f;
     a.out_u = b.out_u;
@@ -1187,21 +1111,6 @@ static void sample_plms(bool latent, dsd_handle* h, const dsd_schedule* sc, cons
                  h->plms_B = B; h->plms_n = n; h->plms_steps = sc->steps;
              });
     finish(h, b, s);
-}
-
-int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp, float dynamic_threshold,
-                    const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                    void* stream) {
-    DSD_TRY
-    sample_plms(false, h, sc, g, inp, dynamic_threshold, cond, Cc, x, 1, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, const dsd_inpaint* inp,
-                           float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B, int H,
-                           int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    sample_plms(true, h, sc, g, inp, dynamic_threshold, cond, Cc, x, Cz, philox_seed, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
@@ -1231,33 +1140,22 @@ int dsd_op_plms_step(int order, float a_t, float a_prev, float sqrt_1m_at, const
 
 // ------------------------------------------------------------------------------------------- DDIM inversion
 // ddim.py:263-308: the sampling loops' bindings, the inversion step in place of the update
-static void invert(bool latent, dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                   int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
+int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B,
+               int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
-    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h && h->has_cond));
-    const int out_ch = check_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, Cz);
+    if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
+    const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the inversion takes 1", h->cfg.out_channels);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
-    const LoopBinding b = bind_denoiser(latent, h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
+    const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s, [](int) {}, [&](int k) {
         ddim_invert_step(sc->coef[2 * k], sc->coef[2 * k + 1], b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs, B, Cz, (int)b.hw, s, b.x_bs,
                          out_ch * b.hw);
     });
     finish(h, b, s);
-}
-
-int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
-               int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    invert(false, h, sc, g, cond, Cc, x, 1, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_invert_latent(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                      int Cz, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    invert(true, h, sc, g, cond, Cc, x, Cz, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 
@@ -1309,9 +1207,10 @@ static VlbStep vlb_step(const dsd_schedule* sc, int k, float post_log_var) {
     return a;
 }
 
-static void calc_bpd(bool latent, dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc,
-                     const float* x_start, int Cz, const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps,
-                     void* stream) {
+int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start, int Cz,
+                 const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
     check_bpd_schedule(sc);
     DSD_CHECK(bpd, "null dsd_bpd");
     DSD_CHECK(bpd->post_log_var, "the bound needs the true posterior's log-variances (post_log_var is null; %d steps)", sc->steps);
@@ -1320,7 +1219,7 @@ static void calc_bpd(bool latent, dsd_handle* h, const dsd_schedule* sc, const d
     DSD_CHECK(!(sc->learned_range && Cz > 1) || is_dit(h),
               "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
     const int want_ch = (sc->learned_range ? 2 : 1) * Cz;
-    const int out_ch = check_denoiser(latent, h, nullptr, cond, Cc, x_start, Cz, B, H, W, want_ch);
+    const int out_ch = check_denoiser(h, nullptr, cond, Cc, x_start, Cz, B, H, W, want_ch);
     DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d%s", h->cfg.out_channels,
               out_ch, sc->learned_range ? " (learned_range needs a variance half)" : "");
     set_device(h->device);
@@ -1332,7 +1231,7 @@ static void calc_bpd(bool latent, dsd_handle* h, const dsd_schedule* sc, const d
     // the four-stream model reads its state plane in place: it gets the loop's own; the latent binding copies into lat_in and
     // only finish() would write back
     float* state = latent ? const_cast<float*>(x_start) : h->bpd_buf + part_bytes / sizeof(float);
-    const LoopBinding b = bind_denoiser(latent, h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s);
+    const LoopBinding b = bind_denoiser(h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s);
     const float* c_first = sc->coef;
     if (bpd->prior) prior_bpd(c_first[0], bpd->prior_log_var, x_start, part, bpd->prior, B, n, s);
     run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s,
@@ -1353,20 +1252,6 @@ static void calc_bpd(bool latent, dsd_handle* h, const dsd_schedule* sc, const d
                  vlb_terms(a, k == sc->steps - 1, bpd->vb + k, bpd->xstart_mse + k, bpd->mse + k, sc->steps, B, Cz, (int)hw, s);
              });
     net_check_overflow(h, s);
-}
-
-int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
-                 const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
-    DSD_TRY
-    calc_bpd(false, h, sc, bpd, cond, Cc, x_start, 1, noise, philox_seed, B, H, W, first_step, n_steps, stream);
-    DSD_CATCH
-}
-
-int dsd_calc_bpd_latent(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
-                        int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                        void* stream) {
-    DSD_TRY
-    calc_bpd(true, h, sc, bpd, cond, Cc, x_start, Cz, noise, philox_seed, B, H, W, first_step, n_steps, stream);
     DSD_CATCH
 }
 

@@ -1,7 +1,7 @@
 """DDIMSampler — drop-in for ldm/models/diffusion/ddim.py (make_schedule :25-55, sample :57-126,
 ddim_sampling :128-185, p_sample_ddim :187-261), executed by dsd_sample (mode B_DDIM); with
-``unconditional_guidance_scale`` / ``unconditional_conditioning`` / ``ucg_schedule`` by dsd_sample_guided; with ``mask`` / ``x0``
-by dsd_sample_masked.  encode :263-308 runs dsd_invert, stochastic_encode :310-324 dsd_op_q_sample, decode :326-346 the tail of
+``unconditional_guidance_scale`` / ``unconditional_conditioning`` / ``ucg_schedule`` by dsd_sample with a dsd_guidance; with ``mask`` / ``x0``
+by dsd_sample with a dsd_inpaint.  encode :263-308 runs dsd_invert, stochastic_encode :310-324 dsd_op_q_sample, decode :326-346 the tail of
 the sampling loop."""
 from __future__ import annotations
 

@@ -187,7 +187,7 @@ class LatentDiffusion(DDPM):
     """The sampling surface of ldm/models/diffusion/ddpm.py:526-1115 (LatentDiffusion) as trainers/trainer_latent_diffusion.py
     uses it: a KL first stage (AutoencoderKL) around a native UNetModel under any of the reference's conditioning keys.  ``sample`` (DDPM,
     :1048-1115) and the DDIMSampler / DPMSolverSampler handed this object run in the library's device-resident latent loops
-    (dsd_sample_latent / dsd_sample_dpm_latent).  Training (losses, scale_by_std estimation, EMA, Lightning) is out of scope."""
+    (dsd_sample / dsd_sample_dpm).  Training (losses, scale_by_std estimation, EMA, Lightning) is out of scope."""
 
     def __init__(self, first_stage_config, cond_stage_config=None, num_timesteps_cond=None, cond_stage_key="image",
                  cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None,

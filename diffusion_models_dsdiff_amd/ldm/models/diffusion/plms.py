@@ -1,5 +1,5 @@
 """PLMSSampler — drop-in for ldm/models/diffusion/plms.py (make_schedule :26-57, sample :59-116, plms_sampling :118-176,
-p_sample_plms :178-245 with sampling_util.norm_thresholding), executed by dsd_sample_plms / dsd_sample_plms_latent: the history of
+p_sample_plms :178-245 with sampling_util.norm_thresholding), executed by dsd_sample_plms: the history of
 noise predictions, the first step's predictor / corrector pair, classifier-free guidance, the mask blend and the norm threshold all
 run in the device loop."""
 from __future__ import annotations

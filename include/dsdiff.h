@@ -23,20 +23,19 @@
  *                                        Disc_diff/guided_diffusion/gaussian_diffusion.py:524-616,705-786
  *                                     DDPMModel.p_sample_loop        trainers/trainer_ddpm.py:447-482
  *                                     DDIMSampler.ddim_sampling      ldm/models/diffusion/ddim.py:128-261
- *   dsd_sample_latent              <- DDIMSampler.ddim_sampling / LatentDiffusion.p_sample_loop on VAE latents
+ *                                     the same two on VAE latents (a DSD_BLOCK_UNET / DSD_BLOCK_DIT handle)
  *                                        ldm/models/diffusion/ddim.py:128-261, ldm/models/diffusion/ddpm.py:1048-1115
  *                                        (call sites trainers/trainer_latent_diffusion.py:492-544)
- *   dsd_sample_dpm_latent          <- DPMSolverSampler.sample on VAE latents  ldm/models/diffusion/dpm_solver_new/sampler.py:35-103
- *   dsd_sample_guided / dsd_sample_latent_guided / dsd_sample_dpm_guided / dsd_sample_dpm_latent_guided
- *                                  <- the same samplers with unconditional_guidance_scale / unconditional_conditioning
+ *                                     with g: unconditional_guidance_scale / unconditional_conditioning
  *                                        ldm/models/diffusion/ddim.py:194-219 (p_sample_ddim, ucg_schedule :165-167)
+ *   dsd_sample_dpm                 <- DPMSolverSampler.sample  ldm/models/diffusion/dpm_solver_new/sampler.py:35-103
+ *                                     with g: model_wrapper guidance_type="classifier-free"
  *                                        ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:324-332
- *                                        (model_wrapper guidance_type="classifier-free")
- *   dsd_sample_plms / dsd_sample_plms_latent / dsd_op_plms_step
+ *   dsd_sample_plms / dsd_op_plms_step
  *                                  <- PLMSSampler.sample / p_sample_plms  ldm/models/diffusion/plms.py:59-245
  *                                        with sampling_util.norm_thresholding (dynamic_threshold)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
- *   dsd_sample_dpm_program / dsd_sample_dpm_program_latent / dsd_op_dpm_eval
+ *   dsd_sample_dpm_program / dsd_op_dpm_eval
  *                                  <- DPM_Solver.sample / .inverse with method "multistep" order 1..3, "singlestep",
  *                                        "singlestep_fixed", return_intermediate, guided or not
  *                                        Disc_diff/guided_diffusion/sampler.py:445-501,555-868,1001-1217
@@ -240,7 +239,7 @@ int dsd_graph_stats(dsd_handle* h, int* captures, int* launches);
  * the batch, so a volume gives the same samples however its slices are sharded over GPUs or grouped into batches. */
 int dsd_set_slice_ids(dsd_handle* h, const int64_t* ids_host, int n);
 enum { DSD_MODE_A_DDPM = 0, DSD_MODE_A_DDIM = 1, DSD_MODE_B_DDPM = 2, DSD_MODE_B_DDIM = 3,
-       /* PLMSSampler: dsd_sample_plms / dsd_sample_plms_latent only; every other entry point rejects it */
+       /* PLMSSampler: dsd_sample_plms only; every other entry point rejects it */
        DSD_MODE_B_PLMS = 4 };
 enum { DSD_PRED_EPS = 0, DSD_PRED_X0 = 1, DSD_PRED_V = 2 };
 #define DSD_NCOEF 8
@@ -268,42 +267,113 @@ typedef struct dsd_schedule {
     const int32_t* nonzero;/* host, steps */
 } dsd_schedule;
 
-/* Runs the whole loop on the device.  x: [B,1,H,W] in = x_T, out = x_0 (in place).  cond: [B,Cc,H,W]
- * (Cc in {1,3}) concatenated after x every step (DiffusionWrapper 'concat', ddpm.py:1331-1333).
- * noise: NULL -> on-device Philox4x32-10 N(0,1) from philox_seed; else [steps,B,1,H,W] pre-drawn
- * normals, noise[k] used at iteration k (parity mode).  first_step/n_steps select a sub-range of
- * iterations (n_steps<=0 = all) so a caller can time or checkpoint part of the chain. */
-int dsd_sample(dsd_handle* h, const dsd_schedule* sched, const float* cond, int Cc, float* x, const float* noise,
-               uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
+/* ---- the two kinds of denoiser ---------------------------------------------------------------
+ * Every loop below (dsd_sample, dsd_sample_dpm, dsd_sample_dpm_program, dsd_sample_plms, dsd_invert, dsd_calc_bpd) runs whole on
+ * the device and takes the same (h, ..., cond, Cc, x, Cz, ..., B, H, W, ...): the HANDLE picks the denoiser, the call does not.
+ *   - A model handle (dsd_create: DSUnetModel; dsd_create_disc: UNet_disc_Model) is the four-stream model.  x: [B,1,H,W], so
+ *     Cz must be 1 (anything else is rejected before device work).  cond: [B,Cc,H,W] (Cc in {1,3}; 3 for UNet_disc_Model)
+ *     concatenated after x every step (DiffusionWrapper 'concat', ddpm.py:1331-1333); the planes are read in place.
+ *   - A DSD_BLOCK_UNET handle (the plain UNetModel; with a spatial transformer or a label_emb its context / y come through
+ *     dsd_set_conditioning, below, and Cc may be 0) or a DSD_BLOCK_DIT handle reads the state from its own input.  x: [B,Cz,H,W]
+ *     (VAE latents).  The UNetModel has in_channels = Cz + Cc and out_channels = Cz (2 with a learned-range variance, which needs
+ *     Cz = 1).  cond [B,Cc,H,W] is concatenated after the state: both are copied ONCE into the denoiser's persistent NCHW input,
+ *     and every update writes x_{t-1} straight into its state channels.  dsd_set_graph replay runs on one stream, no forks; the
+ *     Philox counter is (seed, step, slice, channel, pixel).  Replaces DDIMSampler.sample / ddim_sampling
+ *     (ldm/models/diffusion/ddim.py:57-261) and LatentDiffusion.p_sample_loop (ddpm.py:1048-1115) as
+ *     trainers/trainer_latent_diffusion.py:492-544 calls them.
+ *     The DiT is the network the reference's trainer swaps in for the U-Net behind the same DiffusionWrapper
+ *     (trainers/trainer_use_gaussian_diff.py:84-86): in_channels = Cz + Cc (Cc = 0 and cond = NULL for an unconditional DiT),
+ *     H = W = input_size, t as the handle's aux and no labels (none reaches the DiT through the wrapper).  Its output has Cz
+ *     channels, or 2*Cz with learn_sigma (in_channels // 3 * 2, sic): the prediction is channels [0,Cz), the learned-range
+ *     variance of (b, c, p) is channel Cz + c — read by DSD_MODE_A_DDPM with learned_range for any Cz, left unread by every other
+ *     mode and loop (gaussian_diffusion.py:484-485).  DSD_PREC_F16 / DSD_PREC_BF16 apply to the network only: the state, the
+ *     updates and the model output stay fp32.
+ *     Any other block handle is rejected.  Each misfit (channels, size, output channels, learned_range without a variance half)
+ *     is rejected with its numbers before any device work.
+ * x is updated in place (in = x_T, out = the sample).  Schedules, first_step / n_steps (a sub-range of iterations, n_steps <= 0
+ * = all, so a caller can time or checkpoint part of the chain), dsd_set_slice_ids and dsd_set_graph work alike for both kinds.
+ * g: NULL, or classifier-free guidance (dsd_guidance, below).  inp: NULL, or the mask (dsd_inpaint, below). */
+/* ---- classifier-free guidance -------------------------------------------------------------
+ * The reference's unconditional_guidance_scale / unconditional_conditioning (DDIMSampler.sample, DPMSolverSampler.sample,
+ * model_wrapper(guidance_type="classifier-free")).  Per step the denoiser is evaluated in ONE pass over 2B rows —
+ * x_in = cat([x]*2), c_in = cat([uncond, cond]) (ddim.py:197-218) — in library-owned buffers, and the two output halves are
+ * combined in front of the update, each sampler in its reference's order (fp32, nothing contracted):
+ *   DDIM        out   = out_u   + s*(out_c   - out_u)    on the raw network outputs (ddim.py:219), then the B_DDIM update
+ *   DPM-Solver  noise = noise_u + s*(noise_c - noise_u)  on the noise predictions each half forms from its own output and the
+ *               shared x_t (dpm_solver_pytorch.py:324-332), then data prediction / thresholding (quantile per logical sample) /
+ *               multistep update
+ * The update writes x_{t-1} to both state rows of a sample.  Noise (fed: [steps,B,..]; Philox) and dsd_set_slice_ids are keyed by
+ * the B logical samples, never by the 2B rows: a guided run with seed S draws the normals of the unguided run with seed S.
+ * dsd_set_share_zero_streams, the stream lanes and dsd_set_graph replay work as in the unguided loops.
+ * uncond: device, laid out like cond ([B,Cc,H,W]).  scale: host, one fp32 scale per executed step (a constant
+ * unconditional_guidance_scale is the array filled with it; ucg_schedule is the array itself, ddim.py:165-167); n_scale must
+ * equal the schedule's steps.  A step whose scale is 1.0 still runs the guided arithmetic.  The callers keep guidance OFF
+ * (uncond None or scale 1.0, ddim.py:194) by passing g = NULL.  Where a loop takes g: dsd_sample in DSD_MODE_B_DDIM only (the
+ * reference has no guidance in the family-A loops or the DDPM loop) and without a learned-range variance; dsd_sample_dpm,
+ * dsd_sample_dpm_program (scale[k] belongs to network evaluation k), dsd_sample_plms and dsd_invert; dsd_calc_bpd takes none. */
+typedef struct dsd_guidance {
+    const float* uncond;   /* device, [B,Cc,H,W] like cond */
+    const float* scale;    /* host, n_scale */
+    int32_t n_scale;
+} dsd_guidance;
+/* ---- masked sampling (image-to-image, inpainting) --------------------------------------------
+ * Masked sampling (DDIMSampler.sample(mask=, x0=), ddim.py:160-163; LatentDiffusion.p_sample_loop(mask=, x0=), ddpm.py:1085-1087):
+ *   img_orig = sqrt_acp[t]*x0 + sqrt_1m_acp[t]*z        (q_sample, ddpm.py:356-359; coef[k][0], coef[k][1] of the iteration)
+ *   x        = img_orig*mask + (1 - mask)*x             (mask 1 keeps x0, 0 samples)
+ * DSD_MODE_B_DDIM blends BEFORE the network evaluation of every executed iteration (none after the last update);
+ * DSD_MODE_B_DDPM blends AFTER every update, the last included, so the kept region ends as q_sample(x0, 0).  The family-A
+ * loops have no mask in the reference and are rejected; so is a masked B_DDPM loop with guidance.
+ * z: noise[k] of the fed [steps,B,Cz,H,W], or Philox normals of the stream (philox_seed, k + 2^32) — the update of iteration k
+ * draws from (philox_seed, k) — keyed by logical sample and dsd_set_slice_ids like the update's noise.
+ * The blend runs outside the captured network (dsd_set_graph), next to the update.  inp = NULL: unmasked.  dsd_sample and
+ * dsd_sample_plms take inp (the latter blends in front of the first network evaluation of every iteration, as B_DDIM does). */
+typedef struct dsd_inpaint {
+    const float* x0;        /* device, [B,Cz,H,W] like the state */
+    const float* mask;      /* device, [B,mask_channels,H,W] */
+    int32_t mask_channels;  /* 1 (broadcast over the state's channels) or Cz */
+    const float* noise;     /* device, [steps,B,Cz,H,W] blend noise, or NULL: Philox */
+} dsd_inpaint;
+/* ---- cross-attention and vector conditioning of the latent loops ----------------------------
+ * The conditioning keys beside 'concat' that the reference's latent inference runs on: trainers/trainer_latent_diffusion.py:153-189
+ * builds {"c_crossattn": [c], "c_adm": c_adm, "c_concat": [...]}, :492-524 samples with an unconditional_conditioning dict that
+ * replaces c_crossattn and keeps c_adm / c_concat, DiffusionWrapper.forward (ldm/models/diffusion/ddpm.py:1328-1365) dispatches
+ * 'crossattn', 'hybrid', 'adm', 'hybrid-adm', 'crossattn-adm', and UNetModel.forward
+ * (ldm/modules/diffusionmodules/openaimodel.py:926-958) adds label_emb(y) (:696-712) to the time embedding.
+ * dsd_set_conditioning installs one bundle on a DSD_BLOCK_UNET handle; NULL clears it.  The struct holds DEVICE pointers that
+ * must stay valid until the bundle is cleared or replaced; the library reads them when a call binds:
+ *   - every loop (dsd_sample ... dsd_calc_bpd, masked and guided alike) copies the parts once per call into buffers of its own
+ *     of `rows` rows (rows = B, or 2B under a dsd_guidance: the unconditional twins first, as for the denoiser's input), which the network
+ *     reads every step; a cached plan or a replayed graph sees stable addresses, a different `tokens` re-plans.  The context
+ *     projections run every step, as in the reference.
+ *   - dsd_block_forward on a DSD_BLOCK_UNET handle with label_emb reads y (B rows) from the bundle; its context stays aux2.
+ * Checked before any device work, each misfit with its numbers: a spatial-transformer handle without a context and a context
+ * for a handle without one; y if and only if the handle has label_emb; y_width against the handle's kind (0 for int classes,
+ * 1 for "continuous", adm_in_channels for "sequential"); B against the call's; int labels outside [0, num_classes).  Under a
+ * dsd_guidance every part that is set needs its unconditional twin (a twin equal to the conditional part is legal: the
+ * reference's c_adm), and Cc = 0 is allowed when a context or y is there to be replaced (g->uncond may then be NULL).  DSD_BLOCK_DIT
+ * and four-stream handles refuse any bundle. */
+typedef struct dsd_conditioning {
+    const float* context;        /* [B,tokens,context_dim], or NULL */
+    const float* context_uncond; /* [B,tokens,context_dim], or NULL */
+    int32_t tokens;              /* context length */
+    const void* y;               /* int64 [B] (y_width 0) or fp32 [B,y_width], or NULL */
+    const void* y_uncond;        /* like y, or NULL */
+    int32_t y_width;             /* 0 = int64 labels, else fp32 floats per row */
+    int32_t B;                   /* batch size */
+} dsd_conditioning;
+int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c);
+
+/* DDPM / DDIM (dsd_schedule).  noise: NULL -> on-device Philox4x32-10 N(0,1) from philox_seed; else [steps,B,Cz,H,W] pre-drawn
+ * normals, noise[k] used at iteration k (parity mode). */
+int dsd_sample(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond, int Cc,
+               float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
+               void* stream);
 /* The fused sampler update alone (iteration k): model_out [B,Cm,H,W]; x updated in place; pred_xstart
  * (optional, [B,1,H,W]) receives the clipped x_0 prediction (the reference's out["pred_xstart"]).  A state of Cz channels is B*Cz
  * one-channel images; with a learned-range variance it is B images of (Cz*H) x W: the output row [mean(Cz), variance(Cz)] is
  * the one-channel layout at that height, and element (b, c, p) keeps its Philox counter b*Cz*H*W + c*H*W + p. */
 int dsd_op_sampler_update(const dsd_schedule* sched, int k, const float* model_out, float* x, const float* noise,
                           uint64_t philox_seed, int B, int H, int W, float* pred_xstart, void* stream);
-
-/* ---- latent sampling loops (DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser) --------------------
- * The loops of dsd_sample / dsd_sample_dpm on a multi-channel state: x [B,Cz,H,W] (VAE latents, in = x_T, out = sample, in
- * place) denoised by a DSD_BLOCK_UNET handle (the plain UNetModel; with a spatial transformer or a label_emb its context / y come through
- * dsd_set_conditioning, below, and Cc may be 0) with in_channels = Cz + Cc and
- * out_channels = Cz (2 with a learned-range variance, which needs Cz = 1).  cond [B,Cc,H,W] is concatenated after the state
- * (DiffusionWrapper 'concat', ldm/models/diffusion/ddpm.py:1331-1333): both are copied ONCE into the denoiser's persistent
- * NCHW input, and every update writes x_{t-1} straight into its state channels.  Schedules, first_step / n_steps,
- * dsd_set_slice_ids (Philox counter (seed, step, slice, channel, pixel)) and dsd_set_graph replay (one stream, no forks) work
- * as for the four-stream model.  noise: NULL -> Philox, else [steps,B,Cz,H,W].
- * Replaces DDIMSampler.sample / ddim_sampling (ldm/models/diffusion/ddim.py:57-261) and LatentDiffusion.p_sample_loop
- * (ddpm.py:1048-1115) as trainers/trainer_latent_diffusion.py:492-544 calls them.
- * Every *_latent* entry (this one, _guided, _masked, dsd_sample_dpm_latent(_guided), dsd_sample_plms_latent, dsd_invert_latent)
- * also takes a DSD_BLOCK_DIT handle, the network the reference's trainer swaps in for the U-Net behind the same DiffusionWrapper
- * (trainers/trainer_use_gaussian_diff.py:84-86): in_channels = Cz + Cc (Cc = 0 and cond = NULL for an unconditional DiT),
- * H = W = input_size, t as the handle's aux and no labels (none reaches the DiT through the wrapper).  Its output has Cz
- * channels, or 2*Cz with learn_sigma (in_channels // 3 * 2, sic): the prediction is channels [0,Cz), the learned-range variance
- * of (b, c, p) is channel Cz + c — read by DSD_MODE_A_DDPM with learned_range for any Cz, left unread by every other mode
- * (gaussian_diffusion.py:484-485).  Each misfit (channels, size, output channels, learned_range without a variance half) is
- * rejected with its numbers before any device work.  DSD_PREC_F16 / DSD_PREC_BF16 apply to the network only: the state, the
- * updates and the model output stay fp32. */
-int dsd_sample_latent(dsd_handle* h, const dsd_schedule* sched, const float* cond, int Cc, float* x, int Cz, const float* noise,
-                      uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
 
 /* ---- DPM-Solver(++) multistep sampler -----------------------------------------------------
  * Replaces DPM_Solver(...).sample(method="multistep", order<=2) of Disc_diff/guided_diffusion/sampler.py:1017-1222
@@ -329,53 +399,15 @@ typedef struct dsd_dpm_schedule {
     const float* t_input;     /* host, steps: fp32 model time (t - 1/N)*1000, sampler.py:236-245 */
     const int32_t* order;     /* host, steps */
 } dsd_dpm_schedule;
-/* x: [B,1,H,W] in = x_T, out = sample (in place); cond as in dsd_sample.  A 2-channel (learned-sigma) network
- * contributes its first channel only (gaussian_diffusion.py:484-485). */
-int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int B, int H, int W,
-                   void* stream);
-/* dsd_sample_dpm on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET denoiser (out_channels = Cz) or a DSD_BLOCK_DIT one
- * (Cz or 2*Cz output channels, the first Cz read), set up as in dsd_sample_latent.  Dynamic thresholding takes the quantile per sample over all Cz*H*W elements (dynamic_thresholding_fn,
- * ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:418).  Replaces DPMSolverSampler.sample (sampler.py:35-103). */
-int dsd_sample_dpm_latent(dsd_handle* h, const dsd_dpm_schedule* sched, const float* cond, int Cc, float* x, int Cz, int B, int H,
-                          int W, void* stream);
+/* A four-stream network with 2 output channels (learned sigma) contributes its first only (gaussian_diffusion.py:484-485); a DiT
+ * its first Cz.  Dynamic thresholding takes the quantile per sample over all Cz*H*W elements (dynamic_thresholding_fn,
+ * ldm/models/diffusion/dpm_solver_new/dpm_solver_pytorch.py:418). */
+int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
+                   int B, int H, int W, void* stream);
 /* Iteration k's post-network part alone: model_out [B,Cm,H,W], x updated in place, m_cur [B,1,H,W] receives m_k,
  * m_prev = m_{k-1} (may be NULL when order[k] < 2). */
 int dsd_op_dpm_step(const dsd_dpm_schedule* sched, int k, const float* model_out, int Cm, float* x, float* m_cur,
                     const float* m_prev, int B, int H, int W, void* stream);
-/* ---- classifier-free guidance -------------------------------------------------------------
- * The reference's unconditional_guidance_scale / unconditional_conditioning (DDIMSampler.sample, DPMSolverSampler.sample,
- * model_wrapper(guidance_type="classifier-free")).  Per step the denoiser is evaluated in ONE pass over 2B rows —
- * x_in = cat([x]*2), c_in = cat([uncond, cond]) (ddim.py:197-218) — in library-owned buffers, and the two output halves are
- * combined in front of the update, each sampler in its reference's order (fp32, nothing contracted):
- *   DDIM        out   = out_u   + s*(out_c   - out_u)    on the raw network outputs (ddim.py:219), then the B_DDIM update
- *   DPM-Solver  noise = noise_u + s*(noise_c - noise_u)  on the noise predictions each half forms from its own output and the
- *               shared x_t (dpm_solver_pytorch.py:324-332), then data prediction / thresholding (quantile per logical sample) /
- *               multistep update
- * The update writes x_{t-1} to both state rows of a sample.  Noise (fed: [steps,B,..]; Philox) and dsd_set_slice_ids are keyed by
- * the B logical samples, never by the 2B rows: a guided run with seed S draws the normals of the unguided run with seed S.
- * dsd_set_share_zero_streams, the stream lanes and dsd_set_graph replay work as in the unguided loops.
- * uncond: device, laid out like cond ([B,Cc,H,W]).  scale: host, one fp32 scale per executed step (a constant
- * unconditional_guidance_scale is the array filled with it; ucg_schedule is the array itself, ddim.py:165-167); n_scale must
- * equal the schedule's steps.  A step whose scale is 1.0 still runs the guided arithmetic.  The callers keep guidance OFF
- * (uncond None or scale 1.0, ddim.py:194) on the unguided entry points. */
-typedef struct dsd_guidance {
-    const float* uncond;   /* device, [B,Cc,H,W] like cond */
-    const float* scale;    /* host, n_scale */
-    int32_t n_scale;
-} dsd_guidance;
-/* dsd_sample with guidance: DSD_MODE_B_DDIM only (the reference has no guidance in the family-A loops or the DDPM loop), no
- * learned-range variance.  Other arguments as dsd_sample. */
-int dsd_sample_guided(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                      const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
-/* dsd_sample_latent with guidance (DSD_MODE_B_DDIM only): the denoiser's persistent NCHW input holds 2B rows. */
-int dsd_sample_latent_guided(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                             int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                             void* stream);
-/* dsd_sample_dpm / dsd_sample_dpm_latent with guidance; scale[k] belongs to network evaluation k. */
-int dsd_sample_dpm_guided(dsd_handle* h, const dsd_dpm_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                          int B, int H, int W, void* stream);
-int dsd_sample_dpm_latent_guided(dsd_handle* h, const dsd_dpm_schedule* sched, const dsd_guidance* g, const float* cond, int Cc,
-                                 float* x, int Cz, int B, int H, int W, void* stream);
 /* One guided update alone (iteration k, DSD_MODE_B_DDIM).  out_uncond / out_cond: the two [B,Cz,H,W] halves of the network
  * output.  x: the 2B-row state, logical sample b at x + b*x_row_stride and x + (B+b)*x_row_stride (x_row_stride = 0: Cz*H*W,
  * i.e. a contiguous [2B,Cz,H,W]); the first B rows are read, all 2B receive x_{t-1}.  noise [B,Cz,H,W] or NULL (Philox),
@@ -388,37 +420,6 @@ int dsd_op_sampler_update_guided(const dsd_schedule* sched, int k, const float* 
 int dsd_op_dpm_step_guided(const dsd_dpm_schedule* sched, int k, const float* out_uncond, const float* out_cond, int Cm, float scale,
                            float* x, int64_t x_row_stride, float* m_cur, const float* m_prev, int B, int Cz, int H, int W,
                            void* stream);
-/* ---- cross-attention and vector conditioning of the latent loops ----------------------------
- * The conditioning keys beside 'concat' that the reference's latent inference runs on: trainers/trainer_latent_diffusion.py:153-189
- * builds {"c_crossattn": [c], "c_adm": c_adm, "c_concat": [...]}, :492-524 samples with an unconditional_conditioning dict that
- * replaces c_crossattn and keeps c_adm / c_concat, DiffusionWrapper.forward (ldm/models/diffusion/ddpm.py:1328-1365) dispatches
- * 'crossattn', 'hybrid', 'adm', 'hybrid-adm', 'crossattn-adm', and UNetModel.forward
- * (ldm/modules/diffusionmodules/openaimodel.py:926-958) adds label_emb(y) (:696-712) to the time embedding.
- * dsd_set_conditioning installs one bundle on a DSD_BLOCK_UNET handle; NULL clears it.  The struct holds DEVICE pointers that
- * must stay valid until the bundle is cleared or replaced; the library reads them when a call binds:
- *   - every latent entry (dsd_sample_latent*, dsd_sample_dpm*_latent*, dsd_sample_plms_latent, dsd_invert_latent,
- *     dsd_calc_bpd_latent, masked and guided variants) copies the parts once per call into buffers of its own of `rows` rows
- *     (rows = B, or 2B under a dsd_guidance: the unconditional twins first, as for the denoiser's input), which the network
- *     reads every step; a cached plan or a replayed graph sees stable addresses, a different `tokens` re-plans.  The context
- *     projections run every step, as in the reference.
- *   - dsd_block_forward on a DSD_BLOCK_UNET handle with label_emb reads y (B rows) from the bundle; its context stays aux2.
- * Checked before any device work, each misfit with its numbers: a spatial-transformer handle without a context and a context
- * for a handle without one; y if and only if the handle has label_emb; y_width against the handle's kind (0 for int classes,
- * 1 for "continuous", adm_in_channels for "sequential"); B against the call's; int labels outside [0, num_classes).  Under a
- * dsd_guidance every part that is set needs its unconditional twin (a twin equal to the conditional part is legal: the
- * reference's c_adm), and Cc = 0 is allowed when a context or y is there to be replaced (g->uncond may then be NULL).  DSD_BLOCK_DIT
- * and four-stream handles refuse any bundle. */
-typedef struct dsd_conditioning {
-    const float* context;        /* [B,tokens,context_dim], or NULL */
-    const float* context_uncond; /* [B,tokens,context_dim], or NULL */
-    int32_t tokens;              /* context length */
-    const void* y;               /* int64 [B] (y_width 0) or fp32 [B,y_width], or NULL */
-    const void* y_uncond;        /* like y, or NULL */
-    int32_t y_width;             /* 0 = int64 labels, else fp32 floats per row */
-    int32_t B;                   /* batch size */
-} dsd_conditioning;
-int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c);
-
 /* ---- the DPM-Solver family as a program of evaluations -------------------------------------
  * Replaces DPM_Solver(...).sample / .inverse of Disc_diff/guided_diffusion/sampler.py:1001-1217 (and of the twin
  * dpm_solver_pytorch.py) for method = "multistep" with order 1..3 (:818-868 adds the third), "singlestep" and "singlestep_fixed"
@@ -465,57 +466,27 @@ typedef struct dsd_dpm_program {
     const int32_t* slot;      /* host, n_eval*4: plane written, planes read as ma, mb, mc (unread ones: any value in 0..2) */
     const int32_t* keep;      /* host, n_eval, or NULL = none kept */
 } dsd_dpm_program;
-/* x [B,1,H,W] in place with the four-stream model, cond as in dsd_sample.  g: NULL, or classifier-free guidance with one scale
- * per evaluation.  intermediates: NULL, or device [n_kept,B,1,H,W] (n_kept = the nonzero keep entries), filled in order.
- * dsd_set_graph, the stream lanes and dsd_set_slice_ids work as in the other loops. */
+/* g carries one scale per evaluation.  intermediates: NULL, or device [n_kept,B,Cz,H,W] (n_kept = the nonzero keep entries),
+ * filled in order. */
 int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                           int B, int H, int W, float* intermediates, void* stream);
-/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, as dsd_sample_dpm_latent. */
-int dsd_sample_dpm_program_latent(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc,
-                                  float* x, int Cz, int B, int H, int W, float* intermediates, void* stream);
+                           int Cz, int B, int H, int W, float* intermediates, void* stream);
 /* Evaluation k's post-network part alone (host loops, kernel-level tests).  out_cond [B,Cm*Cz,H,W] is the network output
  * (Cm = 1, or 2 with a learned sigma in the second half of the channels, which is left unread; any Cz); out_uncond NULL, or the unconditional half: then x holds 2B rows as in dsd_op_dpm_step_guided and both rows of a sample are
  * written.  hist: the three history planes [3,B,Cz,H,W]; base [B,Cz,H,W] (may be NULL for the multistep kinds). */
 int dsd_op_dpm_eval(const dsd_dpm_program* prog, int k, const float* out_uncond, const float* out_cond, int Cm, float scale, float* x,
                     int64_t x_row_stride, float* hist, float* base, int B, int Cz, int H, int W, void* stream);
-/* ---- image-to-image: masked sampling and DDIM inversion -----------------------------------
- * Masked sampling (DDIMSampler.sample(mask=, x0=), ddim.py:160-163; LatentDiffusion.p_sample_loop(mask=, x0=), ddpm.py:1085-1087):
- *   img_orig = sqrt_acp[t]*x0 + sqrt_1m_acp[t]*z        (q_sample, ddpm.py:356-359; coef[k][0], coef[k][1] of the iteration)
- *   x        = img_orig*mask + (1 - mask)*x             (mask 1 keeps x0, 0 samples)
- * DSD_MODE_B_DDIM blends BEFORE the network evaluation of every executed iteration (none after the last update);
- * DSD_MODE_B_DDPM blends AFTER every update, the last included, so the kept region ends as q_sample(x0, 0).  The family-A
- * loops have no mask in the reference and are rejected; so is a masked B_DDPM loop with guidance.
- * z: noise[k] of the fed [steps,B,Cz,H,W], or Philox normals of the stream (philox_seed, k + 2^32) — the update of iteration k
- * draws from (philox_seed, k) — keyed by logical sample and dsd_set_slice_ids like the update's noise.
- * The blend runs outside the captured network (dsd_set_graph), next to the update; first_step / n_steps as in dsd_sample. */
-typedef struct dsd_inpaint {
-    const float* x0;        /* device, [B,Cz,H,W] like the state */
-    const float* mask;      /* device, [B,mask_channels,H,W] */
-    int32_t mask_channels;  /* 1 (broadcast over the state's channels) or Cz */
-    const float* noise;     /* device, [steps,B,Cz,H,W] blend noise, or NULL: Philox */
-} dsd_inpaint;
-/* dsd_sample / dsd_sample_guided (g != NULL) with a mask; dsd_sample_latent / dsd_sample_latent_guided with a mask. */
-int dsd_sample_masked(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp, const float* cond,
-                      int Cc, float* x, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps,
-                      void* stream);
-int dsd_sample_latent_masked(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
-                             const float* cond, int Cc, float* x, int Cz, const float* noise, uint64_t philox_seed, int B, int H,
-                             int W, int first_step, int n_steps, void* stream);
-/* DDIM inversion (DDIMSampler.encode, ddim.py:263-308).  Iteration i evaluates the network at model time t_model[i] — the
- * reference passes the loop index i itself (:282), not a timestep of the schedule; the caller fills t_model accordingly — and
- * applies x <- coef[2i]*x + coef[2i+1]*e  (xt_weighted + weighted_noise_pred, :292-295), e the network output or, with guidance,
+/* ---- DDIM inversion (DDIMSampler.encode, ddim.py:263-308) ----------------------------------
+ * Iteration i evaluates the network at model time t_model[i] — the reference passes the loop index i itself (:282), not a
+ * timestep of the schedule; the caller fills t_model accordingly — and applies x <- coef[2i]*x + coef[2i+1]*e  (xt_weighted + weighted_noise_pred, :292-295), e the network output or, with guidance,
  * e_u + s*(e_c - e_u) (:287-290).  coef: host, produced with the reference's expressions and dtypes, rounded to fp32 once. */
 typedef struct dsd_invert_schedule {
     int32_t steps;
     const float* coef;      /* host, steps*2: cx, ce */
     const float* t_model;   /* host, steps */
 } dsd_invert_schedule;
-/* x: [B,1,H,W] (four-stream model) / [B,Cz,H,W] (DSD_BLOCK_UNET, DSD_BLOCK_DIT) in = x0, out = the encoded state, in place.  g: NULL or the
- * guidance (2B network rows per step, as in the guided sampling loops). */
-int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x, int B,
-               int H, int W, int first_step, int n_steps, void* stream);
-int dsd_invert_latent(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x,
-                      int Cz, int B, int H, int W, int first_step, int n_steps, void* stream);
+/* x: in = x0, out = the encoded state, in place. */
+int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sched, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
+               int B, int H, int W, int first_step, int n_steps, void* stream);
 /* The blend alone.  x: state rows at x + b*x_row_stride (0: Cz*H*W); guided != 0: the 2B-row state, row b is read, rows b and
  * B+b are written.  noise [B,Cz,H,W] or NULL: Philox stream (philox_seed, step + 2^32). */
 int dsd_op_mask_blend(float a, float s, const float* x0, const float* mask, int mask_channels, float* x, int64_t x_row_stride,
@@ -544,8 +515,8 @@ int dsd_op_ddim_invert_step(float cx, float ce, const float* out_uncond, const f
  * dsd_set_slice_ids.  Column k of the [B,steps] outputs is iteration k: the reference's stack order.  first_step / n_steps
  * and dsd_set_graph work as in dsd_sample; columns outside the range are left as they are.
  * Rejected before any device work: a mode other than DSD_MODE_A_DDPM, null outputs or a null post_log_var, learned_range on a
- * model without a variance half, and the channel / shape / slice-id misfits of the sampling loops.  The entry points take no
- * dsd_guidance: the reference evaluates the bound unguided. */
+ * model without a variance half, and the channel / shape / slice-id misfits of the sampling loops.  It takes no dsd_guidance:
+ * the reference evaluates the bound unguided. */
 typedef struct dsd_bpd {
     const float* post_log_var; /* host, steps: posterior_log_variance_clipped[t] in iteration order (fp32 of the float64 table) */
     float* vb;                 /* device, [B,steps] */
@@ -555,11 +526,7 @@ typedef struct dsd_bpd {
     float prior_log_var;       /* log(1 - alphas_cumprod[T-1]) */
 } dsd_bpd;
 int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sched, const dsd_bpd* bpd, const float* cond, int Cc, const float* x_start,
-                 const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
-/* The same on x_start [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, set up as in dsd_sample_latent. */
-int dsd_calc_bpd_latent(dsd_handle* h, const dsd_schedule* sched, const dsd_bpd* bpd, const float* cond, int Cc,
-                        const float* x_start, int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step,
-                        int n_steps, void* stream);
+                 int Cz, const float* noise, uint64_t philox_seed, int B, int H, int W, int first_step, int n_steps, void* stream);
 /* The terms of iteration k alone, on caller buffers: model_out rows at model_out + b*out_row_stride (0: Cz*H*W, or 2*Cz*H*W
  * with learned_range), x_t rows at x_t + b*x_row_stride (0: Cz*H*W), x_start and noise [B,Cz,H,W] (noise NULL: Philox stream
  * (philox_seed, k + 2^32)).  Sample b's scalars go to vb / xstart_mse / mse [b*term_stride] (0: 1; each may be NULL); mean /
@@ -580,7 +547,7 @@ int dsd_op_ddim_reverse_step(const dsd_schedule* sched, int k, float alpha_bar_n
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
- * dsd_sample_guided) and combines the noise prediction e_t with the up to three earlier ones (plms.py:228-241, fp32, left to
+ * the guided dsd_sample) and combines the noise prediction e_t with the up to three earlier ones (plms.py:228-241, fp32, left to
  * right, true division):
  *   k = 0   x' = upd(e_t); e_next = network(x', t_model[min(1, steps-1)]); e' = (e_t + e_next) / 2     (two evaluations)
  *   k = 1   e' = (3 e_t - o1) / 2          k = 2   e' = (23 e_t - 16 o1 + 5 o2) / 12
@@ -592,17 +559,12 @@ int dsd_op_ddim_reverse_step(const dsd_schedule* sched, int k, float alpha_bar_n
  * the history the previous call on this handle left for iteration k (same B, state shape and schedule length), and fails
  * otherwise; split runs are bit-identical to the whole run.  The threshold's per-sample sum is formed from fixed per-block
  * partial sums in fp64, combined in a fixed order: two runs are bit-identical.
- * g: NULL or the guidance; inp: NULL or the mask, blended in front of the (first) network evaluation of every iteration as in
- * the masked DDIM loop, with inp->noise / Philox stream (philox_seed, k + 2^32).  dynamic_threshold <= 0: off.
+ * inp is blended with inp->noise / Philox stream (philox_seed, k + 2^32).  dynamic_threshold <= 0: off.
  * Rejected: any other mode, sigma != 0, learned_range, a prediction type other than DSD_PRED_EPS (the reference feeds the
  * network output to the update as a noise prediction whatever the parameterization). */
 int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
-                    float dynamic_threshold, const float* cond, int Cc, float* x, uint64_t philox_seed, int B, int H, int W,
+                    float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B, int H, int W,
                     int first_step, int n_steps, void* stream);
-/* The same on a latent state x [B,Cz,H,W] with a DSD_BLOCK_UNET or DSD_BLOCK_DIT denoiser, set up as in dsd_sample_latent. */
-int dsd_sample_plms_latent(dsd_handle* h, const dsd_schedule* sched, const dsd_guidance* g, const dsd_inpaint* inp,
-                           float dynamic_threshold, const float* cond, int Cc, float* x, int Cz, uint64_t philox_seed, int B,
-                           int H, int W, int first_step, int n_steps, void* stream);
 /* One PLMS update (with its norm pass) on caller buffers.  order: DSD_PLMS_PREDICT / DSD_PLMS_CORRECT are the two halves of
  * iteration 0 around its second network evaluation, DSD_PLMS_AB2..AB4 the multistep updates on 1..3 earlier predictions.
  * out_uncond == NULL: e = out_cond [B,Cz,H,W], x has B rows; else the guided combination and x is the 2B-row state (row b

@@ -23,6 +23,44 @@ def test_header_symbols_exported():
     assert sorted(_lib.EXPORTS) == names, "python binding list out of sync with the header"
 
 
+# one entry point per device loop (the handle picks the denoiser, g / inp are nullable), and the per-variant twins each once had
+VARIANTS = {"dsd_sample": ("_latent", "_guided", "_latent_guided", "_masked", "_latent_masked"),
+            "dsd_sample_dpm": ("_latent", "_guided", "_latent_guided"), "dsd_sample_dpm_program": ("_latent",),
+            "dsd_sample_plms": ("_latent",), "dsd_invert": ("_latent",), "dsd_calc_bpd": ("_latent",)}
+LOOPS = tuple(VARIANTS)
+REMOVED = [loop + v for loop, vs in VARIANTS.items() for v in vs]
+
+
+def test_one_entry_point_per_device_loop():
+    names = header_functions()
+    assert len(REMOVED) == 12
+    for n in LOOPS:
+        assert n in names and n in _lib.EXPORTS, n
+    for n in REMOVED:
+        assert n not in names, f"{n} is declared in include/dsdiff.h again"
+        assert n not in _lib.EXPORTS, n
+
+
+def test_loop_signatures_match_header():
+    """Parameter count, scalar types and pointer sizes of the ctypes argtypes against the declaration, for every device loop and
+    dsd_op_plms_step."""
+    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dsdiff.h")).read(), flags=re.S)
+    L = _lib.lib()
+    ctype = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float}
+    for sym in LOOPS + ("dsd_op_plms_step",):
+        assert sym in _lib.EXPORTS
+        decl = re.search(r"\bint %s\((.*?)\);" % sym, code, flags=re.S)
+        assert decl, sym
+        params = [p.strip() for p in decl.group(1).split(",")]
+        argtypes = getattr(L, sym).argtypes
+        assert argtypes is not None and len(argtypes) == len(params), (sym, argtypes and len(argtypes), len(params))
+        for p, a in zip(params, argtypes):                                    # scalars by type; every pointer is pointer-sized
+            if "*" in p:
+                assert C.sizeof(a) == C.sizeof(C.c_void_p), (sym, p)
+            else:
+                assert a is ctype[p.split()[0]], (sym, p, a)
+
+
 def test_struct_layouts_match_header():
     # dsd_config: 3 + 1 + 8 + 8 + 1 + 8 + 7 int32 ; dsd_schedule: 5 int32 + float + 3 pointers
     assert C.sizeof(_lib.DsdConfig) == 4 * (3 + 1 + 8 + 8 + 1 + 8 + 7)

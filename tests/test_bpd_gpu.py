@@ -1,5 +1,5 @@
 """Variational bound on the MI355X: the terms / prior / ddim-reverse kernels against the fixture the reference generated
-(tests/golden/bpd.npz, tests/golden/gen_bpd.py), and the device loop dsd_calc_bpd(_latent) against the per-step path, the
+(tests/golden/bpd.npz, tests/golden/gen_bpd.py), and the device loop dsd_calc_bpd against the per-step path, the
 reference's recorded loops and its own invariants.
 
 Bars.  Scalars (vb, xstart_mse, mse, prior): the reference's fp32 result is only so close to exact arithmetic (the KL's
@@ -380,7 +380,7 @@ def test_rejections_leave_outputs_and_x_start_untouched():
         bpd.vb, bpd.xstart_mse, bpd.mse, bpd.prior = (out[k].data_ptr() for k in ("vb", "xstart_mse", "mse", "prior_bpd"))
         for k in null:
             setattr(bpd, k, None)
-        return L.lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), L.dptr(cond), cond.shape[1], L.dptr(x_start), None,
+        return L.lib().dsd_calc_bpd(unet._h, C.byref(sched.c), C.byref(bpd), L.dptr(cond), cond.shape[1], L.dptr(x_start), 1, None,
                                     C.c_uint64(1), B, x_start.shape[2], x_start.shape[3], 0, 0, L.stream_ptr())
     for field, msg in (("vb", b"null output"), ("mse", b"null output"), ("post_log_var", b"post_log_var is null; 10 steps")):
         assert raw(**{field: True}) != 0 and msg in L.lib().dsd_last_error(), field

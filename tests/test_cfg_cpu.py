@@ -206,6 +206,5 @@ def test_guidance_struct_and_header_agree():
     from diffusion_models_dsdiff_amd import _lib
     assert C.sizeof(_lib.DsdGuidance) == 24 and _lib.DsdGuidance.scale.offset == 8 and _lib.DsdGuidance.n_scale.offset == 16
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dsdiff.h")).read()
-    for sym in ("dsd_sample_guided", "dsd_sample_latent_guided", "dsd_sample_dpm_guided", "dsd_sample_dpm_latent_guided",
-                "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided"):
+    for sym in ("dsd_sample", "dsd_sample_dpm", "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided"):
         assert sym in _lib.EXPORTS and re.search(r"\bint %s\(" % sym, hdr), sym

@@ -280,7 +280,7 @@ def test_uncond_equal_cond_is_the_unguided_run_with_the_same_philox_noise(env):
 
 # ---------------------------------------------------------------------------------------- device loop vs host loop, graph replay
 def test_device_loop_matches_host_loop_and_graph_replay(env):
-    """dsd_sample_guided / dsd_sample_latent_guided against the loop written here — one 2B forward through the module, then
+    """dsd_sample with a dsd_guidance (both denoisers) against the loop written here — one 2B forward through the module, then
     the guided update op — with the same fed noise; hipGraph replay bit-identical to host launches; first_step / n_steps."""
     from diffusion_models_dsdiff_amd._sched import Guidance, run_device_loop, sampler_update_guided
     L = _lib()
@@ -363,11 +363,8 @@ def test_guided_loops_reject_what_the_reference_does_not_have(env):
     scales = np.full(STEPS, 3.0, np.float32)
 
     def call(guid):
-        if e["key"] == "lat":
-            return L.lib().dsd_sample_latent_guided(unet._h, C.byref(sched.c), C.byref(guid), L.dptr(c), c.shape[1], L.dptr(x), Cz,
-                                                    None, C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
-        return L.lib().dsd_sample_guided(unet._h, C.byref(sched.c), C.byref(guid), L.dptr(c), c.shape[1], L.dptr(x), None,
-                                         C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
+        return L.lib().dsd_sample(unet._h, C.byref(sched.c), C.byref(guid), None, L.dptr(c), c.shape[1], L.dptr(x), Cz, None,
+                                  C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
     guid = L.DsdGuidance(u.data_ptr(), scales.ctypes.data_as(C.POINTER(C.c_float)), STEPS - 1)
     assert call(guid) != 0 and "scales" in L.lib().dsd_last_error().decode()
     guid = L.DsdGuidance(None, scales.ctypes.data_as(C.POINTER(C.c_float)), STEPS)

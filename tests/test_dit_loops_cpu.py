@@ -70,7 +70,7 @@ def test_find_unet_takes_no_stub_for_a_dit():
 
 
 def test_multichannel_learned_range_rows_reproduce_the_oracle_loop():
-    """The coefficient rows handed to dsd_sample_latent, replayed on the CPU in the update kernel's fp32 operation order
+    """The coefficient rows handed to dsd_sample, replayed on the CPU in the update kernel's fp32 operation order
     (sampler.hip sampler_update_value, emulated with torch fp32 ops), must reproduce the oracle's p_sample_loop on an analytic
     network of two state channels whose output carries a variance half: this pins the split by Cz, the pairing of channel c with
     variance channel Cz + c and frac*max_log + (1 - frac)*min_log without a GPU."""

@@ -426,11 +426,11 @@ def test_rejections_by_message_leave_the_state_alone():
     learned = diffusion(learn_sigma=True)._schedule(False, 0.0, True)
 
     def raw(e, sc, x, c, Cz):
-        """dsd_sample_latent itself, past the Python-side checks."""
+        """dsd_sample itself, past the Python-side checks."""
         B, _, H, W = x.shape
         keep = x.clone()
-        rc = L.lib().dsd_sample_latent(e["unet"]._h, C.byref(sc.c), L.dptr(c), c.shape[1], L.dptr(x), Cz, None, C.c_uint64(1), B, H, W,
-                                       0, 0, L.stream_ptr())
+        rc = L.lib().dsd_sample(e["unet"]._h, C.byref(sc.c), None, None, L.dptr(c), c.shape[1], L.dptr(x), Cz, None, C.c_uint64(1), B, H,
+                                W, 0, 0, L.stream_ptr())
         torch.cuda.synchronize()
         assert rc != 0 and torch.equal(x, keep)
         return L.lib().dsd_last_error().decode()
@@ -457,7 +457,8 @@ def test_rejections_by_message_leave_the_state_alone():
     # a block that is neither denoiser keeps the UNetModel's message
     from diffusion_models_dsdiff_amd.blocks import AttentionBlock
     blk = AttentionBlock(32, num_heads=1)
-    rc = L.lib().dsd_sample_latent(blk._h, C.byref(sched.c), L.dptr(c), 3, L.dptr(x), 1, None, C.c_uint64(1), 2, 16, 16, 0, 0, L.stream_ptr())
+    rc = L.lib().dsd_sample(blk._h, C.byref(sched.c), None, None, L.dptr(c), 3, L.dptr(x), 1, None, C.c_uint64(1), 2, 16, 16, 0, 0,
+                            L.stream_ptr())
     assert rc != 0 and "the latent loops take a DSD_BLOCK_UNET handle (the plain UNetModel)" in L.lib().dsd_last_error().decode()
     assert torch.equal(x, keep)
 

@@ -172,7 +172,7 @@ def test_fixture_cases_latent(lat, name):
 
 # ---------------------------------------------------------------------------------------- 3. the existing loop as a program
 def test_multistep_program_equals_the_existing_loop(pix, lat):
-    """Order <= 2 through dsd_sample_dpm_program equals dsd_sample_dpm(_guided) on the same schedule bit for bit, pixel and
+    """Order <= 2 through dsd_sample_dpm_program equals dsd_sample_dpm (guided or not) on the same schedule bit for bit, pixel and
     latent, unguided and guided, with thresholding and denoise_to_zero."""
     from diffusion_models_dsdiff_amd._sched import Guidance
     dsa = _sampler()
@@ -304,11 +304,8 @@ def test_rejections_leave_the_state_untouched(pix, lat):
 
         def call(p, guid=None, inter=None, cond=e["c"], xx=x):
             gp = C.byref(guid) if guid is not None else None
-            if e["key"] == "lat":
-                return L.lib().dsd_sample_dpm_program_latent(e["unet"]._h, C.byref(p.c), gp, L.dptr(cond), e["c"].shape[1], L.dptr(xx),
-                                                             Cz, B, H, W, inter, L.stream_ptr())
-            return L.lib().dsd_sample_dpm_program(e["unet"]._h, C.byref(p.c), gp, L.dptr(cond), e["c"].shape[1], L.dptr(xx), B, H, W,
-                                                  inter, L.stream_ptr())
+            return L.lib().dsd_sample_dpm_program(e["unet"]._h, C.byref(p.c), gp, L.dptr(cond), e["c"].shape[1], L.dptr(xx), Cz, B, H,
+                                                  W, inter, L.stream_ptr())
 
         def rejected(rc, text):
             msg = L.lib().dsd_last_error().decode()

@@ -227,8 +227,7 @@ def test_structs_and_header_agree():
     assert C.sizeof(_lib.DsdInvertSchedule) == 24 and _lib.DsdInvertSchedule.coef.offset == 8
     assert C.sizeof(_lib.DsdSchedule) == 48 and C.sizeof(_lib.DsdGuidance) == 24            # the existing layouts stay
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dsdiff.h")).read()
-    for sym in ("dsd_sample_masked", "dsd_sample_latent_masked", "dsd_invert", "dsd_invert_latent", "dsd_op_mask_blend",
-                "dsd_op_q_sample", "dsd_op_ddim_invert_step"):
+    for sym in ("dsd_sample", "dsd_invert", "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step"):
         assert sym in _lib.EXPORTS and re.search(r"\bint %s\(" % sym, hdr), sym
 
 

@@ -318,7 +318,7 @@ def test_latent_diffusion_q_sample_masked_ddpm_and_sample_log(lat):
 
 
 def test_pixel_masked_ddpm_loop_matches_the_restatement(pix, lat):
-    """dsd_sample_masked in mode B_DDPM (the four-stream model; blend after every update) against the torch chain of
+    """dsd_sample with a mask in mode B_DDPM (the four-stream model; blend after every update) against the torch chain of
     test_img2img_cpu.py with the oracle network: independent of the project's own ops."""
     from diffusion_models_dsdiff_amd._sched import Inpaint, run_device_loop
     e, T = pix, 8
@@ -338,7 +338,7 @@ def test_pixel_masked_ddpm_loop_matches_the_restatement(pix, lat):
 # ---------------------------------------------------------------------------------------- loop-level checks
 @pytest.mark.parametrize("mode", ["ddim_guided", "ddim", "ddpm"])
 def test_device_loop_matches_host_loop_graph_replay_and_split(env, lat, mode):
-    """dsd_sample_masked / dsd_sample_latent_masked against the loop written here — forward through the module, the update op,
+    """dsd_sample with a mask (both denoisers) against the loop written here — forward through the module, the update op,
     the blend op in the loop's own order — with the same fed noise; hipGraph replay and a first_step split bit-identical."""
     from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, run_device_loop, sampler_update, sampler_update_guided,
                                                     mask_blend)
@@ -482,11 +482,8 @@ def test_masked_and_inversion_loops_reject_with_a_reason(env, lat):
 
     def call(p, g=None, sc=sched):
         gp = C.byref(g) if g is not None else None
-        if e["key"] == "lat":
-            return L.lib().dsd_sample_latent_masked(unet._h, C.byref(sc.c), gp, C.byref(p), L.dptr(c), c.shape[1], L.dptr(x), Cz,
-                                                    None, C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
-        return L.lib().dsd_sample_masked(unet._h, C.byref(sc.c), gp, C.byref(p), L.dptr(c), c.shape[1], L.dptr(x), None,
-                                         C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
+        return L.lib().dsd_sample(unet._h, C.byref(sc.c), gp, C.byref(p), L.dptr(c), c.shape[1], L.dptr(x), Cz, None, C.c_uint64(1), 2,
+                                  H, W, 0, 0, L.stream_ptr())
     err = lambda: L.lib().dsd_last_error().decode()
     x0p, mp = e["x0"].data_ptr(), e["mask"].data_ptr()
     assert call(L.DsdInpaint(None, mp, 1, None)) != 0 and "x0 is null" in err()
@@ -507,10 +504,7 @@ def test_masked_and_inversion_loops_reject_with_a_reason(env, lat):
 
     def inv(sc, g=None):
         gp = C.byref(g) if g is not None else None
-        if e["key"] == "lat":
-            return L.lib().dsd_invert_latent(unet._h, C.byref(sc), gp, L.dptr(c), c.shape[1], L.dptr(x), Cz, 2, H, W, 0, 0,
-                                             L.stream_ptr())
-        return L.lib().dsd_invert(unet._h, C.byref(sc), gp, L.dptr(c), c.shape[1], L.dptr(x), 2, H, W, 0, 0, L.stream_ptr())
+        return L.lib().dsd_invert(unet._h, C.byref(sc), gp, L.dptr(c), c.shape[1], L.dptr(x), Cz, 2, H, W, 0, 0, L.stream_ptr())
     assert inv(L.DsdInvertSchedule(0, fp(coef), fp(tm))) != 0 and "bad inversion schedule" in err()
     assert inv(L.DsdInvertSchedule(4, None, fp(tm))) != 0 and "bad inversion schedule" in err()
     assert inv(L.DsdInvertSchedule(4, fp(coef), fp(tm)), guid) != 0 and "scales" in err()

@@ -1,7 +1,7 @@
 """Latent diffusion sampling as the latent trainer runs it (trainers/trainer_latent_diffusion.py:153-189,492-544): the f = 8
 KL first stage with scale_factor, K condition keys encoded in one pass, and the three sample_log branches (DDIMSampler,
 DPMSolverSampler, LatentDiffusion.sample) on a native UNetModel with 4-channel latents, all in the device-resident latent
-loops (dsd_sample_latent / dsd_sample_dpm_latent).  Fixtures: the reference's own samplers (tests/golden/latent_ldm.npz,
+loops (dsd_sample / dsd_sample_dpm on a DSD_BLOCK_UNET handle).  Fixtures: the reference's own samplers (tests/golden/latent_ldm.npz,
 tests/golden/gen_latent_ldm.py)."""
 import ctypes as C
 import json
@@ -127,7 +127,7 @@ def _ddim_sched(ld, eta=1.0):
 
 
 def test_device_loop_matches_host_loop_and_graph_replay(ldm):
-    """dsd_sample_latent against the per-step host loop (network call + dsd_op_sampler_update over B*Cz planes) with the same
+    """dsd_sample against the per-step host loop (network call + dsd_op_sampler_update over B*Cz planes) with the same
     pre-drawn noise; graph replay on / off bit-identical."""
     from diffusion_models_dsdiff_amd import _lib
     from diffusion_models_dsdiff_amd._sched import run_device_loop, sampler_update
@@ -203,8 +203,8 @@ def test_latent_loops_reject_bad_input(ldm):
         run_device_loop(unet, lr, randn((2, 4, 8, 8), 1).cuda(), cc)
     # a block that is not a UNetModel (the first stage's decoder handle)
     x = randn((2, 4, 8, 8), 1).cuda()
-    rc = _lib.lib().dsd_sample_latent(ld.first_stage_model._dec._h, C.byref(sched.c), dptr(cc), 8, dptr(x), 4, None,
-                                      C.c_uint64(1), 2, 8, 8, 0, 0, stream_ptr())
+    rc = _lib.lib().dsd_sample(ld.first_stage_model._dec._h, C.byref(sched.c), None, None, dptr(cc), 8, dptr(x), 4, None,
+                               C.c_uint64(1), 2, 8, 8, 0, 0, stream_ptr())
     assert rc != 0 and "DSD_BLOCK_UNET" in _lib.lib().dsd_last_error().decode()
     with pytest.raises(_lib.DsdError, match="input channels"):
         run_device_loop(unet, sched, randn((2, 3, 8, 8), 1).cuda(), cc)
@@ -246,7 +246,7 @@ def test_trainer_shape_smoke():
 
 
 def test_dpm_latent_dynamic_thresholding_per_sample_over_all_channels(ldm):
-    """dsd_sample_dpm_latent with dynamic thresholding on a Cz = 4 state: the quantile is taken per sample over all C*h*w
+    """dsd_sample_dpm with dynamic thresholding on a Cz = 4 state: the quantile is taken per sample over all C*h*w
     elements (dynamic_thresholding_fn, dpm_solver_pytorch.py:418), against oracle.dpm on the same network; a low threshold
     makes the clamp bite on every step."""
     from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
@@ -273,7 +273,7 @@ def test_dpm_latent_dynamic_thresholding_per_sample_over_all_channels(ldm):
 
 def test_guided_diffusion_loop_routes_unet_model_to_latent_loop(ldm):
     """The guided-diffusion ddim_sample_loop / p_sample_loop handed a bare UNetModel with c_concat (no hooks) run
-    dsd_sample_latent, against oracle.samplers.DiffusionA with the same fed noise."""
+    dsd_sample, against oracle.samplers.DiffusionA with the same fed noise."""
     from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion.script_util import create_gaussian_diffusion
     from diffusion_models_dsdiff_amd import _lib
     g, ld, dd, embed, up, sd = ldm

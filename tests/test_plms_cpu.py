@@ -213,17 +213,5 @@ def test_structs_enums_and_header_agree():
     m = re.search(r"enum \{ DSD_PLMS_PREDICT = 0, DSD_PLMS_CORRECT = 1, DSD_PLMS_AB2 = 2, DSD_PLMS_AB3 = 3, DSD_PLMS_AB4 = 4 \}", code)
     assert m and (_lib.PLMS_PREDICT, _lib.PLMS_CORRECT, _lib.PLMS_AB2, _lib.PLMS_AB3, _lib.PLMS_AB4) == (0, 1, 2, 3, 4)
     assert C.sizeof(_lib.DsdSchedule) == 48 and C.sizeof(_lib.DsdGuidance) == 24 and C.sizeof(_lib.DsdInpaint) == 32   # unchanged
-    L = _lib.lib()
-    ctype = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float}
-    for sym in ("dsd_sample_plms", "dsd_sample_plms_latent", "dsd_op_plms_step"):
+    for sym in ("dsd_sample_plms", "dsd_op_plms_step"):                       # signatures: tests/test_abi.py checks them against the header
         assert sym in _lib.EXPORTS
-        decl = re.search(r"\bint %s\((.*?)\);" % sym, code, flags=re.S)
-        assert decl, sym
-        params = [p.strip() for p in decl.group(1).split(",")]
-        argtypes = getattr(L, sym).argtypes
-        assert len(argtypes) == len(params), (sym, len(argtypes), len(params))
-        for p, a in zip(params, argtypes):                                    # scalars by type; every pointer is pointer-sized
-            if "*" in p:
-                assert C.sizeof(a) == C.sizeof(C.c_void_p), (sym, p)
-            else:
-                assert a is ctype[p.split()[0]], (sym, p, a)

@@ -384,11 +384,8 @@ def test_modes_are_rejected_with_a_reason(env):
 
     def call(p=None, g=None):
         gp, ip = C.byref(g) if g is not None else None, C.byref(p) if p is not None else None
-        if e["key"] == "lat":
-            return L.lib().dsd_sample_plms_latent(unet._h, C.byref(sched.c), gp, ip, 0.0, L.dptr(c), c.shape[1], L.dptr(x), Cz,
-                                                  C.c_uint64(1), 2, H, W, 0, 0, L.stream_ptr())
-        return L.lib().dsd_sample_plms(unet._h, C.byref(sched.c), gp, ip, 0.0, L.dptr(c), c.shape[1], L.dptr(x), C.c_uint64(1), 2, H,
-                                       W, 0, 0, L.stream_ptr())
+        return L.lib().dsd_sample_plms(unet._h, C.byref(sched.c), gp, ip, 0.0, L.dptr(c), c.shape[1], L.dptr(x), Cz, C.c_uint64(1), 2,
+                                       H, W, 0, 0, L.stream_ptr())
     err = lambda: L.lib().dsd_last_error().decode()
     x0p, mp = e["x0"].data_ptr(), e["mask"].data_ptr()
     assert call(L.DsdInpaint(None, mp, 1, None)) != 0 and "x0 is null" in err()

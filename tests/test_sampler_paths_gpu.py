@@ -231,3 +231,54 @@ def test_update_modes_match_torch(mode, shape):
     x0 = sampler_update(sc, 1, out.cuda(), xd, z.cuda(), want_x0=True)
     print(f"{mode} {shape}: x {rel_l2(xd, want):.3e}, pred_xstart {rel_l2(x0, want_x0):.3e}")
     assert rel_l2(xd, want) < TOL_OP and rel_l2(x0, want_x0) < TOL_OP
+
+
+# ---------------------------------------------------------------------------------------- one entry point per loop
+from test_cfg_gpu import pix, lat          # noqa: E402,F401  the tiny DSUnetModel of model.npz, the UNetModel of latent_ldm.npz; B = 2
+
+
+def _ddim4(m):
+    from diffusion_models_dsdiff_amd.ldm.models.diffusion.ddim import DDIMSampler
+    s = DDIMSampler(m)
+    s.make_schedule(4, ddim_eta=0.5, verbose=False)                           # eta > 0: the Philox seed reaches the result
+    return s._schedule(False, True)
+
+
+def test_four_stream_handle_takes_one_state_channel(pix):
+    """dsd_sample on a four-stream handle with Cz = 2: rejected before device work, both numbers named, x untouched."""
+    L = _lib()
+    sched, c = _ddim4(pix["m"]), pix["c"]
+    x = torch.cat([pix["xT"], pix["xT"]], 1).contiguous()
+    keep = x.clone()
+    rc = L.lib().dsd_sample(pix["unet"]._h, C.byref(sched.c), None, None, L.dptr(c), c.shape[1], L.dptr(x), 2, None, C.c_uint64(1), 2,
+                            32, 32, 0, 0, L.stream_ptr())
+    msg = L.lib().dsd_last_error().decode()
+    torch.cuda.synchronize()
+    assert rc != 0 and "state of 1 channel" in msg and "Cz = 2" in msg and "the denoised image has one channel" in msg, msg
+    assert torch.equal(x, keep)
+
+
+def test_null_guidance_and_mask_are_the_plain_loops(pix, lat):
+    """dsd_sample(g = NULL, inp = NULL) and dsd_sample_dpm(g = NULL) with Cz = 1 on the four-stream handle and Cz = 4 on the
+    UNetModel handle: the bits of run_device_loop / run_dpm_loop on the same inputs and seed."""
+    from diffusion_models_dsdiff_amd._sched import run_device_loop
+    from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
+    L = _lib()
+    for e in (pix, lat):
+        c, (B, Cz, H, W) = e["c"], e["xT"].shape
+        assert Cz == (1 if e["key"] == "pix" else 4)
+        sched = _ddim4(e["m"])
+        want = run_device_loop(e["unet"], sched, e["xT"], c, seed=77)
+        x = e["xT"].clone()
+        L.check(L.lib().dsd_sample(e["unet"]._h, C.byref(sched.c), None, None, L.dptr(c), c.shape[1], L.dptr(x), Cz, None,
+                                   C.c_uint64(77), B, H, W, 0, 0, L.stream_ptr()))
+        assert torch.equal(x, want) and not torch.equal(x, e["xT"]), e["key"]
+        ns = dsa.NoiseScheduleVP("discrete", betas=e["m"].betas.detach().float().cpu())
+        fn = dsa.model_wrapper(e["wrap"], ns, model_type="v", model_kwargs=dict(c_concat=[c]))
+        dpm = dsa.DPM_Solver(fn, ns, algorithm_type="dpmsolver++").build_schedule(steps=4, order=2, skip_type="time_uniform",
+                                                                                 lower_order_final=True)
+        want = dsa.run_dpm_loop(fn, dpm, e["xT"])
+        x = e["xT"].clone()
+        L.check(L.lib().dsd_sample_dpm(e["unet"]._h, C.byref(dpm.c), None, L.dptr(c), c.shape[1], L.dptr(x), Cz, B, H, W,
+                                       L.stream_ptr()))
+        assert torch.equal(x, want) and not torch.equal(x, e["xT"]), e["key"]

@@ -7,7 +7,8 @@ ds 1/2/4), built without and with spatial transformers (context 77 x 768, 'hybri
   - the 20-step DDIM (eta 0) device loop against the per-step loop (network call + dsd_op_sampler_update), both builds;
   - with --baseline FILE (repeatable): the 'concat'-only device loop of this build over the same loop of another build's
     library, whose lines were written by `DSD_LIBRARY=<that build's libdsdiff.so> python tools/bench_cond_keys.py --concat-only
-    --json FILE` on the same machine, run in turn with this one.  The ratio is recorded, not asserted.
+    --json FILE` on the same machine, run in turn with this one.  The ratio is recorded, not asserted.  (A library from before
+    the loops took one entry point each no longer matches the binding's loop signatures: run that build from its own checkout.)
 Every timed run follows one untimed run of the same loop; the loops alternate; hipEvents; medians of --repeats runs.
 
     python tools/bench_cond_keys.py [--batch 16] [--steps 20] [--repeats 3] [--concat-only] [--baseline other.json ...] [--json out.json]

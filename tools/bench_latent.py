@@ -2,30 +2,30 @@
 """The latent trainer's inference (trainers/trainer_latent_diffusion.py:153-189,492-544) on one GPU with synthetic weights:
 batch 16 of 256^2 one-channel slices, the SD-v1 f = 8 first stage (32x32x4 latents), K condition keys encoded in one pass,
 50-step DDIM (eta 0) on a UNetModel with the unet_config of the reference's v2-1-cddpm-disc yaml (in_channels 4*(K+1)), decode.
-Three loops for the same steps, alternated in one process: the device loop (dsd_sample_latent) with graph replay off, with
+Three loops for the same steps, alternated in one process: the device loop (dsd_sample) with graph replay off, with
 replay on, and the per-step Python loop (network call + dsd_op_sampler_update, the closure path).  hipEvents, median / min / max
 of --repeats runs.  Prints one JSON line.
 With --guidance-scale S (S != 1) three more loops join the alternation: the guided device loop at the batch
-(dsd_sample_latent_guided: 2B network rows per step, u = zeros), the unguided loop at the batch, and the unguided loop at twice
+(dsd_sample with a dsd_guidance: 2B network rows per step, u = zeros), the unguided loop at the batch, and the unguided loop at twice
 the batch — the same network work as the guided one, so guided(B) against unguided(2B) is what the combine and the doubled
 state cost.  Each of the three is preceded by one untimed step of its own, so that no timed run pays for the plan of another
 batch size.
-With --mask the masked device loop (dsd_sample_latent_masked: centre half of the latent sampled, Philox blend noise) is timed
-against the unmasked loop, and with --encode the DDIM inversion loop (dsd_invert_latent, all steps) against plain sampling — the
+With --mask the masked device loop (dsd_sample with a dsd_inpaint: centre half of the latent sampled, Philox blend noise) is timed
+against the unmasked loop, and with --encode the DDIM inversion loop (dsd_invert, all steps) against plain sampling — the
 same network work per step, so each ratio is what the blend kernel / the inversion step costs.  Same alternation and untimed
 first step as the guided loops.
-With --plms the PLMS device loop (dsd_sample_plms_latent: one network evaluation per step plus one more at the first step, so
+With --plms the PLMS device loop (dsd_sample_plms: one network evaluation per step plus one more at the first step, so
 steps + 1 in all) is timed against the DDIM loop of the same steps: plms_over_ddim is expected near (steps + 1) / steps and is
 measured here, not assumed.  The network of this bench is a v-model, which PLMS does not take; the PLMS schedule is packed as for
 a noise-predicting one — the same kernels and the same work.
 With --dpm-family LIST (of ss3, ms3, ms2) the DPM-Solver++ loops of 21 network evaluations are timed in the same alternation:
-singlestep order 3 and multistep order 3 (dsd_sample_dpm_program_latent) and multistep order 2 (dsd_sample_dpm_latent, the loop
+singlestep order 3 and multistep order 3 (dsd_sample_dpm_program) and multistep order 2 (dsd_sample_dpm, the loop
 that existed before them).  The host tables are built once outside the timed region, every timed run follows an untimed run of
 the same loop, and the result holds the ms per network evaluation of each and the ratios to ms2.  For a build from before the
 program entry, copy this script into a checkout of that commit (this tree's binding does not load such a library) and run
 `--dpm-family ms2` there; --baseline with those lines then also records this build's ms2 loop over that build's.
-With --bpd the variational-bound loop (dsd_calc_bpd_latent: q_sample, one network evaluation and the terms / finalize launches per
-step, Philox noise) is timed against the mode-A DDPM sampling loop of the same handle, schedule and step count (dsd_sample_latent):
+With --bpd the variational-bound loop (dsd_calc_bpd: q_sample, one network evaluation and the terms / finalize launches per
+step, Philox noise) is timed against the mode-A DDPM sampling loop of the same handle, schedule and step count (dsd_sample):
 bpd_over_ddpm is what the three small launches cost beside a network evaluation.  Same alternation and untimed first step.
 With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
 run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this

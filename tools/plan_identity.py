@@ -5,6 +5,8 @@ network the builder assembles, as a JSON that two builds can be compared on fiel
     DSD_LIBRARY=<a build> python tools/plan_identity.py --out a.json        # one fresh process per library
     python tools/plan_identity.py --out b.json                              # (the in-tree build)
     python tools/plan_identity.py --compare a.json b.json [--json verdict.json]
+A library from before the device loops took one entry point each no longer matches the binding's loop signatures (the
+zero-stream case runs a loop): run such a build from its own checkout, not through DSD_LIBRARY.
 
 Per case: plan_info() (workspace_bytes, launches, flops, device_bytes), every op of profile_ops() as (kind, flops, bytes,
 layer name) in launch order (the times are dropped), and the SHA-256 of the output of one forward on seeded inputs.
