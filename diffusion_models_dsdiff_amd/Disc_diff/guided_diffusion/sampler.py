@@ -10,8 +10,11 @@ with ``order`` 1..3, ``method='singlestep'`` ("DPM-Solver-fast", orders and time
 ``DPM_Solver.inverse``, dynamic thresholding, classifier-free guidance (both halves in one 2B-row network pass).  Multistep of
 order 1 or 2 without intermediates runs through ``dsd_sample_dpm`` (include/dsdiff.h); everything else is packed by
 ``build_program`` into a ``dsd_dpm_program`` — one row per network evaluation — for ``dsd_sample_dpm_program``.
-``method='adaptive'`` (its step count follows a per-step error norm: a host read-back every step, and no call site uses it),
-``correcting_xt_fn``, classifier guidance and score-type networks raise ``NotImplementedError`` — there is no CPU fallback.
+``DPM_Solver.dpm_solver_adaptive`` is the adaptive step-size solver (:921-980): every trial — one singlestep step of ``order``
+evaluations, the lower-order result from the same model values and the per-sample error norm between the two — is one call of
+``dsd_sample_dpm_adaptive_trial``, and the host keeps what the reference keeps on (1,)-tensors: the step size, accept or
+reject, the end test.  ``sample(method='adaptive')`` still raises and names that method; ``correcting_xt_fn``, classifier
+guidance and score-type networks raise ``NotImplementedError`` — there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -413,6 +416,14 @@ class DPM_Solver:
             ev(s2, DPM_SS_T3_TAYLOR, [cx_to(la_t, sig_t), lead_t * phi_1, c2 if pp else -c2, lead_t * phi_3, 1. / r1, 1. / r2, r1, r2,
                                       r2 - r1], (2, 0, 1, 2), True)
 
+    def _eval_row(self, t_eval, kind, coef, slot, keep):
+        """One DpmProgram row: the evaluation's time, model time, alpha / sigma there and its coefficients as fp32 values."""
+        ns = self.noise_schedule
+        f = lambda v: float(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[0])
+        t_eval = torch.as_tensor(t_eval, dtype=torch.float32).reshape(-1)
+        return dict(kind=kind, t=f(t_eval), t_input=f(self.model_fn_.input_time(t_eval)), alpha=f(ns.marginal_alpha(t_eval)),
+                    sigma=f(ns.marginal_std(t_eval)), coef=[f(v) for v in coef], slot=slot, keep=bool(keep))
+
     def build_program(self, steps, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
                       lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver",
                       return_intermediate=False) -> DpmProgram:
@@ -422,8 +433,9 @@ class DPM_Solver:
         if solver_type not in ["dpmsolver", "taylor"]:
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         if method == "adaptive":
-            raise NotImplementedError("method='adaptive' is not built: its step count follows a per-step error norm, which needs a "
-                                      "host read-back every step, and no call site uses it")
+            raise NotImplementedError("method='adaptive' is not a program of evaluations: its step count follows a per-step error norm, "
+                                      "read back every trial.  Call DPM_Solver.dpm_solver_adaptive(x, order, t_T, t_0, atol=, rtol=) "
+                                      "— sample() passes it exactly these")
         if method not in ("multistep", "singlestep", "singlestep_fixed"):
             raise ValueError("Got wrong method {}".format(method))
         if order not in (1, 2, 3):
@@ -432,14 +444,10 @@ class DPM_Solver:
         t_0 = 1. / ns.total_N if t_end is None else t_end
         t_T = ns.T if t_start is None else t_start
         assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
-        f = lambda v: float(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[0])
         evals = []
 
         def ev(t_eval, kind, coef, slot, keep):
-            t_eval = torch.as_tensor(t_eval, dtype=torch.float32).reshape(-1)
-            evals.append(dict(kind=kind, t=f(t_eval), t_input=f(self.model_fn_.input_time(t_eval)), alpha=f(ns.marginal_alpha(t_eval)),
-                              sigma=f(ns.marginal_std(t_eval)), coef=[f(v) for v in coef], slot=slot,
-                              keep=bool(keep and return_intermediate)))
+            evals.append(self._eval_row(t_eval, kind, coef, slot, keep and return_intermediate))
 
         if method == "multistep":
             assert steps >= order
@@ -522,6 +530,78 @@ class DPM_Solver:
             return y
         lead = [x.detach().float().clone()] if prog.lead_intermediate else []
         return y, lead + list(kept.unbind(0))
+
+    # ------------------------------------------------------------------ adaptive step size
+    def adaptive_trial_program(self, s, t, order, solver_type="dpmsolver"):
+        """One trial of dpm_solver_adaptive from s to t (:949-968): (the DpmProgram of the higher-order singlestep step — r1 = 0.5,
+        or r1 = 1/3 and r2 = 2/3, as Python floats like the reference's — and the three coefficients of the update of order - 1
+        from the same model values).  Order 2: dpm_solver_first_update, the first parenthesis of the SS_T2 row; order 3: the
+        second-order singlestep update with r1 = 1/3, whose model_s1 is the one the third-order step evaluates."""
+        if order not in (2, 3):
+            raise ValueError("For adaptive step size solver, order must be 2 or 3, got {}".format(order))
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        evals, low = [], []
+        r1, r2 = (0.5, None) if order == 2 else (1. / 3., 2. / 3.)
+        self._singlestep_evals(s, t, order, r1, r2, solver_type, lambda *row: evals.append(self._eval_row(*row[:4], False)))
+        if order == 2:
+            lower = evals[-1]["coef"][:2] + [0.]
+        else:
+            self._singlestep_evals(s, t, 2, r1, None, solver_type, lambda *row: low.append(self._eval_row(*row[:4], False)))
+            lower = low[-1]["coef"][:3]
+        thr = self.correcting_x0_fn == "dynamic_thresholding"
+        prog = DpmProgram(_PRED[self.model_fn_.model_type], self.algorithm_type == "dpmsolver++", thr,
+                          self.dynamic_thresholding_ratio, self.thresholding_max_val, evals)
+        return prog, np.asarray(lower, dtype=np.float32)
+
+    @torch.no_grad()
+    def dpm_solver_adaptive(self, x, order, t_T, t_0, h_init=0.05, atol=0.0078, rtol=0.05, theta=0.9, t_err=1e-5,
+                            solver_type='dpmsolver', max_nfe=None, return_trace=False):
+        """:921-980 — the adaptive step-size solver on singlestep DPM-Solver of ``order`` 2 or 3: the reference's signature and
+        return value.  The host side is the reference's own fp32 expressions on (1,)-tensors; a trial (``order`` network
+        evaluations, x_lower, the error norm) is one device call whose B error norms are read back.  Extensions: ``max_nfe`` —
+        the reference has no guard; with it a loop that would pass that many evaluations raises RuntimeError with the count;
+        ``return_trace`` — returns (x_0, [(s, t, h, E, accepted) per trial])."""
+        if order not in (2, 3):
+            raise ValueError("For adaptive step size solver, order must be 2 or 3, got {}".format(order))
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        if not (t_T > t_0 > 0):
+            raise ValueError(f"dpm_solver_adaptive integrates down from t_T to t_0 > 0 (got t_T {t_T}, t_0 {t_0}); the adaptive "
+                             "inverse is not built")
+        if not (atol > 0 and rtol >= 0 and theta > 0 and h_init > 0):
+            raise ValueError(f"dpm_solver_adaptive needs atol > 0, rtol >= 0, theta > 0 and h_init > 0 (got atol {atol}, rtol {rtol}, "
+                             f"theta {theta}, h_init {h_init})")
+        if not x.is_cuda:
+            raise NotImplementedError("the adaptive solver runs on the MI355X only (there is no CPU implementation and no CPU "
+                                      "fallback): x is on the CPU")
+        ns = self.noise_schedule
+        s = t_T * torch.ones((1,))
+        lambda_s = ns.marginal_lambda(s)
+        lambda_0 = ns.marginal_lambda(t_0 * torch.ones_like(s))
+        h = h_init * torch.ones_like(s)
+        x = x.detach().float().contiguous()
+        x_prev = x
+        nfe, trace = 0, []
+        with AdaptiveTrial(self.model_fn_, x, order) as trial:
+            while torch.abs((s - t_0)).mean() > t_err:
+                if max_nfe is not None and nfe + order > max_nfe:
+                    raise RuntimeError(f"dpm_solver_adaptive did not reach t_0 = {t_0} within max_nfe = {max_nfe} network evaluations: "
+                                       f"{nfe} spent in {len(trace)} trials, now at s = {float(s):.6g} with h = {float(h):.3g}")
+                t = ns.inverse_lambda(lambda_s + h)
+                prog, lower = self.adaptive_trial_program(s, t, order, solver_type)
+                x_higher, x_lower, E_b = trial.run(prog, lower, atol, rtol, x, x_prev)
+                E = E_b.max()
+                accepted = bool(torch.all(E <= 1.))
+                trace.append((float(s), float(t), float(h), float(E), accepted))
+                if accepted:
+                    x = x_higher
+                    s = t
+                    x_prev = x_lower
+                    lambda_s = ns.marginal_lambda(s)
+                h = torch.min(theta * h * torch.float_power(E, -1. / order).float(), lambda_0 - lambda_s)
+                nfe += order
+        return (x, trace) if return_trace else x
 
     def inverse(self, x, steps=20, t_start=None, t_end=None, **sample_kwargs):
         """DPM_Solver.inverse (:1001-1015): sample() run upwards in time, from ``t_start`` (default: the schedule's first time,
@@ -631,6 +711,65 @@ def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance:
             kept[j].copy_(x)
             j += 1
     return x, kept
+
+
+class AdaptiveTrial:
+    """The device side of dpm_solver_adaptive's trials for one start state: settles once what every trial shares — the native
+    denoiser behind ``fn`` (or the per-evaluation path of any other callable), the 'concat' condition, the guidance with one scale
+    per evaluation, the rest of the conditioning held on the handle — and ``run`` executes one trial."""
+
+    def __init__(self, fn: _ModelFn, x: torch.Tensor, order: int, guidance: Optional[Guidance] = None):
+        self.fn, self.order = fn, int(order)
+        self.unet, cc, self.guidance, bundle = _loop_denoiser_and_guidance(fn, self.order, x, guidance)
+        if not x.is_cuda:
+            raise NotImplementedError("the adaptive solver runs on the MI355X only (there is no CPU implementation and no CPU "
+                                      "fallback): x is on the CPU")
+        self.ready = _native_loop_inputs(self.unet, cc, bundle, self.guidance, x.detach().float().contiguous())
+        self.err = np.zeros(x.shape[0], dtype=np.float32)
+
+    def __enter__(self):
+        if self.ready is not None:
+            self.ready[2].__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self.ready is not None:
+            return self.ready[2].__exit__(*exc)
+        return False
+
+    @torch.no_grad()
+    def run(self, prog: DpmProgram, lower, atol, rtol, x: torch.Tensor, x_prev: torch.Tensor):
+        """One trial from the state ``x`` (left as it is): returns (x_higher, x_lower, E [B] on the CPU)."""
+        if prog.steps != self.order:
+            raise ValueError(f"a trial of order {self.order} has {self.order} evaluations; the program has {prog.steps}")
+        if x_prev.shape != x.shape or x_prev.device != x.device or x_prev.dtype != torch.float32 or x.dtype != torch.float32:
+            raise ValueError(f"x_prev must have the shape, dtype and device of x: {tuple(x_prev.shape)} {x_prev.dtype} {x_prev.device} "
+                             f"against {tuple(x.shape)} {x.dtype} {x.device}")
+        lower = np.ascontiguousarray(lower, dtype=np.float32).reshape(3)
+        lp = lower.ctypes.data_as(C.POINTER(C.c_float))
+        xh, x_prev = x.contiguous().clone(), x_prev.contiguous()
+        x_lower = torch.empty_like(xh)
+        B, Cx, H, W = xh.shape
+        if self.ready is not None:
+            cond, g, _ = self.ready
+            check(lib().dsd_sample_dpm_adaptive_trial(self.unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], lp, float(atol),
+                                                      float(rtol), dptr(xh), dptr(x_prev), dptr(x_lower), Cx, B, H, W,
+                                                      self.err.ctypes.data_as(C.POINTER(C.c_float)), stream_ptr()))
+            return xh, x_lower, torch.from_numpy(self.err.copy())
+        # any other callable: python loop over the network, the fused HIP evaluation step after each, then the error kernel
+        hist, base = xh.new_empty((3, B, Cx, H, W)), torch.empty_like(xh)
+        for k in range(prog.steps):
+            t_in = torch.full((B,), float(prog.t_input[k]), device=xh.device, dtype=torch.float32)
+            out = self.fn.network(xh, t_in).float().contiguous()
+            if out.shape[1] not in (Cx, 2 * Cx):
+                raise ValueError(f"the network returned {out.shape[1]} channels for a state of {Cx}")
+            check(lib().dsd_op_dpm_eval(C.byref(prog.c), k, None, dptr(out), out.shape[1] // Cx, 1., dptr(xh), 0, dptr(hist), dptr(base),
+                                        B, Cx, H, W, stream_ptr()))
+        err = torch.empty(B, device=xh.device, dtype=torch.float32)
+        ma, mb = hist[int(prog.slot[0, 0])], hist[int(prog.slot[1, 0])]
+        check(lib().dsd_op_dpm_adaptive_error(self.order - 1, lp, float(atol), float(rtol), dptr(base), dptr(ma), dptr(mb), dptr(xh), 0,
+                                              dptr(x_prev), dptr(x_lower), dptr(err), B, Cx, H, W, stream_ptr()))
+        return xh, x_lower, err.cpu()
 
 
 @torch.no_grad()

@@ -34,6 +34,7 @@ EXPORTS = [
     "dsd_op_posterior_sample_scaled", "dsd_op_sampler_update_guided", "dsd_op_dpm_step_guided",
     "dsd_invert", "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
     "dsd_sample_plms", "dsd_op_plms_step", "dsd_sample_dpm_program", "dsd_op_dpm_eval",
+    "dsd_sample_dpm_adaptive_trial", "dsd_op_dpm_adaptive_error",
     "dsd_set_conditioning",
     "dsd_calc_bpd", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
     "dsd_create_disc", "dsd_op_disc_bottleneck",
@@ -232,6 +233,11 @@ def lib() -> C.CDLL:
     L.dsd_op_plms_step.argtypes = [i32, C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, f32p, i64,
                                    C.c_float, i32, i32, i32, i32, vp]
     L.dsd_op_dpm_eval.argtypes = [C.POINTER(DsdDpmProgram), i32, f32p, f32p, i32, C.c_float, f32p, i64, f32p, f32p, i32, i32, i32, i32, vp]
+    if hasattr(L, "dsd_sample_dpm_adaptive_trial"):   # (absent from an older build under DSD_LIBRARY)
+        L.dsd_sample_dpm_adaptive_trial.argtypes = [vp, C.POINTER(DsdDpmProgram), gp, f32p, i32, C.POINTER(C.c_float), C.c_float,
+                                                    C.c_float, f32p, f32p, f32p, i32, i32, i32, i32, C.POINTER(C.c_float), vp]
+        L.dsd_op_dpm_adaptive_error.argtypes = [i32, C.POINTER(C.c_float), C.c_float, C.c_float, f32p, f32p, f32p, f32p, i64, f32p,
+                                                f32p, f32p, i32, i32, i32, i32, vp]
     L.dsd_op_vlb_terms.argtypes = [sp, i32, C.c_float, f32p, i64, f32p, i64, f32p, f32p, C.c_uint64, f32p, f32p, f32p, i64, f32p, f32p,
                                    f32p, i32, i32, i32, i32, vp]
     L.dsd_op_prior_bpd.argtypes = [C.c_float, C.c_float, f32p, f32p, i32, i32, i32, i32, vp]

@@ -1,4 +1,5 @@
 // api.cpp — the extern "C" surface of libdsdiff.so (see include/dsdiff.h).
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <vector>
@@ -267,7 +268,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->ctx_cap + h->y_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->bpd_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->ctx_cap + h->y_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->dpm_adapt_cap + h->bpd_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -991,10 +992,11 @@ static void dpm_program_eval(const dsd_dpm_program* p, int k, const float* out_u
 }
 
 // One driver for the four-stream model and the state-in-input denoisers, guided or not.  The history planes, the base plane and
-// the thresholds share one handle buffer, sized before the loop and left alone inside it.
-int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
-                           int B, int H, int W, float* inter, void* stream) {
-    DSD_TRY
+// the thresholds share one handle buffer, sized before the loop and left alone inside it.  dpm_program_checks is everything the
+// call is checked for (before any device work) and returns Cm; dpm_program_loop binds, runs every evaluation, calls
+// after(binding, hist, base) on the planes the program left, and finishes.
+static int dpm_program_checks(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, const float* x,
+                              int Cz, int B, int H, int W, const float* inter) {
     const bool latent = state_in_input(h);
     check_dpm_program(p);
     if (g) check_guidance(g, p->n_eval, !(latent && Cc == 0 && h->has_cond));                          // one scale per evaluation
@@ -1003,8 +1005,12 @@ int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_gu
     const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     const int Cm = latent ? out_ch / Cz : h->cfg.out_channels;
     DSD_CHECK(Cm == 1 || Cm == 2, "model has %d output channels; the solver takes 1 (or 2 with a learned sigma)", Cm);
-    set_device(h->device);
-    hipStream_t s = (hipStream_t)stream;
+    return Cm;
+}
+
+static void dpm_program_loop(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, float* x,
+                             int Cz, int B, int H, int W, int Cm, float* inter, hipStream_t s,
+                             const std::function<void(const LoopBinding&, float*, float*)>& after) {
     const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cm * Cz, s);
     const size_t plane = (size_t)B * b.n();
     ensure_buf(&h->dpm_prog, &h->dpm_prog_cap, (4 * plane + B) * sizeof(float));
@@ -1017,7 +1023,108 @@ int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_gu
             DSD_HIP(hipMemcpy2DAsync(inter + (size_t)n_kept++ * plane, sample, b.xs, (size_t)b.x_bs * sizeof(float), sample, B,
                                      hipMemcpyDeviceToDevice, s));
     });
+    after(b, hist, base);
     finish(h, b, s);
+}
+
+int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
+                           int B, int H, int W, float* inter, void* stream) {
+    DSD_TRY
+    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, inter);
+    set_device(h->device);
+    dpm_program_loop(h, p, g, cond, Cc, x, Cz, B, H, W, Cm, inter, (hipStream_t)stream, [](const LoopBinding&, float*, float*) {});
+    DSD_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- adaptive DPM-Solver
+// The lower-order row of a trial against the step it belongs to: both results start from the same c0*x_s - c1*model_s
+// (sampler.py:509-553, 592-631, 692-753 share sigma_t/sigma_s | exp(log_alpha_t - log_alpha_s) and the phi_1 term).
+static void check_adaptive_lower(int lower_order, const float* lower, const float* step_row, float atol, float rtol) {
+    DSD_CHECK(lower, "adaptive trial: the lower-order coefficients are null");
+    DSD_CHECK(lower[0] == step_row[0] && lower[1] == step_row[1],
+              "adaptive trial: the lower-order row (c0 %.9g, c1 %.9g) does not belong to the step (c0 %.9g, c1 %.9g): both updates "
+              "go from the same s to the same t", (double)lower[0], (double)lower[1], (double)step_row[0], (double)step_row[1]);
+    DSD_CHECK(lower_order == 2 ? std::isfinite(lower[2]) : lower[2] == 0.f,
+              "adaptive trial: c2 of the lower-order row is %g; the first-order update has none (0) and the second-order one a finite "
+              "value", (double)lower[2]);
+    DSD_CHECK(atol > 0.f, "adaptive trial: atol %g; it must be positive (it bounds delta from below, and the error is divided by delta)",
+              (double)atol);
+    DSD_CHECK(rtol >= 0.f, "adaptive trial: rtol %g; it must not be negative", (double)rtol);
+}
+
+int dsd_sample_dpm_adaptive_trial(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc,
+                                  const float* lower_coef, float atol, float rtol, float* x, const float* x_prev, float* x_lower, int Cz,
+                                  int B, int H, int W, float* err_host, void* stream) {
+    DSD_TRY
+    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, nullptr);
+    const int n_eval = p->n_eval, last = p->kind[n_eval - 1];
+    const bool one_step = (n_eval == 2 && p->kind[0] == DSD_DPM_SS_S1 && last == DSD_DPM_SS_T2) ||
+                          (n_eval == 3 && p->kind[0] == DSD_DPM_SS_S1 && p->kind[1] == DSD_DPM_SS_S2 &&
+                           (last == DSD_DPM_SS_T3 || last == DSD_DPM_SS_T3_TAYLOR));
+    DSD_CHECK(one_step,
+              "adaptive trial: the program has %d evaluation(s) (first kind %d, last kind %d); a trial is exactly one singlestep step of "
+              "order 2 (SS_S1, SS_T2) or 3 (SS_S1, SS_S2, SS_T3 / SS_T3_TAYLOR)", n_eval, p->kind[0], last);
+    check_adaptive_lower(n_eval - 1, lower_coef, p->coef + (size_t)(n_eval - 1) * DSD_DPM_NCOEF, atol, rtol);
+    DSD_CHECK(x_prev && x_lower && err_host, "adaptive trial: null array (x_prev %p x_lower %p err %p)", (const void*)x_prev,
+              (const void*)x_lower, (const void*)err_host);
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    // the partial sums first (hipMalloc aligns them), the B results behind; the pinned mirror of the results
+    const size_t part_bytes = dpm_adaptive_part_doubles(B) * sizeof(double);
+    ensure_buf(&h->dpm_adapt, &h->dpm_adapt_cap, part_bytes + (size_t)B * sizeof(float));
+    if (h->dpm_adapt_host_n < B) {
+        if (h->dpm_adapt_host) DSD_HIP(hipHostFree(h->dpm_adapt_host));
+        h->dpm_adapt_host = nullptr;
+        h->dpm_adapt_host_n = 0;
+        DSD_HIP(hipHostMalloc((void**)&h->dpm_adapt_host, (size_t)B * sizeof(float), hipHostMallocDefault));
+        h->dpm_adapt_host_n = B;
+    }
+    float* err_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(h->dpm_adapt) + part_bytes);
+    dpm_program_loop(h, p, g, cond, Cc, x, Cz, B, H, W, Cm, nullptr, s, [&](const LoopBinding& b, float* hist, float* base) {
+        const size_t plane = (size_t)B * b.n();
+        DpmAdaptiveErr a;
+        for (int j = 0; j < 3; ++j) a.c[j] = lower_coef[j];
+        a.lower_order = n_eval - 1;
+        a.atol = atol; a.rtol = rtol;
+        a.base = base;
+        a.ma = hist + p->slot[0] * plane;                                       // model_s, model_s1: the planes evaluations 0, 1 wrote
+        a.mb = hist + p->slot[4] * plane;
+        a.xh = b.xs; a.x_bs = b.x_bs;
+        a.x_prev = x_prev; a.x_lower = x_lower;
+        a.part = reinterpret_cast<double*>(h->dpm_adapt);
+        a.err = err_dev;
+        dpm_adaptive_error(a, B, b.n(), s);
+    });
+    // the trial's one synchronisation, outside any capture (the network's graph was replayed, not recorded, on s)
+    DSD_HIP(hipMemcpyAsync(h->dpm_adapt_host, err_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
+    DSD_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) err_host[b] = h->dpm_adapt_host[b];
+    DSD_CATCH
+}
+
+int dsd_op_dpm_adaptive_error(int lower_order, const float* lower_coef, float atol, float rtol, const float* base, const float* ma,
+                              const float* mb, const float* x_higher, int64_t x_row_stride, const float* x_prev, float* x_lower,
+                              float* err, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(lower_order == 1 || lower_order == 2, "adaptive error estimate: lower order %d; it is 1 or 2", lower_order);
+    DSD_CHECK(lower_coef, "adaptive error estimate: the lower-order coefficients are null");
+    check_adaptive_lower(lower_order, lower_coef, lower_coef, atol, rtol);
+    DSD_CHECK(base && ma && (mb || lower_order == 1) && x_higher && x_prev && x_lower && err,
+              "adaptive error estimate: null array (base %p ma %p mb %p x_higher %p x_prev %p x_lower %p err %p)", (const void*)base,
+              (const void*)ma, (const void*)mb, (const void*)x_higher, (const void*)x_prev, (const void*)x_lower, (const void*)err);
+    check_op_state(B, Cz, H, W, x_row_stride);
+    Tmp part(dpm_adaptive_part_doubles(B) * sizeof(double));
+    DpmAdaptiveErr a;
+    for (int j = 0; j < 3; ++j) a.c[j] = lower_coef[j];
+    a.lower_order = lower_order;
+    a.atol = atol; a.rtol = rtol;
+    a.base = base; a.ma = ma; a.mb = mb;
+    a.xh = x_higher; a.x_bs = x_row_stride;
+    a.x_prev = x_prev; a.x_lower = x_lower;
+    a.part = part.as<double>();
+    a.err = err;
+    dpm_adaptive_error(a, B, (int64_t)Cz * H * W, (hipStream_t)stream);
+    DSD_HIP(hipStreamSynchronize((hipStream_t)stream));
     DSD_CATCH
 }
 

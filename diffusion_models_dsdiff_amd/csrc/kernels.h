@@ -307,6 +307,27 @@ struct DpmEval {
 };
 void dpm_eval(const DpmCoef& c, const DpmEval& e, const float* out_u, const float* out_c, int Cm, float scale, float* s_buf,
               float ratio, float max_val, int B, int HW, hipStream_t s);
+// The error estimate of one adaptive DPM-Solver trial (dpm_solver_adaptive, sampler.py:965-977) on B logical samples of n
+// elements, from the planes a singlestep step leaves behind: x_lower = c0*base - c1*ma (lower_order 1) or (c0*base - c1*ma) -
+// c2*(mb - ma) (lower_order 2) through dpm_eval_value, written to x_lower [B,n]; delta = max(atol, rtol*max(|x_lower|,
+// |x_prev|)); err[b] = sqrt(mean(((x_higher - x_lower)/delta)^2)).  base / ma / mb / x_prev are [B,n]; x_higher row b sits at
+// xh + b*x_bs (0 = n; the first B rows of a guided 2B-row state).  part: dpm_adaptive_part_doubles(B) doubles of scratch.
+struct DpmAdaptiveErr {
+    float c[3] = {};
+    int lower_order = 1;
+    float atol = 0.f, rtol = 0.f;
+    const float* base = nullptr;
+    const float* ma = nullptr;
+    const float* mb = nullptr;     // null for lower_order 1
+    const float* xh = nullptr;
+    const float* x_prev = nullptr;
+    float* x_lower = nullptr;
+    int64_t x_bs = 0;
+    double* part = nullptr;
+    float* err = nullptr;          // device [B]
+};
+size_t dpm_adaptive_part_doubles(int B);
+void dpm_adaptive_error(const DpmAdaptiveErr& a, int B, int64_t n, hipStream_t s);
 // Image-to-image.  q_sample (+ mask blend): img_orig = a*x0 + s*z with a, s scalars or per row from the device arrays a_row /
 // s_row; mask != nullptr ([B,mask_ch,HW], mask_ch 1 or Cz): x = img_orig*mask + (1 - mask)*x, else x = img_orig.  x0 / noise are
 // [B,Cz,HW]; the state row b is x + b*x_bs (0 = Cz*HW); dup: also written to row B+b (guided 2B-row state).  noise == nullptr:

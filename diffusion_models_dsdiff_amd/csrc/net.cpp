@@ -729,6 +729,8 @@ void dsd::net_free(dsd_handle* h) {
     if (h->zplane) (void)hipFree(h->zplane);
     if (h->dpm_m) (void)hipFree(h->dpm_m);
     if (h->dpm_prog) (void)hipFree(h->dpm_prog);
+    if (h->dpm_adapt) (void)hipFree(h->dpm_adapt);
+    if (h->dpm_adapt_host) (void)hipHostFree(h->dpm_adapt_host);
     if (h->lat_in) (void)hipFree(h->lat_in);
     if (h->ctx_buf) (void)hipFree(h->ctx_buf);
     if (h->y_buf) (void)hipFree(h->y_buf);

@@ -160,6 +160,11 @@ struct dsd_handle {
     float* y_buf = nullptr;    // [rows] int64 or [rows, y_width] fp32
     float* cfg_io = nullptr;   // guided four-stream binding: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)
     float* dpm_prog = nullptr; // DPM-Solver program: three history planes + the base-state plane [B,Cz*H*W] each + thresholds [B]
+    // one adaptive trial (dsd_sample_dpm_adaptive_trial): the error kernel's partial sums and its B results on the device, and the
+    // pinned host buffer they are read back through
+    float* dpm_adapt = nullptr;
+    float* dpm_adapt_host = nullptr;
+    int dpm_adapt_host_n = 0;
     // PLMS loops: three history planes [B,Cz,h,w] (a ring: iteration k >= 1 reads its newest prediction from plane (k-1) % 3 and
     // retires plane k % 3) followed by the threshold's per-block partial sums.  The history outlives a call, so a later call
     // with first_step > 0 continues it: plms_next is the iteration it is valid for (-1: none), for plms_B samples of plms_n
@@ -214,7 +219,7 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
-    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, bpd_cap = 0, ctx_cap = 0, y_cap = 0;
+    size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, dpm_adapt_cap = 0, bpd_cap = 0, ctx_cap = 0, y_cap = 0;
 
     float* P(const std::string& name) const;
     float* slab_at(size_t off) const { return reinterpret_cast<float*>(slab + off); }

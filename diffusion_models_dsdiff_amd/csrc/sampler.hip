@@ -971,6 +971,79 @@ void ddim_reverse_step(const StepCoef& sc, float abar_next, const float* out, fl
     check_launch("ddim_reverse");
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Adaptive DPM-Solver (dpm_solver_adaptive, sampler.py:921-980): the error estimate of one trial (DpmAdaptiveErr in kernels.h).
+// One pass over the sample recomputes the lower-order result from the planes the singlestep step left — dpm_eval_value with
+// kind MS1 (c0*base - c1*ma, dpm_solver_first_update) or SS_T2 ((c0*base - c1*ma) - c2*(mb - ma), the second-order singlestep
+// update on the model_s1 the third-order step evaluated) — writes it out, and sums ((x_higher - x_lower)/delta)^2 per sample,
+// delta = max(atol, rtol*max(|x_lower|, |x_prev|)) (:969-971), every operation a single fp32 one in the reference's order.
+// The sum follows plms_x0_norm_kernel: fp64 per thread, a fixed LDS tree per block, block j of sample b into part[b*gridDim.x +
+// j], at most kAdaptiveBlocks partials per sample, which dpm_adaptive_finish_kernel adds in index order.  No atomics: two runs
+// are bit-identical.  As in vlb_terms_kernel a thread owns four consecutive elements and V only selects how they are loaded and
+// stored, so the scalar path adds the same values in the same order as the 16-byte one.
+static constexpr int kAdaptiveBlocks = 32;
+template <int V>
+__global__ __launch_bounds__(256) void dpm_adaptive_error_kernel(DpmAdaptiveErr a, DpmEval lo, int n) {
+    __shared__ double red[256];
+    const int b = blockIdx.y;
+    const int64_t row = (int64_t)b * n;
+    const float* xh = a.xh + (int64_t)b * a.x_bs;
+    double acc = 0.0;
+    for (int p = (blockIdx.x * 256 + threadIdx.x) * 4; p < n; p += gridDim.x * 1024) {
+        const int valid = n - p < 4 ? n - p : 4;
+        const Pack<4> xb = ld_quad<V>(a.base + row + p, valid), ma = ld_quad<V>(a.ma + row + p, valid);
+        const Pack<4> mb = a.mb ? ld_quad<V>(a.mb + row + p, valid) : ma;
+        const Pack<4> hi = ld_quad<V>(xh + p, valid), xp = ld_quad<V>(a.x_prev + row + p, valid);
+        Pack<4> xl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            xl.v[j] = dpm_eval_value(lo, xb.v[j], ma.v[j], mb.v[j], ma.v[j]);
+            const float delta = fmaxf(a.atol, a.rtol * fmaxf(fabsf(xl.v[j]), fabsf(xp.v[j])));
+            const float q = (hi.v[j] - xl.v[j]) / delta;
+            if (j < valid) acc += (double)q * (double)q;
+        }
+        st_quad<V>(a.x_lower + row + p, xl, valid);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.part[(int64_t)b * gridDim.x + blockIdx.x] = red[0];
+}
+
+__global__ void dpm_adaptive_finish_kernel(const double* __restrict__ part, int nblk, int n, float* __restrict__ err, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double sum = 0.0;
+    for (int j = 0; j < nblk; ++j) sum += part[(int64_t)b * nblk + j];
+    err[b] = (float)sqrt(sum / (double)n);
+}
+
+size_t dpm_adaptive_part_doubles(int B) { return (size_t)B * kAdaptiveBlocks; }
+
+void dpm_adaptive_error(const DpmAdaptiveErr& arg, int B, int64_t n, hipStream_t s) {
+    DpmAdaptiveErr a = arg;
+    if (!B || !n) return;
+    DSD_CHECK(n <= (int64_t)1 << 30, "adaptive error estimate: one sample has %lld elements; up to 2^30 are taken", (long long)n);
+    DSD_CHECK(B <= 65535, "adaptive error estimate: %d samples; up to 65535 are taken", B);
+    DSD_CHECK(a.part && a.err, "adaptive error estimate: it needs its scratch and its output");
+    if (a.x_bs <= 0) a.x_bs = n;
+    if (a.lower_order == 1) a.mb = nullptr;
+    DpmEval lo;
+    for (int j = 0; j < 3; ++j) lo.c[j] = a.c[j];
+    lo.kind = a.lower_order == 1 ? DSD_DPM_MS1 : DSD_DPM_SS_T2;
+    const bool v4 = can_vec4(n, a.x_bs, a.base, a.ma, a.mb, a.xh, a.x_prev, a.x_lower);
+    const int nblk = (int)std::min<int64_t>((n + 1023) / 1024, kAdaptiveBlocks);
+    launch_vec(v4, [&](auto V) {
+        hipLaunchKernelGGL(dpm_adaptive_error_kernel<decltype(V)::value>, dim3(nblk, B), dim3(256), 0, s, a, lo, (int)n);
+    });
+    check_launch("dpm_adaptive_error");
+    hipLaunchKernelGGL(dpm_adaptive_finish_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, a.part, nblk, (int)n, a.err, B);
+    check_launch("dpm_adaptive_finish");
+}
+
 // scale: LatentDiffusion.get_first_stage_encoding's scale_factor * z (ddpm.py:660-667), applied after the sample is formed
 // (1.0 for the plain DiagonalGaussianDistribution.sample: x * 1.0f is exact).  With B = batch*K rows ordered (sample, key),
 // z [B*K,E,HW] IS the [batch,K*E,HW] 'concat' conditioning: key k of a sample lands in channels [k*E,(k+1)*E).

@@ -35,6 +35,8 @@
  *                                  <- PLMSSampler.sample / p_sample_plms  ldm/models/diffusion/plms.py:59-245
  *                                        with sampling_util.norm_thresholding (dynamic_threshold)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
+ *   dsd_sample_dpm_adaptive_trial / dsd_op_dpm_adaptive_error
+ *                                  <- one trial of DPM_Solver.dpm_solver_adaptive  sampler.py:921-980 (the loop stays on the host)
  *   dsd_sample_dpm_program / dsd_op_dpm_eval
  *                                  <- DPM_Solver.sample / .inverse with method "multistep" order 1..3, "singlestep",
  *                                        "singlestep_fixed", return_intermediate, guided or not
@@ -475,6 +477,33 @@ int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* prog, const dsd
  * written.  hist: the three history planes [3,B,Cz,H,W]; base [B,Cz,H,W] (may be NULL for the multistep kinds). */
 int dsd_op_dpm_eval(const dsd_dpm_program* prog, int k, const float* out_uncond, const float* out_cond, int Cm, float scale, float* x,
                     int64_t x_row_stride, float* hist, float* base, int B, int Cz, int H, int W, void* stream);
+/* ---- adaptive step-size DPM-Solver: one trial ------------------------------------------------
+ * Replaces the body of the while loop of DPM_Solver.dpm_solver_adaptive (sampler.py:921-980 and the twin dpm_solver_pytorch.py:
+ * 958-1012); the loop itself — the step size h, accept or reject, the end test — stays with the host, which needs the error of
+ * every trial to decide the next.  prog is exactly ONE singlestep step from s to t: DSD_DPM_SS_S1, DSD_DPM_SS_T2 (order 2, r1 =
+ * 0.5) or DSD_DPM_SS_S1, DSD_DPM_SS_S2, DSD_DPM_SS_T3 / _T3_TAYLOR (order 3, r1 = 1/3, r2 = 2/3), i.e. `order` network
+ * evaluations, run by the driver of dsd_sample_dpm_program for every denoiser it takes, guided (g carries `order` scales) or
+ * not, with thresholding, with or without graph replay of the network.  lower_coef = {c0, c1, c2} is the update of order - 1
+ * from the same model values: x_lower = c0*x_s - c1*model_s (order 2; c2 = 0), or (c0*x_s - c1*model_s) - c2*(model_s1 - model_s)
+ * (order 3: the second-order singlestep update with r1 = 1/3, 'dpmsolver' or 'taylor' coefficient in c2); c0 and c1 are those
+ * of the step's last row.  After the step one pass forms x_lower, delta = max(atol, rtol*max(|x_lower|, |x_prev|)) and, per
+ * sample b, err[b] = sqrt(mean(((x_higher - x_lower)/delta)^2)) (fp64 sums in a fixed order: two runs give the same bits).
+ * x [B,Cz,H,W] (device): x_s on entry, x_higher on return — also when the caller then rejects the trial, so a caller that may
+ * reject passes a copy.  x_prev (device, in), x_lower (device, out): [B,Cz,H,W].  err (HOST, B floats) is copied back through a
+ * pinned buffer of the handle: the one synchronisation of the trial, outside any graph capture.  The trial is accepted when
+ * max_b err[b] <= 1.
+ * Rejected before any device work, each with its numbers: everything dsd_sample_dpm_program rejects; a program that is not
+ * exactly one singlestep step of order 2 or 3 (one that keeps intermediates has no output for them); a lower-order row whose c0 / c1 differ from the
+ * step's or whose c2 is non-zero for order 2 / not finite for order 3; atol <= 0; rtol < 0; null arrays. */
+int dsd_sample_dpm_adaptive_trial(dsd_handle* h, const dsd_dpm_program* prog, const dsd_guidance* g, const float* cond, int Cc,
+                                  const float* lower_coef, float atol, float rtol, float* x, const float* x_prev, float* x_lower, int Cz,
+                                  int B, int H, int W, float* err, void* stream);
+/* The error estimate alone on caller-supplied planes (kernel-level tests): lower_order 1 or 2, base / ma / mb (NULL for lower_order
+ * 1) / x_prev / x_lower [B,Cz,H,W], x_higher row b at x_higher + b*x_row_stride (0 = Cz*H*W; the first B rows of a guided 2B-row
+ * state), err: DEVICE array of B floats. */
+int dsd_op_dpm_adaptive_error(int lower_order, const float* lower_coef, float atol, float rtol, const float* base, const float* ma,
+                              const float* mb, const float* x_higher, int64_t x_row_stride, const float* x_prev, float* x_lower,
+                              float* err, int B, int Cz, int H, int W, void* stream);
 /* ---- DDIM inversion (DDIMSampler.encode, ddim.py:263-308) ----------------------------------
  * Iteration i evaluates the network at model time t_model[i] — the reference passes the loop index i itself (:282), not a
  * timestep of the schedule; the caller fills t_model accordingly — and applies x <- coef[2i]*x + coef[2i+1]*e  (xt_weighted + weighted_noise_pred, :292-295), e the network output or, with guidance,

@@ -27,12 +27,17 @@ program entry, copy this script into a checkout of that commit (this tree's bind
 With --bpd the variational-bound loop (dsd_calc_bpd: q_sample, one network evaluation and the terms / finalize launches per
 step, Philox noise) is timed against the mode-A DDPM sampling loop of the same handle, schedule and step count (dsd_sample):
 bpd_over_ddpm is what the three small launches cost beside a network evaluation.  Same alternation and untimed first step.
+With --adaptive the adaptive step-size solver (DPM_Solver.dpm_solver_adaptive, order 2, --adaptive-tol atol,rtol: one
+dsd_sample_dpm_adaptive_trial and one read-back of B floats per trial) is run once untimed for its count of network evaluations
+and then timed against a singlestep_fixed program of exactly that many (dsd_sample_dpm_program) in the same alternation:
+adaptive_over_fixed_same_nfe is what the error kernel, the read-back, the per-trial binding and the host's coefficient rows
+(adaptive_host_rows_ms_per_trial) cost beside the network.
 With --baseline FILE (repeatable) the bench lines that another build wrote with --json on the same machine — the parent commit's,
 run in turn with this one — are recorded beside the result: their device_loop_ms medians per K, and the ratio of this
 build's plain loop (the median of its device, unmasked and sample loops, which are the same call) to their mean.
 
     python tools/bench_latent.py [--batch 16] [--steps 50] [--keys 1,3] [--repeats 3] [--guidance-scale 3] [--mask] [--encode]
-                                 [--plms] [--bpd] [--dpm-family ss3,ms3,ms2] [--baseline other.json ...] [--json out.json]
+                                 [--plms] [--bpd] [--dpm-family ss3,ms3,ms2] [--adaptive] [--baseline other.json ...] [--json out.json]
 """
 import argparse
 import json
@@ -162,6 +167,34 @@ def run_k(K, args):
                 assert prog.steps == DPM_EVALS
                 dpm_runs[kind] = lambda prog=prog: dsa.run_dpm_program(fn, prog, xT)[0]
 
+    ad = {}
+
+    def adaptive_prepare():
+        """The adaptive loop (order 2, --adaptive-tol) once, untimed, for its count of evaluations; then a singlestep_fixed program
+        of exactly that many — the same network work without the error kernel, the read-back and the per-trial binding."""
+        import time
+        from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
+        ns = dsa.NoiseScheduleVP("discrete", alphas_cumprod=ld.alphas_cumprod.detach().float().cpu())
+        fn = dsa.model_wrapper(unet, ns, model_type="v", model_kwargs=dict(c_concat=[c]))
+        sol = dsa.DPM_Solver(fn, ns, algorithm_type="dpmsolver++")
+        atol, rtol = (float(v) for v in args.adaptive_tol.split(","))
+        rows, host_ms = sol.adaptive_trial_program, [0.]
+
+        def timed_rows(*a):                                        # host time of the coefficient rows of a trial
+            t0 = time.perf_counter()
+            out = rows(*a)
+            host_ms[0] += (time.perf_counter() - t0) * 1e3
+            return out
+        sol.adaptive_trial_program = timed_rows
+        run = lambda: sol.dpm_solver_adaptive(xT, 2, 1., 1. / ns.total_N, atol=atol, rtol=rtol, max_nfe=400, return_trace=True)
+        _, trace = run()
+        nfe = 2 * len(trace)
+        prog = sol.build_program(nfe, order=2, skip_type="logSNR", method="singlestep_fixed")
+        assert prog.steps == nfe
+        ad.update(nfe=nfe, trials=len(trace), rejected=sum(not t[4] for t in trace), atol=atol, rtol=rtol, host_ms=host_ms)
+        dpm_runs["adaptive"] = lambda: run()[0]
+        dpm_runs["fixed_same_nfe"] = lambda: dsa.run_dpm_program(fn, prog, xT)[0]
+
     i2i_kinds = ((("masked", "unmasked") if args.mask else ()) + (("invert", "sample") if args.encode else ()) +
                  (("plms", "ddim") if args.plms else ()) + (("bpd", "ddpm_a") if args.bpd else ()))
     cfg_kinds = ("guided", "unguided", "unguided_2x") if args.guidance_scale != 1. else ()
@@ -172,6 +205,9 @@ def run_k(K, args):
         i2i_loop(kind)
     if dpm_kinds:
         dpm_prepare()
+    if args.adaptive:
+        adaptive_prepare()
+        dpm_kinds = dpm_kinds + ("adaptive", "fixed_same_nfe")
     for kind in dpm_kinds:
         dpm_runs[kind]()
     y = device(False)
@@ -207,8 +243,12 @@ def run_k(K, args):
         for kind in dpm_kinds:
             dpm_runs[kind]()                                       # untimed run of the same loop
             torch.cuda.synchronize()
+            if kind == "adaptive":
+                ad["host_ms"][0] = 0.
             _, ms = timed(dpm_runs[kind])
             t[kind + "_loop_ms"].append(ms)
+            if kind == "adaptive":
+                t.setdefault("adaptive_host_rows_ms", []).append(ad["host_ms"][0])
     res = {k: stats(v) for k, v in t.items()}
     for k in ("device_loop", "device_loop_graph", "python_loop") + tuple(kind + "_loop" for kind in cfg_kinds + i2i_kinds):
         res[k + "_ms_per_step"] = res[k + "_ms"]["median"] / sched.steps
@@ -225,6 +265,15 @@ def run_k(K, args):
         res["plms_network_evaluations"] = sched.steps + 1
     if args.bpd:
         res["bpd_over_ddpm"] = res["bpd_loop_ms"]["median"] / res["ddpm_a_loop_ms"]["median"]
+    if args.adaptive:
+        nfe = ad["nfe"]
+        res.update(adaptive_network_evaluations=nfe, adaptive_trials=ad["trials"], adaptive_rejected=ad["rejected"],
+                   adaptive_atol=ad["atol"], adaptive_rtol=ad["rtol"],
+                   adaptive_ms_per_evaluation=res["adaptive_loop_ms"]["median"] / nfe,
+                   fixed_same_nfe_ms_per_evaluation=res["fixed_same_nfe_loop_ms"]["median"] / nfe,
+                   adaptive_over_fixed_same_nfe=res["adaptive_loop_ms"]["median"] / res["fixed_same_nfe_loop_ms"]["median"],
+                   adaptive_host_rows_ms_per_trial=res["adaptive_host_rows_ms"]["median"] / ad["trials"])
+        dpm_kinds = tuple(k for k in dpm_kinds if k not in ("adaptive", "fixed_same_nfe"))
     if dpm_kinds:
         res["dpm_network_evaluations"] = DPM_EVALS
         for kind in dpm_kinds:
@@ -254,6 +303,9 @@ def main():
     ap.add_argument("--plms", action="store_true", help="also time the PLMS loop against the DDIM loop of the same steps")
     ap.add_argument("--bpd", action="store_true", help="also time the variational-bound loop against the mode-A DDPM sampling loop")
     ap.add_argument("--dpm-family", default="", help="comma list of ss3, ms3, ms2: also time those DPM-Solver++ loops of 21 evaluations")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="also time DPM_Solver.dpm_solver_adaptive (order 2) against a singlestep_fixed program of the same evaluations")
+    ap.add_argument("--adaptive-tol", default="0.0078,0.05", help="atol,rtol of --adaptive")
     ap.add_argument("--baseline", action="append", default=[],
                     help="bench line of another build on the same machine (repeatable): record its plain loop beside this one's")
     ap.add_argument("--json", default=None)
