@@ -35,7 +35,7 @@ EXPORTS = [
     "dsd_invert", "dsd_op_mask_blend", "dsd_op_q_sample", "dsd_op_ddim_invert_step",
     "dsd_sample_plms", "dsd_op_plms_step", "dsd_sample_dpm_program", "dsd_op_dpm_eval",
     "dsd_sample_dpm_adaptive_trial", "dsd_op_dpm_adaptive_error",
-    "dsd_set_conditioning",
+    "dsd_set_conditioning", "dsd_set_trace",
     "dsd_calc_bpd", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
     "dsd_create_disc", "dsd_op_disc_bottleneck",
 ]
@@ -84,6 +84,10 @@ class DsdGuidance(C.Structure):
 class DsdConditioning(C.Structure):
     _fields_ = [("context", C.c_void_p), ("context_uncond", C.c_void_p), ("tokens", C.c_int32), ("y", C.c_void_p),
                 ("y_uncond", C.c_void_p), ("y_width", C.c_int32), ("B", C.c_int32)]
+
+
+class DsdTrace(C.Structure):
+    _fields_ = [("keep", C.POINTER(C.c_int32)), ("n_keep", C.c_int32), ("x", C.c_void_p), ("pred_x0", C.c_void_p)]
 
 
 class DsdInpaint(C.Structure):
@@ -248,6 +252,8 @@ def lib() -> C.CDLL:
                                              C.POINTER(vp), i32, vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
+    if hasattr(L, "dsd_set_trace"):            # (likewise)
+        L.dsd_set_trace.argtypes = [vp, C.POINTER(DsdTrace)]
     _lib = L
     return L
 

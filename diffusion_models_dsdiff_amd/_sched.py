@@ -8,7 +8,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import DSD_NCOEF, DsdBpd, DsdConditioning, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, check, dptr, lib, stream_ptr
+from ._lib import (DSD_NCOEF, DsdBpd, DsdConditioning, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, DsdTrace, check, dptr,
+                   lib, stream_ptr)
 
 
 class Schedule:
@@ -493,15 +494,126 @@ def _loop_inputs(unet, x_T: torch.Tensor, cond: torch.Tensor, steps: int, guidan
     return x, cond, g, inp, held
 
 
+def kept_iterations(total_steps: int, log_every_t: int) -> list:
+    """The loop iterations k (0 = the first executed, largest t) whose result the reference's samplers append to their
+    intermediates: ``index % log_every_t == 0 or index == total_steps - 1`` with index = total_steps - 1 - k (ddim.py:157,181;
+    plms.py likewise; ddpm.py:1041,1089 and trainer_ddpm.py:455 with index = the timestep i)."""
+    total_steps, log_every_t = int(total_steps), int(log_every_t)
+    return [k for k in range(total_steps) if (total_steps - 1 - k) % log_every_t == 0 or k == 0]
+
+
+class Trace:
+    """The intermediates of a device loop (dsd_set_trace): ``keep`` = ascending loop iterations, ``x`` / ``pred_x0`` = which of the
+    two buffers are wanted.  After the loop ``states`` / ``pred_x0s`` are lists of per-entry [B,Cz,H,W] tensors, one per kept
+    iteration the call's window covered (views of one [n_keep,B,Cz,H,W] buffer each)."""
+
+    def __init__(self, keep: Sequence[int], x: bool = True, pred_x0: bool = True):
+        self.keep = [int(k) for k in keep]
+        self.want_x, self.want_x0 = bool(x), bool(pred_x0)
+        self.x = self.pred_x0 = None
+        self.states, self.pred_x0s = [], []
+
+    def alloc(self, like: torch.Tensor) -> None:
+        """The two buffers for a state like ``like``; kept when they are there already, so the calls of a split run fill one pair."""
+        shape = (max(len(self.keep), 1),) + tuple(like.shape)
+        have = self.x if self.x is not None else self.pred_x0
+        if have is not None and tuple(have.shape) == shape and have.device == like.device:
+            return
+        new = lambda want: torch.zeros(shape, device=like.device, dtype=torch.float32) if want else None
+        self.x, self.pred_x0 = new(self.want_x), new(self.want_x0)
+
+    def collect(self, k0: int, k1: int) -> None:
+        js = [j for j, k in enumerate(self.keep) if k0 <= k < k1]
+        self.states = [self.x[j] for j in js] if self.x is not None else []
+        self.pred_x0s = [self.pred_x0[j] for j in js] if self.pred_x0 is not None else []
+
+
+@contextlib.contextmanager
+def trace_set(unet, keep: Sequence[int], x: Optional[torch.Tensor], pred_x0: Optional[torch.Tensor]):
+    """dsd_set_trace around one or more loop calls on the denoiser's handle: installs (keep, x, pred_x0) — the two tensors are
+    [len(keep),B,Cz,H,W] device buffers or None — and always clears it afterwards, whatever the loop did."""
+    keep_arr = np.ascontiguousarray(keep, dtype=np.int32).reshape(-1)
+    t = DsdTrace()
+    t.keep = keep_arr.ctypes.data_as(C.POINTER(C.c_int32))
+    t.n_keep = int(keep_arr.shape[0])
+    t.x = x.data_ptr() if x is not None else None
+    t.pred_x0 = pred_x0.data_ptr() if pred_x0 is not None else None
+    check(lib().dsd_set_trace(unet._h, C.byref(t)))
+    try:
+        yield
+    finally:
+        check(lib().dsd_set_trace(unet._h, None))
+
+
+class StepCallbacks:
+    """The reference's per-step ``callback(i)`` and ``img_callback(image, i)``, called in that order after every iteration.
+    ``index``: iteration k -> the ``i`` the reference passes (DDIM / PLMS: k itself, ddim.py:178-179; the DDPM loops: the timestep
+    steps - 1 - k, ddpm.py:1091-1092).  ``image``: "pred_x0" (DDIM, PLMS) or "x" (the DDPM loops: the state, after the blend)."""
+
+    def __init__(self, callback=None, img_callback=None, index=None, image: str = "pred_x0"):
+        assert image in ("pred_x0", "x")
+        self.callback, self.img_callback, self.index, self.image = callback, img_callback, index or (lambda k: k), image
+
+    def __bool__(self):
+        return self.callback is not None or self.img_callback is not None
+
+    @property
+    def needs_x0(self) -> bool:
+        return self.img_callback is not None and self.image == "pred_x0"
+
+    def after(self, k: int, x: torch.Tensor, pred_x0: Optional[torch.Tensor]) -> None:
+        i = self.index(k)
+        if self.callback:
+            self.callback(i)
+        if self.img_callback:
+            self.img_callback((pred_x0 if self.image == "pred_x0" else x).clone(), i)
+
+
+def _run_traced(unet, call, x: torch.Tensor, steps: int, first_step: int, n_steps: int, trace: Optional[Trace],
+                callbacks: Optional[StepCallbacks]) -> None:
+    """``call(first_step, n_steps)`` runs iterations of a device loop in place on ``x``.  Plain: one call.  With ``trace``: the
+    same call with the trace installed.  With ``callbacks``: single-step segments (n_steps = 1; the loops' state between them is
+    ``x``, PLMS's history stays on the handle), each with a one-entry trace pointing at the slots of ``trace`` where the iteration
+    is kept, and the callbacks after each.  Every route returns the same bits."""
+    k0 = max(int(first_step), 0)
+    k1 = steps if n_steps <= 0 else min(steps, k0 + int(n_steps))
+    if trace is not None:
+        trace.alloc(x)
+    if not callbacks:
+        if trace is None or not trace.keep:
+            call(first_step, n_steps)
+        else:
+            with trace_set(unet, trace.keep, trace.x, trace.pred_x0):
+                call(first_step, n_steps)
+    else:
+        slot = {k: j for j, k in enumerate(trace.keep)} if trace is not None else {}
+        scratch = torch.empty_like(x) if callbacks.needs_x0 else None
+        for k in range(k0, k1):
+            j = slot.get(k)
+            tx = trace.x[j] if j is not None and trace.x is not None else None
+            t0 = trace.pred_x0[j] if j is not None and trace.pred_x0 is not None else scratch
+            if tx is None and t0 is None:
+                call(k, 1)
+            else:
+                with trace_set(unet, [k], tx, t0):
+                    call(k, 1)
+            callbacks.after(k, x, t0)
+    if trace is not None:
+        trace.collect(k0, k1)
+
+
 @torch.no_grad()
 def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor,
                     step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                     first_step: int = 0, n_steps: int = 0, guidance: Optional[Guidance] = None,
-                    inpaint: Optional[Inpaint] = None) -> torch.Tensor:
+                    inpaint: Optional[Inpaint] = None, trace: Optional[Trace] = None,
+                    callbacks: Optional[StepCallbacks] = None) -> torch.Tensor:
     """dsd_sample.  x_T [B,1,H,W], cond [B,Cc,H,W] (CUDA fp32).  Returns x after the selected iterations.
     With the plain UNetModel or the DiT the state is a latent x_T [B,Cz,H,W]; step_noise is [steps,B,Cz,H,W].
     ``guidance``: classifier-free guidance (mode B_DDIM); its unconditional conditioning must have the shape, dtype and device
-    of ``cond``.  ``inpaint``: masked sampling (modes B_DDIM and B_DDPM), guided or not."""
+    of ``cond``.  ``inpaint``: masked sampling (modes B_DDIM and B_DDPM), guided or not.  ``trace``: the intermediates
+    (dsd_set_trace), filled in place; ``callbacks``: the reference's per-step callbacks, which cut the run into single-step
+    calls.  Neither changes a bit of the returned sample."""
     x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
                                          "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     B, Cz, H, W = x.shape
@@ -510,30 +622,40 @@ def run_device_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor
         step_noise = step_noise.detach().float().contiguous()
         if tuple(step_noise.shape) != (sched.steps, B, Cz, H, W):
             raise ValueError(f"step_noise must be [steps,B,Cz,H,W] = {(sched.steps, B, Cz, H, W)}, got {tuple(step_noise.shape)}")
-    with held:
+    seed = C.c_uint64(philox_seed(seed))
+
+    def call(first, n):
         check(lib().dsd_sample(unet._h, C.byref(sched.c), _ref(g), _ref(inp), dptr(cond), cond.shape[1], dptr(x), Cz,
-                               dptr(step_noise), C.c_uint64(philox_seed(seed)), B, H, W, first_step, n_steps, stream_ptr()))
+                               dptr(step_noise), seed, B, H, W, first, n, stream_ptr()))
+
+    with held:
+        _run_traced(unet, call, x, sched.steps, first_step, n_steps, trace, callbacks)
     return x
 
 
 @torch.no_grad()
 def run_plms_loop(unet, sched: Schedule, x_T: torch.Tensor, cond: torch.Tensor, threshold: Optional[float] = None,
                   guidance: Optional[Guidance] = None, inpaint: Optional[Inpaint] = None, seed: Optional[int] = None,
-                  first_step: int = 0, n_steps: int = 0) -> torch.Tensor:
+                  first_step: int = 0, n_steps: int = 0, trace: Optional[Trace] = None,
+                  callbacks: Optional[StepCallbacks] = None) -> torch.Tensor:
     """The PLMS device loop (dsd_sample_plms) on a DSD_MODE_B_PLMS schedule: x_T [B,1,H,W] with the four-stream model,
     [B,Cz,H,W] with the plain UNetModel.  ``threshold``: dynamic_threshold of norm_thresholding (None / <= 0:
     off).  The history of noise predictions stays on the denoiser's handle: ``first_step`` = k > 0 continues the run whose
     iterations 0 .. k-1 ran last on it (x_T = the state they returned) and fails otherwise.  ``seed`` keys the blend noise of
-    ``inpaint`` when it carries none; PLMS itself draws no noise."""
+    ``inpaint`` when it carries none; PLMS itself draws no noise.  ``trace`` / ``callbacks``: as in run_device_loop."""
     x, cond, g, inp, held = _loop_inputs(unet, x_T, cond, sched.steps, guidance, inpaint,
                                          "sampling runs on the MI355X only (no CPU fallback): x_T is on the CPU")
     thr = C.c_float(float(threshold) if threshold is not None else 0.0)
     seed = C.c_uint64(philox_seed(seed) if inp is not None and inp.noise is None else 0)
     B, Cz, H, W = x.shape
     _check_four_stream_io(unet, x, cond)
-    with held:
+
+    def call(first, n):
         check(lib().dsd_sample_plms(unet._h, C.byref(sched.c), _ref(g), _ref(inp), thr, dptr(cond), cond.shape[1], dptr(x), Cz, seed,
-                                    B, H, W, first_step, n_steps, stream_ptr()))
+                                    B, H, W, first, n, stream_ptr()))
+
+    with held:
+        _run_traced(unet, call, x, sched.steps, first_step, n_steps, trace, callbacks)
     return x
 
 

@@ -451,6 +451,28 @@ int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c) {
     DSD_CATCH
 }
 
+int dsd_set_trace(dsd_handle* h, const dsd_trace* t) {
+    DSD_TRY
+    DSD_CHECK(h, "null handle");
+    if (t) {   // checked whole before the handle changes: a rejected trace leaves the installed one in place
+        DSD_CHECK(t->n_keep >= 1, "trace: n_keep is %d; a trace keeps at least one iteration (NULL clears it)", t->n_keep);
+        DSD_CHECK(t->keep, "trace: keep is null");
+        DSD_CHECK(t->x || t->pred_x0, "trace: both buffers are NULL (x and pred_x0); nothing would be written");
+        DSD_CHECK(t->keep[0] >= 0, "trace: keep[0] = %d is out of range; iterations start at 0", t->keep[0]);
+        for (int j = 1; j < t->n_keep; ++j)
+            DSD_CHECK(t->keep[j] > t->keep[j - 1], "trace: keep is not strictly ascending (unsorted or repeated): keep[%d] = %d after keep[%d] = %d",
+                      j, t->keep[j], j - 1, t->keep[j - 1]);
+        h->trace_keep.assign(t->keep, t->keep + t->n_keep);
+        h->trace_x = t->x;
+        h->trace_x0 = t->pred_x0;
+    } else {
+        h->trace_keep.clear();
+        h->trace_x = h->trace_x0 = nullptr;
+    }
+    h->has_trace = t != nullptr;
+    DSD_CATCH
+}
+
 int dsd_block_forward(dsd_handle* h, const float* x, int B, int C, int H, int W, const float* aux, int aux_len,
                       const float* aux2, int aux_len2, float* out, void* stream) {
     DSD_TRY
@@ -721,6 +743,42 @@ void finish(dsd_handle* h, const LoopBinding& b, hipStream_t s) {
     net_check_overflow(h, s);
 }
 
+// dsd_set_trace as one loop call sees it.  The loop asks for iteration k's slots in ascending k, so `j` only moves forward; with
+// no trace installed every slot is null and the loop launches what it launches without one.
+struct Trace {
+    const dsd_handle* h;
+    size_t plane;                   // B*Cz*H*W: one entry of either buffer
+    size_t j = 0;
+    Trace(const dsd_handle* h_, const LoopBinding& b) : h(h_), plane((size_t)b.B * b.n()) {}
+    bool kept(int k) {
+        if (!h->has_trace) return false;
+        while (j < h->trace_keep.size() && h->trace_keep[j] < k) ++j;
+        return j < h->trace_keep.size() && h->trace_keep[j] == k;
+    }
+    // where the update kernel of iteration k writes its pred_x0 (it forms the value anyway), or null
+    float* x0_slot(int k) { return h->trace_x0 && kept(k) ? h->trace_x0 + j * plane : nullptr; }
+    // the B logical rows of the state after iteration k, dense, whatever row stride the binding keeps them at (under guidance the
+    // first half of the 2B rows; the update wrote both)
+    void state(int k, const LoopBinding& b, hipStream_t s) {
+        if (!h->trace_x || !kept(k)) return;
+        const size_t sample = (size_t)b.n() * sizeof(float);
+        DSD_HIP(hipMemcpy2DAsync(h->trace_x + j * plane, sample, b.xs, (size_t)b.x_bs * sizeof(float), sample, b.B,
+                                 hipMemcpyDeviceToDevice, s));
+    }
+};
+
+void check_trace(const dsd_handle* h, int steps) {
+    if (!h->has_trace) return;
+    DSD_CHECK(h->trace_keep.back() < steps, "trace: keep[%d] = %d is out of range; the schedule executes iterations 0..%d",
+              (int)h->trace_keep.size() - 1, h->trace_keep.back(), steps - 1);
+}
+
+// the loops that hand out no intermediates through a trace say so instead of ignoring one
+void refuse_trace(const dsd_handle* h, const char* loop) {
+    DSD_CHECK(!h->has_trace, "%s does not honour a trace (dsd_set_trace): dsd_sample and dsd_sample_plms do; clear it with "
+              "dsd_set_trace(h, NULL) before this call", loop);
+}
+
 StepCoef step_coef(const dsd_schedule* sc, int k) {
     StepCoef c{};
     for (int j = 0; j < DSD_NCOEF; ++j) c.c[j] = sc->coef[(size_t)k * DSD_NCOEF + j];
@@ -799,19 +857,22 @@ int dsd_sample(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g, con
     const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, want_ch);
     DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the schedule expects %d", h->cfg.out_channels,
               out_ch);
+    check_trace(h, sc->steps);
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
     const LoopBinding b = bind_denoiser(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s);
     const bool blend_first = inp && sc->mode == DSD_MODE_B_DDIM, blend_last = inp && !blend_first;
+    Trace tr(h, b);   // x after the update and (B_DDPM, ddpm.py:1085-1090) its blend; pred_x0 straight from the update kernel
     run_loop(h, b, sc->t_model, step_range(first_step, n_steps, sc->steps), s,
              [&](int k) {
                  if (blend_first) blend_step(sc, k, inp, b, seed, s);
              },
              [&](int k) {
                  sampler_update(step_coef(sc, k), b.out_u, b.out_c, g ? g->scale[k] : 1.f, b.xs,
-                                noise ? noise + (size_t)k * B * b.n() : nullptr, seed, (uint64_t)k, B, (int)b.hw, s, nullptr, b.ids, Cz,
-                                b.x_bs, out_ch * b.hw);
+                                noise ? noise + (size_t)k * B * b.n() : nullptr, seed, (uint64_t)k, B, (int)b.hw, s, tr.x0_slot(k), b.ids,
+                                Cz, b.x_bs, out_ch * b.hw);
                  if (blend_last) blend_step(sc, k, inp, b, seed, s);
+                 tr.state(k, b, s);
              });
     finish(h, b, s);
     DSD_CATCH
@@ -875,6 +936,7 @@ int dsd_sample_dpm(dsd_handle* h, const dsd_dpm_schedule* sc, const dsd_guidance
                    int B, int H, int W, void* stream) {
     DSD_TRY
     const bool latent = state_in_input(h);
+    refuse_trace(h, "dsd_sample_dpm");
     check_dpm_schedule(sc);
     if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
     const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
@@ -996,8 +1058,9 @@ static void dpm_program_eval(const dsd_dpm_program* p, int k, const float* out_u
 // call is checked for (before any device work) and returns Cm; dpm_program_loop binds, runs every evaluation, calls
 // after(binding, hist, base) on the planes the program left, and finishes.
 static int dpm_program_checks(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, const float* x,
-                              int Cz, int B, int H, int W, const float* inter) {
+                              int Cz, int B, int H, int W, const float* inter, bool inter_loop) {
     const bool latent = state_in_input(h);
+    refuse_trace(h, inter_loop ? "dsd_sample_dpm_program (its intermediates come through `intermediates`)" : "dsd_sample_dpm_adaptive_trial");
     check_dpm_program(p);
     if (g) check_guidance(g, p->n_eval, !(latent && Cc == 0 && h->has_cond));                          // one scale per evaluation
     const int kept = dpm_program_kept(p);
@@ -1030,7 +1093,7 @@ static void dpm_program_loop(dsd_handle* h, const dsd_dpm_program* p, const dsd_
 int dsd_sample_dpm_program(dsd_handle* h, const dsd_dpm_program* p, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz,
                            int B, int H, int W, float* inter, void* stream) {
     DSD_TRY
-    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, inter);
+    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, inter, true);
     set_device(h->device);
     dpm_program_loop(h, p, g, cond, Cc, x, Cz, B, H, W, Cm, inter, (hipStream_t)stream, [](const LoopBinding&, float*, float*) {});
     DSD_CATCH
@@ -1056,7 +1119,7 @@ int dsd_sample_dpm_adaptive_trial(dsd_handle* h, const dsd_dpm_program* p, const
                                   const float* lower_coef, float atol, float rtol, float* x, const float* x_prev, float* x_lower, int Cz,
                                   int B, int H, int W, float* err_host, void* stream) {
     DSD_TRY
-    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, nullptr);
+    const int Cm = dpm_program_checks(h, p, g, cond, Cc, x, Cz, B, H, W, nullptr, false);
     const int n_eval = p->n_eval, last = p->kind[n_eval - 1];
     const bool one_step = (n_eval == 2 && p->kind[0] == DSD_DPM_SS_S1 && last == DSD_DPM_SS_T2) ||
                           (n_eval == 3 && p->kind[0] == DSD_DPM_SS_S1 && p->kind[1] == DSD_DPM_SS_S2 &&
@@ -1171,6 +1234,7 @@ int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g
     const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
     DSD_CHECK(latent || h->cfg.out_channels == 1, "model has %d output channels but the schedule expects 1", h->cfg.out_channels);
     const int64_t n = (int64_t)Cz * H * W, plane = (int64_t)B * n;
+    check_trace(h, sc->steps);
     const Range r = step_range(first_step, n_steps, sc->steps);
     if (r.k0 > 0 && r.k0 < r.k1)
         DSD_CHECK(h->plms_next == r.k0 && h->plms_B == B && h->plms_n == n && h->plms_steps == sc->steps,
@@ -1192,6 +1256,7 @@ int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g
     a.x_bs = b.x_bs;
     a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->plms_hist) + planes);
     float* hist[3] = {h->plms_hist, h->plms_hist + plane, h->plms_hist + 2 * plane};
+    Trace tr(h, b);   // pred_x0 of the step's final get_x_prev_and_pred_x0: iteration 0's from its corrector, not its predictor
     run_loop(h, b, sc->t_model, r, s,
              [&](int k) {
                  h->plms_next = -1;                                           // until this iteration's e_t is in its plane
@@ -1208,12 +1273,15 @@ int dsd_sample_plms(dsd_handle* h, const dsd_schedule* sc, const dsd_guidance* g
                      fill_t(h->tbuf, b.rows, sc->t_model[std::min(1, sc->steps - 1)], s);
                      net_run_cached(h, s);
                      a.order = DSD_PLMS_CORRECT;
+                     a.x0_out = tr.x0_slot(k);
                      plms_step(a, B, Cz, (int)b.hw, s);
                  } else {                                                     // newest prediction in plane (k-1) % 3; plane k % 3 retires
                      a.order = std::min(k, 3) + 1;
                      a.h_new = hist[k % 3]; a.o1 = hist[(k + 2) % 3]; a.o2 = hist[(k + 1) % 3]; a.x_saved = nullptr;
+                     a.x0_out = tr.x0_slot(k);
                      plms_step(a, B, Cz, (int)b.hw, s);
                  }
+                 tr.state(k, b, s);
                  h->plms_next = k + 1;
                  h->plms_B = B; h->plms_n = n; h->plms_steps = sc->steps;
              });
@@ -1251,6 +1319,7 @@ int dsd_invert(dsd_handle* h, const dsd_invert_schedule* sc, const dsd_guidance*
                int H, int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
     const bool latent = state_in_input(h);
+    refuse_trace(h, "dsd_invert");
     DSD_CHECK(sc && sc->coef && sc->t_model && sc->steps >= 1, "bad inversion schedule");
     if (g) check_guidance(g, sc->steps, !(latent && Cc == 0 && h->has_cond));
     const int out_ch = check_denoiser(h, g, cond, Cc, x, Cz, B, H, W, Cz);
@@ -1318,6 +1387,7 @@ int dsd_calc_bpd(dsd_handle* h, const dsd_schedule* sc, const dsd_bpd* bpd, cons
                  const float* noise, uint64_t seed, int B, int H, int W, int first_step, int n_steps, void* stream) {
     DSD_TRY
     const bool latent = state_in_input(h);
+    refuse_trace(h, "dsd_calc_bpd");
     check_bpd_schedule(sc);
     DSD_CHECK(bpd, "null dsd_bpd");
     DSD_CHECK(bpd->post_log_var, "the bound needs the true posterior's log-variances (post_log_var is null; %d steps)", sc->steps);

@@ -360,6 +360,7 @@ struct PlmsStep {
     int64_t x_bs = 0;
     int64_t o_bs = 0;        // row stride of out_u / out_c (0 = n; 2n for a model with a variance half, left unread)
     double* part = nullptr;
+    float* x0_out = nullptr; // optional [B,n]: the pred_x0 this update forms (after the threshold), get_x_prev_and_pred_x0's second value
 };
 size_t plms_norm_doubles(int B, int64_t n);
 void plms_step(const PlmsStep& a, int B, int Cz, int HW, hipStream_t s);

@@ -156,6 +156,11 @@ struct dsd_handle {
     // copies of `rows` rows each (uncond half first under guidance), which io.aux2 / io.aux3 point at
     dsd_conditioning cond{};
     bool has_cond = false;
+    // dsd_set_trace: the kept iterations (copied) and the caller's two output buffers, read by dsd_sample / dsd_sample_plms
+    std::vector<int32_t> trace_keep;
+    float* trace_x = nullptr;
+    float* trace_x0 = nullptr;
+    bool has_trace = false;
     float* ctx_buf = nullptr;  // [rows, tokens, context_dim]
     float* y_buf = nullptr;    // [rows] int64 or [rows, y_width] fp32
     float* cfg_io = nullptr;   // guided four-stream binding: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)

@@ -692,6 +692,7 @@ __global__ __launch_bounds__(256) void plms_update_kernel(PlmsStep a, int B, int
         if (a.order == DSD_PLMS_PREDICT) st_pack<V>(a.x_saved + li, xt);
         st_pack<V>(xr + p, res);
         if (a.out_u) st_pack<V>(xr + p + (int64_t)B * a.x_bs, res);
+        if (a.x0_out) st_pack<V>(a.x0_out + li, x0);
     }
 }
 
@@ -706,6 +707,10 @@ void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
     if (a.x_bs <= 0) a.x_bs = n;
     if (a.o_bs <= 0) a.o_bs = n;
     const bool v4 = can_vec4(n, a.x_bs, a.out_u, a.out_c, a.h_new, a.o1, a.o2, a.x_saved, a.x) && a.o_bs % 4 == 0;
+    // x0_out does not choose the pack width: the threshold's partial sums follow it, and an update with the output must give the
+    // bits of the update without
+    DSD_CHECK(!v4 || ((uintptr_t)a.x0_out & 15u) == 0, "PLMS update: the pred_x0 output %p must be 16-byte aligned (samples of %lld floats)",
+              (const void*)a.x0_out, (long long)n);
     const int64_t blocks = (n / (v4 ? 4 : 1) + 255) / 256;
     const int nblk = (int)std::min<int64_t>(blocks, kPlmsNormBlocks);
     if (a.thr > 0.f) {

@@ -9,8 +9,9 @@ import numpy as np
 import torch
 
 from .... import _lib
-from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active, wrapper_key,
-                         invert_coefficients, philox_seed, q_sample_rows, run_device_loop, run_invert_loop)
+from ...._sched import (Guidance, Inpaint, Schedule, StepCallbacks, Trace, cat_conditioning, cat_unconditional, find_unet,
+                         guidance_active, wrapper_key, invert_coefficients, kept_iterations, philox_seed, q_sample_rows,
+                         run_device_loop, run_invert_loop)
 
 
 class MaskWithoutX0(AssertionError, NotImplementedError):
@@ -103,7 +104,10 @@ class DDIMSampler(object):
         ``conditioning`` (dict with c_concat lists, list, or tensor); ``ucg_schedule`` holds one scale per executed step.
         ``mask`` / ``x0`` (:160-163) run in the device loop too, guided or not: in front of every network evaluation the state
         becomes q_sample(x0, t)*mask + (1 - mask)*state.  ``mask_noise`` ([steps,B,C,H,W]) feeds q_sample's draws (an extension
-        like ``step_noise``); without it they are Philox normals of ``seed``."""
+        like ``step_noise``); without it they are Philox normals of ``seed``.
+        Intermediates (:149,178-183): {"x_inter": [x_T, ...], "pred_x0": [x_T, ...]}, the state and pred_x0 after every step
+        whose index is a multiple of ``log_every_t`` and after the first; ``callback(i)`` then ``img_callback(pred_x0, i)`` run
+        after every step, which cuts the device loop into single-step calls (same bits)."""
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None or temperature != 1. or noise_dropout != 0.:
             raise NotImplementedError("quantisation / score corrector / dynamic threshold / temperature / noise dropout are not "
                                       "on the medical hot path")
@@ -126,9 +130,12 @@ class DDIMSampler(object):
         inpaint = None
         if mask is not None:                                                          # x0 alone changes nothing (:160)
             inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
+        # :149,178-183: the state and pred_x0 of every log_every_t-th step, callback(i) then img_callback(pred_x0, i) after each
+        trace = Trace(kept_iterations(sched.steps, log_every_t))
         out = run_device_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device, wrapper_key(self.model)), step_noise=step_noise,
-                              seed=seed, guidance=guidance, inpaint=inpaint)
-        return out, {"x_inter": [img, out], "pred_x0": [img, out]}
+                              seed=seed, guidance=guidance, inpaint=inpaint, trace=trace,
+                              callbacks=StepCallbacks(callback, img_callback, image="pred_x0"))
+        return out, {"x_inter": [img] + trace.states, "pred_x0": [img] + trace.pred_x0s}
 
     def _unet(self):
         return find_unet(self.model.model if hasattr(self.model, "model") else self.model)

@@ -183,6 +183,37 @@ def select_checkpoint(sd, own_keys, ignore_keys=()):
     return keep, missing, unexpected
 
 
+def _ancestral_loop(self, cond, shape, x_T, callback, timesteps, quantize_denoised, mask, x0, img_callback, start_T, log_every_t,
+                    step_noise, seed, mask_noise, want_x, want_x0):
+    """The B_DDPM device loop behind p_sample_loop and progressive_denoising -> (sample, [x_T] + kept states, kept x0s)."""
+    from ...._sched import Inpaint, StepCallbacks, Trace, cat_conditioning, find_unet, kept_iterations, run_device_loop
+    if quantize_denoised:
+        raise NotImplementedError("quantize_denoised needs a VQ first stage; not on the device loop")
+    if (callback is not None or img_callback is not None) and not self.betas.is_cuda and x_T is not None and not x_T.is_cuda:
+        raise NotImplementedError("per-step callbacks (callback / img_callback) run between single-step calls of the device loop: "
+                                  "they need the state on the GPU (no CPU fallback)")
+    if mask is not None:
+        assert x0 is not None                                            # :1072
+        assert x0.shape[2:3] == mask.shape[2:3]                          # :1073 spatial size has to match
+    if not log_every_t:                                                  # :1053-1054
+        log_every_t = self.log_every_t
+    device = self.betas.device if self.betas.is_cuda else torch.device("cuda")
+    img = x_T if x_T is not None else torch.randn(shape, device=device)
+    if start_T is not None:
+        timesteps = min(timesteps or self.num_timesteps, start_T)
+    inpaint = None
+    if mask is not None:
+        inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
+    sched = self._schedule(timesteps)
+    T = sched.steps
+    trace = Trace(kept_iterations(T, log_every_t), x=want_x, pred_x0=want_x0) if (want_x or want_x0) else None
+    out = run_device_loop(find_unet(self.model), sched, img.to(device),
+                          cat_conditioning(cond, device, self.model.conditioning_key), step_noise=step_noise, seed=seed,
+                          inpaint=inpaint, trace=trace,
+                          callbacks=StepCallbacks(callback, img_callback, index=lambda k: T - 1 - k, image="x"))
+    return out, [img] + (trace.states if trace else []), (trace.pred_x0s if trace else [])
+
+
 class LatentDiffusion(DDPM):
     """The sampling surface of ldm/models/diffusion/ddpm.py:526-1115 (LatentDiffusion) as trainers/trainer_latent_diffusion.py
     uses it: a KL first stage (AutoencoderKL) around a native UNetModel under any of the reference's conditioning keys.  ``sample`` (DDPM,
@@ -350,26 +381,48 @@ class LatentDiffusion(DDPM):
                       step_noise=None, seed=None, mask_noise=None):
         """:1048-1093 on the device.  ``step_noise`` ([steps,B,C,h,w]) / ``seed`` are extensions for reproducible runs.
         ``mask`` / ``x0`` (:1071-1073,1085-1087): after every update, the last included, the state becomes
-        q_sample(x0, t)*mask + (1 - mask)*state; ``mask_noise`` ([steps,B,C,h,w]) feeds q_sample's draws, else Philox of ``seed``."""
-        from ...._sched import Inpaint, cat_conditioning, find_unet, run_device_loop
-        if quantize_denoised or callback is not None or img_callback is not None:
-            raise NotImplementedError("quantize / per-step callbacks are not on the device loop")
-        if mask is not None:
-            assert x0 is not None                                            # :1072
-            assert x0.shape[2:3] == mask.shape[2:3]                          # :1073 spatial size has to match
-        device = self.betas.device if self.betas.is_cuda else torch.device("cuda")
-        img = x_T if x_T is not None else torch.randn(shape, device=device)
-        if start_T is not None:
-            timesteps = min(timesteps or self.num_timesteps, start_T)
-        inpaint = None
-        if mask is not None:
-            inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
-        out = run_device_loop(find_unet(self.model), self._schedule(timesteps), img.to(device),
-                              cat_conditioning(cond, device, self.model.conditioning_key), step_noise=step_noise, seed=seed,
-                              inpaint=inpaint)
+        q_sample(x0, t)*mask + (1 - mask)*state; ``mask_noise`` ([steps,B,C,h,w]) feeds q_sample's draws, else Philox of ``seed``.
+        ``return_intermediates`` (:1062,1089-1090): [x_T] + the state (after the blend) of every timestep i with
+        i % log_every_t == 0 and of the first; ``callback(i)`` then ``img_callback(img, i)`` after every step (:1091-1092) with the
+        timestep i, which cuts the device loop into single-step calls (same bits)."""
+        out, kept, _ = _ancestral_loop(self, cond, shape, x_T, callback, timesteps, quantize_denoised, mask, x0, img_callback, start_T,
+                                       log_every_t, step_noise, seed, mask_noise, want_x=return_intermediates, want_x0=False)
         if return_intermediates:
-            return out, [img, out]
+            return out, kept
         return out
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None, mask=None,
+                              x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                              batch_size=None, x_T=None, start_T=None, log_every_t=None, step_noise=None, seed=None,
+                              mask_noise=None):
+        """:991-1045 on the device -> (img, [x0_partial ...]): the clipped x_recon (p_sample(return_x0=True)) of every timestep
+        i with i % log_every_t == 0 and of the first, no leading x_T; ``callback(i)`` then ``img_callback(img, i)`` after every
+        step.  ``step_noise`` / ``seed`` / ``mask_noise``: the extensions of p_sample_loop."""
+        if temperature != 1.:
+            raise NotImplementedError("temperature other than 1. is not on the device loop")
+        if noise_dropout != 0.:
+            raise NotImplementedError("noise_dropout other than 0. is not on the device loop")
+        if score_corrector is not None:
+            raise NotImplementedError("score_corrector is not on the device loop")
+        if batch_size is not None:                                           # :999-1003
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        if cond is not None:                                                 # :1009-1014
+            if isinstance(cond, dict):
+                cond = {k: [x[:batch_size] for x in v] if isinstance(v, list) else v[:batch_size] for k, v in cond.items()}
+            else:
+                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        out, _, x0s = _ancestral_loop(self, cond, shape, x_T, callback, None, quantize_denoised, mask, x0, img_callback, start_T,
+                                      log_every_t, step_noise, seed, mask_noise, want_x=False, want_x0=True)
+        return out, x0s
+
+    @torch.no_grad()
+    def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):
+        """:648-658: every entry through decode_first_stage, then the grid of rows (one row per sample, one column per entry)."""
+        from ...util import denoise_grid
+        return denoise_grid([self.decode_first_stage(z) for z in samples])
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,

@@ -7,8 +7,8 @@ from __future__ import annotations
 import torch
 
 from .... import _lib
-from ...._sched import (Guidance, Inpaint, Schedule, cat_conditioning, cat_unconditional, find_unet, guidance_active, wrapper_key,
-                         run_plms_loop)
+from ...._sched import (Guidance, Inpaint, Schedule, StepCallbacks, Trace, cat_conditioning, cat_unconditional, find_unet,
+                         guidance_active, kept_iterations, wrapper_key, run_plms_loop)
 from .ddim import DDIMSampler, MaskWithoutX0, pack_schedule
 
 
@@ -44,13 +44,15 @@ class PLMSSampler(object):
         first step's predictor included.  ``mask`` / ``x0`` blend q_sample(x0, t) into the state in front of every step (:152-155);
         ``mask_noise`` ([S,B,C,H,W]) feeds q_sample's draws, else they are Philox normals of ``seed`` (both extensions, as in
         DDIMSampler.sample).  The conditioning comes as a tensor, a list or dict(c_concat=[...]), the unconditional one alike.
-        Unsupported reference options raise instead of being ignored."""
+        Intermediates and ``callback`` / ``img_callback`` as in DDIMSampler.sample (:139,169-174); pred_x0 is the one of the step's
+        final get_x_prev_and_pred_x0.  Unsupported reference options raise instead of being ignored."""
         if quantize_x0:
             raise NotImplementedError("quantize_x0 needs a VQ first stage; not on the device loop")
         if score_corrector is not None:
             raise NotImplementedError("score correctors are not on the device loop")
-        if callback is not None or img_callback is not None:
-            raise NotImplementedError("per-step callbacks are not on the device loop")
+        if (callback is not None or img_callback is not None) and not self.model.betas.is_cuda:
+            raise NotImplementedError("per-step callbacks (callback / img_callback) run between single-step calls of the device loop: "
+                                      "they need the model on the GPU (no CPU fallback)")
         if self.model.parameterization == "v":
             raise NotImplementedError("PLMSSampler takes the network output as a noise prediction (plms.py:227-243); for a "
                                       "v-model the reference's update is not one, so it is not reproduced")
@@ -69,6 +71,9 @@ class PLMSSampler(object):
         inpaint = None
         if mask is not None:
             inpaint = Inpaint(x0.to(device), mask.to(device), mask_noise.to(device) if mask_noise is not None else None)
+        # :139,169-174: the state and the step's final pred_x0 of every log_every_t-th step; callback(i), img_callback(pred_x0, i)
+        trace = Trace(kept_iterations(sched.steps, log_every_t))
         out = run_plms_loop(self._unet(), sched, img.to(device), cat_conditioning(conditioning, device, wrapper_key(self.model)),
-                            threshold=dynamic_threshold, guidance=guidance, inpaint=inpaint, seed=seed)
-        return out, {"x_inter": [img, out], "pred_x0": [img, out]}
+                            threshold=dynamic_threshold, guidance=guidance, inpaint=inpaint, seed=seed, trace=trace,
+                            callbacks=StepCallbacks(callback, img_callback, image="pred_x0"))
+        return out, {"x_inter": [img] + trace.states, "pred_x0": [img] + trace.pred_x0s}

@@ -42,6 +42,40 @@ def instantiate_from_config(config):
     return get_obj_from_str(config["target"])(**config.get("params", dict()))
 
 
+def make_grid(tensor, nrow=8, padding=2, pad_value=0.):
+    """torchvision.utils.make_grid at its documented defaults, restated (parity unpinned: torchvision is not a dependency of
+    this package and no run of it stands behind this): [N,C,H,W] -> one [3 or C, rows*(H+padding)+padding, cols*(W+padding)+padding]
+    image, ``nrow`` images per row, cell (r, c) at offset (r*(H+padding)+padding, c*(W+padding)+padding), the padding filled with
+    ``pad_value``, no normalisation, one-channel images repeated to three channels; a single image comes back as it is."""
+    import math
+
+    import torch
+    if tensor.dim() != 4:
+        raise ValueError(f"make_grid takes [N,C,H,W], got {tuple(tensor.shape)}")
+    if tensor.shape[1] == 1:
+        tensor = torch.cat((tensor, tensor, tensor), 1)
+    n, c, h, w = tensor.shape
+    if n == 1:
+        return tensor.squeeze(0)
+    cols = min(int(nrow), n)
+    rows = int(math.ceil(n / cols)) if cols else 0
+    ch, cw = h + padding, w + padding
+    grid = tensor.new_full((c, ch * rows + padding, cw * cols + padding), pad_value)
+    for k in range(n):
+        r, q = divmod(k, cols)
+        grid[:, r * ch + padding:r * ch + padding + h, q * cw + padding:q * cw + padding + w] = tensor[k]
+    return grid
+
+
+def denoise_grid(samples):
+    """_get_rows_from_list (trainers/trainer_ddpm.py:473-478; ldm/models/diffusion/ddpm.py:653-658): a list of n [b,c,h,w] entries
+    -> the grid with one row per sample and one column per entry.  Parity unpinned, as make_grid."""
+    import torch
+    stack = torch.stack(list(samples))                                       # n b c h w
+    n = stack.shape[0]
+    return make_grid(stack.transpose(0, 1).reshape((stack.shape[1] * n,) + tuple(stack.shape[2:])), nrow=n)
+
+
 def load_unet_from_yaml(path, **overrides):
     """Build the U-Net named by ``model.params.unet_config`` of a reference model yaml (PyYAML; the hot-path
     yamls use no OmegaConf interpolation — SURVEY.md 5)."""

@@ -8,8 +8,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._sched import Schedule, find_unet, run_device_loop
+from .._sched import Schedule, Trace, find_unet, kept_iterations, run_device_loop
 from ..ldm.models.diffusion.ddpm import DDPM
+from ..ldm.util import denoise_grid
 
 
 class DDPMModel(DDPM):
@@ -43,16 +44,23 @@ class DDPMModel(DDPM):
     @torch.no_grad()
     def p_sample_loop(self, shape, cond=None, return_intermediates=False, x_T=None, step_noise=None, seed=None,
                       *args, **kwargs):
-        """:447-459.  ``x_T`` / ``step_noise`` / ``seed`` are extensions for reproducible runs."""
+        """:447-459.  ``x_T`` / ``step_noise`` / ``seed`` are extensions for reproducible runs.  Intermediates (:451-456): [x_T] +
+        the state after every timestep i with i % self.log_every_t == 0 and after the first."""
         device = self.betas.device
         img = x_T if x_T is not None else torch.randn(shape, device=device)
         c = cond["c_concat"] if isinstance(cond, dict) else (cond if isinstance(cond, list) else [cond])
         unet = find_unet(self.model)
-        out = run_device_loop(unet, self._schedule(self.clip_denoised), img.to(device),
-                              torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed)
+        sched = self._schedule(self.clip_denoised)
+        trace = Trace(kept_iterations(sched.steps, self.log_every_t), pred_x0=False) if return_intermediates else None
+        out = run_device_loop(unet, sched, img.to(device), torch.cat([t.to(device) for t in c], 1), step_noise=step_noise, seed=seed,
+                              trace=trace)
         if return_intermediates:
-            return out, [img, out]
+            return out, [img] + trace.states
         return out
+
+    def _get_rows_from_list(self, samples):
+        """:473-478 with make_grid restated at its documented defaults (ldm/util.py): parity unpinned."""
+        return denoise_grid(samples)
 
     def sample(self, batch_size=16, cond=None, shape=None, return_intermediates=False, *args, **kwargs):
         """:442-445."""
@@ -63,7 +71,9 @@ class DDPMModel(DDPM):
     def log_images(self, batch, N=8, n_row=2, sample=True, return_keys=None, sampler="ddim", pred_mode=False,
                    ddim_eta=0, **kwargs):
         """:394-440 — the sampler switch of the prediction path (``dpm`` | ``ddim`` | DDPM ancestral).  ``batch`` holds
-        the target under ``first_stage_key`` (shape only) and the condition under ``"image"``."""
+        the target under ``first_stage_key`` (shape only) and the condition under ``"image"``.  ``denoise_row`` (:409-433, skipped
+        under ``pred_mode``): the grid of the sampler's kept states, for ``ddim`` of the first quarter of the batch (:421-425); the
+        DPM-Solver sampler returns no intermediates here and logs none."""
         from ..ldm.models.diffusion.ddim import DDIMSampler
         from ..ldm.models.diffusion.dpm_solver_new import DPMSolverSampler
         device = self.betas.device
@@ -80,10 +90,14 @@ class DDPMModel(DDPM):
                 kwargs.pop("ddim_use_original_steps", None)
                 samples, _ = DPMSolverSampler(self).sample(kwargs.pop("ddim_steps"), N, shape, c, **kwargs)
             elif sampler == "ddim":
-                samples, _ = DDIMSampler(self).sample(kwargs.pop("ddim_steps"), N, shape, c, verbose=False, eta=ddim_eta,
-                                                      **kwargs)
+                samples, inter = DDIMSampler(self).sample(kwargs.pop("ddim_steps"), N, shape, c, verbose=False, eta=ddim_eta,
+                                                          **kwargs)
+                if not pred_mode:
+                    log["denoise_row"] = self._get_rows_from_list([img[:int(0.25 * img.shape[0])] for img in inter["x_inter"]])
             else:
-                samples = self.sample(batch_size=N, cond=c, shape=shape)
+                samples, denoise_row = self.sample(batch_size=N, cond=c, shape=shape, return_intermediates=True)
+                if not pred_mode:
+                    log["denoise_row"] = self._get_rows_from_list(denoise_row)
             log["samples"] = samples
         if return_keys:
             keep = [k for k in log if k in return_keys]

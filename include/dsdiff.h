@@ -34,6 +34,9 @@
  *   dsd_sample_plms / dsd_op_plms_step
  *                                  <- PLMSSampler.sample / p_sample_plms  ldm/models/diffusion/plms.py:59-245
  *                                        with sampling_util.norm_thresholding (dynamic_threshold)
+ *   dsd_set_trace                  <- the intermediates those samplers return (x_inter / pred_x0 every log_every_t steps)
+ *                                        ldm/models/diffusion/ddim.py:149,178-183, plms.py likewise, ddpm.py:1062,1089-1092,
+ *                                        trainers/trainer_ddpm.py:451-456
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
  *   dsd_sample_dpm_adaptive_trial / dsd_op_dpm_adaptive_error
  *                                  <- one trial of DPM_Solver.dpm_solver_adaptive  sampler.py:921-980 (the loop stays on the host)
@@ -364,6 +367,36 @@ typedef struct dsd_conditioning {
     int32_t B;                   /* batch size */
 } dsd_conditioning;
 int dsd_set_conditioning(dsd_handle* h, const dsd_conditioning* c);
+/* ---- intermediates of a loop ------------------------------------------------------------------
+ * What the reference's samplers return beside the sample: the state every log_every_t steps and, from DDIM and PLMS, pred_x0
+ * (intermediates of DDIMSampler.ddim_sampling ddim.py:149,178-183 and plms_sampling; LatentDiffusion.p_sample_loop
+ * ddpm.py:1062,1089-1092; progressive_denoising's x0_partial :1034-1040; DDPMModel.p_sample_loop trainer_ddpm.py:451-456).
+ * dsd_set_trace installs a trace on the handle, NULL clears it; the loops' own signatures stay as they are.  dsd_sample (all four
+ * modes) and dsd_sample_plms honour it — unguided, guided and masked, for every denoiser they take:
+ *   x[j]        the B logical rows of the state after the update of iteration keep[j], dense [B,Cz,H,W] whatever row stride
+ *               the loop keeps its state at; under guidance one half of the 2B rows (both hold the same value).  A masked
+ *               DSD_MODE_B_DDPM loop blends after the update and the entry is taken after that blend (ddpm.py:1085-1090);
+ *               DSD_MODE_B_DDIM and PLMS blend in front of the evaluation, so theirs is the update's own result.
+ *   pred_x0[j]  what the update kernel of iteration keep[j] forms anyway, written by that kernel (no extra pass): DDIM's
+ *               pred_x0 from the guided e_t (v-models: predict_start_from_z_and_v), family B DDPM's clipped x_recon
+ *               (p_sample(return_x0=True)), family A's clipped pred_xstart (the Cz state channels only under a learned-range
+ *               variance), PLMS's pred_x0 of the step's final get_x_prev_and_pred_x0, after norm thresholding.
+ * A call with first_step / n_steps writes the entries whose keep[j] lies in its window and no others: a split run fills the
+ * buffers an unsplit one fills.  The snapshots lie outside the network graph of dsd_set_graph; with or without replay the
+ * buffers hold the same bits, and so does the sample with or without a trace.  With no trace installed the loops launch what
+ * they launch without this feature.
+ * Rejected by dsd_set_trace, which then leaves the installed trace in place: n_keep < 1, keep not strictly ascending,
+ * keep[0] < 0, both buffers NULL.  Rejected by the loop before any device work: a keep entry >= the schedule's steps.  (PLMS
+ * with samples of a multiple of four floats wants pred_x0 16-byte aligned and says so.)  Every other loop (dsd_sample_dpm, dsd_sample_dpm_program, dsd_sample_dpm_adaptive_trial,
+ * dsd_invert, dsd_calc_bpd) fails while a trace is installed instead of ignoring it.  The buffers must stay valid until the
+ * trace is cleared or replaced. */
+typedef struct dsd_trace {
+    const int32_t* keep;  /* HOST, n_keep strictly ascending loop iterations k in [0, steps); copied by the call */
+    int32_t n_keep;
+    float* x;             /* DEVICE [n_keep,B,Cz,H,W] or NULL: the state as the reference appends it after iteration keep[j] */
+    float* pred_x0;       /* DEVICE [n_keep,B,Cz,H,W] or NULL: the pred_x0 the reference's step returns at iteration keep[j] */
+} dsd_trace;
+int dsd_set_trace(dsd_handle* h, const dsd_trace* t);   /* NULL clears */
 
 /* DDPM / DDIM (dsd_schedule).  noise: NULL -> on-device Philox4x32-10 N(0,1) from philox_seed; else [steps,B,Cz,H,W] pre-drawn
  * normals, noise[k] used at iteration k (parity mode). */
