@@ -6,7 +6,9 @@ Same constructor, enums and sampling entry points as the reference (``p_sample_l
 :141-178 does; the loop itself (network + fused update) runs on the MI355X through dsd_sample.  The evaluation half — ``calc_bpd_loop``
 :938-991 with ``_vb_terms_bpd`` / ``_prior_bpd``, ``p_mean_variance`` as a method, ``ddim_reverse_sample`` and the q_* helpers —
 runs through dsd_calc_bpd and the dsd_op_vlb_terms / dsd_op_prior_bpd / dsd_op_ddim_reverse_step kernels.
-Training losses are out of scope.
+``training_losses`` :821-920 (and its training_project/utils twin :824-) is here as an EVALUATION — the validation loss of a
+checkpoint, forward only, one timestep per sample — through dsd_eval_loss; the contrastive ``disentangle=`` heads and anything
+with a gradient stay out.
 """
 from __future__ import annotations
 
@@ -17,8 +19,9 @@ import numpy as np
 import torch as th
 
 from ... import _lib
-from ..._sched import (Schedule, ddim_reverse_step, disc_planes, is_disc, is_dit, kwargs_conditioning, loop_denoiser, model_output_of, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop,
-                       run_device_loop, sampler_update, vlb_terms, _seed_from_torch)
+from ..._sched import (Schedule, ddim_reverse_step, disc_planes, is_disc, is_dit, kwargs_conditioning, loop_denoiser, loss_rows,
+                       model_output_of, pair_mse_rows, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop, run_device_loop,
+                       run_eval_loss, sampler_update, vlb_terms, vlb_terms_rows, _seed_from_torch)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
@@ -479,6 +482,117 @@ class GaussianDiffusion:
                           mse=res["mse"][:, k])
         res["total_bpd"] = res["vb"].sum(dim=1) + res["prior_bpd"]             # :984
         return res
+
+    # ------------------------------------------------------------------ the denoising loss (evaluation)
+    def get_v(self, x, noise, t):
+        """:375-379."""
+        return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x.shape) * noise
+                - _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x.shape) * x)
+
+    def _loss_rows(self, t):
+        """The per-sample values of a batch of timesteps ``t`` [B]: (network timestep, a = sqrt_alphas_cumprod[t], s =
+        sqrt_one_minus_alphas_cumprod[t], (vlb coefficient rows, posterior_log_variance_clipped[t], t == 0)), each the fp32 of the
+        float64 table as _extract_into_tensor rounds it."""
+        idx = t.detach().cpu().numpy().astype(np.int64)
+        if idx.ndim != 1:
+            raise ValueError(f"t must be a [B] tensor of timestep indices, got shape {tuple(t.shape)}")
+        T = self.num_timesteps
+        if idx.size and (idx.min() < 0 or idx.max() >= T):
+            raise ValueError(f"t must lie in [0, {T - 1}], got [{idx.min()}, {idx.max()}]")
+        f32 = lambda a: np.asarray(a, dtype=np.float64)[idx].astype(np.float32)
+        sched = self._schedule(False, 0.0, False)                       # clip_denoised=False (:847, :872)
+        vlb = (sched.coef[T - 1 - idx], f32(self.posterior_log_variance_clipped), (idx == 0).astype(np.int32))
+        return self._model_timestep_values()[idx], f32(self.sqrt_alphas_cumprod), f32(self.sqrt_one_minus_alphas_cumprod), vlb
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, disentangle=None, disen_lambda=0.1, seed=None):
+        """The reference's training_losses, forward only: a dict of [N] tensors.  ``t`` [N] (long) may hold a different timestep
+        for every sample.  The denoiser picks the form: a UNet_disc_Model takes Disc_diff/guided_diffusion/gaussian_diffusion.py:
+        821-920 (``t1`` / ``t2`` / ``dwi`` of ``model_kwargs`` behind x_t; terms "mse", "com", "dist", "disent" = com / dist, "vb"
+        with a learned sigma, "loss"); any other takes training_project/utils/gaussian_diffusion.py:824- (the condition from
+        ``c_concat``, or from ``F_Data1``, ``F_Data2``, ``S_Data1`` [, ``edge``] as there; terms "mse", "vb", "loss").  "mse" is the
+        Charbonnier loss both copies compute under that name (smooth_L1).  A native denoiser runs dsd_eval_loss (q_sample, one
+        forward with per-sample t, the loss kernels); a foreign callable is called as ``model(x_t, t)`` around the same
+        kernels.  ``noise`` None: on-device Philox normals keyed by ``seed`` (an extension, as on the loops), else by torch's
+        generator."""
+        if disentangle is not None:
+            raise NotImplementedError("disentangle= adds the contrastive content / style / anatomy / lesion heads "
+                                      "(training_project/utils/gaussian_diffusion.py:908-975): that is training and is not built")
+        if not isinstance(self.loss_type, LossType):
+            raise NotImplementedError(self.loss_type)
+        if not x_start.is_cuda:
+            raise RuntimeError("training_losses runs on the MI355X only (no CPU fallback): x_start is on the CPU")
+        model_kwargs = model_kwargs or {}
+        device = x_start.device
+        xs = x_start.detach().float().contiguous()
+        if noise is not None:
+            assert noise.shape == x_start.shape
+            noise = noise.to(device)
+        seed = philox_seed(seed) if noise is None else 0
+        t_model, a, s, vlb = self._loss_rows(t)
+        unet = loop_denoiser(model, {k: v for k, v in model_kwargs.items() if k in ("t1", "t2", "dwi", "c_concat", "context", "y",
+                                                                                   "c_crossattn", "c_adm")})
+        disc = is_disc(unet) if unet is not None else "t1" in model_kwargs      # a foreign callable: the form its kwargs spell
+        if disc:
+            planes = [model_kwargs[k].to(device) for k in ("t1", "t2", "dwi")]          # KeyError as the reference's (:840)
+        else:
+            planes = model_kwargs.get("c_concat")
+            if planes is None and "F_Data1" in model_kwargs:                            # training_project :881-884
+                planes = [model_kwargs["F_Data1"], model_kwargs["F_Data2"], model_kwargs["S_Data1"]]
+                if "edge" in model_kwargs:
+                    planes.append(model_kwargs["edge"])
+            planes = [planes] if th.is_tensor(planes) else planes
+            planes = None if planes is None else [c.to(device) for c in planes]
+        learned = self.model_var_type == ModelVarType.LEARNED_RANGE
+        kl = self.loss_type.is_vb()
+        want_vb = kl or learned
+        pred = self._pred_code()                                        # p_mean_variance's reading of the output (vb)
+        if self.parameterization not in ("eps", "x0", "v"):             # :878-885: the target follows `parameterization` alone
+            raise NotImplementedError(f"Parameterization {self.parameterization} not yet supported")
+        target = {"eps": _lib.PRED_EPS, "x0": _lib.PRED_X0, "v": _lib.PRED_V}[self.parameterization]
+        if unet is not None:
+            bundle = kwargs_conditioning(unet, model, model_kwargs, device) if not is_dit(unet) and not disc else None
+            if bundle is None:
+                if planes is None and is_dit(unet):
+                    planes = [xs.new_zeros((xs.shape[0], 0) + tuple(xs.shape[2:]))]
+                if planes is None:
+                    raise KeyError("training_losses needs the condition: 'c_concat', or 'F_Data1' / 'F_Data2' / 'S_Data1' [/ 'edge']")
+                bundle = th.cat(planes, 1)
+            got = run_eval_loss(unet, pred, _lib.LOSS_CHARBONNIER, xs, bundle, t_model, a, s, noise=noise, seed=seed,
+                                vlb=vlb if want_vb else None, learned_range=learned, target=target)
+        else:
+            rows = [th.from_numpy(np.ascontiguousarray(r)).to(device) for r in (a, s)]
+            x_t = q_sample_rows(rows[0], rows[1], xs, noise, seed, 0)
+            tv = th.from_numpy(np.ascontiguousarray(t_model)).to(device)
+            x_in = x_t if planes is None or not disc else th.cat([x_t] + planes, 1)
+            kw = {} if disc or planes is None else {"c_concat": planes}
+            if kl:              # the KL types call the network inside p_mean_variance (:271-276): model(x_input, t, **model_kwargs)
+                x_in, kw = (th.cat([x_t] + planes, 1) if model_kwargs.get("t1") is not None else x_t), dict(model_kwargs)
+            full = model(x_in, tv if self.rescale_timesteps else tv.long(), **kw)
+            out = model_output_of(full).float()
+            got = {"mse": loss_rows(target, _lib.LOSS_CHARBONNIER, out, xs, noise, rows[0], rows[1], seed, 0)}
+            if want_vb:
+                got["vb"] = vlb_terms_rows(pred, learned, False, th.from_numpy(vlb[0]), th.from_numpy(vlb[1]), th.from_numpy(vlb[2]),
+                                           out, x_t, xs, noise, seed, 0)[0]
+            if disc and not kl:
+                com = [f for f in full[0:4] if f is not None]
+                dist = [f for f in full[4:8] if f is not None]
+                got["com"], got["dist"] = pair_mse_rows(com), pair_mse_rows(dist)
+        terms = {}
+        if kl:                                                          # :841-851
+            terms["loss"] = got["vb"] * self.num_timesteps if self.loss_type == LossType.RESCALED_KL else got["vb"]
+            return terms
+        if learned:                                                     # :857-877
+            terms["vb"] = got["vb"]
+            if self.loss_type == LossType.RESCALED_MSE:
+                terms["vb"] = terms["vb"] * (self.num_timesteps / 1000.0)
+        terms["mse"] = got["mse"]
+        if disc:                                                        # :898-916
+            terms["com"], terms["dist"] = got["com"], got["dist"]
+            terms["disent"] = terms["com"] / terms["dist"]
+            terms["loss"] = terms["mse"] + terms["disent"] + terms["vb"] if "vb" in terms else terms["mse"] + terms["disent"]
+        else:                                                           # training_project :977-980
+            terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
+        return terms
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -66,6 +66,11 @@ class SpacedDiffusion(GaussianDiffusion):
     def _scale_timesteps(self, t):
         return t
 
+    def training_losses(self, model, *args, **kwargs):
+        """respace.py:93-96.  The base class hands the network _model_timestep_values()[t]: the timestep map (and the optional
+        rescale) exactly as _WrappedModel applies it, so a wrapped model is unwrapped, not mapped twice."""
+        return super().training_losses(model.model if isinstance(model, _WrappedModel) else model, *args, **kwargs)
+
     def _wrap_model(self, model):
         if isinstance(model, _WrappedModel):
             return model

@@ -901,3 +901,129 @@ def ddim_invert_step(cx: float, ce: float, out_cond: torch.Tensor, x: torch.Tens
     ou, oc = _f32c(out_uncond), _f32c(out_cond)
     check(lib().dsd_op_ddim_invert_step(float(cx), float(ce), dptr(ou), dptr(oc), float(scale), dptr(x), stride, B, Cz, H, W,
                                         stream_ptr()))
+
+
+# ------------------------------------------------------------------------------------------------ the denoising loss (loss.hip)
+LOSS_KINDS = {"l2": 0, "l1": 1, "charbonnie": 2}     # DSD_LOSS_*; 'charbonnie' is the reference's spelling (ddpm.py:377)
+LOSS_TERMS = ("mse", "vb", "com", "dist")            # the columns of dsd_eval_loss's [B, DSD_LOSS_NTERMS] result
+
+
+def _loss_on_gpu(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"the denoising loss runs on the MI355X only (no CPU fallback): {what} is on the CPU")
+
+
+def _row(t, device) -> torch.Tensor:
+    """A per-sample row [B] as contiguous device fp32."""
+    return torch.as_tensor(t).detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+@torch.no_grad()
+def loss_rows(pred: int, kind: int, model_out: torch.Tensor, x_start: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+              a: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0) -> torch.Tensor:
+    """[B] mean over C*H*W of kind(target - prediction) (dsd_op_loss_rows).  ``pred`` (PRED_*) names the target: the noise,
+    x_start, or get_v's a[b]*noise - s[b]*x_start; ``kind``: LOSS_L2 / LOSS_L1 / LOSS_CHARBONNIER.  ``model_out`` is [B,C,H,W] or,
+    with a variance half, [B,2C,H,W] (its first C channels are read in place).  ``noise`` None: the Philox normals q_sample_rows
+    draws for the same (seed, step)."""
+    ref = x_start if x_start is not None else noise
+    _loss_on_gpu(model_out, "model_out")
+    B, Cz, H, W = ref.shape
+    mo, xs, z = _f32c(model_out), _f32c(x_start), _f32c(noise)
+    assert mo.shape[0] == B and mo.shape[1] in (Cz, 2 * Cz) and tuple(mo.shape[2:]) == (H, W)
+    ar, sr = (None, None) if a is None else (_row(a, mo.device), _row(s, mo.device))
+    out = torch.empty((B,), device=mo.device, dtype=torch.float32)
+    check(lib().dsd_op_loss_rows(int(pred), int(kind), dptr(mo), mo.shape[1] * H * W, dptr(xs), dptr(z), C.c_uint64(seed),
+                                 C.c_uint64(step), dptr(ar), dptr(sr), dptr(out), 1, B, Cz, H, W, stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def pair_mse_rows(feats: Sequence[torch.Tensor]) -> torch.Tensor:
+    """[B]: the sum over the pairs of 2, 3 or 4 feature tensors [B,...] of mean_flat((f_i - f_j)^2), in the order of
+    training_losses' com / dist terms (dsd_op_pair_mse_rows)."""
+    fs = [_f32c(f) for f in feats]
+    _loss_on_gpu(fs[0], "the features")
+    B = fs[0].shape[0]
+    n = fs[0].numel() // B
+    assert all(f.shape == fs[0].shape for f in fs)
+    ptrs = (C.c_void_p * len(fs))(*[f.data_ptr() for f in fs])
+    out = torch.empty((B,), device=fs[0].device, dtype=torch.float32)
+    check(lib().dsd_op_pair_mse_rows(ptrs, len(fs), B, n, dptr(out), stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def vlb_terms_rows(pred: int, learned_range: bool, clip_denoised: bool, coef: torch.Tensor, post_log_var: torch.Tensor,
+                   decoder: torch.Tensor, model_out: torch.Tensor, x_t: torch.Tensor, x_start: torch.Tensor,
+                   noise: Optional[torch.Tensor], seed: int = 0, step: int = 0):
+    """The bound's terms with a timestep per sample (dsd_op_vlb_terms_rows): ``coef`` [B,DSD_NCOEF] (the MODE_A_DDPM rows),
+    ``post_log_var`` [B], ``decoder`` [B] (t == 0).  Returns (vb, xstart_mse, mse), [B] each."""
+    _loss_on_gpu(model_out, "model_out")
+    B, Cz, H, W = x_start.shape
+    mo, xt, xs, z = _f32c(model_out), _f32c(x_t), _f32c(x_start), _f32c(noise)
+    dev = mo.device
+    cf, plv = _row(coef, dev), _row(post_log_var, dev)
+    dec = torch.as_tensor(decoder).to(device=dev, dtype=torch.int32).contiguous()
+    assert tuple(cf.shape) == (B, DSD_NCOEF) and tuple(plv.shape) == (B,) and tuple(dec.shape) == (B,)
+    if learned_range and mo.shape[1] != 2 * Cz:
+        raise ValueError(f"a learned-range variance needs {2 * Cz} output channels; the model output has {mo.shape[1]}")
+    outs = torch.empty((3, B), device=dev, dtype=torch.float32)
+    check(lib().dsd_op_vlb_terms_rows(int(pred), int(bool(learned_range)), int(bool(clip_denoised)), dptr(cf), dptr(plv), dptr(dec),
+                                      dptr(mo), mo.shape[1] * H * W, dptr(xt), 0, dptr(xs), dptr(z), C.c_uint64(seed),
+                                      C.c_uint64(step), dptr(outs[0]), dptr(outs[1]), dptr(outs[2]), 1, B, Cz, H, W, stream_ptr()))
+    return outs[0], outs[1], outs[2]
+
+
+@torch.no_grad()
+def run_eval_loss(unet, pred: int, kind: int, x_start: torch.Tensor, cond, t_model, a, s, noise: Optional[torch.Tensor] = None,
+                  seed: int = 0, step: int = 0, vlb=None, learned_range: bool = False, target: Optional[int] = None) -> dict:
+    """dsd_eval_loss: q_sample with the rows ``a`` / ``s``, one evaluation of the native denoiser with ``t_model`` [B] as its
+    timesteps, and the loss kernels.  ``pred``: what the network predicts; ``target`` (default: the same) the target of the mse
+    term where the reference reads the two off different attributes.  ``cond``: the 'concat' tensor or a Conditioning, as in the loops.  ``vlb``: None, or
+    (coef [B,DSD_NCOEF], post_log_var [B], decoder [B]) for the vb term.  Returns {"mse": [B]} plus "vb" (with ``vlb``) and
+    "com" / "dist" (UNet_disc_Model), read back from one [B, LOSS_NTERMS] buffer."""
+    from ._lib import DsdLoss, LOSS_NTERMS
+    if unet is None:
+        raise RuntimeError("no native denoiser (DSUnetModel / UNet_disc_Model / UNetModel / DiT) behind the model handed to the loss")
+    _loss_on_gpu(x_start, "x_start")
+    unet.sync_params()
+    xs = x_start.detach().float().contiguous()
+    dev = xs.device
+    bundle = cond
+    if is_latent_denoiser(unet):
+        check_latent_io(unet, xs, bundle)
+    elif isinstance(bundle, Conditioning):
+        raise ValueError("the four-stream model takes 'concat' conditioning only: 'c_crossattn' / 'c_adm' cannot reach it")
+    cond = concat_of(bundle, xs).detach().float().contiguous()
+    B, Cz, H, W = xs.shape
+    z = _f32c(noise)
+    if z is not None and tuple(z.shape) != (B, Cz, H, W):
+        raise ValueError(f"noise must have the shape of x_start {(B, Cz, H, W)}, got {tuple(z.shape)}")
+    rows = [_row(r, dev) for r in (t_model, a, s)]
+    for r in rows:
+        if tuple(r.shape) != (B,):
+            raise ValueError(f"t / a / s must be [B] = [{B}], got {tuple(r.shape)}")
+    terms = torch.zeros((B, LOSS_NTERMS), device=dev, dtype=torch.float32)
+    spec = DsdLoss()
+    spec.target, spec.pred = int(pred if target is None else target), int(pred)
+    spec.kind, spec.learned_range = int(kind), int(bool(learned_range))
+    spec.t_model, spec.a, spec.s = (r.data_ptr() for r in rows)
+    held = []
+    if vlb is not None:
+        cf, plv = _row(vlb[0], dev), _row(vlb[1], dev)
+        dec = torch.as_tensor(vlb[2]).to(device=dev, dtype=torch.int32).contiguous()
+        assert tuple(cf.shape) == (B, DSD_NCOEF) and tuple(plv.shape) == (B,) and tuple(dec.shape) == (B,)
+        held = [cf, plv, dec]
+        spec.vlb_coef, spec.post_log_var, spec.decoder = cf.data_ptr(), plv.data_ptr(), dec.data_ptr()
+    spec.terms = terms.data_ptr()
+    _check_four_stream_io(unet, xs, cond)
+    with conditioning_set(unet, bundle):
+        check(lib().dsd_eval_loss(unet._h, C.byref(spec), dptr(cond), cond.shape[1], dptr(xs), Cz, dptr(z), C.c_uint64(seed),
+                                  C.c_uint64(step), B, H, W, stream_ptr()))
+    del held
+    out = {"mse": terms[:, 0]}
+    if vlb is not None:
+        out["vb"] = terms[:, 1]
+    if is_disc(unet):
+        out["com"], out["dist"] = terms[:, 2], terms[:, 3]
+    return out

@@ -1,4 +1,5 @@
 // api.cpp — the extern "C" surface of libdsdiff.so (see include/dsdiff.h).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -268,7 +269,7 @@ int64_t dsd_workspace_bytes(dsd_handle* h) { return h && h->plan.valid ? (int64_
 int64_t dsd_device_bytes(dsd_handle* h) {
     if (!h) return -1;
     return (int64_t)(h->slab_bytes + h->staging_bytes + h->arena_cap + net_piece_bytes(h) + h->tbuf_cap + h->mout_cap +
-                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->ctx_cap + h->y_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->dpm_adapt_cap + h->bpd_cap);
+                     h->zplane_cap + h->dpm_m_cap + h->lat_in_cap + h->ctx_cap + h->y_cap + h->cfg_io_cap + h->plms_hist_cap + h->dpm_prog_cap + h->dpm_adapt_cap + h->bpd_cap + h->loss_cap);
 }
 
 int dsd_set_graph(dsd_handle* h, int on) {
@@ -391,16 +392,27 @@ int dsd_profile_enable(dsd_handle* h, int on) {
     if (on) {
         h->prof_names.clear();
         h->prof_runs = 0;
+        h->prof_x_names.clear(); h->prof_x_ms.clear(); h->prof_x_bytes.clear(); h->prof_x_calls.clear();
     }
     DSD_CATCH
 }
 
-int dsd_profile_count(dsd_handle* h) { return h ? (int)h->prof_names.size() : -1; }
+int dsd_profile_count(dsd_handle* h) { return h ? (int)(h->prof_names.size() + h->prof_x_names.size()) : -1; }
 
 int dsd_profile_get(dsd_handle* h, int idx, const char** kind, double* total_ms, double* flops, double* bytes,
                     int64_t* calls, int* runs) {
     DSD_TRY
-    DSD_CHECK(h && idx >= 0 && idx < (int)h->prof_names.size(), "profile index out of range");
+    DSD_CHECK(h && idx >= 0 && idx < dsd_profile_count(h), "profile index out of range");
+    if (idx >= (int)h->prof_names.size()) {   // the records behind the plan's kinds (dsd_eval_loss)
+        const size_t j = (size_t)idx - h->prof_names.size();
+        if (kind) *kind = h->prof_x_names[j].c_str();
+        if (total_ms) *total_ms = h->prof_x_ms[j];
+        if (flops) *flops = 0.0;
+        if (bytes) *bytes = h->prof_x_bytes[j];
+        if (calls) *calls = h->prof_x_calls[j];
+        if (runs) *runs = h->prof_runs;
+        return 0;
+    }
     if (kind) *kind = h->prof_names[idx].c_str();
     if (total_ms) *total_ms = h->prof_ms[idx];
     if (flops) *flops = h->prof_flops[idx];
@@ -614,10 +626,10 @@ LoopBinding make_binding(dsd_handle* h, const dsd_guidance* g, float* xs, int64_
 // unguided the caller's x and cond; guided (ddim.py:197-218) the 2B-row planes of cfg_io — state [2B,1,H,W] then conditions
 // [2B,Cc,H,W] = cat([uncond, cond]) — whose step-invariant halves are copied once per call.
 LoopBinding bind_four_stream(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int B, int H, int W,
-                             int out_ch, hipStream_t s) {
+                             int out_ch, hipStream_t s, int want_feats = 0) {
     const int64_t hw = (int64_t)H * W;
     const int rows = g ? 2 * B : B;
-    net_plan(h, rows, Cc + 1, H, W, Cc == 1, 0, 0, 0, (Cc == 1 && (g || B > 1)) ? h->share_zero_streams : 0, s);
+    net_plan(h, rows, Cc + 1, H, W, Cc == 1, want_feats, 0, 0, (Cc == 1 && (g || B > 1)) ? h->share_zero_streams : 0, s);
     ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
     ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
     float* xs = x;
@@ -717,10 +729,11 @@ int check_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int 
     return want_ch;
 }
 
+// want_feats (four-stream handles): net_plan's — 2 keeps UNet_disc_Model's bottleneck tensors in the workspace (dsd_eval_loss)
 LoopBinding bind_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B, int H, int W,
-                          int out_ch, hipStream_t s) {
+                          int out_ch, hipStream_t s, int want_feats = 0) {
     return state_in_input(h) ? bind_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s)
-                             : bind_four_stream(h, g, cond, Cc, x, B, H, W, out_ch, s);
+                             : bind_four_stream(h, g, cond, Cc, x, B, H, W, out_ch, s, want_feats);
 }
 
 // iterations [r.k0, r.k1): pre(k) in front of the network evaluation at time t[k] (through the cached graph), step(k) after it
@@ -1464,6 +1477,189 @@ int dsd_op_prior_bpd(float sqrt_acp, float log_1m_acp, const float* x_start, flo
     check_op_state(B, Cz, H, W, 0);
     Tmp part(vlb_part_doubles(B, (int64_t)Cz * H * W) * sizeof(double));
     prior_bpd(sqrt_acp, log_1m_acp, x_start, part.as<double>(), prior, B, (int64_t)Cz * H * W, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- denoising loss
+// training_losses / p_losses, forward only (include/dsdiff.h): q_sample with per-row coefficients into a state of the call's own
+// (as dsd_calc_bpd keeps one), the per-sample t copied into the handle's timestep rows, one evaluation through the cached
+// graph, then the reductions of loss.hip into the caller's [B,DSD_LOSS_NTERMS] rows.
+static void check_loss_codes(int pred, int kind) {
+    DSD_CHECK(pred >= DSD_PRED_EPS && pred <= DSD_PRED_V, "unknown prediction type %d", pred);
+    DSD_CHECK(kind >= DSD_LOSS_L2 && kind <= DSD_LOSS_CHARBONNIER, "unknown loss kind %d (DSD_LOSS_L2 / _L1 / _CHARBONNIER)", kind);
+}
+
+// fn() on s; while the handle profiles, between two events whose distance is added to the record of `kind` (algorithmic bytes)
+static void profiled_launch(dsd_handle* h, const char* kind, double bytes, hipStream_t s, const std::function<void()>& fn) {
+    if (!h->profiling) {
+        fn();
+        return;
+    }
+    hipEvent_t e0, e1;
+    DSD_HIP(hipEventCreate(&e0));
+    DSD_HIP(hipEventCreate(&e1));
+    DSD_HIP(hipEventRecord(e0, s));
+    fn();
+    DSD_HIP(hipEventRecord(e1, s));
+    DSD_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    DSD_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    size_t j = 0;
+    while (j < h->prof_x_names.size() && h->prof_x_names[j] != kind) ++j;
+    if (j == h->prof_x_names.size()) {
+        h->prof_x_names.push_back(kind);
+        h->prof_x_ms.push_back(0.0); h->prof_x_bytes.push_back(0.0); h->prof_x_calls.push_back(0);
+    }
+    h->prof_x_ms[j] += ms; h->prof_x_bytes[j] += bytes; h->prof_x_calls[j] += 1;
+}
+
+static VlbStep vlb_rows_step(int pred, int learned_range, int clip, uint64_t step) {
+    VlbStep a;
+    a.sc = StepCoef{};
+    a.sc.mode = DSD_MODE_A_DDPM; a.sc.pred = pred; a.sc.learned_range = learned_range; a.sc.clip = clip; a.sc.nonzero = 1;
+    a.step = step;
+    return a;
+}
+
+int dsd_eval_loss(dsd_handle* h, const dsd_loss* spec, const float* cond, int Cc, const float* x_start, int Cz, const float* noise,
+                  uint64_t seed, uint64_t step, int B, int H, int W, void* stream) {
+    DSD_TRY
+    const bool latent = state_in_input(h);
+    refuse_trace(h, "dsd_eval_loss");
+    DSD_CHECK(spec, "null dsd_loss");
+    check_loss_codes(spec->pred, spec->kind);
+    check_loss_codes(spec->target, spec->kind);
+    DSD_CHECK(spec->t_model && spec->a && spec->s && spec->terms, "null rows: t_model %p a %p s %p terms %p", (void*)spec->t_model,
+              (void*)spec->a, (void*)spec->s, (void*)spec->terms);
+    DSD_CHECK(!spec->vlb_coef || (spec->post_log_var && spec->decoder),
+              "the vb term needs post_log_var and decoder beside vlb_coef (post_log_var %p decoder %p)", (void*)spec->post_log_var,
+              (void*)spec->decoder);
+    DSD_CHECK(!spec->learned_range || spec->vlb_coef, "learned_range is read by the vb term only, which needs vlb_coef (null)");
+    DSD_CHECK(!(spec->learned_range && Cz > 1) || is_dit(h),
+              "learned-range variance needs one state channel (the model output interleaves mean and variance per sample); Cz = %d", Cz);
+    const int want_ch = (spec->learned_range ? 2 : 1) * Cz;
+    const int out_ch = check_denoiser(h, nullptr, cond, Cc, x_start, Cz, B, H, W, want_ch);
+    DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the loss expects %d%s", h->cfg.out_channels,
+              out_ch, spec->learned_range ? " (learned_range needs a variance half)" : "");
+    set_device(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hw = (int64_t)H * W, n = Cz * hw;
+    const bool disc = !latent && h->is_disc;
+    // UNet_disc_Model: planned first (bind_four_stream asks for the same plan again), since the size of its bottleneck tensors,
+    // which the com / dist reduction's partials follow, comes from the plan
+    if (disc) net_plan(h, B, Cc + 1, H, W, 0, 2, 0, 0, 0, s);
+    const size_t part_doubles = std::max({vlb_part_doubles(B, n), loss_part_doubles(B, n), disc ? pair_part_doubles(B, h->plan.feat_n) : (size_t)0});
+    const size_t part_bytes = (part_doubles * sizeof(double) + 15) / 16 * 16;
+    ensure_buf(&h->loss_buf, &h->loss_cap, part_bytes + (latent ? 0 : (size_t)B * n * sizeof(float)));
+    // the four-stream model reads its state plane in place: it gets the call's own; the latent binding copies into lat_in
+    float* state = latent ? const_cast<float*>(x_start) : h->loss_buf + part_bytes / sizeof(float);
+    const LoopBinding b = bind_denoiser(h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s, disc ? 2 : 0);
+    double* part = reinterpret_cast<double*>(h->loss_buf);
+    q_sample_blend(0.f, 0.f, spec->a, spec->s, x_start, nullptr, 0, b.xs, noise, seed, step, B, Cz, (int)hw, s, b.x_bs, false, b.ids);
+    DSD_HIP(hipMemcpyAsync(h->tbuf, spec->t_model, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_run_cached(h, s);
+    LossRows l;
+    l.out = b.out_c; l.o_bs = out_ch * hw;
+    l.x_start = x_start; l.noise = noise;
+    l.a_row = spec->a; l.s_row = spec->s;
+    l.target = spec->target; l.kind = spec->kind;
+    l.seed = seed; l.step = step; l.slice_ids = b.ids;
+    l.part = part;
+    l.loss = spec->terms + DSD_LOSS_TERM_MSE; l.stride = DSD_LOSS_NTERMS;
+    const double plane = (double)B * n * sizeof(float);   // one [B,Cz,H,W] tensor
+    profiled_launch(h, "loss_rows", plane * (spec->target == DSD_PRED_V ? 3 : 2), s, [&] { loss_rows(l, B, Cz, (int)hw, s); });
+    if (spec->vlb_coef) {
+        VlbStep a = vlb_rows_step(spec->pred, spec->learned_range, 0, step);   // clip_denoised=False (:847, :872)
+        a.x_start = x_start;
+        a.xt = b.xs; a.x_bs = b.x_bs;
+        a.out = b.out_c; a.o_bs = out_ch * hw;
+        a.noise = noise;
+        a.seed = seed;
+        a.slice_ids = b.ids;
+        a.part = part;
+        VlbRows r;
+        r.coef = spec->vlb_coef; r.post_log_var = spec->post_log_var; r.decoder = spec->decoder;
+        profiled_launch(h, "vlb_terms_rows", plane * (spec->learned_range ? 5 : 4), s, [&] {
+            vlb_terms_rows(a, r, spec->terms + DSD_LOSS_TERM_VB, nullptr, nullptr, DSD_LOSS_NTERMS, B, Cz, (int)hw, s);
+        });
+    }
+    if (disc) {
+        for (int half = 0; half < 2; ++half) {
+            PairMse pm;
+            pm.nf = 4;
+            for (int i = 0; i < 4; ++i) pm.f[i] = h->at<float>(h->plan.feat_off[4 * half + i]);
+            pm.part = part;
+            pm.out = spec->terms + (half ? DSD_LOSS_TERM_DIST : DSD_LOSS_TERM_COM);
+            pm.stride = DSD_LOSS_NTERMS;
+            profiled_launch(h, "pair_mse_rows", 4.0 * B * h->plan.feat_n * sizeof(float), s,
+                            [&] { pair_mse_rows(pm, B, h->plan.feat_n, s); });
+        }
+    }
+    net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_op_loss_rows(int pred, int kind, const float* model_out, int64_t out_row_stride, const float* x_start, const float* noise,
+                     uint64_t philox_seed, uint64_t step, const float* a, const float* s, float* loss, int64_t loss_stride, int B,
+                     int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    check_loss_codes(pred, kind);
+    DSD_CHECK(model_out && loss, "null argument");
+    check_op_state(B, Cz, H, W, out_row_stride);
+    DSD_CHECK(loss_stride >= 0, "loss_stride %lld", (long long)loss_stride);
+    Tmp part(loss_part_doubles(B, (int64_t)Cz * H * W) * sizeof(double));
+    LossRows l;
+    l.out = model_out; l.o_bs = out_row_stride;
+    l.x_start = x_start; l.noise = noise;
+    l.a_row = a; l.s_row = s;
+    l.target = pred; l.kind = kind;
+    l.seed = philox_seed; l.step = step;
+    l.part = part.as<double>();
+    l.loss = loss; l.stride = loss_stride;
+    loss_rows(l, B, Cz, H * W, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_pair_mse_rows(const float* const* feats, int n_feats, int B, int64_t n, float* out, void* stream) {
+    DSD_TRY
+    DSD_CHECK(feats && out, "null argument");
+    DSD_CHECK(n_feats >= 2 && n_feats <= 4, "pair_mse_rows takes 2, 3 or 4 feature tensors, got %d", n_feats);
+    DSD_CHECK(B >= 1 && n >= 1, "bad shape: B %d n %lld", B, (long long)n);
+    Tmp part(pair_part_doubles(B, n) * sizeof(double));
+    PairMse pm;
+    pm.nf = n_feats;
+    for (int i = 0; i < n_feats; ++i) pm.f[i] = feats[i];
+    pm.part = part.as<double>();
+    pm.out = out;
+    pair_mse_rows(pm, B, n, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_vlb_terms_rows(int pred, int learned_range, int clip_denoised, const float* coef, const float* post_log_var,
+                          const int32_t* decoder, const float* model_out, int64_t out_row_stride, const float* x_t,
+                          int64_t x_row_stride, const float* x_start, const float* noise, uint64_t philox_seed, uint64_t step,
+                          float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int H, int W, void* stream) {
+    DSD_TRY
+    DSD_CHECK(pred >= DSD_PRED_EPS && pred <= DSD_PRED_V, "unknown prediction type %d", pred);
+    DSD_CHECK(coef && post_log_var && decoder && model_out && x_t && x_start, "null argument");
+    check_op_state(B, Cz, H, W, x_row_stride);
+    const int64_t need = (int64_t)(learned_range ? 2 : 1) * Cz * H * W;
+    DSD_CHECK(out_row_stride == 0 || out_row_stride >= need, "out_row_stride %lld is smaller than one output row (%lld)",
+              (long long)out_row_stride, (long long)need);
+    DSD_CHECK(term_stride >= 0, "term_stride %lld", (long long)term_stride);
+    Tmp part(vlb_part_doubles(B, (int64_t)Cz * H * W) * sizeof(double));
+    VlbStep a = vlb_rows_step(pred, learned_range != 0, clip_denoised != 0, step);
+    a.x_start = x_start;
+    a.xt = x_t; a.x_bs = x_row_stride;
+    a.out = model_out; a.o_bs = out_row_stride;
+    a.noise = noise;
+    a.seed = philox_seed;
+    a.part = part.as<double>();
+    VlbRows r;
+    r.coef = coef; r.post_log_var = post_log_var; r.decoder = decoder;
+    vlb_terms_rows(a, r, vb, xstart_mse, mse, term_stride, B, Cz, H * W, (hipStream_t)stream);
     DSD_CATCH
 }
 

@@ -386,6 +386,10 @@ struct VlbStep {
     float* pred_xstart = nullptr;
 };
 size_t vlb_part_doubles(int B, int64_t n);
+// the one finalize of every per-sample reduction (vlb_terms, prior_bpd, loss.hip): out_q[b*stride] = fp32(sum_q / n) from
+// part[b][nblk][nq] (nq <= 3; null outputs skipped), added in index order by one wave; bits: quantity 0 is divided by ln 2
+void rows_finalize(const double* part, int nblk, int nq, int n, float* o0, float* o1, float* o2, int64_t stride, int bits, int B,
+                   hipStream_t s);
 // decoder: t == 0, the term is the discretised decoder NLL instead of the KL.  Sample b's vb (bits), mean (pred_xstart - x_start)^2
 // and mean (eps - noise)^2 go to vb / xstart_mse / mse [b*term_stride] (each optional; all null: the planes only).
 void vlb_terms(const VlbStep& a, bool decoder, float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int HW,
@@ -402,5 +406,52 @@ void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_
 void gaussian_sample(const float* moments, const float* noise, uint64_t seed, int B, int E, int HW, float* z, hipStream_t s,
                      float scale = 1.0f);
 void fill_t(float* t, int B, float v, hipStream_t s);
+
+// ---------------------------------------------------------------- loss.hip
+// The denoising losses (training_losses / p_losses, forward only): one scalar per sample, every timestep-dependent value a
+// device row [B].  Reductions as vlb_terms': fixed per-block fp64 partials, one finalize, no atomics.
+// loss[b*stride] = mean over the n = Cz*HW elements of kind(target - out): target (DSD_PRED_*) = the noise, x_start, or
+// a_row[b]*noise - s_row[b]*x_start (get_v); kind (DSD_LOSS_*) = d^2, |d| or sqrt(d^2 + 1e-6).  Output row b at out + b*o_bs
+// (0 = n; 2n reads the prediction half of an output with a variance half in place); x_start / noise [B,n] (each read only by
+// the targets that need it); noise == nullptr: the normals q_sample_blend drew x_t from (Philox stream (seed, step + 2^32),
+// counter keyed by slice_ids).  part: loss_part_doubles(B, n) doubles of scratch.
+struct LossRows {
+    const float* out = nullptr;
+    int64_t o_bs = 0;
+    const float* x_start = nullptr;
+    const float* noise = nullptr;
+    const float* a_row = nullptr;
+    const float* s_row = nullptr;
+    int target = 0, kind = 0;
+    uint64_t seed = 0, step = 0;
+    const int64_t* slice_ids = nullptr;
+    double* part = nullptr;
+    float* loss = nullptr;
+    int64_t stride = 1;
+};
+size_t loss_part_doubles(int B, int64_t n);
+void loss_rows(const LossRows& a, int B, int Cz, int HW, hipStream_t s);
+// out[b*stride] = sum over the pairs (i, j) of the nf (2..4) feature tensors of mean((f_i - f_j)^2) over n elements, each pair's
+// mean rounded to fp32 and added in the reference's order: (1,2) + (2,3) + (1,3), then + ((1,4) + (2,4) + (3,4)).  Row b of
+// tensor i at f[i] + b*bs (0 = n).  part: pair_part_doubles(B, n) doubles.
+struct PairMse {
+    const float* f[4] = {};
+    int nf = 0;
+    int64_t bs = 0;
+    double* part = nullptr;
+    float* out = nullptr;
+    int64_t stride = 1;
+};
+size_t pair_part_doubles(int B, int64_t n);
+void pair_mse_rows(const PairMse& a, int B, int64_t n, hipStream_t s);
+// vlb_terms with a timestep per sample: coef [B,DSD_NCOEF] (the DSD_MODE_A_DDPM rows), post_log_var [B], decoder [B] (t == 0:
+// the discretised decoder NLL instead of the KL), all on the device; a.sc gives pred / learned_range / clip, its c is unread.
+struct VlbRows {
+    const float* coef = nullptr;
+    const float* post_log_var = nullptr;
+    const int32_t* decoder = nullptr;
+};
+void vlb_terms_rows(const VlbStep& a, const VlbRows& r, float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz,
+                    int HW, hipStream_t s);
 
 }  // namespace dsd

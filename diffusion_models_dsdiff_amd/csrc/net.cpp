@@ -737,6 +737,7 @@ void dsd::net_free(dsd_handle* h) {
     if (h->cfg_io) (void)hipFree(h->cfg_io);
     if (h->plms_hist) (void)hipFree(h->plms_hist);
     if (h->bpd_buf) (void)hipFree(h->bpd_buf);
+    if (h->loss_buf) (void)hipFree(h->loss_buf);
     if (h->freqs) (void)hipFree(h->freqs);
     if (h->ovf) (void)hipFree(h->ovf);
     if (h->slice_ids) (void)hipFree(h->slice_ids);
@@ -1870,8 +1871,10 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
 // Disc_diff/guided_diffusion/unet.py:985-1044.  Four encoders with their own weights over the planes x, T1, T2, DWI; every
 // skip is the four-stream mean (fused into the decoder's concat, as for DSUnetModel); conv_common / conv_distinct (one weight
 // set each, applied to all four streams) feed the bottleneck head of disc.hip; Conv1x1 + SiLU; middle block, decoder, out.
-// want_feats: io.feats[0..7] receive com_h1..4 (after the SiLU) and dist_h1..4 (after their SE), NCHW.
-void build_disc(Builder& b, int H, int W, bool want_feats) {
+// want_feats 1: io.feats[0..7] receive com_h1..4 (after the SiLU) and dist_h1..4 (after their SE), NCHW.  want_feats 2
+// (dsd_eval_loss): the eight stay where the head wrote them, NHWC, until the forward ends — Plan::feat_off — and nothing is exported.
+void build_disc(Builder& b, int H, int W, int feats_mode) {
+    const bool want_feats = feats_mode != 0, keep_feats = feats_mode == 2;
     dsd_handle* hd = b.hd;
     const dsd_config& cfg = hd->cfg;
     const Spec sp = build_spec(cfg);
@@ -1941,11 +1944,15 @@ void build_disc(Builder& b, int H, int W, bool want_feats) {
         }
     }
     for (int s = 0; s < 4; ++s) { b.release(com[s]); b.release(dist[s]); }
-    if (want_feats)
+    if (keep_feats) {
+        for (int i = 0; i < 8; ++i) b.plan.feat_off[i] = feat[i].off;
+        b.plan.feat_n = (int64_t)HW * half;
+    } else if (want_feats) {
         for (int i = 0; i < 8; ++i) {
             b.export_out(feat[i], true, i);
             b.release(feat[i]);
         }
+    }
     // ---- dim_reduction_non_zeros: Conv1x1 then SiLU (the activation comes after the convolution); the SiLU pass also emits
     // the GroupNorm statistics middle_block.0.in_layers.0 reads
     Tn r = b.conv("dim_reduction_non_zeros.0", cat, sp.conv_ch, 1);
@@ -2374,7 +2381,7 @@ void dsd::net_plan(dsd_handle* h, int B, int C, int H, int W, int zero_al_l, int
         if (h->is_block)
             build_block(b, C, H, W, aux_len, aux_len2);
         else if (h->is_disc)
-            build_disc(b, H, W, want_feats != 0);
+            build_disc(b, H, W, want_feats);
         else
             build_unet(b, H, W, zero_al_l != 0, want_feats != 0, share != 0);
     } catch (...) {

@@ -76,6 +76,8 @@ struct Plan {
     int zero_al_l = 0, want_feats = 0, share = 0;
     int disc_unfused = 0;   // UNet_disc_Model: the bottleneck head composed from the older ops (DSD_DISC_UNFUSED) instead of disc.hip
     int aux_len = 0, aux_len2 = 0;
+    size_t feat_off[8] = {};   // want_feats == 2 (UNet_disc_Model): arena offsets of com_h1..4 / dist_h1..4, NHWC, feat_n elements per sample
+    int64_t feat_n = 0;
     bool valid = false;
     std::vector<std::function<void(hipStream_t)>> ops;
     std::vector<signed char> op_lane;   // -1: the caller's stream after joining every lane; 0..3: encoder stream lanes (run concurrently)
@@ -176,6 +178,8 @@ struct dsd_handle {
     // elements under a schedule of plms_steps iterations.
     float* plms_hist = nullptr;
     float* bpd_buf = nullptr;  // variational-bound loops: the per-block partial sums (doubles), then the four-stream loop's x_t state [B,H*W]
+    float* loss_buf = nullptr; // dsd_eval_loss: the reductions' partial sums (doubles), then the four-stream call's x_t state [B,H*W]
+    size_t loss_cap = 0;
     int plms_next = -1, plms_B = 0, plms_steps = 0;
     int64_t plms_n = 0;
     float* freqs = nullptr;    // [model_channels/2] optional timestep-embedding frequency table (host-supplied)
@@ -224,6 +228,11 @@ struct dsd_handle {
     std::vector<float> prof_op_ms;                         // per op of the plan, last profiled forward
     std::vector<std::string> prof_names;
     int prof_runs = 0;
+    // records of kernels a driver launches behind the plan's ops while profiling (dsd_eval_loss: loss_rows, vlb_terms_rows,
+    // pair_mse_rows), served by dsd_profile_count / dsd_profile_get after the plan's kinds
+    std::vector<std::string> prof_x_names;
+    std::vector<double> prof_x_ms, prof_x_bytes;
+    std::vector<int64_t> prof_x_calls;
     size_t tbuf_cap = 0, mout_cap = 0, zplane_cap = 0, dpm_m_cap = 0, lat_in_cap = 0, cfg_io_cap = 0, plms_hist_cap = 0, dpm_prog_cap = 0, dpm_adapt_cap = 0, bpd_cap = 0, ctx_cap = 0, y_cap = 0;
 
     float* P(const std::string& name) const;

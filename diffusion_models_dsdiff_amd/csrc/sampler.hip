@@ -7,8 +7,7 @@
 //           PLMSSampler.p_sample_plms with norm thresholding (ldm/models/diffusion/plms.py:178-245), further down.
 // The arithmetic is written in the reference's fp32 operation order; coefficient tables come from the host
 // (float64 there, rounded to fp32 once, like _extract_into_tensor(...).float() / the registered fp32 buffers).
-#include "kernels.h"
-#include "../../include/dsdiff.h"
+#include "sampler_dev.h"
 
 // The reference evaluates these updates as separate fp32 torch ops, so nothing in this file may be contracted into an
 // FMA: plain operators under contract(off) (HIP's __fmul_rn/__fsub_rn are header inlines that stay contractable);
@@ -16,39 +15,6 @@
 #pragma clang fp contract(off)
 
 namespace dsd {
-
-// ---- Philox4x32-10 (Salmon et al. 2011): counter = (idx, step), key = seed
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                               uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// element i of the normal stream for (seed, step): Box-Muller on the Philox block i/4... each block yields 4 normals
-__device__ __forceinline__ float philox_normal_at(int64_t i, uint64_t seed, uint64_t step) {
-    uint32_t r[4];
-    const uint64_t blk = (uint64_t)i >> 2;
-    philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    const int lane = (int)(i & 3);
-    const uint32_t a = r[lane & 2], b = r[(lane & 2) + 1];
-    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
-    const float u2 = (float)b * 2.3283064365386963e-10f;           // [0,1)
-    const float rad = sqrtf(-2.0f * logf(u1));
-    const float ang = 6.283185307179586f * u2;
-    return (lane & 1) ? rad * sinf(ang) : rad * cosf(ang);
-}
 
 __global__ void philox_normal_kernel(float* __restrict__ y, int64_t n, uint64_t seed, uint64_t step) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -61,45 +27,6 @@ void philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, hipStream_
     check_launch("philox_normal");
 }
 
-// V = 4: 16-byte accesses (n, x_bs multiples of 4 and 16-byte aligned pointers; the launchers check), V = 1 otherwise.
-template <int V> struct alignas(4 * V) Pack { float v[V]; };
-template <int V> __device__ __forceinline__ Pack<V> ld_pack(const float* p) { return *reinterpret_cast<const Pack<V>*>(p); }
-template <int V> __device__ __forceinline__ void st_pack(float* p, const Pack<V>& a) { *reinterpret_cast<Pack<V>*>(p) = a; }
-
-// normals i .. i+V-1 of the (seed, step) stream; i % V == 0.  V = 4 is one Philox block: the values philox_normal_at gives
-template <int V> __device__ __forceinline__ Pack<V> philox_normal_pack(int64_t i, uint64_t seed, uint64_t step) {
-    Pack<V> z;
-    if constexpr (V == 4) {
-        uint32_t r[4];
-        const uint64_t blk = (uint64_t)i >> 2;
-        philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;
-            const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
-            const float rad = sqrtf(-2.0f * logf(u1));
-            const float ang = 6.283185307179586f * u2;
-            z.v[2 * h] = rad * cosf(ang);
-            z.v[2 * h + 1] = rad * sinf(ang);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j) z.v[j] = philox_normal_at(i + j, seed, step);
-    }
-    return z;
-}
-
-// The launchers' side of V: 16-byte accesses when one sample (n elements) and the state's row stride are multiples of four
-// floats and every pointer the kernel takes packs from is 16-byte aligned (a null one counts as aligned).
-template <class... P> static bool can_vec4(int64_t n, int64_t x_bs, const P*... ptrs) {
-    return n % 4 == 0 && x_bs % 4 == 0 && (... && (((uintptr_t)ptrs & 15u) == 0));
-}
-// launch(std::integral_constant<int, V>) with V = 4 or 1
-template <class F> static void launch_vec(bool v4, F&& launch) {
-    if (v4) launch(std::integral_constant<int, 4>{});
-    else launch(std::integral_constant<int, 1>{});
-}
 static int ew_blocks(int64_t work) { return (int)std::min<int64_t>((work + 255) / 256, 2048); }
 
 // p_sample_ddim after the network output is formed (ddim.py:222-260): returns x_{t-1}, x0 = the (clipped) pred_x0
@@ -116,27 +43,6 @@ __device__ __forceinline__ float ddim_update(const StepCoef& sc, float out, floa
     if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     const float dir = sqrtf(1.f - c[5] - c[6] * c[6]) * e_t;
     return sqrtf(c[5]) * x0 + dir + c[6] * z;
-}
-
-// pred_xstart of the guided-diffusion family and of ldm's DDPM (gaussian_diffusion.py:311-341): the network output as v, eps or
-// x_start, then process_xstart's clip
-__device__ __forceinline__ float pred_xstart_value(const StepCoef& sc, float out, float xt) {
-    const float* c = sc.c;
-    float x0;
-    if (sc.pred == DSD_PRED_V)
-        x0 = c[0] * xt - c[1] * out;
-    else if (sc.pred == DSD_PRED_EPS)
-        x0 = c[2] * xt - c[3] * out;
-    else
-        x0 = out;
-    if (sc.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    return x0;
-}
-// the learned-range log-variance (gaussian_diffusion.py:287-293) from the variance channel, or the step's fixed one
-__device__ __forceinline__ float model_log_variance(const StepCoef& sc, float var) {
-    if (!sc.learned_range) return sc.c[6];
-    const float frac = (var + 1.f) / 2.f;
-    return frac * sc.c[7] + (1.f - frac) * sc.c[6];
 }
 
 // x_{t-1} of one element in any of the four modes; var = the learned-range variance channel (read only with learned_range)
@@ -505,7 +411,6 @@ void dpm_eval(const DpmCoef& c, const DpmEval& ev, const float* out_u, const flo
 // z is fed, or normal slice*n + p of the Philox stream (seed, step + 2^32): the update of iteration `step` draws from (seed, step),
 // so the two never share a counter block.  V = 4 needs n % 4 == 0 and, for a one-channel mask, HW % 4 == 0 (a pack stays inside
 // one channel); the launcher checks.
-static constexpr uint64_t kBlendStream = 1ull << 32;
 
 // Grid: x over the packs of one sample (capped, strided), y = the sample — the row's coefficients and its slice id are
 // block-uniform and no 64-bit division is left.  BLEND selects the mask blend (scalar a, s) or the plain q_sample (a_row, s_row,
@@ -735,117 +640,12 @@ void plms_step(const PlmsStep& step, int B, int Cz, int HW, hipStream_t s) {
 // grid-stride loop: out of a loop the compiler hoists the constants of the inlined logf / sinf / cosf / expf / tanhf into scalar
 // registers and spilled them (12-38 per instantiation), as it did in sampler_update_kernel.  V only selects how the four are
 // loaded and stored (one 16-byte access, or guarded scalar ones), so both forms add the same values in the same order.
-static constexpr int kVlbPiece = 1024;
-
-template <int V> __device__ __forceinline__ Pack<4> ld_quad(const float* p, int valid) {
-    if constexpr (V == 4) return ld_pack<4>(p);
-    Pack<4> r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r.v[j] = j < valid ? p[j] : 0.f;
-    return r;
-}
-template <int V> __device__ __forceinline__ void st_quad(float* p, const Pack<4>& a, int valid) {
-    if constexpr (V == 4) {
-        st_pack<4>(p, a);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < valid) p[j] = a.v[j];
-    }
-}
-
-// the NQ sums of a block: the 256 threads' sums folded in the fixed tree, thread 0 writes them
-template <int NQ>
-__device__ __forceinline__ void vlb_block_fold(const double (&acc)[NQ], double* red, double* dst) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) red[q * 256 + threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) red[q * 256 + threadIdx.x] += red[q * 256 + threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) dst[q] = red[q * 256];
-    }
-}
-
-// normal_kl (losses.py:32-38), left to right
-__device__ __forceinline__ float normal_kl_value(float mean1, float logvar1, float mean2, float logvar2) {
-    const float d = mean1 - mean2;
-    return 0.5f * (-1.0f + logvar2 - logvar1 + expf(logvar1 - logvar2) + (d * d) * expf(-logvar2));
-}
-// approx_standard_normal_cdf (losses.py:41-46); pow(x, 3) is x*x*x in torch
-__device__ __forceinline__ float approx_normal_cdf(float x) {
-    return 0.5f * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * (x * x * x))));
-}
-// discretized_gaussian_log_likelihood (losses.py:49-77)
-__device__ __forceinline__ float discretized_log_likelihood(float x, float mean, float log_scale) {
-    const float centered = x - mean;
-    const float inv_stdv = expf(-log_scale);
-    const float cdf_plus = approx_normal_cdf(inv_stdv * (centered + (float)(1.0 / 255.0)));
-    const float cdf_min = approx_normal_cdf(inv_stdv * (centered - (float)(1.0 / 255.0)));
-    float arg = fmaxf(cdf_plus - cdf_min, 1e-12f);
-    if (x > 0.999f) arg = fmaxf(1.0f - cdf_min, 1e-12f);
-    if (x < -0.999f) arg = fmaxf(cdf_plus, 1e-12f);
-    return logf(arg);                                          // one logf: the selects choose its argument
-}
-
 template <int V, bool DECODER>
 __global__ __launch_bounds__(256) void vlb_terms_kernel(VlbStep a, int n) {
     __shared__ double red[3 * 256];
     const int b = blockIdx.y;
-    const StepCoef& sc = a.sc;
-    const int64_t row = (int64_t)b * n;
-    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
-    const int valid = n - p;                                   // <= 0: nothing of this thread's lies inside the sample
     double acc[3] = {0.0, 0.0, 0.0};
-    if (valid > 0) {
-        const float* orow = a.out + (int64_t)b * a.o_bs + p;
-        const Pack<4> xs = ld_quad<V>(a.x_start + row + p, valid), xt = ld_quad<V>(a.xt + (int64_t)b * a.x_bs + p, valid);
-        const Pack<4> out = ld_quad<V>(orow, valid);
-        Pack<4> z, var = {};
-        if (a.noise) {
-            z = ld_quad<V>(a.noise + row + p, valid);
-        } else {
-            const int64_t ctr = (a.slice_ids ? a.slice_ids[b] * n : row) + p;
-            if constexpr (V == 4) {
-                z = philox_normal_pack<4>(ctr, a.seed, a.step + kBlendStream);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z.v[j] = j < valid ? philox_normal_at(ctr + j, a.seed, a.step + kBlendStream) : 0.f;
-            }
-        }
-        if (sc.learned_range) var = ld_quad<V>(orow + n, valid);
-        Pack<4> mean, lv, x0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x0.v[j] = pred_xstart_value(sc, out.v[j], xt.v[j]);
-            mean.v[j] = sc.c[4] * x0.v[j] + sc.c[5] * xt.v[j];                 // q_posterior_mean_variance :220-223
-            lv.v[j] = model_log_variance(sc, var.v[j]);
-            float term;
-            if constexpr (DECODER) {
-                term = -discretized_log_likelihood(xs.v[j], mean.v[j], 0.5f * lv.v[j]);
-            } else {
-                const float true_mean = sc.c[4] * xs.v[j] + sc.c[5] * xt.v[j];
-                term = normal_kl_value(true_mean, a.post_log_var, mean.v[j], lv.v[j]);
-            }
-            const float dx = x0.v[j] - xs.v[j];
-            const float eps = (sc.c[2] * xt.v[j] - x0.v[j]) / sc.c[3];         // _predict_eps_from_xstart :369-373
-            const float de = eps - z.v[j];
-            if (j < valid) {
-                acc[0] += (double)term;
-                acc[1] += (double)(dx * dx);
-                acc[2] += (double)(de * de);
-            }
-        }
-        if (a.mean) st_quad<V>(a.mean + row + p, mean, valid);
-        if (a.log_variance) st_quad<V>(a.log_variance + row + p, lv, valid);
-        if (a.pred_xstart) st_quad<V>(a.pred_xstart + row + p, x0, valid);
-    }
+    vlb_thread_terms<V, DECODER>(a, a.sc, a.post_log_var, b, n, (blockIdx.x * 256 + threadIdx.x) * 4, acc);
     vlb_block_fold<3>(acc, red, a.part + ((int64_t)b * gridDim.x + blockIdx.x) * 3);
 }
 
@@ -873,29 +673,24 @@ __global__ __launch_bounds__(256) void prior_kl_kernel(float c0, float logvar, c
 // in fp64 rounded to fp32 once, then (quantity 0) the reference's fp32 division by np.log(2.0).  Quantity q of sample b goes to
 // out[q][b*stride].
 __global__ __launch_bounds__(64) void vlb_finalize_kernel(const double* __restrict__ part, int nblk, int nq, int n, float* o0,
-                                                          float* o1, float* o2, int64_t stride) {
+                                                          float* o1, float* o2, int64_t stride, int bits) {
     __shared__ double red[3 * 64];
     const int b = blockIdx.x;
-    for (int q = 0; q < nq; ++q) {
-        double sum = 0.0;
-        for (int j = threadIdx.x; j < nblk; j += 64) sum += part[((int64_t)b * nblk + j) * nq + q];
-        red[q * 64 + threadIdx.x] = sum;
-    }
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-            for (int q = 0; q < nq; ++q) red[q * 64 + threadIdx.x] += red[q * 64 + threadIdx.x + w];
-        __syncthreads();
-    }
+    rows_fold_partials(part, b, nblk, nq, red);
     if (threadIdx.x == 0) {
         float* outs[3] = {o0, o1, o2};
         for (int q = 0; q < nq; ++q) {
             if (!outs[q]) continue;
-            float v = (float)(red[q * 64] / (double)n);
-            if (q == 0) v = v / 0.6931471805599453f;
-            outs[q][(int64_t)b * stride] = v;
+            outs[q][(int64_t)b * stride] = rows_mean_value(red[q * 64], n, bits && q == 0);
         }
     }
+}
+
+// bits: quantity 0 is a bound term (divided by ln 2); loss.hip's means pass 0
+void rows_finalize(const double* part, int nblk, int nq, int n, float* o0, float* o1, float* o2, int64_t stride, int bits, int B,
+                   hipStream_t s) {
+    hipLaunchKernelGGL(vlb_finalize_kernel, dim3(B), dim3(64), 0, s, part, nblk, nq, n, o0, o1, o2, stride, bits);
+    check_launch("vlb_finalize");
 }
 
 static int vlb_blocks(int64_t n) { return (int)((n + kVlbPiece - 1) / kVlbPiece); }
@@ -921,9 +716,7 @@ void vlb_terms(const VlbStep& step, bool decoder, float* vb, float* xstart_mse, 
     });
     check_launch("vlb_terms");
     if (!vb && !xstart_mse && !mse) return;
-    hipLaunchKernelGGL(vlb_finalize_kernel, dim3(B), dim3(64), 0, s, a.part, nblk, 3, (int)n, vb, xstart_mse, mse,
-                       term_stride > 0 ? term_stride : (int64_t)1);
-    check_launch("vlb_finalize");
+    rows_finalize(a.part, nblk, 3, (int)n, vb, xstart_mse, mse, term_stride > 0 ? term_stride : (int64_t)1, 1, B, s);
 }
 
 void prior_bpd(float c0, float logvar, const float* x_start, double* part, float* prior, int B, int64_t n, hipStream_t s) {
@@ -935,8 +728,7 @@ void prior_bpd(float c0, float logvar, const float* x_start, double* part, float
         hipLaunchKernelGGL(prior_kl_kernel<decltype(V)::value>, dim3(nblk, B), dim3(256), 0, s, c0, logvar, x_start, (int)n, part);
     });
     check_launch("prior_kl");
-    hipLaunchKernelGGL(vlb_finalize_kernel, dim3(B), dim3(64), 0, s, part, nblk, 1, (int)n, prior, nullptr, nullptr, (int64_t)1);
-    check_launch("vlb_finalize");
+    rows_finalize(part, nblk, 1, (int)n, prior, nullptr, nullptr, 1, 1, B, s);
 }
 
 // ddim_reverse_sample (gaussian_diffusion.py:691-701): eps re-derived from the clipped pred_xstart, x_{t+1} written in place

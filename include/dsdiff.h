@@ -606,6 +606,59 @@ int dsd_op_prior_bpd(float sqrt_acp, float log_1m_acp, const float* x_start, flo
 int dsd_op_ddim_reverse_step(const dsd_schedule* sched, int k, float alpha_bar_next, const float* model_out,
                              int64_t out_row_stride, float* x, int64_t x_row_stride, float* pred_xstart, int B, int Cz, int H,
                              int W, void* stream);
+/* ---- the denoising loss, forward only --------------------------------------------------------
+ * Replaces GaussianDiffusion.training_losses (Disc_diff/guided_diffusion/gaussian_diffusion.py:821-920 and
+ * training_project/utils/gaussian_diffusion.py:824-), DDPM.p_losses / get_loss / get_v (ldm/models/diffusion/ddpm.py:361-415)
+ * and LatentDiffusion.p_losses (:892-927) as an evaluation: no gradient, no optimiser.  It is the one evaluation with a
+ * timestep per SAMPLE, so whatever depends on t arrives as device rows of B values, gathered by the caller from its tables.
+ * One call: x_t[b] = a[b]*x_start[b] + s[b]*z[b] in a state of the call's own, one network evaluation with t_model[b] per row,
+ * then per sample, over the Cz*H*W elements, into row b of terms [B, DSD_LOSS_NTERMS]:
+ *   DSD_LOSS_TERM_MSE   mean kind(target - prediction); target: z, x_start, or a[b]*z - s[b]*x_start (get_v);
+ *                       kind: DSD_LOSS_L2 d^2, DSD_LOSS_L1 |d|, DSD_LOSS_CHARBONNIER sqrt(d^2 + 1e-6) (L1_Charbonnier_loss)
+ *   DSD_LOSS_TERM_VB    (vlb_coef != NULL) _vb_terms_bpd with clip_denoised = False: sample b's DSD_MODE_A_DDPM coefficient row
+ *                       vlb_coef[b], post_log_var[b], and the decoder NLL where decoder[b] != 0 (t == 0); with learned_range the
+ *                       variance half of the output is read in place
+ *   DSD_LOSS_TERM_COM / DSD_LOSS_TERM_DIST   (dsd_create_disc handles) the sums over the six pairs of the four com_h / dist_h
+ *                       bottleneck tensors of mean (f_i - f_j)^2, read straight from the workspace
+ * Columns a call does not compute are left as they are.  z: noise [B,Cz,H,W], or NULL: the Philox normals of stream
+ * (philox_seed, step + 2^32) — the ones dsd_op_q_sample draws with the same seed and step.  Every reduction adds fixed
+ * per-block fp64 partials in index order (no atomics): two calls agree bit for bit.  The handle picks the denoiser as in the
+ * loops (cond / Cc / Cz as there; dsd_set_conditioning applies); after the first call of a shape nothing is allocated.
+ * Rejected before any device work: null rows or results, an unknown pred / kind, learned_range on a model without a variance
+ * half, an installed trace, and the channel / shape / slice-id misfits of the loops. */
+enum { DSD_LOSS_L2 = 0, DSD_LOSS_L1 = 1, DSD_LOSS_CHARBONNIER = 2 };
+enum { DSD_LOSS_TERM_MSE = 0, DSD_LOSS_TERM_VB = 1, DSD_LOSS_TERM_COM = 2, DSD_LOSS_TERM_DIST = 3, DSD_LOSS_NTERMS = 4 };
+typedef struct dsd_loss {
+    int32_t target;            /* DSD_PRED_*: the target of the mse term (training_losses reads it off `parameterization`) */
+    int32_t pred;              /* DSD_PRED_*: what the vb term's p_mean_variance reads the output as (model_mean_type; the two
+                                * differ in the reference for predict_xstart with parameterization "eps") */
+    int32_t kind;              /* DSD_LOSS_* */
+    int32_t learned_range;     /* the output carries a variance half [Cz,2Cz) (read by the vb term only) */
+    const float* t_model;      /* device, [B]: the value the network receives as t */
+    const float* a;            /* device, [B]: sqrt_alphas_cumprod[t] */
+    const float* s;            /* device, [B]: sqrt_one_minus_alphas_cumprod[t] */
+    const float* vlb_coef;     /* device, [B,DSD_NCOEF], or NULL: no vb term */
+    const float* post_log_var; /* device, [B]: posterior_log_variance_clipped[t] (with vlb_coef) */
+    const int32_t* decoder;    /* device, [B]: t == 0 (with vlb_coef) */
+    float* terms;              /* device, [B,DSD_LOSS_NTERMS] */
+} dsd_loss;
+int dsd_eval_loss(dsd_handle* h, const dsd_loss* spec, const float* cond, int Cc, const float* x_start, int Cz, const float* noise,
+                  uint64_t philox_seed, uint64_t step, int B, int H, int W, void* stream);
+/* The mse term alone, on caller buffers: model_out rows at model_out + b*out_row_stride (0: Cz*H*W); x_start (unread by the eps
+ * target) and noise (unread by the x0 target; NULL: Philox as above) [B,Cz,H,W]; a, s device [B] (v target only); loss[b*loss_stride]
+ * (0: 1). */
+int dsd_op_loss_rows(int pred, int kind, const float* model_out, int64_t out_row_stride, const float* x_start, const float* noise,
+                     uint64_t philox_seed, uint64_t step, const float* a, const float* s, float* loss, int64_t loss_stride, int B,
+                     int Cz, int H, int W, void* stream);
+/* out[b] = sum over the pairs of the n_feats (2, 3 or 4) device tensors feats[i] [B,n] of mean (f_i - f_j)^2, pairs and fp32 sums in
+ * the reference's order: (1,2) + (2,3) + (1,3), then + ((1,4) + (2,4) + (3,4)). */
+int dsd_op_pair_mse_rows(const float* const* feats, int n_feats, int B, int64_t n, float* out, void* stream);
+/* dsd_op_vlb_terms with a timestep per sample: coef device [B,DSD_NCOEF], post_log_var device [B], decoder device [B] (t == 0).
+ * Same device functions; with one t shared by the batch the results are dsd_op_vlb_terms' bits. */
+int dsd_op_vlb_terms_rows(int pred, int learned_range, int clip_denoised, const float* coef, const float* post_log_var,
+                          const int32_t* decoder, const float* model_out, int64_t out_row_stride, const float* x_t,
+                          int64_t x_row_stride, const float* x_start, const float* noise, uint64_t philox_seed, uint64_t step,
+                          float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int H, int W, void* stream);
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
