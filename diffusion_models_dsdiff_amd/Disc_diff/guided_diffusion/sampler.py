@@ -277,29 +277,24 @@ class DPM_Solver:
         raise ValueError(
             "Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
 
-    def build_schedule(self, steps, t_start=None, t_end=None, order=2, skip_type="time_uniform",
-                       lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver") -> DpmSchedule:
-        """Per-evaluation coefficient rows of the multistep loop (:1130-1176) for dsd_sample_dpm."""
-        if solver_type not in ["dpmsolver", "taylor"]:
-            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
-        if order not in (1, 2):
-            raise NotImplementedError("a dsd_dpm_schedule holds multistep order 1 and 2 (got {}); build_program packs order 3 and "
-                                      "the singlestep solvers".format(order))
-        ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
+    def _time_range(self, t_start, t_end):
+        """(t_T, t_0) of sample() :1113-1115."""
+        ns = self.noise_schedule
         t_0 = 1. / ns.total_N if t_end is None else t_end
         t_T = ns.T if t_start is None else t_start
         assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        return t_T, t_0
+
+    def _multistep_evals(self, steps, t_T, t_0, order, skip_type, lower_order_final, solver_type, ev):
+        """The evaluations of the multistep loop (:1130-1176), one ev(time, kind, coef, slot, keep) per step: the step's order,
+        then cx, lead * phi_1 and, for order 2 (:784-815), cd and 1 / r0, for order 3 (:840-867) its six further terms — every
+        scalar in the reference's fp32 expressions.  History planes k % 3, (k-1) % 3, (k-2) % 3.  The one place these are formed:
+        build_schedule packs the rows of order <= 2 for dsd_sample_dpm, build_program all of them."""
+        ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
         assert steps >= order
         ts = self.get_time_steps(skip_type, t_T, t_0, steps)
         assert ts.shape[0] - 1 == steps
-        rows, orders, tin = [], [], []
-        f = lambda v: float(v.reshape(-1)[0])
-
-        def row(t_eval, cx=0., cm=0., cd=0., ir0=0.):
-            r = [f(ns.marginal_alpha(t_eval)), f(ns.marginal_std(t_eval)), cx, cm, cd, ir0] + [0.] * (DSD_NCOEF - 6)
-            rows.append(r)
-            tin.append(f(self.model_fn_.input_time(torch.as_tensor(t_eval, dtype=torch.float32).reshape(-1))))
-
+        lam = [ns.marginal_lambda(t) for t in ts]
         for k in range(steps):
             s, t, step = ts[k], ts[k + 1], k + 1
             if step < order:
@@ -308,8 +303,7 @@ class DPM_Solver:
                 so = min(order, steps + 1 - step)
             else:
                 so = order
-            lam_s, lam_t = ns.marginal_lambda(s), ns.marginal_lambda(t)
-            h = lam_t - lam_s
+            h = lam[k + 1] - lam[k]
             la_s, la_t = ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(t)
             sig_s, sig_t = ns.marginal_std(s), ns.marginal_std(t)
             alpha_t = torch.exp(la_t)
@@ -319,25 +313,45 @@ class DPM_Solver:
             else:
                 phi_1 = torch.expm1(h)
                 cx, lead = torch.exp(la_t - la_s), sig_t
-            cm = lead * phi_1
-            cd = ir0 = torch.zeros(1)
+            coef = [cx, lead * phi_1]
             if so == 2:
-                h_0 = lam_s - ns.marginal_lambda(ts[k - 1])
-                ir0 = 1. / (h_0 / h)
+                h_0 = lam[k] - lam[k - 1]
+                r0 = h_0 / h
                 if solver_type == "dpmsolver":
                     cd = 0.5 * (lead * phi_1)
                 elif pp:
                     cd = -(lead * (phi_1 / h + 1.))
                 else:
                     cd = lead * (phi_1 / h - 1.)
-            row(s, f(cx), f(cm), f(cd), f(ir0))
-            orders.append(so)
+                coef += [cd, 1. / r0]
+            elif so == 3:
+                h_1, h_0 = lam[k - 1] - lam[k - 2], lam[k] - lam[k - 1]
+                r0, r1 = h_0 / h, h_1 / h
+                phi_2 = phi_1 / h + 1. if pp else phi_1 / h - 1.
+                phi_3 = phi_2 / h - 0.5
+                c2 = lead * phi_2
+                coef += [c2 if pp else -c2, lead * phi_3, 1. / r0, 1. / r1, r0 / (r0 + r1), 1. / (r0 + r1)]
+            ev(s, (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3)[so], coef, (k % 3, k % 3, (k - 1) % 3, (k - 2) % 3), True)
+
+    def build_schedule(self, steps, t_start=None, t_end=None, order=2, skip_type="time_uniform",
+                       lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver") -> DpmSchedule:
+        """Per-evaluation coefficient rows of the multistep loop (:1130-1176) for dsd_sample_dpm: alpha, sigma, cx, lead * phi_1,
+        cd, 1 / r0 of every step (the kind DPM_MS<o> of a row is its order o)."""
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        if order not in (1, 2):
+            raise NotImplementedError("a dsd_dpm_schedule holds multistep order 1 and 2 (got {}); build_program packs order 3 and "
+                                      "the singlestep solvers".format(order))
+        t_T, t_0 = self._time_range(t_start, t_end)
+        evals = []
+        ev = lambda *row: evals.append(self._eval_row(*row))
+        self._multistep_evals(steps, t_T, t_0, order, skip_type, lower_order_final, solver_type, ev)
         if denoise_to_zero:
-            row(torch.ones((1,)) * t_0)
-            orders.append(0)
+            ev(torch.ones((1,)) * t_0, DPM_MS0, [], (0, 0, 0, 0), True)
+        rows = [[e["alpha"], e["sigma"]] + (e["coef"] + [0.] * 4)[:4] + [0.] * (DSD_NCOEF - 6) for e in evals]
         thr = self.correcting_x0_fn == "dynamic_thresholding"
-        return DpmSchedule(_PRED[self.model_fn_.model_type], pp, thr, self.dynamic_thresholding_ratio,
-                           self.thresholding_max_val, rows, tin, orders)
+        return DpmSchedule(_PRED[self.model_fn_.model_type], self.algorithm_type == "dpmsolver++", thr, self.dynamic_thresholding_ratio,
+                           self.thresholding_max_val, rows, [e["t_input"] for e in evals], [e["kind"] - DPM_MS0 for e in evals])
 
     def get_orders_and_timesteps_for_singlestep_solver(self, steps, order, skip_type, t_T, t_0, device=None):
         """The singlestep schedule of :445-501 ("DPM-Solver-fast"): ``steps`` evaluations spent on as many steps of ``order`` as
@@ -441,56 +455,14 @@ class DPM_Solver:
         if order not in (1, 2, 3):
             raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
         ns, pp = self.noise_schedule, self.algorithm_type == "dpmsolver++"
-        t_0 = 1. / ns.total_N if t_end is None else t_end
-        t_T = ns.T if t_start is None else t_start
-        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        t_T, t_0 = self._time_range(t_start, t_end)
         evals = []
 
         def ev(t_eval, kind, coef, slot, keep):
             evals.append(self._eval_row(t_eval, kind, coef, slot, keep and return_intermediate))
 
         if method == "multistep":
-            assert steps >= order
-            ts = self.get_time_steps(skip_type, t_T, t_0, steps)
-            assert ts.shape[0] - 1 == steps
-            lam = [ns.marginal_lambda(t) for t in ts]
-            for k in range(steps):
-                s, t, step = ts[k], ts[k + 1], k + 1
-                if step < order:
-                    so = step
-                elif lower_order_final and steps < 10:
-                    so = min(order, steps + 1 - step)
-                else:
-                    so = order
-                h = lam[k + 1] - lam[k]
-                la_s, la_t = ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(t)
-                sig_s, sig_t = ns.marginal_std(s), ns.marginal_std(t)
-                alpha_t = torch.exp(la_t)
-                if pp:
-                    phi_1 = torch.expm1(-h)
-                    cx, lead = sig_t / sig_s, alpha_t
-                else:
-                    phi_1 = torch.expm1(h)
-                    cx, lead = torch.exp(la_t - la_s), sig_t
-                coef = [cx, lead * phi_1]
-                if so == 2:                                                   # :784-815
-                    h_0 = lam[k] - lam[k - 1]
-                    r0 = h_0 / h
-                    if solver_type == "dpmsolver":
-                        cd = 0.5 * (lead * phi_1)
-                    elif pp:
-                        cd = -(lead * (phi_1 / h + 1.))
-                    else:
-                        cd = lead * (phi_1 / h - 1.)
-                    coef += [cd, 1. / r0]
-                elif so == 3:                                                 # :840-867
-                    h_1, h_0 = lam[k - 1] - lam[k - 2], lam[k] - lam[k - 1]
-                    r0, r1 = h_0 / h, h_1 / h
-                    phi_2 = phi_1 / h + 1. if pp else phi_1 / h - 1.
-                    phi_3 = phi_2 / h - 0.5
-                    c2 = lead * phi_2
-                    coef += [c2 if pp else -c2, lead * phi_3, 1. / r0, 1. / r1, r0 / (r0 + r1), 1. / (r0 + r1)]
-                ev(s, (DPM_MS0, DPM_MS1, DPM_MS2, DPM_MS3)[so], coef, (k % 3, k % 3, (k - 1) % 3, (k - 2) % 3), True)
+            self._multistep_evals(steps, t_T, t_0, order, skip_type, lower_order_final, solver_type, ev)
         else:
             if method == "singlestep":
                 outer, orders = self.get_orders_and_timesteps_for_singlestep_solver(steps, order, skip_type, t_T, t_0)
@@ -678,6 +650,26 @@ def run_dpm_loop(fn: _ModelFn, sched: DpmSchedule, x_T: torch.Tensor, guidance: 
     return x
 
 
+def _run_program_per_evaluation(fn: _ModelFn, prog: DpmProgram, x: torch.Tensor, kept: Optional[torch.Tensor] = None):
+    """A DpmProgram on ``x`` (in place) for any callable that is no native denoiser: a python loop over the network with the
+    fused HIP evaluation step (dsd_op_dpm_eval) after each call; the states the program keeps go to ``kept``.  Returns the
+    history planes and the base plane the program left."""
+    B, Cx, H, W = x.shape
+    hist, base = x.new_empty((3, B, Cx, H, W)), torch.empty_like(x)
+    j = 0
+    for k in range(prog.steps):
+        t_in = torch.full((B,), float(prog.t_input[k]), device=x.device, dtype=torch.float32)
+        out = fn.network(x, t_in).float().contiguous()
+        if out.shape[1] not in (Cx, 2 * Cx):
+            raise ValueError(f"the network returned {out.shape[1]} channels for a state of {Cx}")
+        check(lib().dsd_op_dpm_eval(C.byref(prog.c), k, None, dptr(out), out.shape[1] // Cx, 1., dptr(x), 0, dptr(hist), dptr(base),
+                                    B, Cx, H, W, stream_ptr()))
+        if prog.keep[k]:
+            kept[j].copy_(x)
+            j += 1
+    return hist, base
+
+
 @torch.no_grad()
 def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance: Optional[Guidance] = None):
     """A DpmProgram on the device: dsd_sample_dpm_program for the native denoisers, guided or not, and for any other
@@ -697,19 +689,7 @@ def run_dpm_program(fn: _ModelFn, prog: DpmProgram, x_T: torch.Tensor, guidance:
             check(lib().dsd_sample_dpm_program(unet._h, C.byref(prog.c), g, dptr(cond), cond.shape[1], dptr(x), Cx, B, H, W,
                                                dptr(kept), stream_ptr()))
         return x, kept
-    # any other callable: python loop over the network, the fused HIP evaluation step after each
-    hist, base = x.new_empty((3, B, Cx, H, W)), torch.empty_like(x)
-    j = 0
-    for k in range(prog.steps):
-        t_in = torch.full((B,), float(prog.t_input[k]), device=x.device, dtype=torch.float32)
-        out = fn.network(x, t_in).float().contiguous()
-        if out.shape[1] not in (Cx, 2 * Cx):
-            raise ValueError(f"the network returned {out.shape[1]} channels for a state of {Cx}")
-        check(lib().dsd_op_dpm_eval(C.byref(prog.c), k, None, dptr(out), out.shape[1] // Cx, 1., dptr(x), 0, dptr(hist), dptr(base),
-                                    B, Cx, H, W, stream_ptr()))
-        if prog.keep[k]:
-            kept[j].copy_(x)
-            j += 1
+    _run_program_per_evaluation(fn, prog, x, kept)
     return x, kept
 
 
@@ -756,15 +736,7 @@ class AdaptiveTrial:
                                                       float(rtol), dptr(xh), dptr(x_prev), dptr(x_lower), Cx, B, H, W,
                                                       self.err.ctypes.data_as(C.POINTER(C.c_float)), stream_ptr()))
             return xh, x_lower, torch.from_numpy(self.err.copy())
-        # any other callable: python loop over the network, the fused HIP evaluation step after each, then the error kernel
-        hist, base = xh.new_empty((3, B, Cx, H, W)), torch.empty_like(xh)
-        for k in range(prog.steps):
-            t_in = torch.full((B,), float(prog.t_input[k]), device=xh.device, dtype=torch.float32)
-            out = self.fn.network(xh, t_in).float().contiguous()
-            if out.shape[1] not in (Cx, 2 * Cx):
-                raise ValueError(f"the network returned {out.shape[1]} channels for a state of {Cx}")
-            check(lib().dsd_op_dpm_eval(C.byref(prog.c), k, None, dptr(out), out.shape[1] // Cx, 1., dptr(xh), 0, dptr(hist), dptr(base),
-                                        B, Cx, H, W, stream_ptr()))
+        hist, base = _run_program_per_evaluation(self.fn, prog, xh)               # any other callable; then the error kernel
         err = torch.empty(B, device=xh.device, dtype=torch.float32)
         ma, mb = hist[int(prog.slot[0, 0])], hist[int(prog.slot[1, 0])]
         check(lib().dsd_op_dpm_adaptive_error(self.order - 1, lp, float(atol), float(rtol), dptr(base), dptr(ma), dptr(mb), dptr(xh), 0,

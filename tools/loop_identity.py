@@ -15,8 +15,20 @@ guided DDIM (per-step scales 1.5 .. 3.5); masked B_DDIM, guided masked B_DDIM an
 DPM-Solver++ order 2 plain and guided; the DPM program (singlestep 3, multistep 3, with kept states); PLMS plain, thresholded,
 guided + masked, guided split, masked with Philox blend noise; DDIM inversion plain, guided, guided split; the variational bound.
 One DiT (M1 of tests/dit_loops_util.py) and one DisC-Diff network (`tiny` of tests/golden/disc.npz) run a DDIM loop each.
-dsd_graph_stats of every handle is recorded after each pass."""
-import argparse, hashlib, json, os, sys
+dsd_graph_stats of every handle is recorded after each pass.  Further: one adaptive DPM-Solver run of order 2 and of order 3, a
+traced DDIM and a traced PLMS run, dsd_eval_loss on the four-stream, DisC-Diff, latent and DiT fixtures of tests/loss_cases.py, and
+a latent DDIM run with a context and one with a label (tests/cond_keys_util.py).
+
+Two modes need no GPU, and are compared with the same --compare:
+
+    python tools/loop_identity.py --schedules --out a.json   # SHA-256 of the host arrays DPM_Solver.build_schedule / build_program pack
+    python tools/loop_identity.py --refusals --out a.json    # dsd_last_error() of one bad call per rule of the loops' call checks
+
+--schedules walks both algorithm types, both solver types, the three skip types, orders 1-3, steps 1, 2, 3, 5, 9, 10 and 20,
+lower_order_final and denoise_to_zero on and off (a combination the builder rejects records the exception).  --refusals makes
+table-only handles (device -1) of the four denoisers and breaks exactly one rule per call, so every call returns before any device
+work; the pointers it passes are never read."""
+import argparse, hashlib, json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -39,19 +51,358 @@ def compare(pa, pb, out):
     return 0 if verdict["all_equal"] else 1
 
 
+def schedules():
+    """Digests of every host array the two DPM builders pack, over the grid of the docstring."""
+    import itertools
+    import numpy as np
+    import torch
+    from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
+    sha = lambda o, names: {n: hashlib.sha256(np.ascontiguousarray(getattr(o, n)).tobytes()).hexdigest() for n in names}
+    noise = {"discrete": dsa.NoiseScheduleVP("discrete", betas=torch.linspace(1e-4, 2e-2, 1000)), "linear": dsa.NoiseScheduleVP("linear")}
+    cases = {}
+    grid = itertools.product(noise, ("dpmsolver", "dpmsolver++"), ("dpmsolver", "taylor"), ("logSNR", "time_uniform", "time_quadratic"),
+                             (1, 2, 3), (1, 2, 3, 5, 9, 10, 20), (True, False), (True, False))
+    for ns, algo, solver, skip, order, steps, lof, dtz in grid:
+        sol = dsa.DPM_Solver(dsa.model_wrapper(None, noise[ns], model_type="v"), noise[ns], algorithm_type=algo)
+        kw = dict(steps=steps, order=order, skip_type=skip, lower_order_final=lof, denoise_to_zero=dtz, solver_type=solver)
+        builds = [("schedule", lambda: sha(sol.build_schedule(**kw), ("coef", "t_input", "order")))]
+        for method in ("multistep", "singlestep", "singlestep_fixed"):
+            builds.append((method, lambda m=method: sha(sol.build_program(method=m, return_intermediate=True, **kw),
+                                                        ("coef", "t_input", "kind", "alpha", "sigma", "slot", "keep"))))
+        for name, build in builds:
+            try:
+                got = build()
+            except Exception as e:                                                # steps < order, order 3 of a dsd_dpm_schedule, ...
+                got = f"{type(e).__name__}: {e}"
+            cases[f"{ns}_{algo}_{solver}_{skip}_o{order}_n{steps}_lof{int(lof)}_dtz{int(dtz)}_{name}"] = got
+    return cases
+
+
+def refusals():
+    """dsd_last_error() of one bad call per rule, on table-only handles: {case: message}."""
+    import ctypes as C
+    import numpy as np
+    from diffusion_models_dsdiff_amd import _lib
+    import disc_ref as R
+    from util import golden
+    L = _lib.lib()
+    PTR = C.c_void_p(4096)            # stands for every device pointer: a refused call reads none of them
+    f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    keep_alive, out = [], {}
+
+    def floats(n, v=0.):
+        a = np.full(n, v, dtype=np.float32)
+        keep_alive.append(a)
+        return a.ctypes.data_as(f32p)
+
+    def ints(v):
+        a = np.asarray(v, dtype=np.int32)
+        keep_alive.append(a)
+        return a.ctypes.data_as(i32p)
+
+    def model(kw, disc=False, **over):
+        kw = dict(kw, **over)
+        cfg = _lib.DsdConfig()
+        cfg.in_channels, cfg.model_channels, cfg.out_channels = kw["in_channels"], kw["model_channels"], kw["out_channels"]
+        nrb = kw["num_res_blocks"]
+        cfg.n_levels = len(kw["channel_mult"])
+        for i, m in enumerate(kw["channel_mult"]):
+            cfg.channel_mult[i], cfg.num_res_blocks[i] = m, nrb if isinstance(nrb, int) else nrb[i]
+        cfg.n_attention_resolutions = len(kw["attention_resolutions"])
+        for i, a in enumerate(kw["attention_resolutions"]):
+            cfg.attention_resolutions[i] = a
+        cfg.num_heads, cfg.num_head_channels, cfg.num_heads_upsample = kw.get("num_heads", 1 if disc else -1), kw.get("num_head_channels", -1), -1
+        cfg.use_scale_shift_norm, cfg.resblock_updown = int(kw.get("use_scale_shift_norm", False)), int(kw.get("resblock_updown", False))
+        cfg.use_new_attention_order, cfg.legacy = int(kw.get("use_new_attention_order", False)), int(kw.get("legacy", True))
+        h = C.c_void_p()
+        _lib.check((L.dsd_create_disc if disc else L.dsd_create)(C.byref(cfg), -1, C.byref(h)))
+        return h
+
+    def block(kind, ia):
+        h = C.c_void_p()
+        _lib.check(L.dsd_block_create(kind, (C.c_int32 * len(ia))(*ia), len(ia), -1, C.byref(h)))
+        return h
+
+    unet = lambda cin, cout, extra=(): block(_lib.BLOCK_UNET, [cin, 64, cout, 4, -1, -1, 0, 0, 0, 0, 2, 1, 2, 1, 1, 1, 1] + list(extra))
+    dit = lambda learn_sigma: block(_lib.BLOCK_DIT, [8, 2, 4, 64, 2, 4, 256, 0, learn_sigma, 0])
+    tiny = json.loads(str(golden("model")["tiny_cfg"]))
+    H = dict(four=model(tiny), four3=model(tiny, out_channels=3), disc=model(R.case("tiny")[0], disc=True), attn=block(_lib.BLOCK_ATTN, [64, 4, -1]),
+             u=unet(4, 2), u44=unet(4, 4), u_ctx=unet(4, 4, [1, 1, 24, 0]), u_cls=unet(4, 4, [0, 1, 0, 0, 1, 7]),
+             u_seq=unet(4, 4, [0, 1, 0, 0, 3, 12]), dit=dit(0), dit_ls=dit(1))
+    N = 4
+
+    def sched(mode=_lib.MODE_B_DDIM, pred=_lib.PRED_EPS, learned_range=0, steps=N, coef=True, sigma=0.):
+        sc = _lib.DsdSchedule()
+        sc.steps, sc.mode, sc.pred, sc.learned_range = steps, mode, pred, learned_range
+        c = np.zeros((N, _lib.DSD_NCOEF), dtype=np.float32)
+        c[:, 6] = sigma
+        keep_alive.append(c)
+        if coef:
+            sc.coef = c.ctypes.data_as(f32p)
+        sc.t_model = floats(N)
+        return sc
+
+    def dpm_sched(order=(1, 2, 2, 0), pred=_lib.PRED_EPS, thr=0, ratio=0.5, coef=True):
+        sc = _lib.DsdDpmSchedule()
+        sc.steps, sc.pred, sc.thresholding, sc.threshold_ratio = N, pred, thr, ratio
+        if coef:
+            sc.coef = floats(N * _lib.DSD_NCOEF)
+        sc.t_input, sc.order = floats(N), ints(order)
+        return sc
+
+    def program(kinds=(_lib.DPM_MS1, _lib.DPM_MS2), slots=((0, 0, 0, 0), (1, 1, 0, 0)), keep=None, pred=_lib.PRED_EPS, thr=0, ratio=0.5,
+                alpha=True, coef_rows=None):
+        p = _lib.DsdDpmProgram()
+        n = len(kinds)
+        p.n_eval, p.pred, p.thresholding, p.threshold_ratio = n, pred, thr, ratio
+        p.kind, p.t_input, p.sigma, p.slot = ints(kinds), floats(max(n, 1)), floats(max(n, 1)), ints(np.asarray(slots).reshape(-1))
+        if alpha:
+            p.alpha = floats(max(n, 1))
+        c = np.zeros((max(n, 1), _lib.DSD_DPM_NCOEF), dtype=np.float32)
+        for k, row in (coef_rows or {}).items():
+            c[k, :len(row)] = row
+        keep_alive.append(c)
+        p.coef = c.ctypes.data_as(f32p)
+        if keep is not None:
+            p.keep = ints(keep)
+        return p
+
+    def guidance(uncond=PTR, n=N, scale=True):
+        g = _lib.DsdGuidance()
+        g.uncond, g.n_scale = uncond, n
+        if scale:
+            g.scale = floats(max(n, 1), 2.)
+        return g
+
+    def inpaint(x0=PTR, mask=PTR, ch=1):
+        i = _lib.DsdInpaint()
+        i.x0, i.mask, i.mask_channels = x0, mask, ch
+        return i
+
+    def bpd(plv=True, vb=PTR):
+        b = _lib.DsdBpd()
+        if plv:
+            b.post_log_var = floats(N)
+        b.vb, b.xstart_mse, b.mse = vb, PTR, PTR
+        return b
+
+    def loss(pred=_lib.PRED_EPS, target=_lib.PRED_EPS, kind=0, learned_range=0, a=PTR, vlb=None, plv=None, dec=None):
+        l = _lib.DsdLoss()
+        l.target, l.pred, l.kind, l.learned_range = target, pred, kind, learned_range
+        l.t_model, l.a, l.s, l.terms, l.vlb_coef, l.post_log_var, l.decoder = PTR, a, PTR, PTR, vlb, plv, dec
+        return l
+
+    ref = lambda o: None if o is None else C.byref(o)
+    A_DDPM = lambda **kw: sched(mode=_lib.MODE_A_DDPM, **kw)
+    TRIAL = dict(kinds=(_lib.DPM_SS_S1, _lib.DPM_SS_T2), slots=((0, 0, 0, 0), (1, 0, 1, 0)))
+    # the entry points over the arguments they share (a: h, g, cond, Cc, x, Cz, B, H, W) and their own (o)
+    ENTRY = {
+        "sample": lambda a, o: L.dsd_sample(a["h"], ref(o.get("sc", sched(learned_range=0))), ref(a["g"]), ref(o.get("inp")), a["cond"], a["Cc"],
+                                            a["x"], a["Cz"], None, 0, a["B"], a["H"], a["W"], 0, 0, None),
+        "dpm": lambda a, o: L.dsd_sample_dpm(a["h"], ref(o.get("sc", dpm_sched())), ref(a["g"]), a["cond"], a["Cc"], a["x"], a["Cz"], a["B"],
+                                             a["H"], a["W"], None),
+        "program": lambda a, o: L.dsd_sample_dpm_program(a["h"], ref(o.get("p", program())), ref(a["g"]), a["cond"], a["Cc"], a["x"], a["Cz"],
+                                                         a["B"], a["H"], a["W"], o.get("inter"), None),
+        "trial": lambda a, o: L.dsd_sample_dpm_adaptive_trial(a["h"], ref(o.get("p", program(**TRIAL))), ref(a["g"]), a["cond"], a["Cc"],
+                                                              o.get("lower", floats(3)), o.get("atol", 0.01), o.get("rtol", 0.05), a["x"],
+                                                              o.get("x_prev", PTR), PTR, a["Cz"], a["B"], a["H"], a["W"],
+                                                              floats(8), None),
+        "plms": lambda a, o: L.dsd_sample_plms(a["h"], ref(o.get("sc", sched(mode=_lib.MODE_B_PLMS))), ref(a["g"]), ref(o.get("inp")), 0.,
+                                               a["cond"], a["Cc"], a["x"], a["Cz"], 0, a["B"], a["H"], a["W"], o.get("k0", 0), 0, None),
+        "invert": lambda a, o: L.dsd_invert(a["h"], ref(o.get("sc", invert_sched())), ref(a["g"]), a["cond"], a["Cc"], a["x"], a["Cz"], a["B"],
+                                            a["H"], a["W"], 0, 0, None),
+        "bpd": lambda a, o: L.dsd_calc_bpd(a["h"], ref(o.get("sc", A_DDPM())), ref(o.get("bpd", bpd())), a["cond"], a["Cc"], a["x"], a["Cz"], None,
+                                           0, a["B"], a["H"], a["W"], 0, 0, None),
+        "loss": lambda a, o: L.dsd_eval_loss(a["h"], ref(o.get("spec", loss())), a["cond"], a["Cc"], a["x"], a["Cz"], None, 0, 0, a["B"], a["H"],
+                                             a["W"], None),
+    }
+    GUIDED = ("sample", "dpm", "program", "trial", "plms", "invert")          # the bound and the loss take no guidance
+    RANGE = {"sample": dict(sc=A_DDPM(learned_range=1)), "bpd": dict(sc=A_DDPM(learned_range=1)),
+             "loss": dict(spec=loss(learned_range=1, vlb=PTR, plv=PTR, dec=PTR))}   # the loops that read a learned range
+
+    def invert_sched(steps=N, coef=True):
+        sc = _lib.DsdInvertSchedule()
+        sc.steps, sc.t_model = steps, floats(N)
+        if coef:
+            sc.coef = floats(2 * N)
+        return sc
+
+    def bad(name, entry, own=None, **shared):
+        a = dict(h=H["four"], g=None, cond=PTR, Cc=1, x=PTR, Cz=1, B=2, H=8, W=8)
+        a.update(shared)
+        if isinstance(a["h"], str):
+            a["h"] = H[a["h"]]
+        if a["g"] is not None and entry in ("program", "trial") and a["g"].n_scale == N:
+            a["g"].n_scale = 2                                                  # one scale per evaluation of the two-row programs
+        assert ENTRY[entry](a, own or {}) != 0, f"{entry}/{name}: the call was not refused"
+        msg = L.dsd_last_error().decode()
+        assert " failed: " not in msg and not msg.startswith("launch of"), f"{entry}/{name}: reached the device: {msg}"
+        assert f"{entry}/{name}" not in out
+        out[f"{entry}/{name}"] = re.sub(r"0x[0-9a-f]+", "0x..", msg)             # %p of this process's host arrays
+
+    def conditioning(h, context=None, context_uncond=None, tokens=0, y=None, y_uncond=None, y_width=0, B=2):
+        c = _lib.DsdConditioning()
+        c.context, c.context_uncond, c.tokens, c.y, c.y_uncond, c.y_width, c.B = context, context_uncond, tokens, y, y_uncond, y_width, B
+        _lib.check(L.dsd_set_conditioning(H[h], C.byref(c)))
+
+    LAT = dict(h="u", Cc=2, Cz=2)                                               # the plain UNetModel: 2 state + 2 'concat' channels
+    DIT = dict(h="dit", Cc=2, Cz=2)
+    for e in ENTRY:
+        guided = e in GUIDED
+        # ---- the shared call checks, in the order they run
+        bad("null_handle", e, h=None)
+        if guided:
+            bad("guidance_uncond_null", e, g=guidance(None))
+            bad("guidance_scale_count", e, g=guidance(n=N + 1))
+            bad("guidance_scale_null", e, g=guidance(scale=False))
+            bad("latent_guidance_uncond_null", e, g=guidance(None), **LAT)
+        if e in RANGE:
+            bad("learned_range_state_channels", e, RANGE[e], **LAT)
+        bad("four_cond_null", e, cond=None)
+        bad("four_x_null", e, x=None)
+        bad("four_state_channels", e, Cz=2)
+        bad("disc_cond_channels", e, h="disc", Cc=1)
+        bad("four_cond_channels", e, Cc=2)
+        for k in "BHW":
+            bad("four_shape_" + k, e, **{k: 0})
+        bad("four_out_channels", e, h="four3")
+        if e in RANGE:
+            bad("four_out_channels_learned_range", e, RANGE[e])
+        bad("latent_x_null", e, **dict(LAT, x=None))
+        bad("latent_block_kind", e, **dict(LAT, h="attn"))
+        bad("latent_shape", e, **dict(LAT, B=0))
+        bad("latent_cond_null", e, **dict(LAT, cond=None))
+        bad("latent_in_channels", e, **dict(LAT, Cc=1))
+        bad("latent_out_channels", e, **dict(LAT, h="u44"))
+        bad("context_missing", e, h="u_ctx", Cz=4, Cc=0)
+        bad("label_missing", e, h="u_cls", Cz=4, Cc=0)
+        conditioning("u", context=PTR, tokens=3)
+        bad("context_unwanted", e, **LAT)
+        conditioning("u", y=PTR, y_width=12)
+        bad("label_unwanted", e, **LAT)
+        _lib.check(L.dsd_set_conditioning(H["u"], None))
+        conditioning("u_ctx", context=PTR, tokens=3, B=3)
+        bad("conditioning_batch", e, h="u_ctx", Cz=4, Cc=0)
+        conditioning("u_seq", y=PTR, y_width=5)
+        bad("label_width", e, h="u_seq", Cz=4, Cc=0)
+        conditioning("u_cls", y=PTR, y_width=3)
+        bad("label_width_classes", e, h="u_cls", Cz=4, Cc=0)
+        if guided:
+            bad("latent_guidance_nothing_to_replace", e, g=guidance(), h="u44", Cz=4, Cc=0)
+            conditioning("u_ctx", context=PTR, tokens=3)
+            bad("guidance_context_twin", e, g=guidance(None), h="u_ctx", Cz=4, Cc=0)
+            conditioning("u_seq", y=PTR, y_width=12)
+            bad("guidance_label_twin", e, g=guidance(None), h="u_seq", Cz=4, Cc=0)
+        for h in ("u_ctx", "u_seq", "u_cls"):
+            _lib.check(L.dsd_set_conditioning(H[h], None))
+        bad("dit_x_null", e, **dict(DIT, x=None))
+        bad("dit_cond_null", e, **dict(DIT, cond=None))
+        bad("dit_shape", e, **dict(DIT, B=0))
+        if guided:
+            bad("dit_guidance_nothing_to_replace", e, g=guidance(), h="dit", Cz=4, Cc=0)
+        bad("dit_in_channels", e, **dict(DIT, Cc=1))
+        bad("dit_input_size", e, **dict(DIT, H=4))
+        bad("dit_out_channels", e, h="dit_ls", Cz=4, Cc=0)
+        if e in RANGE:
+            bad("dit_learned_range_channels", e, RANGE[e], h="dit_ls", Cz=2, Cc=2)
+    # ---- each entry point's own checks
+    trace = _lib.DsdTrace()
+    trace.keep, trace.n_keep, trace.x = ints([N]), 1, PTR
+    _lib.check(L.dsd_set_trace(H["four"], C.byref(trace)))
+    bad("trace_out_of_range", "sample")
+    bad("trace_out_of_range", "plms")
+    for e in ("dpm", "program", "trial", "invert", "bpd", "loss"):
+        bad("trace_refused", e)
+    _lib.check(L.dsd_set_trace(H["four"], None))
+    for e, mode in (("sample", _lib.MODE_B_DDIM), ("bpd", _lib.MODE_A_DDPM)):
+        bad("schedule_null", e, dict(sc=None))
+        bad("schedule_coef_null", e, dict(sc=sched(mode=mode, coef=False)))
+        bad("schedule_steps", e, dict(sc=sched(mode=mode, steps=0)))
+        bad("schedule_plms_mode", e, dict(sc=sched(mode=_lib.MODE_B_PLMS)))
+        bad("schedule_mode", e, dict(sc=sched(mode=9)))
+        bad("schedule_pred", e, dict(sc=sched(mode=mode, pred=5)))
+    bad("schedule_learned_range_family", "sample", dict(sc=sched(learned_range=1)))
+    bad("mask_null", "sample", dict(inp=inpaint(mask=None)))
+    bad("mask_x0_null", "sample", dict(inp=inpaint(x0=None)))
+    bad("mask_channels", "sample", dict(inp=inpaint(ch=2)), **dict(LAT, Cz=3, Cc=1))
+    bad("mask_mode", "sample", dict(sc=A_DDPM(), inp=inpaint()))
+    bad("mask_ddpm_guided", "sample", dict(sc=sched(mode=_lib.MODE_B_DDPM), inp=inpaint()), g=guidance())
+    bad("guided_learned_range", "sample", dict(sc=A_DDPM(learned_range=1)), g=guidance())
+    bad("guided_mode", "sample", dict(sc=A_DDPM()), g=guidance())
+    bad("schedule_null", "dpm", dict(sc=None))
+    bad("schedule_coef_null", "dpm", dict(sc=dpm_sched(coef=False)))
+    bad("schedule_pred", "dpm", dict(sc=dpm_sched(pred=7)))
+    bad("schedule_order", "dpm", dict(sc=dpm_sched(order=(1, 3, 2, 0))))
+    bad("schedule_first_order", "dpm", dict(sc=dpm_sched(order=(2, 2, 2, 0))))
+    bad("schedule_threshold_ratio", "dpm", dict(sc=dpm_sched(thr=1, ratio=1.5)))
+    for e in ("program", "trial"):
+        two = TRIAL if e == "trial" else {}
+        bad("program_null", e, dict(p=None))
+        bad("program_empty", e, dict(p=program(kinds=(), slots=())))
+        bad("program_array_null", e, dict(p=program(alpha=False, **two)))
+        bad("program_pred", e, dict(p=program(pred=4, **two)))
+        bad("program_threshold_ratio", e, dict(p=program(thr=1, ratio=-0.5, **two)))
+        bad("program_kind", e, dict(p=program(kinds=(_lib.DPM_MS1, 99))))
+        bad("program_stage", e, dict(p=program(kinds=(_lib.DPM_MS1, _lib.DPM_SS_T2))))
+        bad("program_slot", e, dict(p=program(slots=((0, 0, 0, 0), (3, 1, 0, 0)))))
+        bad("program_unwritten_plane", e, dict(p=program(slots=((0, 0, 0, 0), (1, 1, 2, 0)))))
+        bad("program_plane_twice", e, dict(p=program(slots=((0, 0, 0, 0), (0, 0, 0, 0)))))
+        bad("program_plane_twice_third", e, dict(p=program(kinds=(_lib.DPM_MS1, _lib.DPM_MS2, _lib.DPM_MS3),
+                                                           slots=((0, 0, 0, 0), (1, 1, 0, 0), (2, 2, 1, 2)))))
+        bad("program_ends_mid_step", e, dict(p=program(kinds=(_lib.DPM_MS1, _lib.DPM_SS_S1))))
+    bad("kept_without_output", "program", dict(p=program(keep=(0, 1))))
+    bad("trial_not_one_step", "trial", dict(p=program()))
+    bad("trial_lower_null", "trial", dict(lower=None))
+    bad("trial_lower_row", "trial", dict(lower=floats(3, 1.)))
+    bad("trial_lower_c2", "trial", dict(p=program(coef_rows={1: [1., 1.]}, **TRIAL), lower=floats(3, 1.)))
+    bad("trial_atol", "trial", dict(atol=0.))
+    bad("trial_rtol", "trial", dict(rtol=-1.))
+    bad("trial_x_prev_null", "trial", dict(x_prev=None))
+    bad("schedule_null", "plms", dict(sc=None))
+    bad("schedule_mode", "plms", dict(sc=sched()))
+    bad("schedule_learned_range", "plms", dict(sc=sched(mode=_lib.MODE_B_PLMS, learned_range=1)))
+    bad("schedule_pred", "plms", dict(sc=sched(mode=_lib.MODE_B_PLMS, pred=_lib.PRED_V)))
+    bad("schedule_eta", "plms", dict(sc=sched(mode=_lib.MODE_B_PLMS, sigma=0.5)))
+    bad("mask_null", "plms", dict(inp=inpaint(mask=None)))
+    bad("history_not_resident", "plms", dict(k0=2))
+    bad("schedule_null", "invert", dict(sc=None))
+    bad("schedule_coef_null", "invert", dict(sc=invert_sched(coef=False)))
+    bad("schedule_not_the_posterior", "bpd", dict(sc=sched()))
+    bad("bpd_null", "bpd", dict(bpd=None))
+    bad("bpd_post_log_var_null", "bpd", dict(bpd=bpd(plv=False)))
+    bad("bpd_output_null", "bpd", dict(bpd=bpd(vb=None)))
+    bad("spec_null", "loss", dict(spec=None))
+    bad("spec_pred", "loss", dict(spec=loss(pred=3)))
+    bad("spec_target", "loss", dict(spec=loss(target=-1)))
+    bad("spec_kind", "loss", dict(spec=loss(kind=9)))
+    bad("spec_rows_null", "loss", dict(spec=loss(a=None)))
+    bad("spec_vb_parts", "loss", dict(spec=loss(vlb=PTR)))
+    bad("spec_learned_range_without_vb", "loss", dict(spec=loss(learned_range=1)))
+    for h in H.values():
+        L.dsd_destroy(h)
+    return out
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--out")
 ap.add_argument("--compare", nargs=2)
 ap.add_argument("--json")
 ap.add_argument("--commit", default="", help="label stored in the output (the commit the checkout is at)")
+ap.add_argument("--schedules", action="store_true", help="the DPM builders' host arrays (no GPU)")
+ap.add_argument("--refusals", action="store_true", help="the loops' refusal messages on table-only handles (no GPU)")
 args = ap.parse_args()
 if args.compare:
     sys.exit(compare(args.compare[0], args.compare[1], args.json))
+if args.schedules or args.refusals:
+    cases = schedules() if args.schedules else refusals()
+    json.dump({"commit": args.commit, "cases": cases, "graph_stats": {}}, open(args.out, "w"), indent=1)
+    print(f"{len(cases)} cases -> {args.out}")
+    sys.exit(0)
 
 import numpy as np
 import torch
 from diffusion_models_dsdiff_amd import _lib
-from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, Schedule, run_bpd_loop, run_device_loop, run_invert_loop,
+from diffusion_models_dsdiff_amd._sched import (Guidance, Inpaint, Schedule, Trace, run_bpd_loop, run_device_loop, run_invert_loop,
                                                 run_plms_loop, invert_coefficients)
 from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion import sampler as dsa
 from diffusion_models_dsdiff_amd.Disc_diff.guided_diffusion.script_util import create_gaussian_diffusion
@@ -63,6 +414,9 @@ from diffusion_models_dsdiff_amd.trainers.trainer_ddpm import DDPMModel
 from util import golden, fixture_params, randn, cond_image
 import dit_loops_util as U
 import disc_ref as R
+import loss_cases as LC
+import test_loss_gpu as TL          # its network cases: net_env, net_kwargs, product_diffusion
+import test_cond_keys_gpu as CK     # its conditioned UNetModels: env, data, bundle, guidance
 
 _lib.require_gpu(0)
 CASES, STATS = {}, {}
@@ -174,6 +528,60 @@ def one_ddim(tag, unet, xT, c):
     CASES[tag + "_ddim_fed"] = digest(run_device_loop(unet, sched, xT, c, step_noise=randn((STEPS,) + tuple(xT.shape), 41).cuda()))
 
 
+def adaptive_traced(tag, e):
+    """One adaptive trial of order 2 and of order 3, plain and guided; a traced DDIM and a traced PLMS run."""
+    unet, xT, c = e["unet"], e["xT"], e["c"]
+    u = torch.zeros_like(c)
+    ns = dsa.NoiseScheduleVP("discrete", betas=e["m"].betas.detach().float().cpu())
+    fn = dsa.model_wrapper(e["wrap"], ns, model_type="v", model_kwargs=dict(c_concat=[c]))
+    sol = dsa.DPM_Solver(fn, ns, algorithm_type="dpmsolver++", correcting_x0_fn="dynamic_thresholding")
+    s = torch.ones((1,))
+    t = ns.inverse_lambda(ns.marginal_lambda(s) + 0.05)
+    for order in (2, 3):
+        prog, lower = sol.adaptive_trial_program(s, t, order)
+        for name, g in (("", None), ("_guided", Guidance(u, 3.0, order))):
+            with dsa.AdaptiveTrial(fn, xT, order, g) as trial:
+                CASES[f"{tag}_adaptive_trial_o{order}{name}"] = digest(*trial.run(prog, lower, 0.0078, 0.05, xT, xT))
+    z = randn((STEPS,) + tuple(xT.shape), 33).cuda()
+    sm = DDIMSampler(e["m"])
+    sm.make_schedule(STEPS, ddim_eta=1.0, verbose=False)
+    tr = Trace(range(0, STEPS, 3))
+    CASES[f"{tag}_ddim_traced"] = digest(run_device_loop(unet, sm._schedule(False, True), xT, c, step_noise=z, trace=tr), tr.x, tr.pred_x0)
+    keep, e["m"].parameterization = e["m"].parameterization, "eps"
+    p = PLMSSampler(e["m"])
+    p.make_schedule(STEPS, verbose=False)
+    plms = p._schedule()
+    e["m"].parameterization = keep
+    tr = Trace([0, 1, STEPS - 1])
+    CASES[f"{tag}_plms_traced"] = digest(run_plms_loop(unet, plms, xT, c, guidance=Guidance(u, 2.0, STEPS), trace=tr), tr.x, tr.pred_x0)
+
+
+def losses(tag):
+    """dsd_eval_loss behind training_losses on every network case of tests/loss_cases.py, fed and Philox noise."""
+    for name, nc in LC.NET_CASES.items():
+        model, unet, x_start, planes, z, t, ctx = TL.net_env(name)
+        unet.use_graph(tag.endswith("1"))
+        d = TL.product_diffusion(nc)
+        for noise, kw in (("fed", dict(noise=z)), ("philox", dict(seed=77))):
+            got = d.training_losses(model, x_start, t, model_kwargs=TL.net_kwargs(nc, planes, ctx), **kw)
+            CASES[f"{tag}_loss_{name}_{noise}"] = digest(*[got[k] for k in sorted(got)])
+
+
+def conditioned(tag):
+    """A latent DDIM run with a context beside a 'concat' part (hybrid), with a context and int labels (crossattn-adm) and with a
+    vector label alone (adm), each plain and guided."""
+    for name in ("hybrid", "crossattn-adm", "adm"):
+        e = CK.env(name)
+        e["unet"].use_graph(tag.endswith("1"))
+        xT, c, u = CK.data(e)
+        sched = CK.ddim_sampler(e, steps=STEPS, eta=1.0)._schedule(False, True)
+        z = CK.noise(xT, STEPS)
+        CASES[f"{tag}_cond_{name}"] = digest(run_device_loop(e["unet"], sched, xT, CK.bundle(e, c), step_noise=z))
+        if name != "adm":                                                       # adm: the unconditional dict equals the conditional
+            CASES[f"{tag}_cond_{name}_guided"] = digest(run_device_loop(e["unet"], sched, xT, CK.bundle(e, c), step_noise=z,
+                                                                        guidance=CK.guidance(e, c, u, 3.0, STEPS)))
+
+
 pix, lat = pix_env(), lat_env()
 keep, lat["m"].parameterization = lat["m"].parameterization, "eps"       # B_DDPM rows of an eps-model: the tables are the betas' alone
 ddpm = lat["m"]._schedule(STEPS)
@@ -193,6 +601,10 @@ for graph in (0, 1):
     loops(f"lat_graph{graph}", lat, ddpm)
     one_ddim(f"dit_graph{graph}", dit, dit_x, dit_c)
     one_ddim(f"disc_graph{graph}", disc, disc_x, disc_c)
+    adaptive_traced(f"pix_graph{graph}", pix)
+    adaptive_traced(f"lat_graph{graph}", lat)
+    losses(f"graph{graph}")
+    conditioned(f"graph{graph}")
     for name, net in (("pix", pix["unet"]), ("lat", lat["unet"]), ("dit", dit), ("disc", disc)):
         st = net.graph_stats()
         STATS[f"{name}_graph{graph}"] = [st["captures"], st["launches"]]
