@@ -9,11 +9,9 @@
 // exchange with lane^32 (wavefront-level, no LDS).  exp(S^T) is already in the B-operand layout of the
 // second product O^T = V^T P^T, so P never leaves registers; V^T fragments are conflict-free ds_read_b32.
 // The head dim is zero-padded to a multiple of 32 (DT tiles); keys beyond Tk are masked to -inf.
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int DT>
 __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------------
 // The same flash attention on the bf16 matrix cores with the fp32 operands split EXACTLY into three bf16 pieces (the
-// bf16x6 arithmetic of conv_split.hip: a1b1 + a1b2 + a2b1 + a2b2 + a1b3 + a3b1, fp32 accumulation, dropped terms <= 2^-24):
+// bf16x6 arithmetic of device_common.h: split8 / mfma6, fp32 accumulation, dropped terms <= 2^-24):
 // 24 v_mfma_f32_32x32x16_bf16 (768 matrix-pipe cycles) per 32 keys at d = 32 instead of 32 v_mfma_f32_32x32x2_f32 (2048).
 //   * Q (pre-scaled, base-2 logits) is split once into registers in the B-operand layout (lane = query, 8 consecutive d per
 //     k-step).
@@ -172,48 +170,6 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 //   * Softmax as in attention16.hip: base-2 logits, the negated running maximum is the C operand of the first S^T MFMA
 //     (p = exp2(acc), one v_exp_f32), the maximum only moves when a score exceeds it by more than 2^8 (wave-uniform branch;
 //     O, l and the pending tile are rescaled together before the tile is exponentiated).
-typedef __bf16 abf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int au32x4 __attribute__((ext_vector_type(4)));
-typedef short as16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned a_pk(float x, float y) {
-    abf16x2 t;
-    t[0] = (__bf16)x;
-    t[1] = (__bf16)y;
-    return __builtin_bit_cast(unsigned, t);
-}
-__device__ __forceinline__ float a_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float a_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-// 8 fp32 -> three bf16x8 pieces
-__device__ __forceinline__ void a_split8(const float (&v0)[8], abf16x8 (&out)[3]) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = v0[i];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        au32x4 w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned pk = a_pk(v[2 * i], v[2 * i + 1]);
-            w[i] = pk;
-            if (q < 2) {
-                v[2 * i] -= a_lo(pk);
-                v[2 * i + 1] -= a_hi(pk);
-            }
-        }
-        out[q] = __builtin_bit_cast(abf16x8, w);
-    }
-}
-__device__ __forceinline__ void a_mfma6(const abf16x8 (&a)[3], const abf16x8 (&b)[3], f32x16& c) {   // smallest terms first
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-}
-
 template <int NKS>
 __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(AttnArgs a) {
     constexpr int KEYS = 64;                 // keys per LDS stage = two 32-key sub-tiles
@@ -235,10 +191,10 @@ __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(
     const bool q_ok = q < a.Tq;
     const int hch = (a.d + 7) >> 3;          // chunk slots that hold data (head dim % 4 == 0: a chunk may be half valid)
 
-    for (int i = tid * 16; i < 3 * KPC + 3 * VPC; i += 256 * 16) *reinterpret_cast<au32x4*>(lds + i) = au32x4{0u, 0u, 0u, 0u};
+    for (int i = tid * 16; i < 3 * KPC + 3 * VPC; i += 256 * 16) *reinterpret_cast<u32x4*>(lds + i) = u32x4{0u, 0u, 0u, 0u};
 
     // Q pieces (B operand): this lane's query, k-step s covers d = 16 s + 8 half .. + 8; scores come out as base-2 logits
-    abf16x8 qf[NKS][3];
+    bf16x8 qf[NKS][3];
     {
         const float qs = a.scale_q * a.scale_s * LOG2E;
         const float* qp = a.q + ((int64_t)n * a.Tq + (q_ok ? q : 0)) * a.ldq + (int64_t)head * a.q_hs;
@@ -252,7 +208,7 @@ __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(
                 if (q_ok && d < a.d) t = *reinterpret_cast<const float4*>(qp + d);
                 v[i] = t.x * qs; v[i + 1] = t.y * qs; v[i + 2] = t.z * qs; v[i + 3] = t.w * qs;
             }
-            a_split8(v, qf[s]);
+            split8(v, qf[s]);
         }
     }
     f32x16 o[DT];
@@ -304,15 +260,15 @@ __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(
                 const float kv[8] = {kreg[j][0].x * a.scale_k, kreg[j][0].y * a.scale_k, kreg[j][0].z * a.scale_k, kreg[j][0].w * a.scale_k,
                                      kreg[j][1].x * a.scale_k, kreg[j][1].y * a.scale_k, kreg[j][1].z * a.scale_k, kreg[j][1].w * a.scale_k};
                 const float vv[8] = {vreg[j][0].x, vreg[j][0].y, vreg[j][0].z, vreg[j][0].w, vreg[j][1].x, vreg[j][1].y, vreg[j][1].z, vreg[j][1].w};
-                abf16x8 kp[3], vp[3];
-                a_split8(kv, kp);
-                a_split8(vv, vp);
+                bf16x8 kp[3], vp[3];
+                split8(kv, kp);
+                split8(vv, vp);
                 const int ko = (c >> 1) * KPL + ((kr * 32 + (c & 1) * 16) ^ (((kr >> 3) & 1) << 4));
                 const int vo = (c >> 2) * VPL + kr * 64 + (c & 3) * 16;
 #pragma unroll
                 for (int pq = 0; pq < 3; ++pq) {
-                    *reinterpret_cast<abf16x8*>(Kl + pq * KPC + ko) = kp[pq];
-                    *reinterpret_cast<abf16x8*>(Vl + pq * VPC + vo) = vp[pq];
+                    *reinterpret_cast<bf16x8*>(Kl + pq * KPC + ko) = kp[pq];
+                    *reinterpret_cast<bf16x8*>(Vl + pq * VPC + vo) = vp[pq];
                 }
             }
         }
@@ -325,10 +281,10 @@ __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(
             f32x16 sacc = negm;
 #pragma unroll
             for (int s = 0; s < NKS; ++s) {
-                abf16x8 kp[3];
+                bf16x8 kp[3];
 #pragma unroll
-                for (int pq = 0; pq < 3; ++pq) kp[pq] = *reinterpret_cast<const abf16x8*>(Kl + pq * KPC + s * KPL + sub * 1024 + kofs);
-                a_mfma6(kp, qf[s], sacc);
+                for (int pq = 0; pq < 3; ++pq) kp[pq] = *reinterpret_cast<const bf16x8*>(Kl + pq * KPC + s * KPL + sub * 1024 + kofs);
+                mfma6(kp, qf[s], sacc);
             }
             if (k0 + sub * 32 + 32 > a.Tk) {   // last, partial sub-tile: keys beyond Tk take no part
 #pragma unroll
@@ -367,27 +323,27 @@ __global__ __launch_bounds__(256, NKS <= 4 ? 2 : 1) void attention_split_kernel(
             }
             l_run += psum;
             // O^T[d][q] += sum_key V[key][d] P[key][q];  k-step s2 = registers 8 s2 .. 8 s2 + 7 of P, split exactly into 3 pieces
-            abf16x8 pf[2][3];
+            bf16x8 pf[2][3];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 float v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = sacc[8 * s2 + e];
-                a_split8(v, pf[s2]);
+                split8(v, pf[s2]);
             }
 #pragma unroll
             for (int t = 0; t < DT; ++t) {
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    abf16x8 vp[3];
+                    bf16x8 vp[3];
 #pragma unroll
                     for (int pq = 0; pq < 3; ++pq) {
                         const unsigned char* vq = Vl + pq * VPC + t * VPL + sub * 2048 + s2 * 1024 + vofs;
-                        const as16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as16x4*)(vq));
-                        const as16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as16x4*)(vq + 512));
-                        vp[pq] = __builtin_bit_cast(abf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vq));
+                        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vq + 512));
+                        vp[pq] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
                     }
-                    a_mfma6(vp, pf[s2], o[t]);
+                    mfma6(vp, pf[s2], o[t]);
                 }
             }
         }

@@ -23,34 +23,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
 
 namespace a16 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct AF;
-template <>
-struct AF<_Float16> {
-    using v8 = f16x8;
-    using v4 = f16x4;
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct AF<__bf16> {
-    using v8 = bf16x8;
-    using v4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
 
 struct A16P {
     const void *q, *k, *v;
@@ -66,7 +43,7 @@ struct A16P {
 // second product (no V reads, no P V MFMAs), 8 no first product (no K reads, no Q K^T MFMAs)
 template <typename T16, int NKS, int WI = 0>
 __global__ __launch_bounds__(256, 2) void attention16_kernel(A16P a) {
-    using F = AF<T16>;
+    using F = Piece<T16>;
     constexpr int KEYS = 64;
     constexpr int DT = (NKS + 1) / 2;        // 32-wide d tiles of O^T
     constexpr int CH = 2 * NKS;              // 16-byte chunk slots per key row (K side)
@@ -295,7 +272,6 @@ __global__ __launch_bounds__(256, 2) void attention16_kernel(A16P a) {
 // LDS read may alias a DMA still in flight and waits for the older tile at the top of each tile — the counted vmcnt below is the
 // only wait these need.  M0 (the LDS destination) is written in the same statement and restored; rsrc / soffset / M0 come from
 // readfirstlane, hence the leading s_nop (cdna_hip_programming.md "What hipcc does not do").
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 static __device__ __forceinline__ void dma16h(i32x4 rsrc, unsigned lds_addr, unsigned voff, int soff) {
     unsigned keep;
     asm volatile(
@@ -315,11 +291,10 @@ static __device__ __forceinline__ i32x4 make_rsrc16(const void* base, unsigned b
     r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
     r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));   // (stride 0, no swizzle)
     r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
+    r[3] = RSRC_DWORD3;
     return r;
 }
 
-typedef int v2i __attribute__((ext_vector_type(2)));
 // eight ds_read_b64_tr_b16 (d tile t = 0, 1 x k-step s2 = 0, 1 x key octet j = 0, 1) at a0 / a1 + OFF + (16 s2 + 8 j) * 128 AND the
 // wait for them, in ONE statement.  (The first version issued the reads in front of the softmax and waited in a second statement
 // in front of the second product, to hide their latency behind the softmax of the same wave.  hipcc does not know that the
@@ -327,7 +302,7 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 // between the two statements and reused them for v_exp results — non-finite output, caught by tests/test_half_gpu.py.  One
 // statement leaves no live range to tamper with; the latency is covered by the other three waves of the SIMD.)
 template <int OFF>
-static __device__ __forceinline__ void tr_read8(v2i (&r)[2][2][2], unsigned a0, unsigned a1) {
+static __device__ __forceinline__ void tr_read8(i32x2 (&r)[2][2][2], unsigned a0, unsigned a1) {
     asm volatile(
         "ds_read_b64_tr_b16 %0, %8 offset:%10\n\t"
         "ds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
@@ -352,7 +327,7 @@ static __device__ __forceinline__ void tr_read8(v2i (&r)[2][2][2], unsigned a0, 
 // registers): 944 us, between the two.
 template <typename T16, int WI = 0, int NW = 4, int QW = 1>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attention16_dma_kernel(A16P a) {   // (second argument = waves per SIMD: 8 waves in 128 registers, two workgroups per CU)
-    using F = AF<T16>;
+    using F = Piece<T16>;
     constexpr int KEYS = 64, NKS = 4, DT = 2, QPB = 32 * NW * QW, PJ = 8 / NW;   // queries per block; K (and V) pieces per wave and tile
     constexpr int STG = 2 * KEYS * 128;   // K | V
     __shared__ __attribute__((aligned(1024))) unsigned char lds[3 * STG];
@@ -399,8 +374,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attention16_dma_kern
 #pragma unroll
         for (int j = 0; j < PJ; ++j) {
             const bool ok = !tail || k0 + pkey + 32 * j < a.Tk;
-            dma16h(rk, base + j * 4096, ok ? kvo[j] : 0xFFFFFFF0u, sk);
-            dma16h(rv, base + KEYS * 128 + j * 4096, ok ? vvo[j] : 0xFFFFFFF0u, sv);
+            dma16h(rk, base + j * 4096, ok ? kvo[j] : OOB, sk);
+            dma16h(rv, base + KEYS * 128 + j * 4096, ok ? vvo[j] : OOB, sv);
         }
     };
     const int NT = (a.Tk + KEYS - 1) / KEYS;
@@ -563,7 +538,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attention16_dma_kern
             // the eight transposed V fragments of this sub-tile (inline asm: hipcc puts s_waitcnt vmcnt(0) in front of the
             // ds_read_tr BUILTIN when LDS-DMA is in flight — it cannot tell the stages apart — which would serialise the tile
             // behind the two tiles being fetched)
-            v2i vr[DT][2][2];
+            i32x2 vr[DT][2][2];
             if (!(WI & 4)) tr_read8<sub * 32 * 128>(vr, sl_addr + vofs[0], sl_addr + vofs[1]);
             if (WI & 4) {
 #pragma unroll

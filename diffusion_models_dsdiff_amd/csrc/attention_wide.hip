@@ -22,19 +22,14 @@
 //     O^T beyond d are never stored.  K and V addresses past the head dim or past Tk are therefore CLAMPED to the last
 //     valid element rather than zero-filled: what they fetch is multiplied by an exact zero or lands in an unwritten row
 //     (as in the narrow kernels, a non-finite input poisons its head either way).
-// Two arithmetics, as the narrow kernels: exact fp32 MFMA (split == 0) and bf16x6 (split == 1: a_split8 / a_mfma6 of
-// attention.hip restated).
-#include "kernels.h"
+// Two arithmetics, as the narrow kernels: exact fp32 MFMA (split == 0) and bf16x6 (split == 1: split8 / mfma6 of
+// device_common.h).
+#include "device_common.h"
 
 namespace dsd {
 
-typedef float wf32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 wbf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
-
 // S = ((p0 + p1) + p2) + p3 of the four waves' partial tiles; xs is this sub-tile's buffer [wave][register][lane].
-__device__ __forceinline__ void w_exchange(float* xs, int wave, int lane, wf32x16& sacc) {
+__device__ __forceinline__ void w_exchange(float* xs, int wave, int lane, f32x16& sacc) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) xs[(wave * 16 + r) * 64 + lane] = sacc[r];
     __syncthreads();
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(256, 1) void attention_wide_kernel(AttnArgs a) {
             qf[i + 3] = v.w * a.scale_q;
         }
     }
-    wf32x16 o[DT];
+    f32x16 o[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(256, 1) void attention_wide_kernel(AttnArgs a) {
             for (int s = 0; s < 16; ++s) vf[t][s] = vtile[(unsigned)min((s & 3) + 8 * (s >> 2) + 4 * half, klast) * (unsigned)a.ldv + dcl];
         }
         // partial S^T[key][q] = sum over this wave's d of K[key][d] Q[q][d]
-        wf32x16 sacc;
+        f32x16 sacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
@@ -167,43 +162,6 @@ __global__ __launch_bounds__(256, 1) void attention_wide_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------------------------------------
 // bf16x6: operands split exactly into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation;
 // base-2 logits and the optimistic running maximum of attention_split_kernel.
-__device__ __forceinline__ unsigned w_pk(float x, float y) {
-    wbf16x2 t;
-    t[0] = (__bf16)x;
-    t[1] = (__bf16)y;
-    return __builtin_bit_cast(unsigned, t);
-}
-__device__ __forceinline__ float w_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float w_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-// 8 fp32 -> three bf16x8 pieces
-__device__ __forceinline__ void w_split8(const float (&v0)[8], wbf16x8 (&out)[3]) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = v0[i];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        wu32x4 w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned pk = w_pk(v[2 * i], v[2 * i + 1]);
-            w[i] = pk;
-            if (q < 2) {
-                v[2 * i] -= w_lo(pk);
-                v[2 * i + 1] -= w_hi(pk);
-            }
-        }
-        out[q] = __builtin_bit_cast(wbf16x8, w);
-    }
-}
-__device__ __forceinline__ void w_mfma6(const wbf16x8 (&a)[3], const wbf16x8 (&b)[3], wf32x16& c) {   // smallest terms first
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-}
-
 template <int DT>
 __global__ __launch_bounds__(256, 1) void attention_wide_split_kernel(AttnArgs a) {
     constexpr int SW = DT * 32;   // this wave's slice of the (padded) head dim
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void attention_wide_split_kernel(AttnArgs a
     const int dbase = wave * SW;
 
     // Q pieces (B operand): this lane's query, k-step s covers d = dbase + 16 s + 8 half .. + 8; base-2 logits
-    wbf16x8 qf[NKS][3];
+    bf16x8 qf[NKS][3];
     {
         const float qs = a.scale_q * a.scale_s * LOG2E;
         const float* qp = a.q + ((int64_t)n * a.Tq + (q_ok ? q : 0)) * a.ldq + (int64_t)head * a.q_hs;
@@ -233,10 +191,10 @@ __global__ __launch_bounds__(256, 1) void attention_wide_split_kernel(AttnArgs a
                 if (q_ok && d < a.d) t = *reinterpret_cast<const float4*>(qp + d);
                 v[i] = t.x * qs; v[i + 1] = t.y * qs; v[i + 2] = t.z * qs; v[i + 3] = t.w * qs;
             }
-            w_split8(v, qf[s]);
+            split8(v, qf[s]);
         }
     }
-    wf32x16 o[DT];
+    f32x16 o[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -277,16 +235,16 @@ __global__ __launch_bounds__(256, 1) void attention_wide_split_kernel(AttnArgs a
                     vf[t][s2][j] = vtile[(unsigned)min(16 * s2 + 4 * half + (j & 3) + 8 * (j >> 2), klast) * (unsigned)a.ldv + dcl];
         }
         // partial S^T[key][q] = sum over this wave's d of K[key][d] Q[q][d]
-        wf32x16 sacc;
+        f32x16 sacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < NKS; ++s) {
             const float kv[8] = {kreg[s][0].x * a.scale_k, kreg[s][0].y * a.scale_k, kreg[s][0].z * a.scale_k, kreg[s][0].w * a.scale_k,
                                  kreg[s][1].x * a.scale_k, kreg[s][1].y * a.scale_k, kreg[s][1].z * a.scale_k, kreg[s][1].w * a.scale_k};
-            wbf16x8 kp[3];
-            w_split8(kv, kp);
-            w_mfma6(kp, qf[s], sacc);
+            bf16x8 kp[3];
+            split8(kv, kp);
+            mfma6(kp, qf[s], sacc);
         }
         if (k0 + 32 < a.Tk) fetch_k(k0 + 32);
         w_exchange(xs + buf * (4 * 16 * 64), wave, lane, sacc);
@@ -322,21 +280,21 @@ __global__ __launch_bounds__(256, 1) void attention_wide_split_kernel(AttnArgs a
         }
         l_run += psum;
         // O^T[d][q] += sum_key V[key][d] P[key][q];  k-step s2 = registers 8 s2 .. 8 s2 + 7 of P, split exactly into 3 pieces
-        wbf16x8 pf[2][3];
+        bf16x8 pf[2][3];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = sacc[8 * s2 + e];
-            w_split8(v, pf[s2]);
+            split8(v, pf[s2]);
         }
 #pragma unroll
         for (int t = 0; t < DT; ++t)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                wbf16x8 vp[3];
-                w_split8(vf[t][s2], vp);
-                w_mfma6(vp, pf[s2], o[t]);
+                bf16x8 vp[3];
+                split8(vf[t][s2], vp);
+                mfma6(vp, pf[s2], o[t]);
             }
     }
     if (!q_ok) return;

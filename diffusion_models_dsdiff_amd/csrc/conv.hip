@@ -22,15 +22,13 @@
 //   LDS writes 147, i.e. the flat kernel lost 12 % to address arithmetic / branches in the load phase;
 //   buffer loads 143 (91 % of the 157.3 TF/s fp32 matrix peak).  A double-buffered BK=16 / one-barrier
 //   variant and an accumulator-interleaved MFMA order were tried and are not faster (142 / 127).
-#include "kernels.h"
+#include "device_common.h"
 
 #include <string>
 
 #include <cstdlib>
 
 namespace dsd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static constexpr size_t DIRECT_LDS_MAX = 128 * 1024;   // weights of the small-K direct kernel, [K][Cout] fp32 in LDS
 static constexpr int BM = 128;
@@ -267,17 +265,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 // the hardware range check instead of exec-masked branches for padding / ragged rows (an out-of-range offset returns
 // zeros).  The flat-load kernel spends ~12 % of its time issuing address arithmetic and branches (tools/bench_conv.py
 // diagnostics); this one issues 9 loads and two scalar adds per tile.  Needs Cin % 32 == 0 and < 4 GiB operands.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-static constexpr unsigned OOB = 0xFFFFFFF0u;
-
 template <int NT>
 __global__ __launch_bounds__(256, 2) void conv_mfma_buf_kernel(ConvP p) {
     __shared__ __attribute__((aligned(16))) float lds[(BM + NT * 32) * LDS_STRIDE];
     float* As = lds;
     float* Bs = lds + BM * LDS_STRIDE;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;

@@ -31,7 +31,8 @@ __device__ __forceinline__ float row_sum16(float v) {
     return v;
 }
 
-__device__ __forceinline__ float silu_f(float v) {
+// hardware exp2 / reciprocal, ~1 ulp each: faster than device_common.h's exact silu_f and NOT bit-equal to it
+__device__ __forceinline__ float silu_fast_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
 }
 
@@ -86,10 +87,10 @@ __global__ __launch_bounds__(256, 3) void conv_out1_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 float4 a;
-                a.x = silu_f(fmaf(v[u][j].x, sc[j].x, sh[j].x));
-                a.y = silu_f(fmaf(v[u][j].y, sc[j].y, sh[j].y));
-                a.z = silu_f(fmaf(v[u][j].z, sc[j].z, sh[j].z));
-                a.w = silu_f(fmaf(v[u][j].w, sc[j].w, sh[j].w));
+                a.x = silu_fast_f(fmaf(v[u][j].x, sc[j].x, sh[j].x));
+                a.y = silu_fast_f(fmaf(v[u][j].y, sc[j].y, sh[j].y));
+                a.z = silu_fast_f(fmaf(v[u][j].z, sc[j].z, sh[j].z));
+                a.w = silu_fast_f(fmaf(v[u][j].w, sc[j].w, sh[j].w));
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {
                     const float4 wk = wl[k * (C / 4) + 16 * j + wlane];

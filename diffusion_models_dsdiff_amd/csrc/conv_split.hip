@@ -1,12 +1,8 @@
 // conv_split.hip — the same implicit-GEMM convolution on the bf16 matrix cores with fp32 operands SPLIT into bf16 pieces.
 //
-// gfx950 has no TF32/xf32; its fp32-input MFMA runs at 1/16 of the bf16 rate.  An fp32 value is written exactly as a sum
-// of three bf16 values (8 + 8 + 8 significand bits): a = a1 + a2 + a3, w = w1 + w2 + w3.  With fp32 accumulation
-//   bf16x6:  a1w1 + a1w2 + a2w1 + a2w2 + a1w3 + a3w1   drops only terms <= 2^-24 |a w|  -> fp32-grade result
-//            (measured on the CPU oracle: 9e-7 rel-L2 on the full network's output, the same as fp32 re-ordering noise)
-//   bf16x3:  a1w1 + a1w2 + a2w1                         drops terms ~2^-16..2^-17 |a w| -> 1.5e-5 on the network output
-// at 6 (resp. 3) v_mfma_f32_32x32x16_bf16 per 16 k instead of 8 v_mfma_f32_32x32x2_f32: 2.67x (5.3x) fewer matrix-pipe
-// cycles.  Weights are split once at upload (split_weights); activations are split while they are staged into LDS.
+// The arithmetic (exact split into three 16-bit pieces, six or three products, smallest terms first) is described and
+// defined once, in device_common.h.  Weights are split once at upload (split_weights); activations are split while they
+// are staged into LDS.
 //
 // Structures measured (tools/bench_conv.py, tools/ab_conv.sh; 16x256x256x320->320, bf16x6 / bf16x3 TF/s of fp32-equivalent
 // work): both operands staged through LDS 196 / 333 (conv_split_kernel); activations read straight into registers
@@ -75,15 +71,10 @@ __global__ void split_weights_kernel(const float* __restrict__ w, int64_t n, int
         float r = w[i];
         if (f16 && ovf && !(fabsf(r) <= 65504.f)) *ovf = 1;
         for (int q = 0; q < np; ++q) {
-            if (f16) {
-                const _Float16 b = (_Float16)r;
-                planes[(int64_t)q * n + i] = __builtin_bit_cast(unsigned short, b);
-                r -= (float)b;
-            } else {
-                const __bf16 b = (__bf16)r;
-                planes[(int64_t)q * n + i] = __builtin_bit_cast(unsigned short, b);
-                r -= (float)b;
-            }
+            if (f16)
+                store_piece<_Float16>(planes, (int64_t)q * n + i, r);
+            else
+                store_piece<__bf16>(planes, (int64_t)q * n + i, r);
         }
     }
 }
@@ -110,11 +101,7 @@ __global__ void subpixel_weights_kernel(const float* __restrict__ w, int Cout, i
         for (int kh = 0; kh < 3; ++kh)
             for (int kw = 0; kw < 3; ++kw)
                 if (subpixel_tap(py, kh) == ta && subpixel_tap(px, kw) == tb) acc += (double)w[((int64_t)co * 9 + kh * 3 + kw) * Cin + ci];
-        for (int q = 0; q < 3; ++q) {
-            const __bf16 b = (__bf16)(float)acc;
-            planes[(int64_t)q * n + e] = __builtin_bit_cast(unsigned short, b);
-            acc -= (double)(float)b;
-        }
+        for (int q = 0; q < 3; ++q) store_piece<__bf16>(planes, (int64_t)q * n + e, acc);
     }
 }
 

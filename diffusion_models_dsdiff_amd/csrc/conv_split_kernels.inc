@@ -3,7 +3,7 @@
 // (the diagnostic ones: clock stamps / what-if builds), so that the two compile side by side.  The design notes are at the
 // top of conv_split.hip.
 #pragma once
-#include "kernels.h"
+#include "device_common.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -11,17 +11,9 @@
 
 namespace dsd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 static constexpr int SBM = 128;
 static constexpr int SBK = 32;
 static constexpr int RSB = 80;  // LDS row stride in bytes (64 B of bf16 + 16 B pad)
-static constexpr unsigned OOB = 0xFFFFFFF0u;
 
 struct SplitP {
     const float* x;
@@ -46,58 +38,6 @@ struct SplitP {
     const float* gn_shift;
     int sub_cout;   // sub-pixel instantiation: output channels; Cout is then 4 x sub_cout, the GEMM columns (phase, channel)
 };
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// Piece element type: bf16 (8 significand bits, fp32's exponent range) or fp16 (11 bits, range +-65504).
-template <bool F16> struct Elt;
-template <> struct Elt<false> {
-    typedef bf16x8 v8;
-    static __device__ __forceinline__ unsigned pk(float a, float b) {
-        bf16x2 t;
-        t[0] = (__bf16)a;
-        t[1] = (__bf16)b;
-        return __builtin_bit_cast(unsigned, t);
-    }
-    static __device__ __forceinline__ float lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-    static __device__ __forceinline__ float hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Elt<true> {
-    typedef f16x8 v8;
-    static __device__ __forceinline__ unsigned pk(float a, float b) {
-        f16x2 t;
-        t[0] = (_Float16)a;
-        t[1] = (_Float16)b;
-        return __builtin_bit_cast(unsigned, t);
-    }
-    static __device__ __forceinline__ float lo(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-    static __device__ __forceinline__ float hi(unsigned p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// split 4 fp32 into NP bf16 pieces each; out[p] = 4 packed bf16 (8 bytes)
-template <int NP, bool F16 = false>
-__device__ __forceinline__ void split4(f32x4 v, u32x2 (&out)[NP], int* ovf = nullptr) {
-    float a = v.x, b = v.y, c = v.z, d = v.w;
-    if (F16 && ovf) {   // fp16 pieces cannot hold |x| > 65504: flag it instead of silently producing inf
-        const float m = fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d)));
-        if (!(m <= 65504.f)) *ovf = 1;
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const unsigned p01 = Elt<F16>::pk(a, b), p23 = Elt<F16>::pk(c, d);
-        out[p].x = p01;
-        out[p].y = p23;
-        if (p + 1 < NP) {
-            a -= Elt<F16>::lo(p01);
-            b -= Elt<F16>::hi(p01);
-            c -= Elt<F16>::lo(p23);
-            d -= Elt<F16>::hi(p23);
-        }
-    }
-}
 
 // ---- accumulators -> memory: bias + per-(sample,channel) embedding + residual (same fusion as the fp32 kernel)
 // STATS: the GroupNorm statistics of the tensor being written.  Every stored value v of this lane's (up to) 16 rows of a
@@ -299,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(SplitP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[NP * (A_PLANE + B_PLANE)];
     unsigned char* As = lds;
     unsigned char* Bs = lds + NP * A_PLANE;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -402,18 +342,6 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(SplitP p) {
     const unsigned char* a_frag = As + (wave * 32 + lrow) * RSB + half * 16;
     const unsigned char* b_frag = Bs + lrow * RSB + half * 16;
 
-    auto mfma_group = [&](const bf16x8 (&a)[NP], const bf16x8 (&b)[NP], f32x16& c) {
-        // smallest terms first
-        if (NP == 3) {
-            c = Elt<F16>::mfma(a[2], b[0], c);
-            c = Elt<F16>::mfma(a[0], b[2], c);
-            c = Elt<F16>::mfma(a[1], b[1], c);
-        }
-        c = Elt<F16>::mfma(a[1], b[0], c);
-        c = Elt<F16>::mfma(a[0], b[1], c);
-        c = Elt<F16>::mfma(a[0], b[0], c);
-    };
-
     // one k-step (16 k) of the staged tile: fragments of group j+1 are read before the MFMAs of group j
     auto kstep = [&](int s) {
         bf16x8 a_cur[NP], b_cur[NP], b_nxt[NP];
@@ -430,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(SplitP p) {
                 for (int q = 0; q < NP; ++q)
                     b_nxt[q] = *reinterpret_cast<const bf16x8*>(b_frag + q * B_PLANE + (j + 1) * 32 * RSB + s * 32);
             }
-            mfma_group(a_cur, b_cur, acc[j]);
+            mfma6(a_cur, b_cur, acc[j]);
 #pragma unroll
             for (int q = 0; q < NP; ++q) b_cur[q] = b_nxt[q];
         }
@@ -483,29 +411,10 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(SplitP p) {
 // fragment straight from global memory (2 x 16 B per k-step), splits it into bf16 pieces in registers and feeds the MFMA.
 // Only the weight tile (shared by the four waves) is staged through LDS.  This removes 24 KB of LDS writes and 24 KB of LDS
 // reads per block tile (LDS was 42 % busy with 30 % of that in bank conflicts in the staged kernel, PMC).
-template <int NP, bool F16>
-__device__ __forceinline__ void split8(f32x4 lo, f32x4 hi, typename Elt<F16>::v8 (&out)[NP], int* ovf) {
-    typedef typename Elt<F16>::v8 bf16x8;
-    u32x2 pl[NP], ph[NP];
-    split4<NP, F16>(lo, pl, ovf);
-    split4<NP, F16>(hi, ph, ovf);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        u32x4 v;
-        v.x = pl[q].x; v.y = pl[q].y; v.z = ph[q].x; v.w = ph[q].y;
-        out[q] = __builtin_bit_cast(bf16x8, v);
-    }
-}
-
-// (target builtins behind __device__ functions: see lds_dma16)
+// (target builtins behind __device__ functions: see lds_dma16, device_common.h)
 static __device__ __forceinline__ long long clock_core() { return (long long)__builtin_amdgcn_s_memtime(); }
 static __device__ __forceinline__ long long clock_100mhz() { return (long long)__builtin_amdgcn_s_memrealtime(); }
 static __device__ __forceinline__ void wait_all() { __builtin_amdgcn_s_waitcnt(0); }
-// 16 B per lane from a buffer resource straight into LDS (lane-linear from the wave-uniform `lds`).  A __device__ function of
-// its own: the target builtin directly inside a __global__ template makes the HOST pass drop the instantiation silently.
-static __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned char* lds, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)lds, 16, voff, soff, 0, 0);
-}
 
 // RB = 32-row blocks per wave.  RB = 1: block tile 128 x 32*NT, two workgroups per CU.  RB = 2: block tile 256 x 32*NT,
 // ONE workgroup per CU (accumulators alone are 2*NT*16 registers): every weight fragment read from LDS feeds two MFMA
@@ -594,8 +503,8 @@ __device__ __forceinline__ void conv_split_ad_body(SplitP p) {   // (by value: t
     static_assert(!GN || TR, "the fused GroupNorm apply lives in the tap-reuse staging path");
     static_assert((A_OFF + (TR ? 2 * A_STAGE : 0)) * (RB == 1 ? 2 : 1) <= 160 * 1024, "the stages of the resident workgroups must fit the LDS");
     __shared__ __attribute__((aligned(1024))) unsigned char Bs[A_OFF + (TR ? 2 * A_STAGE : 0)];
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -752,16 +661,6 @@ __device__ __forceinline__ void conv_split_ad_body(SplitP p) {   // (by value: t
     const int fsw = (lrow >> 2) & 3;
     const int foff[2] = {DMA ? lrow * RS + ((half ^ fsw) << 4) : lrow * RS + half * 16,
                          DMA ? lrow * RS + (((2 + half) ^ fsw) << 4) : lrow * RS + half * 16 + 32};
-    auto mfma_group = [&](const bf16x8 (&a)[NP], const bf16x8 (&b)[NP], f32x16& c) {
-        if (NP == 3) {
-            c = Elt<F16>::mfma(a[2], b[0], c);
-            c = Elt<F16>::mfma(a[0], b[2], c);
-            c = Elt<F16>::mfma(a[1], b[1], c);
-        }
-        c = Elt<F16>::mfma(a[1], b[0], c);
-        c = Elt<F16>::mfma(a[0], b[1], c);
-        c = Elt<F16>::mfma(a[0], b[0], c);
-    };
 
     // ---- software pipeline over the k-tiles (one barrier per tile, nothing but that barrier and the first fragment
     // read outside the MFMA stream).  While tile kt is multiplied:
@@ -1029,7 +928,7 @@ __device__ __forceinline__ void conv_split_ad_body(SplitP p) {   // (by value: t
                 }
             }
 #pragma unroll
-            for (int r = 0; r < RB; ++r) mfma_group(af[s][r], b_cur, acc[r][j]);
+            for (int r = 0; r < RB; ++r) mfma6(af[s][r], b_cur, acc[r][j]);
 #pragma unroll
             for (int q = 0; q < NP; ++q) b_cur[q] = b_nxt[q];
             __builtin_amdgcn_sched_barrier(0);

@@ -27,8 +27,6 @@
 
 namespace dsd {
 
-typedef float f32x4a __attribute__((ext_vector_type(4)));
-
 template <bool GN>
 __global__ __launch_bounds__(256, 1) void conv_split_tr16_kernel(SplitP p) {
     constexpr int NT = 5, NP = 3, CT = 10;           // CT column tiles of 16
@@ -41,8 +39,8 @@ __global__ __launch_bounds__(256, 1) void conv_split_tr16_kernel(SplitP p) {
     constexpr int A_OFF = 2 * STAGE + 256 * 16;
     static_assert(A_OFF + 2 * A_STAGE <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(1024))) unsigned char Bs[A_OFF + 2 * A_STAGE];
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, quart = lane >> 4;
@@ -124,20 +122,12 @@ __global__ __launch_bounds__(256, 1) void conv_split_tr16_kernel(SplitP p) {
         *reinterpret_cast<u32x4*>(Bs + A_OFF + ((c2 + h2) & 1) * A_STAGE + (i * 256 + tid) * 16) = w;
     };
     u32x4 rb[NBL];
-    f32x4a acc[4][CT];
+    f32x4 acc[4][CT];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int j = 0; j < CT; ++j) acc[r][j] = f32x4a{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < CT; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int foff = l16 * RS + ((quart ^ ((l16 >> 1) & 3)) << 4);   // + piece * B_PLANE + j * 16 * RS
-    auto mfma6 = [&](const bf16x8 (&a)[NP], const bf16x8 (&b)[NP], f32x4a& c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
-    };
 
     const int KT = p.ks * p.ks * p.cchunks;
     int cc = 0, tap = 0, kh = 0, kw = 0;

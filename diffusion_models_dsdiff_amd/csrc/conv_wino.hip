@@ -1,5 +1,5 @@
 // conv_wino.hip — 3x3 stride-1 convolution with HALF the Winograd trick: F(2,3) along the image width only, on the bf16
-// matrix cores with fp32 operands split exactly into three bf16 pieces (the bf16x6 arithmetic of conv_split.hip).
+// matrix cores with fp32 operands split exactly into three bf16 pieces (the bf16x6 arithmetic of device_common.h).
 //
 // 97 % of the network's FLOPs are 3x3 stride-1 convolutions.  Writing two horizontally adjacent outputs of one filter row as
 //     m0 = (d0-d2) g0        m1 = (d1+d2) (g0+g1+g2)/2        m2 = (d2-d1) (g0-g1+g2)/2        m3 = (d1-d3) g2
@@ -23,19 +23,12 @@
 //   * block tile = 128 tiles (256 output pixels) x 128 output channels x 4 positions = 256 accumulator registers per lane,
 //     one workgroup per CU, one barrier per k-tile (16 k of one filter row: 96 MFMAs per wave), two LDS stages.
 //   * k-tile order: filter rows inner, channel chunks outer (a 128-byte line of a pixel is re-read while hot).
-#include "kernels.h"
+#include "device_common.h"
 
 #include <cstdlib>
 
 namespace dsd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-static constexpr unsigned OOB = 0xFFFFFFF0u;
 // 4 positions x 4 column tiles x 16 = 256 accumulator registers = the whole AGPR file (the compiler keeps every MFMA
 // accumulator of a kernel in AGPRs once it uses them at all, so 5 column tiles = 320 spill); a layer whose Cout is not a
 // multiple of 128 gets a narrower LAST N tile whose missing column tiles are simply not multiplied (Cout = 320: 128+128+64)
@@ -64,34 +57,6 @@ struct WinoP {
     int whatif;   // experiments (env DSD_WINO_WHATIF): 1 = no activation loads in the k-loop, 2 = no weight DMA, 4 = no transform/split
 };
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    bf16x2 t;
-    t[0] = (__bf16)a;
-    t[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, t);
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-
-// 8 fp32 (two float4) -> three bf16x8 pieces, a = p0 + p1 + p2 up to 2^-24 |a|
-__device__ __forceinline__ void split8x3(f32x4 lo, f32x4 hi, bf16x8 (&out)[3]) {
-    float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        u32x4 w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned pk = pk_bf16(v[2 * i], v[2 * i + 1]);
-            w[i] = pk;
-            if (q < 2) {
-                v[2 * i] -= bf_lo(pk);
-                v[2 * i + 1] -= bf_hi(pk);
-            }
-        }
-        out[q] = __builtin_bit_cast(bf16x8, w);
-    }
-}
-
 // Measured and removed (round 2): giving the narrow last N tile of TWO neighbouring M tiles to one block, so that every
 // block carries the same MFMA work and the blocks sharing activations stay in step: 228.9 / 240.1 TF/s against 232.1 / 247.4
 // unpaired on 16x256x256x{320,640}->320 — the faster 640-channel layers (267-277) are not faster because their N tiles are
@@ -119,7 +84,7 @@ static constexpr int WLDS = Z_OFF + 64;
 
 template <int NT>
 __device__ __forceinline__ void wino_body(const WinoP& p, unsigned char* Bs) {
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -193,8 +158,7 @@ __device__ __forceinline__ void wino_body(const WinoP& p, unsigned char* Bs) {
         for (int i = 0; i < 4; ++i) {
             const int ih = doh[i] - 1 + kh;
             const unsigned v = (unsigned)ih < (unsigned)p.H ? dcol[i] + (unsigned)(ih >> p.ups) * rowpitch : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (void __attribute__((address_space(3)))*)(Bs + stage_off + (wave * 4 + i) * 1024),
-                                                     16, v, soff, 0, 0);
+            lds_dma16(rx, Bs + stage_off + (wave * 4 + i) * 1024, v, soff);
         }
     };
 
@@ -230,14 +194,6 @@ __device__ __forceinline__ void wino_body(const WinoP& p, unsigned char* Bs) {
         lo = *reinterpret_cast<const f32x4*>(Bs + a0);
         hi = *reinterpret_cast<const f32x4*>(Bs + a1);
     };
-    auto mfma6 = [&](const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& c) {   // smallest terms first
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    };
 
     // ---- prologue: weights of tile 0, activations of tiles 0 and 1; after the barrier U_0 of tile 0 is formed (the only
     // transform that is not hidden behind MFMAs)
@@ -248,7 +204,7 @@ __device__ __forceinline__ void wino_body(const WinoP& p, unsigned char* Bs) {
     f32x4 d1l, d1h, d2l, d2h, xl, xh, yl, yh;
     rd(0, A_BASE, 0, xl, xh);
     rd(2, A_BASE, 0, yl, yh);
-    split8x3(xl - yl, xh - yh, af[0]);
+    split8(xl - yl, xh - yh, af[0]);
 
     // One k-tile = 4 positions x NT units of 6 MFMAs, position-major; the transform of each position runs one position ahead
     // of its products, spread over the units of the position before:
@@ -287,15 +243,15 @@ __device__ __forceinline__ void wino_body(const WinoP& p, unsigned char* Bs) {
                     rd(1, st_cur, kh, d1l, d1h);
                     rd(2, st_cur, kh, d2l, d2h);
                 }
-                if (u == NT - 1) split8x3(d1l + d2l, d1h + d2h, af[1]);
+                if (u == NT - 1) split8(d1l + d2l, d1h + d2h, af[1]);
                 if (u == NT) rd(3, st_cur, kh, xl, xh);
-                if (u == 2 * NT - 1) split8x3(d2l - d1l, d2h - d1h, af[2]);
+                if (u == 2 * NT - 1) split8(d2l - d1l, d2h - d1h, af[2]);
                 if (u == 2 * NT) {
                     rd(0, st_nxt, kh1, yl, yh);
                     rd(2, st_nxt, kh1, d2l, d2h);
                 }
-                if (u == 3 * NT - 1) split8x3(d1l - xl, d1h - xh, af[3]);
-                if (u == 4 * NT - 1) split8x3(yl - d2l, yh - d2h, af[0]);
+                if (u == 3 * NT - 1) split8(d1l - xl, d1h - xh, af[3]);
+                if (u == 4 * NT - 1) split8(yl - d2l, yh - d2h, af[0]);
             }
             mfma6(af[pos], b_cur, acc[pos][j]);
 #pragma unroll
@@ -421,7 +377,7 @@ __global__ void wino_pack_kernel(const float* __restrict__ w, int Cout, int Cin,
         for (int pos = 0; pos < 4; ++pos) {
             float r = v[pos];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
+            for (int q = 0; q < 3; ++q) {   // store_piece (device_common.h) written out: see the note there
                 const __bf16 b = (__bf16)r;
                 base[((q * 4 + pos) * WBROWS + row) * 16 + k] = __builtin_bit_cast(unsigned short, b);
                 r -= (float)b;

@@ -12,14 +12,13 @@
 //   scale  value * gate into the branch's channel slice of cat (and, on request, the eight feature tensors)
 // No atomics and a fixed summation order everywhere: two runs are bit-identical.  All global accesses are 16 bytes wide
 // (half % 4 == 0); the activated values are recomputed by the scale pass instead of stored (one expf against 4 bytes through HBM).
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
 
 namespace {
 
-__device__ __forceinline__ float silu1(float v) { return v / (1.f + expf(-v)); }
-__device__ __forceinline__ float4 silu4(float4 v) { return make_float4(silu1(v.x), silu1(v.y), silu1(v.z), silu1(v.w)); }
+__device__ __forceinline__ float4 silu4(float4 v) { return make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)); }
 
 // what the kernels read of DiscArgs (by value: no array is indexed with a run-time value, so nothing lands in scratch)
 struct DiscK {

@@ -24,53 +24,21 @@
 //   EPI_GATED   x32[m][n] += gate[m / T][n] * round16(acc + bias)                               (x + gate * f(...), fp32 stream)
 #include <cstdlib>
 
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
 
 namespace g16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int GBM = 256, GBN = 256, GBK = 64;
 constexpr int G_TILE_BYTES = GBN * GBK * 2;   // 32 KB per operand and stage
 constexpr int G_EROW = 128 * 2 + 16;          // epilogue staging: a wave's 128 n of one output row + 16 B (bank spread, 16-B aligned)
-
-template <typename T>
-struct Frag;
-template <>
-struct Frag<_Float16> {
-    using v8 = f16x8;
-    using v4 = f16x4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct Frag<__bf16> {
-    using v8 = bf16x8;
-    using v4 = bf16x4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x16 mfma32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
 
 // F.gelu(approximate="tanh") = 0.5 v (1 + tanh(u)), u = sqrt(2/pi) (v + 0.044715 v^3); 0.5 (1 + tanh u) = 1 / (1 + exp(-2u)):
 // one v_exp_f32 and one v_rcp_f32 (the result is rounded to 16 bits right after)
 __device__ __forceinline__ float gelu_tanh_f(float v) {
     const float u2 = -2.f * 0.7978845608028654f * 1.4426950408889634f * (v + 0.044715f * v * v * v);   // -2u log2(e)
     return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(u2));
-}
-
-// 16 B per lane from a buffer resource straight into LDS (lane-linear from the wave-uniform `lds`).  A __device__ function of
-// its own: the target builtin directly inside a __global__ template makes the HOST pass drop the instantiation silently.
-static __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned char* lds, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)lds, 16, voff, soff, 0, 0);
 }
 
 struct G16P {
@@ -99,7 +67,7 @@ struct G16P {
 // keeps the matrix pipe busy meanwhile.
 template <typename T16, int EPI, int WI = 0, bool M32 = false, int LD4 = 0>   // LD4: 1 = loaders issue in a burst, 2 = one piece per 4 MFMAs
 __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
-    using F = Frag<T16>;
+    using F = Piece<T16>;
     // [stage][W tile | X tile]; after the k-loop the same memory transposes the output tile (8 waves x 64 rows x 272 B)
     __shared__ __attribute__((aligned(1024))) unsigned char lds[(4 * G_TILE_BYTES > 8 * 64 * G_EROW) ? 4 * G_TILE_BYTES : 8 * 64 * G_EROW];
 
@@ -124,11 +92,10 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
     // hardware delivers zeros), the k-tile advances through the SCALAR offset — no vector address arithmetic in the loop.
     constexpr int NV = LD4 != 0 ? 2 : 1;                                  // virtual waves staged by this wave (LD4: itself and wave + 4)
     const int rows_w = min(p.N - bn0, GBN), rows_x = min(p.M - bm0, GBM);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const T16*>(p.w) + (int64_t)bn0 * p.K), 0, (unsigned)rows_w * (unsigned)p.K * 2u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxb = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const T16*>(p.x) + (int64_t)bm0 * p.ldx), 0,
-        ((unsigned)(rows_x - 1) * (unsigned)p.ldx + (unsigned)p.K) * 2u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw =
+        make_rsrc(reinterpret_cast<const T16*>(p.w) + (int64_t)bn0 * p.K, (unsigned)rows_w * (unsigned)p.K * 2u);
+    const __amdgpu_buffer_rsrc_t rxb =
+        make_rsrc(reinterpret_cast<const T16*>(p.x) + (int64_t)bm0 * p.ldx, ((unsigned)(rows_x - 1) * (unsigned)p.ldx + (unsigned)p.K) * 2u);
     unsigned wvo[NV][4], xvo[NV][4];
     int schunk[NV];
 #pragma unroll
@@ -138,8 +105,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int r = j * 64 + srow;
-            wvo[v][j] = r < rows_w ? ((unsigned)r * (unsigned)p.K + (unsigned)schunk[v] * 8u) * 2u : 0xFFFFFFF0u;
-            xvo[v][j] = r < rows_x ? ((unsigned)r * (unsigned)p.ldx + (unsigned)schunk[v] * 8u) * 2u : 0xFFFFFFF0u;
+            wvo[v][j] = r < rows_w ? ((unsigned)r * (unsigned)p.K + (unsigned)schunk[v] * 8u) * 2u : OOB;
+            xvo[v][j] = r < rows_x ? ((unsigned)r * (unsigned)p.ldx + (unsigned)schunk[v] * 8u) * 2u : OOB;
         }
     }
     // one DMA piece (q = 0..3: W rows 64 q .., q = 4..7: X rows) of virtual wave v of the k-tile at k0 into stage `buf`
@@ -148,8 +115,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
         const int so = __builtin_amdgcn_readfirstlane(k0 * 2);
         // last, partial k-tile: chunks beyond K are zeros (a row's tail would otherwise read its neighbour's head)
         const bool kok = !tail || k0 + schunk[v] * 8 < p.K;
-        if (q < 4) dma16(rw, base + q * 8192, kok ? wvo[v][q] : 0xFFFFFFF0u, so);
-        else dma16(rxb, base + G_TILE_BYTES + (q - 4) * 8192, kok ? xvo[v][q - 4] : 0xFFFFFFF0u, so);
+        if (q < 4) lds_dma16(rw, base + q * 8192, kok ? wvo[v][q] : OOB, so);
+        else lds_dma16(rxb, base + G_TILE_BYTES + (q - 4) * 8192, kok ? xvo[v][q - 4] : OOB, so);
     };
     auto stage = [&](int buf, int k0) {
         if (LD4 != 0 && wave >= 4) return;                                 // (wave-uniform)
@@ -203,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) c32[i][j] = F::mfma32(a32[ks & 1][i], b32[ks & 1][j], c32[i][j]);
+                    for (int j = 0; j < 2; ++j) c32[i][j] = F::mfma(a32[ks & 1][i], b32[ks & 1][j], c32[i][j]);
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();
@@ -215,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
         const int rows_left32 = min(p.M - bm0, GBM);
         if (EPI == 2) {
             float* xb = p.x32 + (int64_t)bm0 * p.ldx32;
-            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (unsigned)rows_left32 * (unsigned)p.ldx32 * 4u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rx = make_rsrc(xb, (unsigned)rows_left32 * (unsigned)p.ldx32 * 4u);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int m = ml32 + j * 32;
@@ -228,7 +195,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int n = nl32 + i * 32 + g * 8;
-                        const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : 0xFFFFFFF0u;
+                        const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : OOB;
                         xv[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
                         gv[g] = *reinterpret_cast<const f32x4*>(gp + min(n, p.N - 4));
                         bq[g] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + min(n, p.N - 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -236,7 +203,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int n = nl32 + i * 32 + g * 8;
-                        const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : 0xFFFFFFF0u;
+                        const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : OOB;
                         f32x4 r;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) r[e] = fmaf(gv[g][e], (float)(T16)(c32[i][j][4 * g + e] + bq[g][e]), xv[g][e]);
@@ -270,14 +237,14 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
                 }
             }
             T16* yb = reinterpret_cast<T16*>(p.y16) + (int64_t)bm0 * p.ldy;
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)yb, 0, (unsigned)rows_left32 * (unsigned)p.ldy * 2u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ry = make_rsrc(yb, (unsigned)rows_left32 * (unsigned)p.ldy * 2u);
             const int nc = bn0 + wn * 128 + (lane & 15) * 8;
 #pragma unroll
             for (int it = 0; it < 16; ++it) {
                 const int row = it * 4 + (lane >> 4);
                 const int m = bm0 + wm * 64 + row;
                 const u32x4 v = *reinterpret_cast<const u32x4*>(wb + row * G_EROW + (lane & 15) * 16);
-                const unsigned off = (m < p.M && nc < p.N) ? (unsigned)(m - bm0) * (unsigned)p.ldy * 2u + (unsigned)nc * 2u : 0xFFFFFFF0u;
+                const unsigned off = (m < p.M && nc < p.N) ? (unsigned)(m - bm0) * (unsigned)p.ldy * 2u + (unsigned)nc * 2u : OOB;
                 __builtin_amdgcn_raw_buffer_store_b128(v, ry, off, 0, 0);
             }
         }
@@ -356,7 +323,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
     const int rows_left = min(p.M - bm0, GBM);
     if (EPI == 2) {
         float* xb = p.x32 + (int64_t)bm0 * p.ldx32;   // descriptor over this tile's rows only
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (unsigned)rows_left * (unsigned)p.ldx32 * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc(xb, (unsigned)rows_left * (unsigned)p.ldx32 * 4u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int m = ml + j * 16;
@@ -367,14 +334,14 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int n = nl + i * 16;
-                const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : 0xFFFFFFF0u;
+                const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : OOB;
                 xv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));   // out of range -> 0
                 gv[i] = *reinterpret_cast<const f32x4*>(gp + min(n, p.N - 4));
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int n = nl + i * 16;
-                const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : 0xFFFFFFF0u;
+                const unsigned off = (m < p.M && n < p.N) ? rowoff + (unsigned)n * 4u : OOB;
                 const f32x4 v = acc[i][j] + bv[i];
                 f32x4 r;
 #pragma unroll
@@ -408,14 +375,14 @@ __global__ __launch_bounds__(512, 2) void gemm16_kernel(G16P p) {
         }
         // (what-if 16: every m tile stores into the rows of tile 0 — the same instruction stream, but the output stays in L2)
         T16* yb = reinterpret_cast<T16*>(p.y16) + ((WI & 16) ? (int64_t)0 : (int64_t)bm0 * p.ldy);
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)yb, 0, (unsigned)rows_left * (unsigned)p.ldy * 2u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = make_rsrc(yb, (unsigned)rows_left * (unsigned)p.ldy * 2u);
         const int nc = bn0 + wn * 128 + (lane & 15) * 8;          // this lane's 8 columns of a row (N % 8 == 0: valid together)
 #pragma unroll
         for (int it = 0; it < 16; ++it) {
             const int row = it * 4 + (lane >> 4);
             const int m = bm0 + wm * 64 + row;
             const u32x4 v = *reinterpret_cast<const u32x4*>(wb + row * G_EROW + (lane & 15) * 16);
-            const unsigned off = (m < p.M && nc < p.N) ? (unsigned)(m - bm0) * (unsigned)p.ldy * 2u + (unsigned)nc * 2u : 0xFFFFFFF0u;
+            const unsigned off = (m < p.M && nc < p.N) ? (unsigned)(m - bm0) * (unsigned)p.ldy * 2u + (unsigned)nc * 2u : OOB;
             __builtin_amdgcn_raw_buffer_store_b128(v, ry, off, 0, 0);
         }
     }
@@ -470,10 +437,10 @@ __global__ __launch_bounds__(256) void ln_modulate16_kernel(const float* __restr
         if (c < C) {
             const f32x4 sc = *reinterpret_cast<const f32x4*>(mr + scale_off + c);
             const f32x4 sh = *reinterpret_cast<const f32x4*>(mr + shift_off + c);
-            typename Frag<T16>::v4 h;
+            typename Piece<T16>::v4 h;
 #pragma unroll
             for (int r = 0; r < 4; ++r) h[r] = (T16)(((v[i][r] - mean) * rstd) * (1.f + sc[r]) + sh[r]);
-            *reinterpret_cast<typename Frag<T16>::v4*>(y + row * C + c) = h;
+            *reinterpret_cast<typename Piece<T16>::v4*>(y + row * C + c) = h;
         }
     }
 }

@@ -1,10 +1,8 @@
 // misc.hip — the small kernels around the convolutions: timestep embedding, tiny linears, SE gate,
 // skip-average / concat, layout changes, resampling, GEGLU.
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
-
-__device__ __forceinline__ float silu_f(float v) { return v / (1.f + expf(-v)); }
 
 // timestep_embedding, ldm/modules/diffusionmodules/util.py:161-181: cat[cos(t*f), sin(t*f)], f_k = exp(-ln(1e4)*k/half)
 // evaluated like the reference in fp32 (the fp32 argument is formed with fp32 ops, exp itself is taken in fp64 and rounded once).

@@ -13,16 +13,13 @@
 // gn_finalize reduces columns x chunks of a group in a fixed order (deterministic) and folds mean/rstd/gamma/beta (and
 // the FiLM scale/shift of use_scale_shift_norm ResBlocks) into one per-(sample,channel) scale/shift pair, so the apply
 // pass is y = act(x*scale + shift): 1 read + 1 write of the tensor.
-#include "kernels.h"
+#include "device_common.h"
 
 #include <cstdlib>
 
 namespace dsd {
 
 static constexpr int GN_GROUPS = 32;
-
-// (A hardware exp2 / reciprocal SiLU was measured: 18.9 -> 18.4 ms per step for ~3e-7 of extra error; not taken.)
-__device__ __forceinline__ float silu_f(float v) { return v / (1.f + expf(-v)); }
 
 struct GnGeom {
     int threads;  // block size

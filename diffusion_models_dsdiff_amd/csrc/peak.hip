@@ -11,13 +11,9 @@
 //   variant 2 / 3: the same two on ALL-ZERO operands (the clock the chip holds without data toggling)
 //   variant 4 .. 7: the same four on the v_mfma_f32_16x16x32_bf16 shape (below)
 // bench.py runs variants 0 / 1 / 4 / 5 beside the network and reports them as roofline.sustained; DESIGN.md §5.
-#include "kernels.h"
+#include "device_common.h"
 
 namespace dsd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int PK_NT = 5, PK_RB = 2, PK_NP = 3;
 static constexpr int PK_RS = 80;                       // LDS row stride (bytes) of a 32-k weight row, as in conv_split.hip
@@ -64,12 +60,7 @@ __global__ __launch_bounds__(256, 1) void mfma_peak_kernel(const unsigned char* 
 #pragma unroll
             for (int r = 0; r < PK_RB; ++r) {
                 f32x16 c = acc[r][j];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][2], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][0], b[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][1], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][1], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][0], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][r][0], b[0], c, 0, 0, 0);
+                mfma6(af[s][r], b, c);
                 acc[r][j] = c;
             }
         }
@@ -89,7 +80,6 @@ __global__ __launch_bounds__(256, 1) void mfma_peak_kernel(const unsigned char* 
 // 16 x 16 (the same 160 accumulator registers), one 32-deep k-step per k-tile, six products per tile: 240 MFMAs of 16 cycles
 // per k-tile = the 3840 matrix-pipe cycles of the 32x32x16 loop.  LDS variant: the 10 x 3 weight fragments of a k-tile come
 // from LDS ([k chunk][row][16 B]: conflict-free ds_read_b128 for this operand pattern).
-typedef float f32x4p __attribute__((ext_vector_type(4)));
 template <bool LDS>
 __global__ __launch_bounds__(256, 1) void mfma_peak16_kernel(const unsigned char* __restrict__ src, float* __restrict__ sink, int loops) {
     __shared__ __attribute__((aligned(16))) unsigned char Bs[2 * PK_STAGE + 4096];
@@ -103,11 +93,11 @@ __global__ __launch_bounds__(256, 1) void mfma_peak16_kernel(const unsigned char
         for (int q = 0; q < PK_NP; ++q) af[r][q] = *reinterpret_cast<const bf16x8*>(src + ((size_t)(tid * 4 + ((r * 3 + q) & 3)) * 16));
 #pragma unroll
     for (int q = 0; q < PK_NP; ++q) bw[q] = *reinterpret_cast<const bf16x8*>(src + 256 * 64 + (size_t)(q * 64 + lane) * 16);
-    f32x4p acc[4][2 * PK_NT];
+    f32x4 acc[4][2 * PK_NT];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int j = 0; j < 2 * PK_NT; ++j) acc[r][j] = f32x4p{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2 * PK_NT; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     constexpr int PLANE16 = PK_NT * 32 * 64;     // one piece of a 160-row x 32-k tile, [k chunk][row][16 B]
     const unsigned char* frag = Bs + (lane >> 4) * (PK_NT * 32 * 16) + (lane & 15) * 16;
@@ -120,13 +110,8 @@ __global__ __launch_bounds__(256, 1) void mfma_peak16_kernel(const unsigned char
             for (int q = 0; q < PK_NP; ++q) b[q] = LDS ? *reinterpret_cast<const bf16x8*>(bf + q * PLANE16 + j * 256) : bw[q];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                f32x4p c = acc[r][j];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][2], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][0], b[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][1], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][1], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][0], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[r][0], b[0], c, 0, 0, 0);
+                f32x4 c = acc[r][j];
+                mfma6(af[r], b, c);
                 acc[r][j] = c;
             }
         }
