@@ -7,8 +7,9 @@ Same constructor, enums and sampling entry points as the reference (``p_sample_l
 :938-991 with ``_vb_terms_bpd`` / ``_prior_bpd``, ``p_mean_variance`` as a method, ``ddim_reverse_sample`` and the q_* helpers —
 runs through dsd_calc_bpd and the dsd_op_vlb_terms / dsd_op_prior_bpd / dsd_op_ddim_reverse_step kernels.
 ``training_losses`` :821-920 (and its training_project/utils twin :824-) is here as an EVALUATION — the validation loss of a
-checkpoint, forward only, one timestep per sample — through dsd_eval_loss; the contrastive ``disentangle=`` heads and anything
-with a gradient stay out.
+checkpoint, forward only, one timestep per sample — through dsd_eval_loss, with the contrastive ``disentangle=`` terms over the
+content / style / anatomy / lesion heads (:907-975, ``get_disentangle_loss`` :1056-1094) through dsd_set_disentangle /
+dsd_op_contrast_rows; anything with a gradient stays out.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ import numpy as np
 import torch as th
 
 from ... import _lib
+from ... import _sched
 from ..._sched import (Schedule, ddim_reverse_step, disc_planes, is_disc, is_dit, kwargs_conditioning, loop_denoiser, loss_rows,
                        model_output_of, pair_mse_rows, philox_seed, prior_bpd, q_sample_rows, run_bpd_loop, run_device_loop,
                        run_eval_loss, sampler_update, vlb_terms, vlb_terms_rows, _seed_from_torch)
@@ -513,10 +515,19 @@ class GaussianDiffusion:
         Charbonnier loss both copies compute under that name (smooth_L1).  A native denoiser runs dsd_eval_loss (q_sample, one
         forward with per-sample t, the loss kernels); a foreign callable is called as ``model(x_t, t)`` around the same
         kernels.  ``noise`` None: on-device Philox normals keyed by ``seed`` (an extension, as on the loops), else by torch's
-        generator."""
-        if disentangle is not None:
-            raise NotImplementedError("disentangle= adds the contrastive content / style / anatomy / lesion heads "
-                                      "(training_project/utils/gaussian_diffusion.py:908-975): that is training and is not built")
+        generator.
+
+        ``disentangle`` 'contrast' | 'eu' | 'eu&contrast' (training_project form only, :907-975) adds "disen_c_s_loss" and
+        "disen_s_a_l_loss" (0-dim fp32: get_disentangle_loss over content + style at temperature 0.05 and over style + anatomy +
+        lesion at 0.1, labels as :932-951) and "contrast_map" with the four raw [R,R] fp32 matrices (the two logits and the two
+        perfect_logit = 2*mask - 1) under the reference's keys.  The reference passes each through get_heatmap to a viridis RGB
+        image; colouring is presentation and stays with the caller.  A native DSUnetModel computes them inside the same
+        dsd_eval_loss call from the head tensors in its workspace; a foreign callable must return ``(out, dict)`` with the
+        'content' / 'style' / 'anatomy' / 'lesion' lists.  ``disen_lambda`` is unread, as in the reference.  The KL loss types
+        ignore ``disentangle``, as the reference's branch does."""
+        if disentangle is not None and not (isinstance(disentangle, str) and disentangle in _sched.DISENTANGLE_MODES):
+            raise NotImplementedError(f"disentangle={disentangle!r} is not supported: get_disentangle_loss "
+                                      f"(training_project/utils/gaussian_diffusion.py:1056-1094) knows {_sched.DISENTANGLE_MODES}")
         if not isinstance(self.loss_type, LossType):
             raise NotImplementedError(self.loss_type)
         if not x_start.is_cuda:
@@ -549,6 +560,12 @@ class GaussianDiffusion:
         if self.parameterization not in ("eps", "x0", "v"):             # :878-885: the target follows `parameterization` alone
             raise NotImplementedError(f"Parameterization {self.parameterization} not yet supported")
         target = {"eps": _lib.PRED_EPS, "x0": _lib.PRED_X0, "v": _lib.PRED_V}[self.parameterization]
+        if kl:
+            disentangle = None
+        if disentangle is not None and (disc or (unet is not None and _sched.is_latent_denoiser(unet))):
+            raise ValueError(f"disentangle= needs the content / style / anatomy / lesion heads of a DSUnetModel; "
+                             f"{type(unet).__name__ if unet is not None else 'the DisC-Diff form (t1 / t2 / dwi)'} has none")
+        rider = None
         if unet is not None:
             bundle = kwargs_conditioning(unet, model, model_kwargs, device) if not is_dit(unet) and not disc else None
             if bundle is None:
@@ -557,8 +574,10 @@ class GaussianDiffusion:
                 if planes is None:
                     raise KeyError("training_losses needs the condition: 'c_concat', or 'F_Data1' / 'F_Data2' / 'S_Data1' [/ 'edge']")
                 bundle = th.cat(planes, 1)
+            if disentangle is not None:
+                rider = _sched.Disentangle(disentangle, xs.shape[0], device)
             got = run_eval_loss(unet, pred, _lib.LOSS_CHARBONNIER, xs, bundle, t_model, a, s, noise=noise, seed=seed,
-                                vlb=vlb if want_vb else None, learned_range=learned, target=target)
+                                vlb=vlb if want_vb else None, learned_range=learned, target=target, disentangle=rider)
         else:
             rows = [th.from_numpy(np.ascontiguousarray(r)).to(device) for r in (a, s)]
             x_t = q_sample_rows(rows[0], rows[1], xs, noise, seed, 0)
@@ -577,6 +596,22 @@ class GaussianDiffusion:
                 com = [f for f in full[0:4] if f is not None]
                 dist = [f for f in full[4:8] if f is not None]
                 got["com"], got["dist"] = pair_mse_rows(com), pair_mse_rows(dist)
+            if disentangle is not None:
+                if not (isinstance(full, tuple) and len(full) >= 2 and isinstance(full[1], dict)):
+                    raise ValueError("disentangle= reads the feature dict a DSUnetModel returns beside its output: the model must "
+                                     f"return (out, dict), got {type(full).__name__}")
+                c_s, s_a_l = _sched.head_views(full[1])
+                labels = [_sched.label_rows(l) for l in _sched.disentangle_labels(xs.shape[0], len(full[1]["content"]),
+                                                                                 len(full[1]["style"]), len(full[1]["anatomy"]),
+                                                                                 len(full[1]["lesion"]))]
+                mode = {"contrast": "cl", "eu": "eu", "eu&contrast": "eu&cl"}[disentangle]
+                l_cs, m_cs = _sched.contrast_rows(c_s, labels[0], mode, 0.05)           # :960-961
+                l_sal, m_sal = _sched.contrast_rows(s_a_l, labels[1], mode, 0.1)        # :965-966 (the default temperature)
+                got["disen"] = {"disen_c_s_loss": l_cs, "disen_s_a_l_loss": l_sal,
+                                "contrast_map": {"c_s_heatmap": m_cs, "perfect_c_s_heatmap": _sched.perfect_logit(labels[0].to(device)),
+                                                 "s_a_l_heatmap": m_sal, "perfect_s_a_l_heatmap": _sched.perfect_logit(labels[1].to(device))}}
+        if rider is not None:
+            got["disen"] = rider.terms()
         terms = {}
         if kl:                                                          # :841-851
             terms["loss"] = got["vb"] * self.num_timesteps if self.loss_type == LossType.RESCALED_KL else got["vb"]
@@ -591,8 +626,23 @@ class GaussianDiffusion:
             terms["disent"] = terms["com"] / terms["dist"]
             terms["loss"] = terms["mse"] + terms["disent"] + terms["vb"] if "vb" in terms else terms["mse"] + terms["disent"]
         else:                                                           # training_project :977-980
+            terms.update(got.get("disen", {}))                          # :969-975 (the disentangle terms stay out of "loss")
             terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
         return terms
+
+    def get_disentangle_loss(self, feature, label, contrast='eu', temperature=0.1):
+        """:1056-1094 on the device (dsd_op_contrast_rows): (loss, logits, perfect_logit) of ``feature`` [B, n_views, ...] (a CUDA
+        tensor, read in place) and ``label`` [B, n_views].  'contrast': the supervised-contrastive loss on cosine / temperature;
+        'eu': the same-label over different-label ratio of the Euclidean distances / n, returned matrix logits * 2 - 1;
+        'eu&contrast': eu + 0.05 contrast with the cosine logits."""
+        assert feature.shape[0] == label.shape[0]
+        if contrast not in _sched.DISENTANGLE_MODES:
+            raise NotImplementedError(f"contrast {contrast} not supported")
+        if not feature.is_cuda:
+            raise RuntimeError("get_disentangle_loss runs on the MI355X only (no CPU fallback): feature is on the CPU")
+        rows = _sched.label_rows(label)
+        loss, logits = _sched.contrast_rows(th.unbind(feature, dim=1), rows, contrast, temperature)
+        return loss, logits, _sched.perfect_logit(rows.to(feature.device))
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -22,6 +22,8 @@ PLMS_PREDICT, PLMS_CORRECT, PLMS_AB2, PLMS_AB3, PLMS_AB4 = 0, 1, 2, 3, 4
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2
 LOSS_L2, LOSS_L1, LOSS_CHARBONNIER = 0, 1, 2
 LOSS_TERM_MSE, LOSS_TERM_VB, LOSS_TERM_COM, LOSS_TERM_DIST, LOSS_NTERMS = 0, 1, 2, 3, 4
+CONTRAST_CL, CONTRAST_EU, CONTRAST_EU_CL, CONTRAST_L1 = 0, 1, 2, 3
+CONTRAST_MAX_VIEWS, CONTRAST_MAX_ROWS = 8, 256
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 5}
 (BLOCK_RES, BLOCK_ATTN, BLOCK_UPSAMPLE, BLOCK_DOWNSAMPLE, BLOCK_DISENTANGLE, BLOCK_SE, BLOCK_CROSSATTN,
  BLOCK_FF_GEGLU, BLOCK_BASIC_TRANSFORMER, BLOCK_SPATIAL_TRANSFORMER, BLOCK_VAE_ENCODER, BLOCK_VAE_DECODER,
@@ -41,6 +43,7 @@ EXPORTS = [
     "dsd_calc_bpd", "dsd_op_vlb_terms", "dsd_op_prior_bpd", "dsd_op_ddim_reverse_step",
     "dsd_create_disc", "dsd_op_disc_bottleneck",
     "dsd_eval_loss", "dsd_op_loss_rows", "dsd_op_pair_mse_rows", "dsd_op_vlb_terms_rows",
+    "dsd_set_disentangle", "dsd_op_contrast_rows",
 ]
 
 
@@ -110,6 +113,12 @@ class DsdLoss(C.Structure):
     _fields_ = [("target", C.c_int32), ("pred", C.c_int32), ("kind", C.c_int32), ("learned_range", C.c_int32), ("t_model", C.c_void_p), ("a", C.c_void_p),
                 ("s", C.c_void_p), ("vlb_coef", C.c_void_p), ("post_log_var", C.c_void_p), ("decoder", C.c_void_p),
                 ("terms", C.c_void_p)]
+
+
+class DsdDisentangle(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("temperature_cs", C.c_float), ("temperature_sal", C.c_float), ("labels_cs", C.c_void_p),
+                ("n_labels_cs", C.c_int32), ("labels_sal", C.c_void_p), ("n_labels_sal", C.c_int32), ("loss", C.c_void_p),
+                ("logits_cs", C.c_void_p), ("logits_sal", C.c_void_p)]
 
 
 class DsdConvEx(C.Structure):
@@ -266,6 +275,9 @@ def lib() -> C.CDLL:
         L.dsd_op_pair_mse_rows.argtypes = [C.POINTER(vp), i32, i32, i64, f32p, vp]
         L.dsd_op_vlb_terms_rows.argtypes = [i32, i32, i32, f32p, f32p, vp, f32p, i64, f32p, i64, f32p, f32p, C.c_uint64, C.c_uint64,
                                             f32p, f32p, f32p, i64, i32, i32, i32, i32, vp]
+    if hasattr(L, "dsd_set_disentangle"):      # (likewise)
+        L.dsd_set_disentangle.argtypes = [vp, C.POINTER(DsdDisentangle)]
+        L.dsd_op_contrast_rows.argtypes = [C.POINTER(vp), i32, i32, i64, i64, vp, i32, C.c_float, f32p, f32p, vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     if hasattr(L, "dsd_set_trace"):            # (likewise)

@@ -8,6 +8,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import (DSD_NCOEF, DsdBpd, DsdConditioning, DsdGuidance, DsdInpaint, DsdInvertSchedule, DsdSchedule, DsdTrace, check, dptr,
                    lib, stream_ptr)
 
@@ -976,12 +977,14 @@ def vlb_terms_rows(pred: int, learned_range: bool, clip_denoised: bool, coef: to
 
 @torch.no_grad()
 def run_eval_loss(unet, pred: int, kind: int, x_start: torch.Tensor, cond, t_model, a, s, noise: Optional[torch.Tensor] = None,
-                  seed: int = 0, step: int = 0, vlb=None, learned_range: bool = False, target: Optional[int] = None) -> dict:
+                  seed: int = 0, step: int = 0, vlb=None, learned_range: bool = False, target: Optional[int] = None,
+                  disentangle: Optional["Disentangle"] = None) -> dict:
     """dsd_eval_loss: q_sample with the rows ``a`` / ``s``, one evaluation of the native denoiser with ``t_model`` [B] as its
     timesteps, and the loss kernels.  ``pred``: what the network predicts; ``target`` (default: the same) the target of the mse
     term where the reference reads the two off different attributes.  ``cond``: the 'concat' tensor or a Conditioning, as in the loops.  ``vlb``: None, or
     (coef [B,DSD_NCOEF], post_log_var [B], decoder [B]) for the vb term.  Returns {"mse": [B]} plus "vb" (with ``vlb``) and
-    "com" / "dist" (UNet_disc_Model), read back from one [B, LOSS_NTERMS] buffer."""
+    "com" / "dist" (UNet_disc_Model), read back from one [B, LOSS_NTERMS] buffer.  ``disentangle``: a Disentangle installed as the
+    call's rider (dsd_set_disentangle; DSUnetModel only), whose loss / logits buffers the same call fills."""
     from ._lib import DsdLoss, LOSS_NTERMS
     if unet is None:
         raise RuntimeError("no native denoiser (DSUnetModel / UNet_disc_Model / UNetModel / DiT) behind the model handed to the loss")
@@ -1017,7 +1020,7 @@ def run_eval_loss(unet, pred: int, kind: int, x_start: torch.Tensor, cond, t_mod
         spec.vlb_coef, spec.post_log_var, spec.decoder = cf.data_ptr(), plv.data_ptr(), dec.data_ptr()
     spec.terms = terms.data_ptr()
     _check_four_stream_io(unet, xs, cond)
-    with conditioning_set(unet, bundle):
+    with conditioning_set(unet, bundle), disentangle_set(unet, disentangle):
         check(lib().dsd_eval_loss(unet._h, C.byref(spec), dptr(cond), cond.shape[1], dptr(xs), Cz, dptr(z), C.c_uint64(seed),
                                   C.c_uint64(step), B, H, W, stream_ptr()))
     del held
@@ -1027,3 +1030,119 @@ def run_eval_loss(unet, pred: int, kind: int, x_start: torch.Tensor, cond, t_mod
     if is_disc(unet):
         out["com"], out["dist"] = terms[:, 2], terms[:, 3]
     return out
+
+
+# ------------------------------------------------------------------------------------- the disentanglement losses (contrast.hip)
+# get_disentangle_loss's spellings (training_project/utils/gaussian_diffusion.py:1056-1094) and the op's own
+CONTRAST_MODES = {"contrast": _lib.CONTRAST_CL, "cl": _lib.CONTRAST_CL, "eu": _lib.CONTRAST_EU, "eu&contrast": _lib.CONTRAST_EU_CL,
+                  "eu&cl": _lib.CONTRAST_EU_CL, "l1": _lib.CONTRAST_L1}
+DISENTANGLE_MODES = ("contrast", "eu", "eu&contrast")     # what training_losses(disentangle=) takes
+HEAD_VIEWS = dict(content=3, style=3, anatomy=2, lesion=2)  # DSUnetModel's head tensors (model.py:695-725)
+
+
+def disentangle_labels(B: int, n_content: int = 3, n_style: int = 3, n_anatomy: int = 2, n_lesion: int = 2):
+    """The two label tensors of training_losses(disentangle=) (:932-951), int64 on the CPU: c_s [B, n_content + n_style] with
+    row b = [b]*n_content + [-1, -2, ...], s_a_l [B, n_style + n_anatomy + n_lesion] with row b = [-1, -2, ...] +
+    [2b]*n_anatomy + [2b+1]*n_lesion."""
+    style = [-1 - j for j in range(n_style)]
+    c_s = torch.tensor([[b] * n_content + style for b in range(B)], dtype=torch.int64).reshape(B, n_content + n_style)
+    s_a_l = torch.tensor([style + [2 * b] * n_anatomy + [2 * b + 1] * n_lesion for b in range(B)],
+                         dtype=torch.int64).reshape(B, n_style + n_anatomy + n_lesion)
+    return c_s, s_a_l
+
+
+def label_rows(label: torch.Tensor) -> torch.Tensor:
+    """[B, n_views] labels in the row order of the features, torch.cat(torch.unbind(label, 1), 0): row view*B + b."""
+    return torch.cat(torch.unbind(label, dim=1), dim=0).contiguous().view(-1)
+
+
+def perfect_logit(rows: torch.Tensor) -> torch.Tensor:
+    """2*mask - 1 of a [R] label row (:1068-1070; contrastive_loss.py:81 writes the same matrix with torch.where)."""
+    r = rows.view(-1, 1)
+    return 2 * torch.eq(r, r.T).float() - 1
+
+
+@torch.no_grad()
+def contrast_rows(views: Sequence[torch.Tensor], labels: torch.Tensor, metric: str = "eu", temperature: float = 0.1):
+    """(loss, logits [R,R]) of dsd_op_contrast_rows over ``views``, n_views CUDA tensors [B, ...] of one shape whose samples are
+    the R = n_views*B rows view*B + b, and ``labels`` [R] in that order.  ``metric``: "cl" / "contrast" (supervised contrastive
+    on cosine / temperature), "eu" (distance ratio on the fp64 Euclidean distance / n), "eu&cl" / "eu&contrast" (eu + 0.05 cl,
+    the cosine logits returned) or "l1" (the eu ratio on the L1 distance / n: the ``contrast=False`` variant of
+    trainers/trainer_ds_diff.py:341-354).  Views that share one row stride (slices of a stacked [B, n_views, ...] tensor) are
+    read in place."""
+    if metric not in CONTRAST_MODES:
+        raise NotImplementedError(f"contrast {metric} not supported")
+    if len(views) < 1 or len(views) > _lib.CONTRAST_MAX_VIEWS:
+        raise ValueError(f"1 to {_lib.CONTRAST_MAX_VIEWS} views are taken, got {len(views)}")
+    _loss_on_gpu(views[0], "the features")
+    B = int(views[0].shape[0])
+    if any(v.shape != views[0].shape for v in views):
+        raise ValueError("the views differ in shape: " + ", ".join(str(tuple(v.shape)) for v in views))
+    vs = [v.detach().reshape(B, -1) for v in views]
+    n = int(vs[0].shape[1])
+    inplace = all(v.dtype == torch.float32 and (n == 1 or v.stride(1) == 1) and v.stride(0) == vs[0].stride(0) and v.stride(0) >= n
+                  for v in vs)
+    if not inplace:
+        vs = [v.float().contiguous() for v in vs]
+    R = B * len(vs)
+    if R < 2 or R > _lib.CONTRAST_MAX_ROWS:
+        raise ValueError(f"{len(vs)} views of {B} samples are {R} rows; 2 to {_lib.CONTRAST_MAX_ROWS} are taken")
+    lab = torch.as_tensor(labels).detach().reshape(-1).to(device=vs[0].device, dtype=torch.int32).contiguous()
+    if lab.numel() != R:
+        raise ValueError(f"{lab.numel()} labels for {R} rows")
+    loss = torch.zeros((1,), device=vs[0].device, dtype=torch.float32)
+    logits = torch.empty((R, R), device=vs[0].device, dtype=torch.float32)
+    ptrs = (C.c_void_p * len(vs))(*[v.data_ptr() for v in vs])
+    check(lib().dsd_op_contrast_rows(ptrs, len(vs), B, n, int(vs[0].stride(0)) if inplace else n, C.c_void_p(lab.data_ptr()),
+                                     CONTRAST_MODES[metric], C.c_float(float(temperature)), dptr(loss), dptr(logits), stream_ptr()))
+    return loss[0], logits
+
+
+class Disentangle:
+    """The rider of one dsd_eval_loss call on a DSUnetModel (dsd_set_disentangle): ``mode`` as training_losses(disentangle=)
+    spells it, the label rows of a batch of ``B`` (disentangle_labels) and the buffers the call fills: ``loss`` [2] (c_s, s_a_l),
+    ``logits_cs`` [6B,6B], ``logits_sal`` [7B,7B]."""
+
+    def __init__(self, mode: str, B: int, device, temperature_cs: float = 0.05, temperature_sal: float = 0.1):
+        if mode not in DISENTANGLE_MODES:
+            raise NotImplementedError(f"disentangle {mode!r} not supported: one of {DISENTANGLE_MODES}")
+        self.mode, self.B = mode, int(B)
+        self.temperature_cs, self.temperature_sal = float(temperature_cs), float(temperature_sal)
+        self.labels_cs, self.labels_sal = (label_rows(l).to(device=device, dtype=torch.int32) for l in disentangle_labels(self.B))
+        new = lambda *shape: torch.zeros(shape, device=device, dtype=torch.float32)
+        self.loss, self.logits_cs, self.logits_sal = new(2), new(6 * self.B, 6 * self.B), new(7 * self.B, 7 * self.B)
+
+    def terms(self) -> dict:
+        """What training_losses adds (:960-975): the two 0-dim losses and the four raw matrices of ``contrast_map``."""
+        return {"disen_c_s_loss": self.loss[0], "disen_s_a_l_loss": self.loss[1],
+                "contrast_map": {"c_s_heatmap": self.logits_cs, "perfect_c_s_heatmap": perfect_logit(self.labels_cs),
+                                 "s_a_l_heatmap": self.logits_sal, "perfect_s_a_l_heatmap": perfect_logit(self.labels_sal)}}
+
+
+@contextlib.contextmanager
+def disentangle_set(unet, d: Optional[Disentangle]):
+    """dsd_set_disentangle around a dsd_eval_loss call on the denoiser's handle; always cleared afterwards.  None: nothing."""
+    if d is None:
+        yield
+        return
+    spec = _lib.DsdDisentangle()
+    spec.mode = CONTRAST_MODES[d.mode]
+    spec.temperature_cs, spec.temperature_sal = d.temperature_cs, d.temperature_sal
+    spec.labels_cs, spec.n_labels_cs = d.labels_cs.data_ptr(), int(d.labels_cs.numel())
+    spec.labels_sal, spec.n_labels_sal = d.labels_sal.data_ptr(), int(d.labels_sal.numel())
+    spec.loss, spec.logits_cs, spec.logits_sal = d.loss.data_ptr(), d.logits_cs.data_ptr(), d.logits_sal.data_ptr()
+    check(lib().dsd_set_disentangle(unet._h, C.byref(spec)))
+    try:
+        yield
+    finally:
+        check(lib().dsd_set_disentangle(unet._h, None))
+
+
+def head_views(feats: dict):
+    """(content + style, style + anatomy + lesion) view lists of DSUnetModel's feature dict, in the order training_losses
+    concatenates them (:909-918, :940); ValueError naming the keys a dict lacks."""
+    missing = [k for k in HEAD_VIEWS if k not in feats]
+    if missing:
+        raise ValueError(f"disentangle= reads the 'content' / 'style' / 'anatomy' / 'lesion' lists of the model's dict; it lacks {missing}")
+    f = {k: list(feats[k]) for k in HEAD_VIEWS}
+    return f["content"] + f["style"], f["style"] + f["anatomy"] + f["lesion"]

@@ -485,6 +485,26 @@ int dsd_set_trace(dsd_handle* h, const dsd_trace* t) {
     DSD_CATCH
 }
 
+int dsd_set_disentangle(dsd_handle* h, const dsd_disentangle* d) {
+    DSD_TRY
+    DSD_CHECK(h, "null handle");
+    if (d) {   // checked whole before the handle changes, as a trace is
+        DSD_CHECK(d->mode >= DSD_CONTRAST_CL && d->mode <= DSD_CONTRAST_EU_CL,
+                  "disentangle: unknown mode %d (DSD_CONTRAST_CL / _EU / _EU_CL; training_losses has no L1 form)", d->mode);
+        DSD_CHECK(d->mode == DSD_CONTRAST_EU || (d->temperature_cs > 0.f && d->temperature_sal > 0.f),
+                  "disentangle: the cosine modes divide by the temperatures, got %g and %g", (double)d->temperature_cs, (double)d->temperature_sal);
+        DSD_CHECK(d->labels_cs && d->labels_sal && d->loss && d->logits_cs && d->logits_sal,
+                  "disentangle: null argument (labels_cs %p labels_sal %p loss %p logits_cs %p logits_sal %p)", (void*)d->labels_cs,
+                  (void*)d->labels_sal, (void*)d->loss, (void*)d->logits_cs, (void*)d->logits_sal);
+        DSD_CHECK(d->n_labels_cs >= 1 && d->n_labels_sal >= 1, "disentangle: %d and %d labels", d->n_labels_cs, d->n_labels_sal);
+        h->disen = *d;
+    } else {
+        h->disen = dsd_disentangle{};
+    }
+    h->has_disen = d != nullptr;
+    DSD_CATCH
+}
+
 int dsd_block_forward(dsd_handle* h, const float* x, int B, int C, int H, int W, const float* aux, int aux_len,
                       const float* aux2, int aux_len2, float* out, void* stream) {
     DSD_TRY
@@ -629,7 +649,8 @@ LoopBinding bind_four_stream(dsd_handle* h, const dsd_guidance* g, const float* 
                              int out_ch, hipStream_t s, int want_feats = 0) {
     const int64_t hw = (int64_t)H * W;
     const int rows = g ? 2 * B : B;
-    net_plan(h, rows, Cc + 1, H, W, Cc == 1, want_feats, 0, 0, (Cc == 1 && (g || B > 1)) ? h->share_zero_streams : 0, s);
+    // (kept head tensors, dsd_set_disentangle: build_unet refuses zero-stream sharing beside features)
+    net_plan(h, rows, Cc + 1, H, W, Cc == 1, want_feats, 0, 0, (Cc == 1 && (g || B > 1) && !want_feats) ? h->share_zero_streams : 0, s);
     ensure_buf(&h->tbuf, &h->tbuf_cap, (size_t)rows * sizeof(float));
     ensure_buf(&h->mout, &h->mout_cap, (size_t)rows * out_ch * hw * sizeof(float));
     float* xs = x;
@@ -729,7 +750,8 @@ int check_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int 
     return want_ch;
 }
 
-// want_feats (four-stream handles): net_plan's — 2 keeps UNet_disc_Model's bottleneck tensors in the workspace (dsd_eval_loss)
+// want_feats (four-stream handles): net_plan's — 2 keeps UNet_disc_Model's bottleneck tensors, or DSUnetModel's ten head tensors,
+// in the workspace (dsd_eval_loss)
 LoopBinding bind_denoiser(dsd_handle* h, const dsd_guidance* g, const float* cond, int Cc, float* x, int Cz, int B, int H, int W,
                           int out_ch, hipStream_t s, int want_feats = 0) {
     return state_in_input(h) ? bind_latent(h, g, cond, Cc, x, Cz, B, H, W, out_ch, s)
@@ -1543,6 +1565,15 @@ int dsd_eval_loss(dsd_handle* h, const dsd_loss* spec, const float* cond, int Cc
     const int out_ch = check_denoiser(h, nullptr, cond, Cc, x_start, Cz, B, H, W, want_ch);
     DSD_CHECK(latent || h->cfg.out_channels == out_ch, "model has %d output channels but the loss expects %d%s", h->cfg.out_channels,
               out_ch, spec->learned_range ? " (learned_range needs a variance half)" : "");
+    const dsd_disentangle* dz = h->has_disen ? &h->disen : nullptr;
+    if (dz) {
+        DSD_CHECK(!latent && !h->is_disc, "a disentangle rider (dsd_set_disentangle) is installed: only the DSUnetModel of dsd_create has "
+                  "the content / style / anatomy / lesion heads; this handle is %s", h->is_disc ? "a UNet_disc_Model" : "a block handle (UNetModel / DiT)");
+        DSD_CHECK(dz->n_labels_cs == 6 * B && dz->n_labels_sal == 7 * B, "disentangle: %d and %d labels, but a batch of %d has %d "
+                  "content + style rows and %d style + anatomy + lesion rows", dz->n_labels_cs, dz->n_labels_sal, B, 6 * B, 7 * B);
+        DSD_CHECK(7 * B <= DSD_CONTRAST_MAX_ROWS, "disentangle: a batch of %d has %d style + anatomy + lesion rows; up to %d are taken",
+                  B, 7 * B, DSD_CONTRAST_MAX_ROWS);
+    }
     set_device(h->device);
     hipStream_t s = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W, n = Cz * hw;
@@ -1550,12 +1581,15 @@ int dsd_eval_loss(dsd_handle* h, const dsd_loss* spec, const float* cond, int Cc
     // UNet_disc_Model: planned first (bind_four_stream asks for the same plan again), since the size of its bottleneck tensors,
     // which the com / dist reduction's partials follow, comes from the plan
     if (disc) net_plan(h, B, Cc + 1, H, W, 0, 2, 0, 0, 0, s);
-    const size_t part_doubles = std::max({vlb_part_doubles(B, n), loss_part_doubles(B, n), disc ? pair_part_doubles(B, h->plan.feat_n) : (size_t)0});
+    // the head tensors likewise (the binding below asks for the same plan again)
+    if (dz) net_plan(h, B, Cc + 1, H, W, Cc == 1, 2, 0, 0, 0, s);
+    const size_t part_doubles = std::max({vlb_part_doubles(B, n), loss_part_doubles(B, n), disc ? pair_part_doubles(B, h->plan.feat_n) : (size_t)0,
+                                          dz ? contrast_part_doubles(7 * B, h->plan.feat_n) : (size_t)0});
     const size_t part_bytes = (part_doubles * sizeof(double) + 15) / 16 * 16;
     ensure_buf(&h->loss_buf, &h->loss_cap, part_bytes + (latent ? 0 : (size_t)B * n * sizeof(float)));
     // the four-stream model reads its state plane in place: it gets the call's own; the latent binding copies into lat_in
     float* state = latent ? const_cast<float*>(x_start) : h->loss_buf + part_bytes / sizeof(float);
-    const LoopBinding b = bind_denoiser(h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s, disc ? 2 : 0);
+    const LoopBinding b = bind_denoiser(h, nullptr, cond, Cc, state, Cz, B, H, W, out_ch, s, disc || dz ? 2 : 0);
     double* part = reinterpret_cast<double*>(h->loss_buf);
     q_sample_blend(0.f, 0.f, spec->a, spec->s, x_start, nullptr, 0, b.xs, noise, seed, step, B, Cz, (int)hw, s, b.x_bs, false, b.ids);
     DSD_HIP(hipMemcpyAsync(h->tbuf, spec->t_model, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1597,7 +1631,41 @@ int dsd_eval_loss(dsd_handle* h, const dsd_loss* spec, const float* cond, int Cc
                             [&] { pair_mse_rows(pm, B, h->plan.feat_n, s); });
         }
     }
+    if (dz) {   // c_s = content + style, s_a_l = style + anatomy + lesion (:917-918, :940); feat_off: style, content, anatomy, lesion
+        static const int cs[6] = {3, 4, 5, 0, 1, 2}, sal[7] = {0, 1, 2, 6, 7, 8, 9};
+        for (int half = 0; half < 2; ++half) {
+            const int nv = half ? 7 : 6;
+            ContrastRows c;
+            for (int i = 0; i < nv; ++i) c.v[i] = h->at<float>(h->plan.feat_off[half ? sal[i] : cs[i]]);
+            c.labels = half ? dz->labels_sal : dz->labels_cs;
+            c.part = part;
+            c.loss = dz->loss + half;
+            c.logits = half ? dz->logits_sal : dz->logits_cs;
+            const float temp = half ? dz->temperature_sal : dz->temperature_cs;
+            profiled_launch(h, "contrast_rows", (double)nv * B * h->plan.feat_n * sizeof(float), s,
+                            [&] { contrast_rows(c, nv, B, h->plan.feat_n, dz->mode, temp, s); });
+        }
+    }
     net_check_overflow(h, s);
+    DSD_CATCH
+}
+
+int dsd_op_contrast_rows(const float* const* views, int n_views, int B, int64_t n, int64_t row_stride, const int32_t* labels,
+                         int mode, float temperature, float* loss, float* logits, void* stream) {
+    DSD_TRY
+    DSD_CHECK(views && labels && loss && logits, "null argument");
+    contrast_check(n_views, B, n, mode, temperature);
+    for (int i = 0; i < n_views; ++i) DSD_CHECK(views[i], "view %d is null", i);
+    DSD_CHECK(row_stride == 0 || row_stride >= n, "row_stride %lld is smaller than one row (%lld)", (long long)row_stride, (long long)n);
+    Tmp part(contrast_part_doubles(n_views * B, n) * sizeof(double));
+    ContrastRows c;
+    for (int i = 0; i < n_views; ++i) c.v[i] = views[i];
+    c.bs = row_stride;
+    c.labels = labels;
+    c.part = part.as<double>();
+    c.loss = loss;
+    c.logits = logits;
+    contrast_rows(c, n_views, B, n, mode, temperature, (hipStream_t)stream);
     DSD_CATCH
 }
 

@@ -454,4 +454,22 @@ struct VlbRows {
 void vlb_terms_rows(const VlbStep& a, const VlbRows& r, float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz,
                     int HW, hipStream_t s);
 
+// ---------------------------------------------------------------- contrast.hip
+// The disentanglement losses over R = n_views*B feature rows of n elements (row view*B + b at v[view] + b*bs, bs 0 = n): the
+// R x R matrix of fp64 dot products (or L1 distances) from fixed per-slice partials added in index order, then one workgroup
+// that turns the matrix and labels [R] into loss[1] and the fp32 logits [R,R] of `mode` (DSD_CONTRAST_*).  part:
+// contrast_part_doubles(R, n) doubles.  No atomics: two runs agree bit for bit.
+struct ContrastRows {
+    const float* v[8] = {};   // DSD_CONTRAST_MAX_VIEWS
+    int64_t bs = 0;
+    const int32_t* labels = nullptr;
+    double* part = nullptr;
+    float* loss = nullptr;
+    float* logits = nullptr;
+};
+size_t contrast_part_doubles(int R, int64_t n);
+// the argument checks that need no pointer (the callers of the C ABI run them before any device work)
+void contrast_check(int n_views, int B, int64_t n, int mode, float temperature);
+void contrast_rows(const ContrastRows& a, int n_views, int B, int64_t n, int mode, float temperature, hipStream_t s);
+
 }  // namespace dsd

@@ -1789,7 +1789,11 @@ void encode_streams(Builder& b, const Spec& sp, const TimeEmb& te, int H, int W,
 }
 
 // --------------------------------------------------------------------------------- DSUnetModel.forward
-void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool share) {
+// feats_mode 1: io.feats[0..13] receive the ten head tensors and the four n_style_content ones, NCHW.  feats_mode 2 (dsd_eval_loss
+// with dsd_set_disentangle): the ten heads stay where they were written, NHWC, until the forward ends — Plan::feat_off — nothing
+// is exported and the two heads of the noise stream, which only the dict returns, are not evaluated.
+void build_unet(Builder& b, int H, int W, bool zero_al_l, int feats_mode, bool share) {
+    const bool want_feats = feats_mode == 1, keep_feats = feats_mode == 2;
     dsd_handle* hd = b.hd;
     const dsd_config& cfg = hd->cfg;
     const Spec sp = build_spec(cfg);
@@ -1797,7 +1801,7 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
     const int nds = cfg.n_levels - 1;
     DSD_CHECK(H % (1 << nds) == 0 && W % (1 << nds) == 0, "H=%d, W=%d must be multiples of %d (down/up-sampling + skip concat)", H, W, 1 << nds);
     // share: the al / l streams see the same (all-zero) plane and the same timestep for every slice -> batch of ONE
-    DSD_CHECK(!share || (zero_al_l && !want_feats), "zero-stream sharing needs the 2-channel branch and no feature outputs");
+    DSD_CHECK(!share || (zero_al_l && !feats_mode), "zero-stream sharing needs the 2-channel branch and no feature outputs");
     TimeEmb te = time_embed(b, sp, /*t_from_aux=*/false);
 
     // ---- four encoder streams (model.py:674-686): stream order n, a, al, l ; planes io.plane[0..3]
@@ -1846,10 +1850,19 @@ void build_unet(Builder& b, int H, int W, bool zero_al_l, bool want_feats, bool 
         b.export_out(n_content, true, fi++);
         b.release(n_style); b.release(n_content);
     }
-    for (auto& t : st) b.release(t);
-    for (auto& t : ct) b.release(t);
-    for (auto& t : an) b.release(t);
-    for (auto& t : le) b.release(t);
+    if (keep_feats) {   // never released: nothing the rest of the forward allocates lands on them
+        int fi = 0;
+        for (auto& t : st) b.plan.feat_off[fi++] = t.off;
+        for (auto& t : ct) b.plan.feat_off[fi++] = t.off;
+        for (auto& t : an) b.plan.feat_off[fi++] = t.off;
+        for (auto& t : le) b.plan.feat_off[fi++] = t.off;
+        b.plan.feat_n = (int64_t)st[0].h * st[0].w * half;
+    } else {
+        for (auto& t : st) b.release(t);
+        for (auto& t : ct) b.release(t);
+        for (auto& t : an) b.release(t);
+        for (auto& t : le) b.release(t);
+    }
     // ---- h = all_proj(cat[h_n, share_content, style, anatomy, lesion])  (model.py:734-738): SiLU fused into the concat
     Tn cat = b.alloc(B, h_n.h, h_n.w, sp.conv_ch + 4 * half);
     b.avg(&h_n, 1, 1.f, cat, 0, ACT_SILU);
@@ -2383,7 +2396,7 @@ void dsd::net_plan(dsd_handle* h, int B, int C, int H, int W, int zero_al_l, int
         else if (h->is_disc)
             build_disc(b, H, W, want_feats);
         else
-            build_unet(b, H, W, zero_al_l != 0, want_feats != 0, share != 0);
+            build_unet(b, H, W, zero_al_l != 0, want_feats, share != 0);
     } catch (...) {
         // a plan that fails half-way may have enqueued weight-piece kernels on s: let them finish before anybody can free or
         // overwrite what they read, and leave no half-built plan behind

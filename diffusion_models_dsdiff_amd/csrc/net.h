@@ -76,7 +76,9 @@ struct Plan {
     int zero_al_l = 0, want_feats = 0, share = 0;
     int disc_unfused = 0;   // UNet_disc_Model: the bottleneck head composed from the older ops (DSD_DISC_UNFUSED) instead of disc.hip
     int aux_len = 0, aux_len2 = 0;
-    size_t feat_off[8] = {};   // want_feats == 2 (UNet_disc_Model): arena offsets of com_h1..4 / dist_h1..4, NHWC, feat_n elements per sample
+    // want_feats == 2: arena offsets of the tensors the forward keeps, NHWC, feat_n elements per sample.  UNet_disc_Model:
+    // com_h1..4 / dist_h1..4; DSUnetModel: style[3], content[3], anatomy[2], lesion[2] (dsd_set_disentangle)
+    size_t feat_off[10] = {};
     int64_t feat_n = 0;
     bool valid = false;
     std::vector<std::function<void(hipStream_t)>> ops;
@@ -163,6 +165,9 @@ struct dsd_handle {
     float* trace_x = nullptr;
     float* trace_x0 = nullptr;
     bool has_trace = false;
+    // dsd_set_disentangle: the rider dsd_eval_loss reads on a DSUnetModel handle
+    dsd_disentangle disen{};
+    bool has_disen = false;
     float* ctx_buf = nullptr;  // [rows, tokens, context_dim]
     float* y_buf = nullptr;    // [rows] int64 or [rows, y_width] fp32
     float* cfg_io = nullptr;   // guided four-stream binding: state [2B,1,H,W] then conditions [2B,Cc,H,W] (uncond half first)

@@ -37,6 +37,10 @@
  *   dsd_set_trace                  <- the intermediates those samplers return (x_inter / pred_x0 every log_every_t steps)
  *                                        ldm/models/diffusion/ddim.py:149,178-183, plms.py likewise, ddpm.py:1062,1089-1092,
  *                                        trainers/trainer_ddpm.py:451-456
+ *   dsd_set_disentangle / dsd_op_contrast_rows
+ *                                  <- training_losses(disentangle=) / get_disentangle_loss / ContrastiveLoss
+ *                                        training_project/utils/gaussian_diffusion.py:907-975,1056-1094,
+ *                                        loss_function/contrastive_loss.py (csrc/contrast.hip)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
  *   dsd_sample_dpm_adaptive_trial / dsd_op_dpm_adaptive_error
  *                                  <- one trial of DPM_Solver.dpm_solver_adaptive  sampler.py:921-980 (the loop stays on the host)
@@ -659,6 +663,50 @@ int dsd_op_vlb_terms_rows(int pred, int learned_range, int clip_denoised, const 
                           const int32_t* decoder, const float* model_out, int64_t out_row_stride, const float* x_t,
                           int64_t x_row_stride, const float* x_start, const float* noise, uint64_t philox_seed, uint64_t step,
                           float* vb, float* xstart_mse, float* mse, int64_t term_stride, int B, int Cz, int H, int W, void* stream);
+/* ---- the disentanglement losses over the bottleneck heads, forward only ------------------------
+ * Replaces training_losses(disentangle=) (training_project/utils/gaussian_diffusion.py:907-975), get_disentangle_loss
+ * (:1056-1094), ContrastiveLoss(contrast_mode='all', contrastive_method='cl') (loss_function/contrastive_loss.py) and the p = 1
+ * distance of trainers/trainer_ds_diff.py:341-354 as an evaluation.  n_views device tensors views[v] [B,n], sample b of view v at
+ * views[v] + b*row_stride (0: n), are the R = n_views*B rows r = v*B + b of torch.cat(torch.unbind(features, 1), 0); labels is
+ * device int32 [R] in that order.  One pass over the features forms the R x R matrix of fp64 dot products G (DSD_CONTRAST_L1: of
+ * sum |x_i - x_j|) from fixed per-slice fp64 partials added in index order (no atomics: two calls agree bit for bit), then
+ *   cos_ij = G_ij / (max(sqrt G_ii, 1e-8) * max(sqrt G_jj, 1e-8)),   d_ij = sqrt(max(G_ii + G_jj - 2 G_ij, 0))   (fp64)
+ *   DSD_CONTRAST_CL     logits = fp32(cos) / temperature;  loss = -mean_i [ sum_{j != i, label_j == label_i} (logits_ij -
+ *                       log sum_{j != i} exp(logits_ij)) / (#positives_i + 1e-6) ]  (no maximum is subtracted, as the reference)
+ *   DSD_CONTRAST_EU     l = fp32(d) / n;  loss = sum_{same label, i != j} l / sum_{different label} l;  logits = 2 l - 1
+ *   DSD_CONTRAST_EU_CL  loss = loss_eu + 0.05 * loss_cl;  logits = the cosine logits
+ *   DSD_CONTRAST_L1     the EU ratio on l = fp32(G) / n;  logits = l
+ * into loss[1] and logits [R,R] (fp32, device).  R is at most DSD_CONTRAST_MAX_ROWS (seven views of a batch of 32 are 224),
+ * n_views at most DSD_CONTRAST_MAX_VIEWS.  Rejected before any device work: null pointers, an unknown mode, temperature <= 0 in
+ * the two cosine modes, fewer than 2 or more than DSD_CONTRAST_MAX_ROWS rows, row_stride < n. */
+enum { DSD_CONTRAST_CL = 0, DSD_CONTRAST_EU = 1, DSD_CONTRAST_EU_CL = 2, DSD_CONTRAST_L1 = 3 };
+enum { DSD_CONTRAST_MAX_VIEWS = 8, DSD_CONTRAST_MAX_ROWS = 256 };
+int dsd_op_contrast_rows(const float* const* views, int n_views, int B, int64_t n, int64_t row_stride, const int32_t* labels,
+                         int mode, float temperature, float* loss, float* logits, void* stream);
+/* A rider on dsd_eval_loss, as dsd_set_trace is one on the loops: with it installed, dsd_eval_loss on a dsd_create handle
+ * (DSUnetModel) keeps the ten head tensors of the forward in the workspace (style[3], content[3], anatomy[2], lesion[2]; nothing
+ * is exported and the two n_style / n_content heads of dsd_forward's feature mode are not evaluated), plans without zero-stream
+ * sharing, and after the forward runs the op above twice, in the reference's view order (:917-918, :940):
+ *   loss[0], logits_cs  [6B,6B]   content[3] + style[3]               labels_cs  [6B], temperature_cs  (the reference: 0.05)
+ *   loss[1], logits_sal [7B,7B]   style[3] + anatomy[2] + lesion[2]   labels_sal [7B], temperature_sal (the reference: 0.1)
+ * The dsd_loss terms are computed as without it.  NULL clears.  dsd_set_disentangle rejects null pointers, an unknown mode
+ * (DSD_CONTRAST_L1 included: the reference's training_losses has no such form) and non-positive temperatures in the cosine
+ * modes; dsd_eval_loss then fails before any device work on every other handle kind (dsd_create_disc, block handles), when
+ * n_labels_cs != 6B or n_labels_sal != 7B, and when 7B exceeds DSD_CONTRAST_MAX_ROWS.  Without a rider dsd_eval_loss launches
+ * exactly what it launched before there was one. */
+typedef struct dsd_disentangle {
+    int32_t mode;                  /* DSD_CONTRAST_CL / _EU / _EU_CL */
+    float temperature_cs;
+    float temperature_sal;
+    const int32_t* labels_cs;      /* device, [n_labels_cs] */
+    int32_t n_labels_cs;           /* 6B of the dsd_eval_loss calls that follow */
+    const int32_t* labels_sal;     /* device, [n_labels_sal] */
+    int32_t n_labels_sal;          /* 7B */
+    float* loss;                   /* device, [2]: c_s, s_a_l */
+    float* logits_cs;              /* device, [6B,6B] */
+    float* logits_sal;             /* device, [7B,7B] */
+} dsd_disentangle;
+int dsd_set_disentangle(dsd_handle* h, const dsd_disentangle* spec);   /* NULL clears */
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
