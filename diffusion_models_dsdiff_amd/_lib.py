@@ -44,7 +44,12 @@ EXPORTS = [
     "dsd_create_disc", "dsd_op_disc_bottleneck",
     "dsd_eval_loss", "dsd_op_loss_rows", "dsd_op_pair_mse_rows", "dsd_op_vlb_terms_rows",
     "dsd_set_disentangle", "dsd_op_contrast_rows",
+    "dsd_op_tail",
 ]
+# DSD_TAIL_* of include/dsdiff.h, in its order
+TAIL_KINDS = ("se_scale", "avg_into", "nchw_to_nhwc", "nhwc_to_nchw", "avgpool2", "upsample2", "geglu", "softmax_rows", "ln_modulate",
+              "ln_modulate16", "layer_norm", "gated_residual", "gelu_tanh", "patchify", "unpatchify", "add_rows_broadcast", "embed_add",
+              "add2", "cast16", "uncast16")
 
 
 class DsdConfig(C.Structure):
@@ -278,6 +283,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "dsd_set_disentangle"):      # (likewise)
         L.dsd_set_disentangle.argtypes = [vp, C.POINTER(DsdDisentangle)]
         L.dsd_op_contrast_rows.argtypes = [C.POINTER(vp), i32, i32, i64, i64, vp, i32, C.c_float, f32p, f32p, vp]
+    if hasattr(L, "dsd_op_tail"):              # (likewise)
+        L.dsd_op_tail.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     if hasattr(L, "dsd_set_trace"):            # (likewise)

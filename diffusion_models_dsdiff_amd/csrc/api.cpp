@@ -2345,4 +2345,36 @@ int dsd_op_philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, void
     DSD_CATCH
 }
 
+int dsd_op_tail(int kind, void* const* ptrs, const int64_t* ints, const float* floats, void* stream) {
+    DSD_TRY
+    DSD_CHECK(kind >= 0 && kind < DSD_TAIL_NKINDS && ptrs && ints, "dsd_op_tail: bad argument (kind %d)", kind);
+    hipStream_t s = (hipStream_t)stream;
+    auto P = [&](int k) { return (float*)ptrs[k]; };
+    auto I = [&](int k) { return (int)ints[k]; };
+    const float f0 = floats ? floats[0] : 0.f;
+    switch (kind) {
+        case DSD_TAIL_SE_SCALE: se_scale(P(0), I(0), I(1), I(2), P(1), P(2), I(3), P(3), s); break;
+        case DSD_TAIL_AVG_INTO: avg_into(P(0), P(1), P(2), P(3), f0, ints[0], I(1), P(4), I(2), I(3), I(4), s, ints[5], I(6)); break;
+        case DSD_TAIL_NCHW_TO_NHWC: nchw_to_nhwc(P(0), I(0), I(1), I(2), P(1), s); break;
+        case DSD_TAIL_NHWC_TO_NCHW: nhwc_to_nchw(P(0), I(0), I(1), I(2), P(1), s); break;
+        case DSD_TAIL_AVGPOOL2: avgpool2(P(0), I(0), I(1), I(2), I(3), P(1), s); break;
+        case DSD_TAIL_UPSAMPLE2: upsample2(P(0), I(0), I(1), I(2), I(3), P(1), s); break;
+        case DSD_TAIL_GEGLU: geglu(P(0), ints[0], I(1), P(1), s); break;
+        case DSD_TAIL_SOFTMAX_ROWS: softmax_rows(P(0), ints[0], I(1), f0, s); break;
+        case DSD_TAIL_LN_MODULATE: ln_modulate(P(0), I(0), I(1), I(2), P(1), I(3), I(4), I(5), f0, P(2), s); break;
+        case DSD_TAIL_LN_MODULATE16: ln_modulate16(P(0), I(0), I(1), I(2), P(1), I(3), I(4), I(5), f0, ptrs[2], I(6), s); break;
+        case DSD_TAIL_LAYER_NORM: layer_norm(P(0), ints[0], I(1), P(1), P(2), f0, P(3), s); break;
+        case DSD_TAIL_GATED_RESIDUAL: gated_residual(P(0), P(1), I(0), I(1), I(2), P(2), I(3), I(4), s); break;
+        case DSD_TAIL_GELU_TANH: gelu_tanh(P(0), ints[0], s); break;
+        case DSD_TAIL_PATCHIFY: patchify(P(0), I(0), I(1), I(2), I(3), I(4), P(1), s); break;
+        case DSD_TAIL_UNPATCHIFY: unpatchify(P(0), I(0), I(1), I(2), I(3), I(4), P(1), s); break;
+        case DSD_TAIL_ADD_ROWS_BROADCAST: add_rows_broadcast(P(0), P(1), I(0), ints[1], s); break;
+        case DSD_TAIL_EMBED_ADD: embed_add(P(0), P(1), (const long long*)ptrs[2], I(0), I(1), P(3), s); break;
+        case DSD_TAIL_ADD2: add2(P(0), P(1), ints[0], P(2), s); break;
+        case DSD_TAIL_CAST16: cast16(P(0), ints[0], ptrs[1], I(1), s); break;
+        default: uncast16(ptrs[0], ints[0], P(1), I(1), s); break;
+    }
+    DSD_CATCH
+}
+
 }  // extern "C"

@@ -538,8 +538,9 @@ void ln_modulate16(const float* x, int N, int T, int C, const float* mod, int mo
                    void* y, int bf16, hipStream_t s) {
     const int64_t rows = (int64_t)N * T;
     if (rows == 0) return;
-    DSD_CHECK(C % 4 == 0 && C <= 2048 && mod_stride % 4 == 0 && shift_off % 4 == 0 && scale_off % 4 == 0,
-              "ln_modulate16: C=%d must be a multiple of 4 and <= 2048 (strides %% 4)", C);
+    DSD_CHECK(C % 4 == 0 && C <= 2048, "ln_modulate16: C=%d must be a multiple of 4 and <= 2048", C);
+    DSD_CHECK(mod_stride % 4 == 0 && shift_off % 4 == 0 && scale_off % 4 == 0,
+              "ln_modulate16: mod_stride=%d, shift_off=%d and scale_off=%d must be multiples of 4", mod_stride, shift_off, scale_off);
     const dim3 g(cdiv(rows, 4)), b(256);
     const int nv = cdiv(C, 256);
 #define LN16(TT, NV) hipLaunchKernelGGL((ln_modulate16_kernel<TT, NV>), g, b, 0, s, x, rows, T, C, mod, mod_stride, shift_off, scale_off, eps, (TT*)y)

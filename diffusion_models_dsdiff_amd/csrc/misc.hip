@@ -238,6 +238,10 @@ __global__ __launch_bounds__(256) void avg_into_kernel(const float4* __restrict_
 void avg_into(const float* a, const float* b, const float* c, const float* d, float div, int64_t pixels, int C, float* dst,
               int dstC, int coff, int act, hipStream_t s, int64_t per_sample_pixels, int bmask) {
     DSD_CHECK(C % 4 == 0 && dstC % 4 == 0 && coff % 4 == 0, "avg_into: channel counts must be multiples of 4");
+    // a broadcast source is indexed with i % (per_sample_pixels * cols) on the device
+    DSD_CHECK(bmask == 0 || (per_sample_pixels > 0 && pixels % per_sample_pixels == 0),
+              "avg_into: bmask=%d needs per_sample_pixels > 0 that divides pixels=%lld, got %lld", bmask, (long long)pixels,
+              (long long)per_sample_pixels);
     const int cols = C / 4;
     const int64_t total = pixels * cols;
     if (total == 0) return;

@@ -214,6 +214,17 @@ def linear(x, w, bias=None, act_in=0):
     return y
 
 
+def tail(kind, ptrs, ints, floats=()):
+    """One of the small element-wise / layout / LayerNorm kernels alone (dsd_op_tail; argument order per kind in
+    include/dsdiff.h).  kind: a name of _lib.TAIL_KINDS; ptrs: CUDA tensors or views (only the first element's address is
+    used) or None; ints / floats: the launcher's scalars."""
+    from ._lib import TAIL_KINDS
+    p = (C.c_void_p * max(len(ptrs), 1))(*[None if t is None else t.data_ptr() for t in ptrs])
+    i = (C.c_int64 * max(len(ints), 1))(*[int(v) for v in ints])
+    f = (C.c_float * max(len(floats), 1))(*[float(v) for v in floats])
+    check(lib().dsd_op_tail(TAIL_KINDS.index(kind), p, i, f, stream_ptr()))
+
+
 def philox_normal(n, seed, step, device="cuda"):
     y = torch.empty((n,), device=device, dtype=torch.float32)
     check(lib().dsd_op_philox_normal(dptr(y), n, seed, step, stream_ptr()))

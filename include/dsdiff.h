@@ -983,6 +983,33 @@ int dsd_op_posterior_sample_scaled(const float* moments, const float* noise_or_n
                                    int W, float scale, float* z, void* stream);
 /* Philox4x32-10 + Box-Muller stream used by dsd_sample when noise == NULL: fills n normals. */
 int dsd_op_philox_normal(float* y, int64_t n, uint64_t seed, uint64_t step, void* stream);
+/* The small kernels around the convolutions and the transformer blocks (csrc/misc.hip, layer_norm of csrc/norm.hip, the casts and
+ * ln_modulate16 of csrc/gemm16.hip), each launched alone exactly as the networks launch it (test plumbing: no arithmetic
+ * here).  All buffers are device pointers; a kind reads its arguments in the order of its launcher in csrc/kernels.h:
+ *   kind                 ptrs                  ints                                                         floats
+ *   SE_SCALE             x, w1, w2, y          N, HW, C, Cr
+ *   AVG_INTO             a, b, c, d, dst       pixels, C, dstC, coff, act, per_sample_pixels, bmask         div
+ *   NCHW_TO_NHWC         x, y                  N, C, HW             (NHWC_TO_NCHW alike)
+ *   AVGPOOL2             x, y                  N, H, W, C           (UPSAMPLE2 alike; x NHWC)
+ *   GEGLU                x, y                  rows, inner
+ *   SOFTMAX_ROWS         s (in place)          rows, cols                                                   scale
+ *   LN_MODULATE          x, mod, y             N, T, C, mod_stride, shift_off, scale_off                    eps
+ *   LN_MODULATE16        x, mod, y (16-bit)    N, T, C, mod_stride, shift_off, scale_off, bf16              eps
+ *   LAYER_NORM           x, gamma, beta, y     rows, C                                                      eps
+ *   GATED_RESIDUAL       x (in place), y, mod  N, T, C, mod_stride, gate_off
+ *   GELU_TANH            x (in place)          n
+ *   PATCHIFY             x, y                  N, C, H, W, p        (token channels in the order c, ph, pw)
+ *   UNPATCHIFY           x, y                  N, c, h, w, p        (token channels in the order ph, pw, c)
+ *   ADD_ROWS_BROADCAST   x (in place), pos     N, TC
+ *   EMBED_ADD            a (or NULL), table, idx (int64), y         N, C
+ *   ADD2                 a, b, y               n
+ *   CAST16               x, y (16-bit)         n, bf16              (UNCAST16: x 16-bit, y fp32)
+ * Unused trailing arrays may be NULL. */
+enum { DSD_TAIL_SE_SCALE = 0, DSD_TAIL_AVG_INTO, DSD_TAIL_NCHW_TO_NHWC, DSD_TAIL_NHWC_TO_NCHW, DSD_TAIL_AVGPOOL2, DSD_TAIL_UPSAMPLE2,
+       DSD_TAIL_GEGLU, DSD_TAIL_SOFTMAX_ROWS, DSD_TAIL_LN_MODULATE, DSD_TAIL_LN_MODULATE16, DSD_TAIL_LAYER_NORM,
+       DSD_TAIL_GATED_RESIDUAL, DSD_TAIL_GELU_TANH, DSD_TAIL_PATCHIFY, DSD_TAIL_UNPATCHIFY, DSD_TAIL_ADD_ROWS_BROADCAST,
+       DSD_TAIL_EMBED_ADD, DSD_TAIL_ADD2, DSD_TAIL_CAST16, DSD_TAIL_UNCAST16, DSD_TAIL_NKINDS };
+int dsd_op_tail(int kind, void* const* ptrs, const int64_t* ints, const float* floats, void* stream);
 
 #ifdef __cplusplus
 }
