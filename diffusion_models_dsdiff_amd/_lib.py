@@ -24,6 +24,7 @@ LOSS_L2, LOSS_L1, LOSS_CHARBONNIER = 0, 1, 2
 LOSS_TERM_MSE, LOSS_TERM_VB, LOSS_TERM_COM, LOSS_TERM_DIST, LOSS_NTERMS = 0, 1, 2, 3, 4
 CONTRAST_CL, CONTRAST_EU, CONTRAST_EU_CL, CONTRAST_L1 = 0, 1, 2, 3
 CONTRAST_MAX_VIEWS, CONTRAST_MAX_ROWS = 8, 256
+METRICS_MAX_SCALES, METRICS_TILE_W, METRICS_TILE_H = 5, 32, 16
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 5}
 (BLOCK_RES, BLOCK_ATTN, BLOCK_UPSAMPLE, BLOCK_DOWNSAMPLE, BLOCK_DISENTANGLE, BLOCK_SE, BLOCK_CROSSATTN,
  BLOCK_FF_GEGLU, BLOCK_BASIC_TRANSFORMER, BLOCK_SPATIAL_TRANSFORMER, BLOCK_VAE_ENCODER, BLOCK_VAE_DECODER,
@@ -45,6 +46,7 @@ EXPORTS = [
     "dsd_eval_loss", "dsd_op_loss_rows", "dsd_op_pair_mse_rows", "dsd_op_vlb_terms_rows",
     "dsd_set_disentangle", "dsd_op_contrast_rows",
     "dsd_op_tail",
+    "dsd_op_image_metrics",
 ]
 # DSD_TAIL_* of include/dsdiff.h, in its order
 TAIL_KINDS = ("se_scale", "avg_into", "nchw_to_nhwc", "nhwc_to_nchw", "avgpool2", "upsample2", "geglu", "softmax_rows", "ln_modulate",
@@ -124,6 +126,12 @@ class DsdDisentangle(C.Structure):
     _fields_ = [("mode", C.c_int32), ("temperature_cs", C.c_float), ("temperature_sal", C.c_float), ("labels_cs", C.c_void_p),
                 ("n_labels_cs", C.c_int32), ("labels_sal", C.c_void_p), ("n_labels_sal", C.c_int32), ("loss", C.c_void_p),
                 ("logits_cs", C.c_void_p), ("logits_sal", C.c_void_p)]
+
+
+class DsdImageMetrics(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("scales", C.c_int32), ("data_range", C.c_double), ("pre", C.POINTER(C.c_double)), ("scale_out", C.c_void_p),
+                ("elem_out", C.c_void_p)]
 
 
 class DsdConvEx(C.Structure):
@@ -285,6 +293,8 @@ def lib() -> C.CDLL:
         L.dsd_op_contrast_rows.argtypes = [C.POINTER(vp), i32, i32, i64, i64, vp, i32, C.c_float, f32p, f32p, vp]
     if hasattr(L, "dsd_op_tail"):              # (likewise)
         L.dsd_op_tail.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
+    if hasattr(L, "dsd_op_image_metrics"):     # (likewise)
+        L.dsd_op_image_metrics.argtypes = [C.POINTER(DsdImageMetrics), vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     if hasattr(L, "dsd_set_trace"):            # (likewise)

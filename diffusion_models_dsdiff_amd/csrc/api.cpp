@@ -1669,6 +1669,28 @@ int dsd_op_contrast_rows(const float* const* views, int n_views, int B, int64_t 
     DSD_CATCH
 }
 
+int dsd_op_image_metrics(const dsd_image_metrics* spec, void* stream) {
+    DSD_TRY
+    DSD_CHECK(spec, "image_metrics: spec is null");
+    DSD_CHECK(spec->pred, "image_metrics: pred is null");
+    DSD_CHECK(spec->target, "image_metrics: target is null");
+    DSD_CHECK(spec->scale_out, "image_metrics: scale_out is null");
+    DSD_CHECK(spec->elem_out, "image_metrics: elem_out is null");
+    image_metrics_check(spec->B, spec->C, spec->H, spec->W, spec->scales, spec->data_range, spec->pre);
+    Tmp scratch(image_metrics_scratch_doubles(spec->B, spec->C, spec->H, spec->W, spec->scales) * sizeof(double));
+    ImageMetrics m;
+    m.pred = spec->pred; m.target = spec->target;
+    m.B = spec->B; m.C = spec->C; m.H = spec->H; m.W = spec->W;
+    m.scales = spec->scales;
+    m.data_range = spec->data_range;
+    m.pre = spec->pre;
+    m.scratch = scratch.as<double>();
+    m.scale_out = spec->scale_out;
+    m.elem_out = spec->elem_out;
+    image_metrics(m, (hipStream_t)stream);
+    DSD_CATCH
+}
+
 int dsd_op_loss_rows(int pred, int kind, const float* model_out, int64_t out_row_stride, const float* x_start, const float* noise,
                      uint64_t philox_seed, uint64_t step, const float* a, const float* s, float* loss, int64_t loss_stride, int B,
                      int Cz, int H, int W, void* stream) {

@@ -472,4 +472,27 @@ size_t contrast_part_doubles(int R, int64_t n);
 void contrast_check(int n_views, int B, int64_t n, int mode, float temperature);
 void contrast_rows(const ContrastRows& a, int n_views, int B, int64_t n, int mode, float temperature, hipStream_t s);
 
+// ---------------------------------------------------------------- metrics.hip
+// MAE / MSE sums, Gaussian SSIM (11 taps, sigma 1.5, valid interior) and the MS-SSIM scale table of pred against target, fp32
+// [B,C,H,W], in fp64 from the load onward: scale_out[B][scales][2] = the mean of the ssim map and of the contrast-structure map
+// per sample and scale (over the channels and the interior, unclamped), elem_out[B][6] = sum |p - t|, sum (p - t)^2, min t,
+// max t, min p, max p.  data_range 0: each sample's own max(range(pred), range(target)).  pre: NULL or the host's seven doubles
+// (mean_p, div_p, mean_t, div_t, add, lo, hi) of y = clip((x - mean) / div + add, lo, hi), applied at the load.  scratch:
+// image_metrics_scratch_doubles(...) doubles.  Fixed per-tile partials, a fixed fold: two runs agree bit for bit.
+static constexpr int kMtTileW = 32, kMtTileH = 16;   // outputs one workgroup of the map kernel owns (DSD_METRICS_TILE_W / _H)
+struct ImageMetrics {
+    const float* pred = nullptr;
+    const float* target = nullptr;
+    int B = 0, C = 0, H = 0, W = 0, scales = 1;
+    double data_range = 1.0;
+    const double* pre = nullptr;
+    double* scratch = nullptr;
+    double* scale_out = nullptr;
+    double* elem_out = nullptr;
+};
+size_t image_metrics_scratch_doubles(int B, int C, int H, int W, int scales);
+// the argument checks that need no device pointer (the C ABI runs them before any device work)
+void image_metrics_check(int B, int C, int H, int W, int scales, double data_range, const double* pre);
+void image_metrics(const ImageMetrics& a, hipStream_t s);
+
 }  // namespace dsd

@@ -20,6 +20,10 @@ What the reference does around ``sample_fn`` and what is rebuilt here:
   * the "ssim" the metric pass actually reports — torchmetrics' MS-SSIM per axial slice (test_metrics.py:249-274) — restated
     from its published definition (``multiscale_structural_similarity``, ``ssim_torch``; parity unpinned: torchmetrics is
     absent), and the per-id table + mean row of inference/get_metric_BraTs.py:54-126 (``metric_table``, written as CSV).
+  * MONAI's validation metrics (trainers/trainer_ddpm.py:79-80,529-532): ``ssim_gaussian``, ``mae`` and the unclamped per-scale
+    table ``ssim_scale_table`` — the float64 statements the device kernel (csrc/metrics.hip, ``metrics.image_metrics``) is
+    tested against; ``ssim_torch`` / ``metric_row`` / ``metric_table`` take ``device=`` to evaluate the MS-SSIM column there
+    (unset: the host loop, unchanged).  Parity unpinned: MONAI is absent.
 Not rebuilt: CW-SSIM (pyssim), FID / LPIPS (network weights), ANTs similarity / Mattes mutual information (the table's ``mi``
 column holds NaN).
 
@@ -310,14 +314,93 @@ def multiscale_structural_similarity(preds, target, data_range=None, kernel_size
     return float(np.prod(np.asarray(vals) ** np.asarray(betas, dtype=np.float64)))
 
 
-def ssim_torch(true_array, pred_array, mask=None):
+def ssim_scale_table(pred, target, scales=1, data_range=None, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """The per-scale means MS-SSIM is built from, of ONE sample [C,H,W] or [H,W], float64 with scipy: row s holds the mean of
+    the luminance-contrast-structure map and the mean of the contrast-structure map of scale s over all channels and the
+    window-valid interior, NOT clamped; between scales the 2x2 average pool that drops a trailing odd row / column.  The
+    formulas, the window and the range rule (None: max(range(pred), range(target)) of the whole sample) are those of
+    ``multiscale_structural_similarity``; this is the float64 statement csrc/metrics.hip is tested against."""
+    from scipy.ndimage import correlate1d
+    x, y = np.asarray(pred, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    if x.shape != y.shape or x.ndim not in (2, 3):
+        raise ValueError("expected two samples [C,H,W] or [H,W] of the same shape")
+    if x.ndim == 2:
+        x, y = x[None], y[None]
+    if min(x.shape[1:]) >> (scales - 1) < kernel_size:
+        raise ValueError(f"image {x.shape[1:]} too small for {scales} scales of an {kernel_size}-tap window")
+    R = float(max(x.max() - x.min(), y.max() - y.min())) if data_range is None else float(data_range)
+    c1, c2 = (k1 * R) ** 2, (k2 * R) ** 2
+    g = _gauss1d(kernel_size, sigma)
+    pad = (kernel_size - 1) // 2
+    blur = lambda a: correlate1d(correlate1d(a, g, axis=1, mode="mirror"), g, axis=2, mode="mirror")
+    rows = []
+    for i in range(scales):
+        mx, my = blur(x), blur(y)
+        sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
+        upper, lower = 2 * sxy + c2, sxx + syy + c2
+        full = ((2 * mx * my + c1) * upper) / ((mx * mx + my * my + c1) * lower)
+        inner = (slice(None), slice(pad, x.shape[1] - pad), slice(pad, x.shape[2] - pad))
+        rows.append((float(full[inner].mean()), float((upper / lower)[inner].mean())))
+        if i < scales - 1:
+            h2, w2 = (x.shape[1] // 2) * 2, (x.shape[2] // 2) * 2
+            x = x[:, :h2, :w2].reshape(-1, h2 // 2, 2, w2 // 2, 2).mean(axis=(2, 4))
+            y = y[:, :h2, :w2].reshape(-1, h2 // 2, 2, w2 // 2, 2).mean(axis=(2, 4))
+    return np.asarray(rows, dtype=np.float64)
+
+
+def ssim_gaussian(pred, target, data_range=1.0):
+    """monai.metrics.SSIMMetric(spatial_dims=2, data_range=..., kernel_type="gaussian", win_size=11, kernel_sigma=1.5,
+    k1=0.01, k2=0.03) of ONE sample [C,H,W] (or [H,W]) — what every trainer's validation_step reports as val/ssim
+    (trainers/trainer_ddpm.py:79-80,529-532): the window of ``_gauss1d`` applied without padding, biased (co)variances,
+        cs = (2 sxy + c2) / (sx + sy + c2),   ssim = (2 mx my + c1) / (mx^2 + my^2 + c1) * cs,   c = (k R)^2,
+    the map averaged over every channel and window position, not clamped.  data_range None: the sample's own
+    max(range(pred), range(target)).  float64 with scipy.  PARITY UNPINNED: MONAI is not installable here and the reference holds
+    no value of it; tests/test_image_metrics_cpu.py checks it against MONAI's own formulation (a grouped conv2d with the
+    11 x 11 outer-product kernel) and against scale 0 of ``multiscale_structural_similarity``."""
+    from scipy.ndimage import correlate1d
+    x, y = np.asarray(pred, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    if x.shape != y.shape or x.ndim not in (2, 3):
+        raise ValueError("expected two samples [C,H,W] or [H,W] of the same shape")
+    if x.ndim == 2:
+        x, y = x[None], y[None]
+    if min(x.shape[1:]) < 11:
+        raise ValueError(f"image {x.shape[1:]} is smaller than the 11-tap window")
+    R = float(max(x.max() - x.min(), y.max() - y.min())) if data_range is None else float(data_range)
+    c1, c2 = (0.01 * R) ** 2, (0.03 * R) ** 2
+    g = _gauss1d(11, 1.5)
+    valid = lambda a: correlate1d(correlate1d(a, g, axis=2, mode="mirror"), g, axis=1, mode="mirror")[:, 5:a.shape[1] - 5, 5:a.shape[2] - 5]
+    mx, my = valid(x), valid(y)
+    sx, sy, sxy = valid(x * x) - mx * mx, valid(y * y) - my * my, valid(x * y) - mx * my
+    cs = (2 * sxy + c2) / (sx + sy + c2)
+    return float((((2 * mx * my + c1) / (mx * mx + my * my + c1)) * cs).mean())
+
+
+def mae(pred, target):
+    """monai.metrics.MAEMetric of ONE sample: the mean of |pred - target| over every element, float64 (val/mae)."""
+    return float(np.mean(np.abs(np.asarray(pred, dtype=np.float64) - np.asarray(target, dtype=np.float64))))
+
+
+def ssim_torch(true_array, pred_array, mask=None, device=None):
     """inference/test_metrics.py:249-274 — the "ssim" column of the reference's metric table: zero outside the mask, crop
     to the mask's bounding box (exclusive upper bound, as the reference slices), 12-bit rescale of each volume, MS-SSIM of
-    every axial slice pair, averaged.  (The reference zeroes its INPUT arrays in place; copies are used here.)"""
+    every axial slice pair, averaged.  (The reference zeroes its INPUT arrays in place; copies are used here.)
+
+    ``device`` (a torch device; None: the host loop above, unchanged): the slices of the cropped, masked volume go up once as
+    fp32 [D,1,h,w] and ``metrics.image_metrics`` evaluates all of them in one call — five scales, each slice's own range, the
+    12-bit rescale applied on the device at the load with the mean and std taken here in float64 as ``scale12bit`` takes them.
+    A volume whose voxels are fp32 values (what a NIfTI float32 / int16 file holds) gives the host's result to about 1e-13."""
     m = _mask(true_array, mask)
     t, p = np.where(m, true_array, 0), np.where(m, pred_array, 0)
     nz = np.nonzero(m)
     sl = tuple(slice(int(a.min()), int(a.max())) for a in nz)
+    if device is not None:
+        import torch
+        from .metrics import image_metrics
+        t, p = t[sl], p[sl]
+        pre = (np.mean(p), np.std(p) / 400., np.mean(t), np.std(t) / 400., 2048., 1e-10, 4095)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))[:, None].to(device)
+        out = image_metrics(up(p), up(t), scales=5, data_range=0, pre=pre)
+        return float(np.mean(out["ms_ssim"].numpy()))
     t, p = scale12bit(t[sl]), scale12bit(p[sl])
     return float(np.mean([multiscale_structural_similarity(p[i], t[i]) for i in range(t.shape[0])]))
 
@@ -325,21 +408,22 @@ def ssim_torch(true_array, pred_array, mask=None):
 METRIC_COLUMNS = ["nrmse", "smape", "logac", "medsymac", "cc", "mi", "ssim", "lpips", "fid", "psnr"]
 
 
-def metric_row(gt_img, pred_img, mask_img=None):
+def metric_row(gt_img, pred_img, mask_img=None, device=None):
     """One row of inference/get_metric_BraTs.py:78-104 (without the id): the columns the reference fills with a constant 0
     (cc, lpips, fid: their calls are commented out there) stay 0; ``mi`` is ANTs' Mattes mutual information in the
-    reference (test_metrics.py:77-90) — ANTs is not available and is not restated: the column holds NaN."""
+    reference (test_metrics.py:77-90) — ANTs is not available and is not restated: the column holds NaN.  ``device``: see
+    ``ssim_torch`` (the "ssim" column on the device; None: everything on the host, as before)."""
     gt_img, pred_img = np.asarray(gt_img, dtype=np.float64), np.asarray(pred_img, dtype=np.float64)
     return [nrmse(gt_img, pred_img, mask_img), smape(gt_img, pred_img, mask_img), logac(gt_img, pred_img, mask_img),
-            medsymac(gt_img, pred_img, mask_img), 0.0, float("nan"), ssim_torch(gt_img, pred_img, mask_img), 0.0, 0.0,
+            medsymac(gt_img, pred_img, mask_img), 0.0, float("nan"), ssim_torch(gt_img, pred_img, mask_img, device=device), 0.0, 0.0,
             psnr(gt_img, pred_img, mask_img)]
 
 
-def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None):
+def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None, device=None):
     """get_metric_BraTs.py:54-115: for every prediction ``<id>_..._pred.nii.gz`` (id = text before the first '_') or
     ``{id: path}`` entry, the ground truth ``<gt_dir>/<id>/<gt_name>`` (and, with mask_name, ``<gt_dir>/<id>/<mask_name>``
     > 0 as mask); returns the table with the MEAN row first (float32 mean over the ids, as the reference computes it) and
-    the id rows after it: [["ids"] + METRIC_COLUMNS header not included]."""
+    the id rows after it: [["ids"] + METRIC_COLUMNS header not included].  ``device``: see ``ssim_torch``."""
     if not isinstance(pred_files, dict):
         pred_files = {os.path.basename(f).split(".")[0].split("_")[0]: f for f in pred_files if f.endswith(".nii.gz")}
     rows = []
@@ -349,7 +433,7 @@ def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None):
         mask = None
         if mask_name:
             mask = read_nifti(os.path.join(gt_dir, id_, mask_name))[0] > 0
-        rows.append([str(id_)] + metric_row(gt, pred, mask))
+        rows.append([str(id_)] + metric_row(gt, pred, mask, device=device))
     if not rows:
         return []
     mean = np.mean(np.asarray([r[1:] for r in rows], dtype=np.float32), axis=0)

@@ -104,3 +104,43 @@ class DDPMModel(DDPM):
             if keep:
                 return {k: log[k] for k in keep}
         return log
+
+    def _validation_state(self):
+        """:79-84, made on first use so that the constructor and every other call are as they were."""
+        if not hasattr(self, "mae_metric"):
+            from ..metrics import MAEMetric, SSIMMetric
+            self.mae_metric = MAEMetric(reduction="mean", get_not_nans=False)
+            self.ssim_metric = SSIMMetric(spatial_dims=2)
+            self.best_val_mae, self.best_val_ssim, self.best_val_epoch = 1000, 0, 0
+            self._val_epoch = 0
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0, sampler="ddim", ddim_steps=50, **kwargs):
+        """:501-532 without the loss and image logging: sample the whole batch (``log_images`` under ``pred_mode``), then
+        MAEMetric and SSIMMetric of the samples against ``log["inputs"]``, evaluated on the device (metrics.py).  The reference
+        takes ``sampler`` / ``ddim_steps`` from its sampler_setting; here they are arguments.  Returns the per-sample values."""
+        self._validation_state()
+        log = self.log_images(batch, N=len(batch["image"]), sample=True, pred_mode=True, sampler=sampler, ddim_steps=ddim_steps,
+                              **kwargs)
+        outputs, labels = list(log["samples"]), list(log["inputs"])           # decollate_batch (:529-530)
+        return {"mae": self.mae_metric(y_pred=outputs, y=labels), "ssim": self.ssim_metric(y_pred=outputs, y=labels)}
+
+    def on_validation_epoch_end(self):
+        """:540-565: the epoch's means, the best values so far (SSIM up, MAE down) and the epoch of the best SSIM; both metrics
+        are reset.  Returns what the reference passes to ``log_dict``.  ``current_epoch`` is Lightning's where there is one; without
+        it the epochs are counted here."""
+        self._validation_state()
+        mean_val_ssim = self.ssim_metric.aggregate().item()
+        mean_val_mae = self.mae_metric.aggregate().item()
+        self.mae_metric.reset()
+        self.ssim_metric.reset()
+        epoch = getattr(self, "current_epoch", None)
+        if not isinstance(epoch, int):
+            epoch = self._val_epoch
+        self._val_epoch += 1
+        if mean_val_ssim > self.best_val_ssim:
+            self.best_val_ssim = mean_val_ssim
+            self.best_val_epoch = epoch
+        if mean_val_mae < self.best_val_mae:
+            self.best_val_mae = mean_val_mae
+        return {"val/ssim": mean_val_ssim, "val/mae": mean_val_mae}

@@ -41,6 +41,9 @@
  *                                  <- training_losses(disentangle=) / get_disentangle_loss / ContrastiveLoss
  *                                        training_project/utils/gaussian_diffusion.py:907-975,1056-1094,
  *                                        loss_function/contrastive_loss.py (csrc/contrast.hip)
+ *   dsd_op_image_metrics           <- monai.metrics MAEMetric / SSIMMetric at the end of validation_step
+ *                                        trainers/trainer_ddpm.py:501-565, and the per-slice MS-SSIM of
+ *                                        inference/test_metrics.py:249-274 (csrc/metrics.hip)
  *   dsd_op_sampler_update_guided / dsd_op_dpm_step_guided <- one guided step of those loops (kernel-level tests, host loops)
  *   dsd_sample_dpm_adaptive_trial / dsd_op_dpm_adaptive_error
  *                                  <- one trial of DPM_Solver.dpm_solver_adaptive  sampler.py:921-980 (the loop stays on the host)
@@ -707,6 +710,43 @@ typedef struct dsd_disentangle {
     float* logits_sal;             /* device, [7B,7B] */
 } dsd_disentangle;
 int dsd_set_disentangle(dsd_handle* h, const dsd_disentangle* spec);   /* NULL clears */
+/* ---- validation metrics of a batch of samples: MAE / MSE sums, Gaussian SSIM, the MS-SSIM scale table ------------
+ * Replaces, as an evaluation, monai.metrics.MAEMetric and SSIMMetric(spatial_dims=2[, data_range=2.0]) at the end of every
+ * trainer's validation_step (trainers/trainer_ddpm.py:79-80,529-532, trainers/trainer_use_gaussian_diff.py:99-102,519-584 and
+ * the other five trainers) and the per-slice MS-SSIM behind the "ssim" column of the inference metric table
+ * (inference/test_metrics.py:249-274).  PARITY UNPINNED: neither MONAI nor torchmetrics can be run beside this library; the
+ * formulas below are their published definitions, pinned against the float64 host restatements host_io.ssim_gaussian and
+ * host_io.multiscale_structural_similarity.
+ * pred / target: device fp32 [B,C,H,W].  Everything from the load onward is fp64.
+ *   pre (host, NULL or 7 doubles mean_p, div_p, mean_t, div_t, add, lo, hi):  x <- min(max((x - mean) / div + add, lo), hi) at
+ *       the load, one (mean, div) for pred and one for target; the 12-bit rescale of test_metrics.py:21-26 is
+ *       (mean, std / 400, 2048, 1e-10, 4095) and gives the host's bits.  elem and the range are taken after it.
+ *   elem_out (device fp64 [B,6]):  sum |p - t|, sum (p - t)^2, min t, max t, min p, max p over the C*H*W elements of a sample.
+ *   R = data_range, or with data_range == 0 the sample's own max(max p - min p, max t - min t);  c1 = (0.01 R)^2, c2 = (0.03 R)^2.
+ *   window g[i] = exp(-((i - 5) / 1.5)^2 / 2) / sum, 11 taps, applied along the rows, then along the columns, at the
+ *       (H - 10) x (W - 10) positions where it lies inside the image.  With E[.] that blur:
+ *       mx = E[x], my = E[y], sx = E[xx] - mx^2, sy = E[yy] - my^2, sxy = E[xy] - mx my               (biased)
+ *       cs = (2 sxy + c2) / (sx + sy + c2),   ssim = (2 mx my + c1) / (mx^2 + my^2 + c1) * cs
+ *   scale_out (device fp64 [B,scales,2]):  per sample and scale the mean of ssim and the mean of cs over all channels and
+ *       window positions, NOT clamped (MS-SSIM clamps at 0, SSIMMetric does not: that stays with the caller).  Scale s + 1 is
+ *       the 2 x 2 average of scale s, a trailing odd row / column dropped (F.avg_pool2d), kept in fp64.
+ * A map workgroup owns DSD_METRICS_TILE_W x DSD_METRICS_TILE_H window positions of one channel.  Every sum is formed from fixed
+ * per-workgroup fp64 partials folded in a fixed order; no atomics: two calls agree bit for bit.  Scratch is allocated and
+ * released by the call.  Rejected before any device work: null pointers, scales outside 1..DSD_METRICS_MAX_SCALES,
+ * min(H, W) >> (scales - 1) below 11, B > 65535, C*H*W > 2^30, data_range negative or not finite, pre with a div of 0 or
+ * lo > hi. */
+enum { DSD_METRICS_MAX_SCALES = 5, DSD_METRICS_TILE_W = 32, DSD_METRICS_TILE_H = 16 };
+typedef struct dsd_image_metrics {
+    const float* pred;             /* device, [B,C,H,W] */
+    const float* target;           /* device, [B,C,H,W] */
+    int32_t B, C, H, W;
+    int32_t scales;                /* 1..DSD_METRICS_MAX_SCALES */
+    double data_range;             /* > 0, or 0: per sample */
+    const double* pre;             /* host, NULL or [7] */
+    double* scale_out;             /* device, [B,scales,2] */
+    double* elem_out;              /* device, [B,6] */
+} dsd_image_metrics;
+int dsd_op_image_metrics(const dsd_image_metrics* spec, void* stream);
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
