@@ -25,6 +25,13 @@ LOSS_TERM_MSE, LOSS_TERM_VB, LOSS_TERM_COM, LOSS_TERM_DIST, LOSS_NTERMS = 0, 1, 
 CONTRAST_CL, CONTRAST_EU, CONTRAST_EU_CL, CONTRAST_L1 = 0, 1, 2, 3
 CONTRAST_MAX_VIEWS, CONTRAST_MAX_ROWS = 8, 256
 METRICS_MAX_SCALES, METRICS_TILE_W, METRICS_TILE_H = 5, 32, 16
+VOLUME_TILE_W, VOLUME_TILE_H, VOLUME_MAX_LOG2 = 32, 16, 27
+# DSD_VOLUME_* slots of dsd_volume_metrics.out, in the header's order, and the status bits
+VOLUME_SLOTS = ("nrmse", "mape", "smape", "logac", "medsymac", "psnr", "ssim3d", "status", "n_M", "lo_d", "hi_d", "lo_h", "hi_h", "lo_w",
+                "hi_w", "mean_t_M", "std_t_M", "mean_p_M", "std_p_M", "mean_t_Z", "std_t_Z", "mean_p_Z", "std_p_Z", "mean_t_R", "std_t_R",
+                "mean_p_R", "std_p_R")
+VOLUME_NOUT = len(VOLUME_SLOTS)
+VOLUME_EMPTY_MASK, VOLUME_EMPTY_CROP, VOLUME_ZERO_STD, VOLUME_ZERO_RANGE, VOLUME_SMALL_R = 1, 2, 4, 8, 16
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3, "f16": 4, "bf16": 5}
 (BLOCK_RES, BLOCK_ATTN, BLOCK_UPSAMPLE, BLOCK_DOWNSAMPLE, BLOCK_DISENTANGLE, BLOCK_SE, BLOCK_CROSSATTN,
  BLOCK_FF_GEGLU, BLOCK_BASIC_TRANSFORMER, BLOCK_SPATIAL_TRANSFORMER, BLOCK_VAE_ENCODER, BLOCK_VAE_DECODER,
@@ -47,6 +54,7 @@ EXPORTS = [
     "dsd_set_disentangle", "dsd_op_contrast_rows",
     "dsd_op_tail",
     "dsd_op_image_metrics",
+    "dsd_op_volume_metrics", "dsd_op_kth_double",
 ]
 # DSD_TAIL_* of include/dsdiff.h, in its order
 TAIL_KINDS = ("se_scale", "avg_into", "nchw_to_nhwc", "nhwc_to_nchw", "avgpool2", "upsample2", "geglu", "softmax_rows", "ln_modulate",
@@ -132,6 +140,11 @@ class DsdImageMetrics(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("scales", C.c_int32), ("data_range", C.c_double), ("pre", C.POINTER(C.c_double)), ("scale_out", C.c_void_p),
                 ("elem_out", C.c_void_p)]
+
+
+class DsdVolumeMetrics(C.Structure):
+    _fields_ = [("target", C.c_void_p), ("pred", C.c_void_p), ("elem_is_double", C.c_int32), ("mask", C.c_void_p), ("D", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("win", C.c_int32), ("out", C.c_void_p)]
 
 
 class DsdConvEx(C.Structure):
@@ -295,6 +308,9 @@ def lib() -> C.CDLL:
         L.dsd_op_tail.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
     if hasattr(L, "dsd_op_image_metrics"):     # (likewise)
         L.dsd_op_image_metrics.argtypes = [C.POINTER(DsdImageMetrics), vp]
+    if hasattr(L, "dsd_op_volume_metrics"):    # (likewise)
+        L.dsd_op_volume_metrics.argtypes = [C.POINTER(DsdVolumeMetrics), vp]
+        L.dsd_op_kth_double.argtypes = [vp, i64, i64, vp, vp]
     if hasattr(L, "dsd_set_conditioning"):     # (an older build under DSD_LIBRARY, for A/B timing of the loops it has)
         L.dsd_set_conditioning.argtypes = [vp, C.POINTER(DsdConditioning)]
     if hasattr(L, "dsd_set_trace"):            # (likewise)

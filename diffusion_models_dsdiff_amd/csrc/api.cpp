@@ -1691,6 +1691,35 @@ int dsd_op_image_metrics(const dsd_image_metrics* spec, void* stream) {
     DSD_CATCH
 }
 
+int dsd_op_volume_metrics(const dsd_volume_metrics* spec, void* stream) {
+    DSD_TRY
+    DSD_CHECK(spec, "volume_metrics: spec is null");
+    DSD_CHECK(spec->target, "volume_metrics: target is null");
+    DSD_CHECK(spec->pred, "volume_metrics: pred is null");
+    DSD_CHECK(spec->out, "volume_metrics: out is null");
+    volume_metrics_check(spec->D, spec->H, spec->W, spec->win, spec->elem_is_double);
+    Tmp scratch(volume_metrics_scratch_bytes(spec->D, spec->H, spec->W, spec->win));
+    VolumeMetrics m;
+    m.target = spec->target; m.pred = spec->pred;
+    m.elem_is_double = spec->elem_is_double;
+    m.mask = spec->mask;
+    m.D = spec->D; m.H = spec->H; m.W = spec->W;
+    m.win = spec->win;
+    m.scratch = scratch.p;
+    m.out = spec->out;
+    volume_metrics(m, (hipStream_t)stream);
+    DSD_CATCH
+}
+
+int dsd_op_kth_double(const double* x, int64_t n, int64_t k, double* out, void* stream) {
+    DSD_TRY
+    DSD_CHECK(x && out, "kth_double: null argument");
+    kth_double_check(n, k);
+    Tmp scratch(kth_double_scratch_bytes());
+    kth_double(x, n, k, scratch.p, out, (hipStream_t)stream);
+    DSD_CATCH
+}
+
 int dsd_op_loss_rows(int pred, int kind, const float* model_out, int64_t out_row_stride, const float* x_start, const float* noise,
                      uint64_t philox_seed, uint64_t step, const float* a, const float* s, float* loss, int64_t loss_stride, int B,
                      int Cz, int H, int W, void* stream) {

@@ -495,4 +495,29 @@ size_t image_metrics_scratch_doubles(int B, int C, int H, int W, int scales);
 void image_metrics_check(int B, int C, int H, int W, int scales, double data_range, const double* pre);
 void image_metrics(const ImageMetrics& a, hipStream_t s);
 
+// ---------------------------------------------------------------- volume_metrics.hip
+// The metric table of one volume pair [D,H,W] (float or double elements, fp64 from the load onward): NRMSE, MAPE, sMAPE, logac,
+// medsymac over the mask M, PSNR over the masked crop Z, the win^3 box-window SSIM over R, and the auxiliary values, into
+// out[DSD_VOLUME_NOUT] (device) with a status word among them; definitions in include/dsdiff.h.  scratch:
+// volume_metrics_scratch_bytes(...) bytes.  Fixed per-workgroup partials, a fixed fold, integer atomics in the histograms only:
+// two runs agree bit for bit.
+static constexpr int kVmTileW = 32, kVmTileH = 16;   // window positions one workgroup of the ssim3d row kernel owns (DSD_VOLUME_TILE_W / _H)
+struct VolumeMetrics {
+    const void* target = nullptr;
+    const void* pred = nullptr;
+    int elem_is_double = 0;
+    const uint8_t* mask = nullptr;
+    int D = 0, H = 0, W = 0, win = 0;
+    void* scratch = nullptr;
+    double* out = nullptr;
+};
+size_t volume_metrics_scratch_bytes(int D, int H, int W, int win);
+// the argument checks that need no device pointer (the C ABI runs them before any device work)
+void volume_metrics_check(int D, int H, int W, int win, int elem_is_double);
+void volume_metrics(const VolumeMetrics& a, hipStream_t s);
+// out[0] = the k-th smallest (0-based) of x[n] (device, no NaN), exactly: radix selection on the order-preserving image of the bits
+size_t kth_double_scratch_bytes();
+void kth_double_check(int64_t n, int64_t k);
+void kth_double(const double* x, int64_t n, int64_t k, void* scratch, double* out, hipStream_t s);
+
 }  // namespace dsd

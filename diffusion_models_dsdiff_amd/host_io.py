@@ -24,6 +24,10 @@ What the reference does around ``sample_fn`` and what is rebuilt here:
     table ``ssim_scale_table`` — the float64 statements the device kernel (csrc/metrics.hip, ``metrics.image_metrics``) is
     tested against; ``ssim_torch`` / ``metric_row`` / ``metric_table`` take ``device=`` to evaluate the MS-SSIM column there
     (unset: the host loop, unchanged).  Parity unpinned: MONAI is absent.
+  * ``metric_row`` / ``metric_table`` take ``table_on_device=True`` beside ``device=`` to evaluate the other five number columns
+    there as well (nrmse, smape, logac, medsymac, psnr: ``metrics.volume_metrics``, csrc/volume_metrics.hip — masked reductions,
+    the exclusive-bound crop, the median by exact selection); the functions here stay the float64 statements that kernel is
+    tested against, ``ssim`` (the 9^3 box-window SSIM) among them.  Off: exactly what ``device=`` alone returns.
 Not rebuilt: CW-SSIM (pyssim), FID / LPIPS (network weights), ANTs similarity / Mattes mutual information (the table's ``mi``
 column holds NaN).
 
@@ -408,22 +412,50 @@ def ssim_torch(true_array, pred_array, mask=None, device=None):
 METRIC_COLUMNS = ["nrmse", "smape", "logac", "medsymac", "cc", "mi", "ssim", "lpips", "fid", "psnr"]
 
 
-def metric_row(gt_img, pred_img, mask_img=None, device=None):
+def _fp32_valued(a):
+    return bool(np.array_equal(a.astype(np.float32).astype(np.float64), a))
+
+
+def _metric_row_on_device(gt_img, pred_img, mask_img, device):
+    """``metric_row`` with every number column from the device: the two volumes and the mask go up once (fp32 when every value
+    survives the round trip through float32, else fp64), ``metrics.volume_metrics`` gives nrmse, smape, logac, medsymac and psnr,
+    and ``metrics.image_metrics`` the MS-SSIM of the axial slices of Z — formed from the same device tensors, with the 12-bit rescale
+    built from the call's Z means and stds."""
+    import torch
+    from .metrics import image_metrics, volume_metrics
+    dt = torch.float32 if _fp32_valued(gt_img) and _fp32_valued(pred_img) else torch.float64
+    t = torch.from_numpy(np.ascontiguousarray(gt_img)).to(device=device, dtype=dt)
+    p = torch.from_numpy(np.ascontiguousarray(pred_img)).to(device=device, dtype=dt)
+    m = None if mask_img is None else torch.from_numpy(np.ascontiguousarray(np.asarray(mask_img) != 0)).to(device)
+    v = volume_metrics(t, p, m, win=0)
+    sl = tuple(slice(a, b) for a, b in zip(v["lo"], v["hi"]))
+    if m is not None:
+        t, p = torch.where(m, t, torch.zeros((), dtype=dt, device=t.device)), torch.where(m, p, torch.zeros((), dtype=dt, device=t.device))
+    pre = (v["mean_p_Z"], v["std_p_Z"] / 400., v["mean_t_Z"], v["std_t_Z"] / 400., 2048., 1e-10, 4095)
+    up = lambda a: a[sl].float()[:, None].contiguous()
+    ms = image_metrics(up(p), up(t), scales=5, data_range=0, pre=pre)["ms_ssim"]
+    return [v["nrmse"], v["smape"], v["logac"], v["medsymac"], 0.0, float("nan"), float(np.mean(ms.numpy())), 0.0, 0.0, v["psnr"]]
+
+
+def metric_row(gt_img, pred_img, mask_img=None, device=None, table_on_device=False):
     """One row of inference/get_metric_BraTs.py:78-104 (without the id): the columns the reference fills with a constant 0
     (cc, lpips, fid: their calls are commented out there) stay 0; ``mi`` is ANTs' Mattes mutual information in the
     reference (test_metrics.py:77-90) — ANTs is not available and is not restated: the column holds NaN.  ``device``: see
-    ``ssim_torch`` (the "ssim" column on the device; None: everything on the host, as before)."""
+    ``ssim_torch`` (the "ssim" column on the device; None: everything on the host, as before).  ``table_on_device`` with a device:
+    the other five number columns come from the device too (``_metric_row_on_device``); without one it changes nothing."""
     gt_img, pred_img = np.asarray(gt_img, dtype=np.float64), np.asarray(pred_img, dtype=np.float64)
+    if table_on_device and device is not None:
+        return _metric_row_on_device(gt_img, pred_img, mask_img, device)
     return [nrmse(gt_img, pred_img, mask_img), smape(gt_img, pred_img, mask_img), logac(gt_img, pred_img, mask_img),
             medsymac(gt_img, pred_img, mask_img), 0.0, float("nan"), ssim_torch(gt_img, pred_img, mask_img, device=device), 0.0, 0.0,
             psnr(gt_img, pred_img, mask_img)]
 
 
-def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None, device=None):
+def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None, device=None, table_on_device=False):
     """get_metric_BraTs.py:54-115: for every prediction ``<id>_..._pred.nii.gz`` (id = text before the first '_') or
     ``{id: path}`` entry, the ground truth ``<gt_dir>/<id>/<gt_name>`` (and, with mask_name, ``<gt_dir>/<id>/<mask_name>``
     > 0 as mask); returns the table with the MEAN row first (float32 mean over the ids, as the reference computes it) and
-    the id rows after it: [["ids"] + METRIC_COLUMNS header not included].  ``device``: see ``ssim_torch``."""
+    the id rows after it: [["ids"] + METRIC_COLUMNS header not included].  ``device`` / ``table_on_device``: see ``metric_row``."""
     if not isinstance(pred_files, dict):
         pred_files = {os.path.basename(f).split(".")[0].split("_")[0]: f for f in pred_files if f.endswith(".nii.gz")}
     rows = []
@@ -433,7 +465,7 @@ def metric_table(pred_files, gt_dir, gt_name="ce.nii.gz", mask_name=None, device
         mask = None
         if mask_name:
             mask = read_nifti(os.path.join(gt_dir, id_, mask_name))[0] > 0
-        rows.append([str(id_)] + metric_row(gt, pred, mask, device=device))
+        rows.append([str(id_)] + metric_row(gt, pred, mask, device=device, table_on_device=table_on_device))
     if not rows:
         return []
     mean = np.mean(np.asarray([r[1:] for r in rows], dtype=np.float32), axis=0)

@@ -19,7 +19,9 @@ and ``--output <dir>`` — one NIfTI volume per id, the slices stacked at their 
   * ``--gt-dir <dir>`` (+ ``--gt-name ce.nii.gz``, ``--mask-name``): the metric pass of inference/get_metric_BraTs.py:54-126
     over the volumes just written — per-id rows + the mean row first — as ``<output>_metric.csv`` (the reference writes the
     same table as .xlsx; its ``mi`` column is ANTs' Mattes MI, not restated: NaN).  ``--metrics-on-device`` (off by default)
-    evaluates the table's ``ssim`` column on the rank's GPU (host_io.ssim_torch(device=), metrics.image_metrics).
+    evaluates the table's ``ssim`` column on the rank's GPU (host_io.ssim_torch(device=), metrics.image_metrics);
+    ``--metric-table-on-device`` (off by default, needs ``--gt-dir``) evaluates every number column there (nrmse, smape, logac,
+    medsymac and psnr through metrics.volume_metrics as well).
 Remaining differences from the SimpleITK path: NIfTI headers are copied byte for byte, so the on-disk axis convention is
 the template's own (SimpleITK converts LPS <-> RAS when it writes); only single-file NIfTI-1 is handled.
 
@@ -63,7 +65,11 @@ def main(argv=None):
     ap.add_argument("--mask-name", default=None, help="optional <gt-dir>/<id>/<mask-name> (> 0 = inside)")
     ap.add_argument("--metrics-on-device", action="store_true",
                     help="the metric table's ssim column (MS-SSIM of every axial slice) on this rank's GPU instead of the host loop")
+    ap.add_argument("--metric-table-on-device", action="store_true",
+                    help="every number column of the metric table (nrmse, smape, logac, medsymac, ssim, psnr) on this rank's GPU; needs --gt-dir")
     args = ap.parse_args(argv)
+    if args.metric_table_on_device and not args.gt_dir:
+        ap.error("--metric-table-on-device needs --gt-dir")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_launch(args.gpus, sys.argv[1:] if argv is None else list(argv)))
 
@@ -198,7 +204,8 @@ def main(argv=None):
             print(f"wrote {path}: {tuple(vol.shape)} {vol.dtype}")
         if args.gt_dir:
             table = host_io.metric_table(written, args.gt_dir, args.gt_name, args.mask_name,
-                                         device=dev if args.metrics_on_device else None)
+                                         device=dev if args.metrics_on_device or args.metric_table_on_device else None,
+                                         table_on_device=args.metric_table_on_device)
             csv_path = args.output.rstrip("/") + "_metric.csv"
             host_io.write_metric_csv(csv_path, table)
             print(f"wrote {csv_path}: {len(table) - 1} ids + mean row")

@@ -1,4 +1,4 @@
-"""Validation metrics of a batch of samples: MAE, Gaussian SSIM and MS-SSIM, evaluated on the device.
+"""Validation metrics of a batch of samples: MAE, Gaussian SSIM and MS-SSIM, and the metric table of a volume, evaluated on the device.
 
 What every trainer of the reference does at the end of ``validation_step`` — ``MAEMetric`` and ``SSIMMetric(spatial_dims=2[,
 data_range=2.0])`` of monai.metrics on the samples (trainers/trainer_ddpm.py:79-80,529-532, 540-565;
@@ -6,6 +6,11 @@ trainers/trainer_use_gaussian_diff.py:99-102,519-584) — and the per-slice MS-S
 table (inference/test_metrics.py:249-274).  Device tensors go through ``dsd_op_image_metrics`` (csrc/metrics.hip: fp64 from the
 load onward, one launch sequence, one read-back); CPU tensors take the float64 host functions of ``host_io``, so the module works
 without a GPU.  There is no other path: a device tensor without the library is an error.
+
+``volume_metrics`` is the per-id row of the inference metric table (inference/get_metric_BraTs.py:78-104 over the array functions of
+inference/test_metrics.py:149-246,378-400): NRMSE, MAPE, sMAPE, logac, medsymac, PSNR and the box-window SSIM of one [D,H,W] pair.
+Device tensors go through ``dsd_op_volume_metrics`` (csrc/volume_metrics.hip); CPU tensors and arrays through ``host_io.nrmse`` ...
+``host_io.ssim``, which are also what tests/test_volume_metrics_gpu.py holds the device to.
 
 PARITY UNPINNED: MONAI and torchmetrics are not installable here and the reference holds no value of either.  The formulas are the
 published definitions (``host_io.ssim_gaussian``, ``host_io.multiscale_structural_similarity``); tests/test_image_metrics_cpu.py
@@ -171,3 +176,112 @@ class SSIMMetric(_Cumulative):
 
     def _values(self, y_pred, y):
         return image_metrics(y_pred, y, data_range=self.data_range)["ssim"]
+
+
+# ------------------------------------------------------------------------------------------------ the metric table of a volume
+VOLUME_STATUS = (
+    (_lib.VOLUME_EMPTY_MASK, "volume_metrics: the mask is empty"),
+    (_lib.VOLUME_EMPTY_CROP, "volume_metrics: the mask's bounding box [lo, hi) has a side of 0 (the upper bound is exclusive)"),
+    (_lib.VOLUME_ZERO_STD, "volume_metrics: target or pred has a standard deviation of 0 in a domain the 12-bit rescale is taken over"),
+    (_lib.VOLUME_ZERO_RANGE, "volume_metrics: the target's range is 0 under nrmse or psnr"),
+    (_lib.VOLUME_SMALL_R, "win_size must be odd and not exceed any image side"),       # host_io.structural_similarity's own words
+)
+
+
+def _volume_check(shape_t, shape_p, shape_m, win):
+    """The refusals of dsd_op_volume_metrics that need no device, in its words."""
+    if len(shape_t) != 3 or tuple(shape_t) != tuple(shape_p):
+        raise ValueError(f"volume_metrics: target {tuple(shape_t)} and pred {tuple(shape_p)} must be one shape [D,H,W]")
+    if shape_m is not None and tuple(shape_m) != tuple(shape_t):
+        raise ValueError(f"volume_metrics: mask {tuple(shape_m)} does not have the volumes' shape {tuple(shape_t)}")
+    D, H, W = (int(v) for v in shape_t)
+    if min(D, H, W) < 1:
+        raise ValueError(f"volume_metrics: bad shape: D {D} H {H} W {W}")
+    if D * H * W > 1 << _lib.VOLUME_MAX_LOG2:
+        raise ValueError(f"volume_metrics: D*H*W = {D * H * W} voxels; up to 2^{_lib.VOLUME_MAX_LOG2} are taken")
+    if not (win == 0 or (3 <= win <= 11 and win % 2 == 1)):
+        raise ValueError(f"volume_metrics: win is {win}; 0 (no ssim3d) or an odd value from 3 to 11")
+
+
+def _volume_device(target, pred, mask, win):
+    """out [DSD_VOLUME_NOUT] of dsd_op_volume_metrics as a float64 array (``_lib.VOLUME_SLOTS`` names the slots): fp64 tensors go
+    as they are, everything else as fp32; the mask as uint8."""
+    dt = torch.float64 if target.dtype == torch.float64 or pred.dtype == torch.float64 else torch.float32
+    t, p = target.detach().to(dt).contiguous(), pred.detach().to(dt).contiguous()
+    m = None if mask is None else (mask.detach() != 0).to(torch.uint8).contiguous()
+    out = torch.empty(_lib.VOLUME_NOUT, dtype=torch.float64, device=t.device)
+    spec = _lib.DsdVolumeMetrics()
+    spec.target, spec.pred = t.data_ptr(), p.data_ptr()
+    spec.elem_is_double = int(dt == torch.float64)
+    spec.mask = m.data_ptr() if m is not None else None
+    spec.D, spec.H, spec.W = (int(v) for v in t.shape)
+    spec.win = int(win)
+    spec.out = out.data_ptr()
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.lib().dsd_op_volume_metrics(C.byref(spec), _lib.stream_ptr()))
+    return out.cpu().numpy()                                       # the one read-back
+
+
+def _volume_host(t, p, mask, win):
+    """The same slots from the float64 host functions (and numpy for the auxiliary values)."""
+    t, p = np.asarray(t, dtype=np.float64), np.asarray(p, dtype=np.float64)
+    mask = None if mask is None else np.asarray(mask) != 0
+    m = host_io._mask(t, mask)
+    nz = np.nonzero(m)
+    if nz[0].size == 0:
+        raise ValueError(VOLUME_STATUS[0][1])
+    lo, hi = [int(a.min()) for a in nz], [int(a.max()) for a in nz]
+    sl = tuple(slice(a, b) for a, b in zip(lo, hi))
+    out = dict(nrmse=host_io.nrmse(t, p, mask), mape=host_io.mape(t, p, mask), smape=host_io.smape(t, p, mask),
+               logac=host_io.logac(t, p, mask), medsymac=host_io.medsymac(t, p, mask), psnr=host_io.psnr(t, p, mask), ssim3d=float("nan"),
+               status=0.0, n_M=float(nz[0].size))
+    if win == 9:
+        out["ssim3d"] = host_io.ssim(t, p, mask)
+    elif win:                                                      # host_io.ssim's statements with another window
+        tr, pr = (t[sl], p[sl]) if mask is not None else (t, p)
+        tr, pr = host_io.scale12bit(tr), host_io.scale12bit(pr)
+        out["ssim3d"] = host_io.structural_similarity(tr, pr, win_size=win, data_range=tr.max() - tr.min())
+    for a, name in enumerate("dhw"):
+        out["lo_" + name], out["hi_" + name] = float(lo[a]), float(hi[a])
+    doms = {"M": (t[m], p[m]), "Z": (np.where(m, t, 0)[sl], np.where(m, p, 0)[sl]), "R": (t[sl], p[sl]) if mask is not None else (t, p)}
+    for d, (a, b) in doms.items():
+        empty = a.size == 0
+        out["mean_t_" + d], out["std_t_" + d] = (float("nan"),) * 2 if empty else (float(np.mean(a)), float(np.std(a)))
+        out["mean_p_" + d], out["std_p_" + d] = (float("nan"),) * 2 if empty else (float(np.mean(b)), float(np.std(b)))
+    return np.asarray([out[k] for k in _lib.VOLUME_SLOTS], dtype=np.float64)
+
+
+def volume_metrics(target, pred, mask=None, win=0):
+    """target / pred: tensors or arrays [D,H,W]; mask: the same shape (non-zero = inside) or None; win: the window of the 3-D SSIM,
+    0 (skipped: ``ssim3d`` is NaN) or odd 3..11, the reference uses 9.  Returns a dict of Python floats
+
+      nrmse, mape, smape, logac, medsymac   over M, the voxels inside the mask (``host_io.nrmse`` ... ``host_io.medsymac``)
+      psnr                                   over Z: zero outside the mask, cropped to the mask's box [lo, hi) (``host_io.psnr``)
+      ssim3d                                 over R: the raw crop, or the whole volume without a mask (``host_io.ssim``)
+
+    plus the auxiliary values ``n_M`` (int), ``lo`` / ``hi`` (per axis the smallest / largest index holding a mask voxel; the crop
+    drops plane ``hi``) and ``mean_t_M`` ... ``std_p_R``, the mean and population std of target and pred in each domain.  CUDA tensors
+    are evaluated by the library (fp64 tensors as fp64, others as fp32 values, fp64 arithmetic); anything on the CPU by the float64
+    host functions, bit for bit.  An empty mask, a box with a side of 0, a zero std or range, or (win > 0) a side of R below win raise
+    ValueError on the device path; the host functions answer those with numpy's own errors or non-finite values."""
+    win = int(win)
+    on_device = isinstance(target, torch.Tensor) and target.is_cuda
+    _volume_check(target.shape, pred.shape, None if mask is None else mask.shape, win)
+    if on_device:
+        if not (isinstance(pred, torch.Tensor) and pred.device == target.device) or \
+                (mask is not None and not (isinstance(mask, torch.Tensor) and mask.device == target.device)):
+            raise ValueError("volume_metrics: target, pred and mask are on different devices")
+        raw = _volume_device(target, pred, mask, win)
+    else:
+        cpu = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        raw = _volume_host(cpu(target), cpu(pred), None if mask is None else cpu(mask), win)
+    status = int(raw[_lib.VOLUME_SLOTS.index("status")])
+    for bit, text in VOLUME_STATUS:
+        if status & bit:
+            raise ValueError(text)
+    out = {k: float(v) for k, v in zip(_lib.VOLUME_SLOTS, raw)}
+    del out["status"]
+    out["n_M"] = int(out["n_M"])
+    out["lo"] = tuple(int(out.pop("lo_" + a)) for a in "dhw")
+    out["hi"] = tuple(int(out.pop("hi_" + a)) for a in "dhw")
+    return out

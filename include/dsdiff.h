@@ -747,6 +747,61 @@ typedef struct dsd_image_metrics {
     double* elem_out;              /* device, [B,6] */
 } dsd_image_metrics;
 int dsd_op_image_metrics(const dsd_image_metrics* spec, void* stream);
+/* ---- The metric table of a volume on the device: masked errors, exact median, PSNR, box-window SSIM ----------------------------
+ * The columns inference/get_metric.py, get_metric_BraTs.py, get_metric_lh.py and get_metric_rm.py fill per volume id from the array
+ * functions of inference/test_metrics.py (:21-26,149-246,378-400), restated from the float64 host functions of host_io.py (nrmse,
+ * mape, smape, logac, medsymac, psnr, ssim); where this text and such a function differ, the function wins.
+ * target / pred: device [D,H,W], float (elem_is_double 0) or double (1).  mask: device uint8 [D,H,W], non-zero = inside, or NULL.
+ * Everything from the load onward is fp64.
+ *   M = the voxels with mask != 0 (every voxel without a mask); per axis lo / hi = the smallest / largest index holding a voxel
+ *       of M.  The crop is [lo, hi) on every axis: the upper bound is EXCLUSIVE, as the reference slices, so the last plane that
+ *       holds mask voxels is dropped (without a mask the crop is [0, n - 1)).
+ *   Z = the crop of where(m, x, 0);  R = the crop of the raw volume with a mask, the whole volume without one.
+ *   s12(x) = min(max(((x - mean) / (std / 400.)) + 2048., 1e-10), 4095), mean and population std of the domain's own values, pred
+ *       and target each their own;  ts, ps = s12 of target and pred over M.
+ *   nrmse = sqrt(mean_M (t - p)^2) / (max_M t - min_M t)           mape  = mean_M |ts - ps| / |ts|
+ *   smape = mean_M |ps - ts| / (|ts| + |ps|)                       logac = mean_M l,  l = |log(ps / ts)|
+ *   medsymac = exp(median_M l) - 1, the median the middle order statistic, or half the sum of the two middle ones for an even n_M
+ *   psnr = 10 log10((max_Z tz - min_Z tz)^2 / mean_Z (tz - pz)^2)
+ *   ssim3d (win > 0) = the mean over every window position inside R of
+ *       ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  x = s12_R(t), y = s12_R(p), u the plain win^3 window
+ *       means, v the sample (co)variances win^3 / (win^3 - 1) (uxx - ux^2), C = (K (max x - min x))^2, K = 0.01, 0.03.
+ * out (device fp64 [DSD_VOLUME_NOUT]): the slots below; DSD_VOLUME_STATUS holds the status bits as a double.  A condition that
+ * leaves a value undefined sets its bit and the affected slots are NaN: an empty mask (all but n_M), a crop with a side of 0
+ * (psnr, the Z values and with a mask ssim3d and the R values), a zero std of target or pred in M (mape, smape, logac, medsymac) or,
+ * with win > 0, in R (ssim3d), a zero range under nrmse or psnr, with win > 0 a side of R below win (ssim3d).
+ * The median is an exact selection (dsd_op_kth_double's kernels on the l array, padded with +inf outside M).  A workgroup of the
+ * ssim3d row kernel owns DSD_VOLUME_TILE_W x DSD_VOLUME_TILE_H window positions of one slice.  Every sum is formed from fixed
+ * per-workgroup fp64 partials folded in a fixed order; no floating-point atomics: two calls agree bit for bit.  Scratch is
+ * allocated and released by the call: 8 bytes per voxel for l and, with win > 0, 40 bytes per (z, window position in the plane)
+ * of the whole volume, since the box is known on the device only.  Rejected before any device work: a null target, pred or out, a dimension below 1,
+ * D*H*W > 2^DSD_VOLUME_MAX_LOG2, win even or outside 0, 3..11, elem_is_double not 0 or 1. */
+enum { DSD_VOLUME_TILE_W = 32, DSD_VOLUME_TILE_H = 16, DSD_VOLUME_MAX_LOG2 = 27 };
+enum {
+    DSD_VOLUME_NRMSE = 0, DSD_VOLUME_MAPE, DSD_VOLUME_SMAPE, DSD_VOLUME_LOGAC, DSD_VOLUME_MEDSYMAC, DSD_VOLUME_PSNR, DSD_VOLUME_SSIM3D,
+    DSD_VOLUME_STATUS, DSD_VOLUME_N_M,
+    DSD_VOLUME_LO_D, DSD_VOLUME_HI_D, DSD_VOLUME_LO_H, DSD_VOLUME_HI_H, DSD_VOLUME_LO_W, DSD_VOLUME_HI_W,   /* hi: the largest index */
+    DSD_VOLUME_MEAN_T_M, DSD_VOLUME_STD_T_M, DSD_VOLUME_MEAN_P_M, DSD_VOLUME_STD_P_M,
+    DSD_VOLUME_MEAN_T_Z, DSD_VOLUME_STD_T_Z, DSD_VOLUME_MEAN_P_Z, DSD_VOLUME_STD_P_Z,
+    DSD_VOLUME_MEAN_T_R, DSD_VOLUME_STD_T_R, DSD_VOLUME_MEAN_P_R, DSD_VOLUME_STD_P_R,
+    DSD_VOLUME_NOUT
+};
+enum { DSD_VOLUME_EMPTY_MASK = 1, DSD_VOLUME_EMPTY_CROP = 2, DSD_VOLUME_ZERO_STD = 4, DSD_VOLUME_ZERO_RANGE = 8, DSD_VOLUME_SMALL_R = 16 };
+typedef struct dsd_volume_metrics {
+    const void* target;            /* device, [D,H,W] */
+    const void* pred;              /* device, [D,H,W] */
+    int32_t elem_is_double;        /* 0: float, 1: double */
+    const uint8_t* mask;           /* device, [D,H,W], or NULL */
+    int32_t D, H, W;
+    int32_t win;                   /* 0: no ssim3d; else odd, 3..11 (the reference: 9) */
+    double* out;                   /* device, [DSD_VOLUME_NOUT] */
+} dsd_volume_metrics;
+int dsd_op_volume_metrics(const dsd_volume_metrics* spec, void* stream);
+/* out[0] (device) = the k-th smallest, 0-based, of the n doubles x (device; no NaN among them), exactly: most-significant-first
+ * radix selection on the order-preserving uint64 image of the bits (sign flipped for non-negative values, complement for negative
+ * ones), six histogram passes of 11-bit digits; the result is the element itself.  Rejected: null pointers, n outside 1..2^31,
+ * k outside 0..n-1. */
+int dsd_op_kth_double(const double* x, int64_t n, int64_t k, double* out, void* stream);
 /* ---- PLMS sampler with norm thresholding ---------------------------------------------------
  * Replaces PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py:59-245) on a DSD_MODE_B_PLMS
  * schedule.  Iteration k evaluates the network once at t_model[k] (guided: 2B rows, e_t = e_u + s*(e_c - e_u), as in
